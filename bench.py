@@ -15,7 +15,11 @@ is rows / that wall time.  The same step with the reads already resident in HBM 
 reported as `resident` (the kernel pipeline alone, never `value`); building the reference API's list of Python
 tuples from the row array is reported as `python_tuples`.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the steps one by one, `pcie`).
+`--dump-outputs DIR` writes the rows of the last timed step to DIR (see dump_outputs).  Everything else runs
+with `--full` only -- per-kernel stage times, the resident loop, the cold call, the `overlap` command as a
+process, Python tuples, layout stage 1, configs 3 / 4 / 5 and these extra objects:
   roofline      dominant kernel (k_verify): algorithmic bytes of the emitted overlaps
                 (sum 2*ceil(l/4) B, both sides at 2 bit/base) / its HIP-event duration, vs 8 TB/s
   cpu_baseline  the reference overlapper itself (oracle/_ref, built from /root/reference by
@@ -237,6 +241,38 @@ def cpu_throttled():
         return None
 
 
+DUMP_BYTES = 60_000_000         # what --dump-outputs may write in all (under 64 MB)
+
+
+def dump_outputs(out_dir: str, rows: np.ndarray, rank: int, world: int) -> dict:
+    """The rows the timed step handed its caller, as float64 ``(n, 6)`` ``(a_idx, b_idx, astart, aend, bstart, bend)`` in
+    lexicographic order (the multiset is the contract, the order the kernels emit it in is not).  Above the byte budget a
+    fixed sample: evenly spaced rows of that order plus a seeded random choice, the same rows for the same multiset.  With N
+    ranks each rank writes its own share (``rows_rank<r>.npy``; the ranks' arrays together are the merged rows)."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols = ("a_idx", "b_idx", "astart", "aend", "bstart", "bend")
+
+    def key(hi, lo):   # two 32-bit columns as one unsigned 64-bit key in their order (signed ones shifted by 2^31)
+        h, l_ = (rows[c].astype(np.int64) + (0 if rows[c].dtype.kind == "u" else 1 << 31) for c in (hi, lo))
+        return (h.astype(np.uint64) << np.uint64(32)) | l_.astype(np.uint64)
+    order = np.lexsort((key("bstart", "bend"), key("astart", "aend"), key("a_idx", "b_idx")))
+    n = len(order)
+    cap = max(DUMP_BYTES // world // (6 * 8) - 16, 1)
+    if n > cap:
+        pick = np.union1d(np.linspace(0, n - 1, cap // 2).astype(np.int64),
+                          np.random.default_rng(20260).choice(n, cap - cap // 2, replace=False))
+        order = order[pick]
+    tab = np.empty((len(order), 6), dtype=np.float64)
+    for k, c in enumerate(cols):
+        tab[:, k] = rows[c][order]
+    suffix = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(out_dir, "rows%s.npy" % suffix), tab)
+    # the whole output in a few numbers: the row count and each column's sum over ALL rows (exact in float64 at these sizes)
+    col_sums = [float(rows[c].astype(np.int64).sum()) for c in cols]
+    np.save(os.path.join(out_dir, "rows_summary%s.npy" % suffix), np.array([n] + col_sums, dtype=np.float64))
+    return {"dir": out_dir, "rows": n, "rows_written": len(tab)}
+
+
 def other_config_leg(dev_idx: int, name: str, m: int, steps: int = 3) -> dict:
     """Another BASELINE config on ONE GPU, outside the headline's timed region: the host-to-host step (a changed
     read set: streamed upload, kernels, rows home -- what `value` measures at config 2) and the kernels alone (reads resident,
@@ -373,6 +409,12 @@ def main() -> int:
     ap.add_argument("--config", default="cfg2", choices=sorted(synth.CONFIGS))
     ap.add_argument("--reads", type=int, default=0, help="scale the config to this many reads (dev only)")
     ap.add_argument("--min-length", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel stage times, resident loop, roofline and measured peaks, cold call, "
+                         "the `overlap` command, Python tuples, layout stage 1, config 4, CPU baseline, other configs (the --no-* options "
+                         "and --other-configs trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows of the last one to DIR/*.npy (float64, at most 64 MB in all)")
     ap.add_argument("--cpu-sample-reads", type=int, default=800)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tuples", action="store_true", help="skip the Python tuple materialisation leg")
@@ -412,7 +454,7 @@ def main() -> int:
     # the `overlap` COMMAND as a user runs it -- one process, one call (assembler.py:42): FASTA file in, GFA2 file out.
     # Run as a child BEFORE this process touches the GPU (a process that has initialised the GPU starts no children).
     cli_leg = None
-    if world == 1 and not args.dist_path and not args.no_cli:
+    if args.full and world == 1 and not args.dist_path and not args.no_cli:
         cli_leg = cli_overlap_leg(reads_once, args.min_length)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the overlap path has no CPU fallback)")
@@ -458,7 +500,9 @@ def main() -> int:
 
     pcie = {"h2d_s": 0.0, "d2h_s": 0.0}
 
-    def step(timed: bool, inclusive: bool = True) -> int:
+    kept = []   # the last timed step's result, held for --dump-outputs (freed once its rows are written)
+
+    def step(timed: bool, inclusive: bool = True, keep: bool = False) -> int:
         if inclusive:
             # the call starts from host memory: packed reads host -> device (po_invalidate + po_upload)
             t_a = time.perf_counter()
@@ -494,7 +538,10 @@ def main() -> int:
             del rows
             if timed:
                 pcie["d2h_s"] += time.perf_counter() - t_a
-        res.free()
+        if keep:
+            kept.append(res)
+        else:
+            res.free()
         st = ov.stats()
         if world > 1 or args.dist_path:
             if not inclusive:
@@ -537,14 +584,19 @@ def main() -> int:
     t0 = time.perf_counter()
     n_rows = 0
     step_ms = []
-    for _ in range(args.steps):
+    for i in range(args.steps):
         t_s = time.perf_counter()
-        n_rows = step(True)
+        n_rows = step(True, keep=args.dump_outputs is not None and i == args.steps - 1)
         step_ms.append((time.perf_counter() - t_s) * 1e3)   # (a step ends with its rows in host memory: nothing is in flight here)
     fence()
     dt = time.perf_counter() - t0
     throttled1 = cpu_throttled()
     gc.enable()
+    dumped = None
+    if kept:
+        res = kept.pop()
+        dumped = dump_outputs(args.dump_outputs, res.rows(), rank, world)
+        res.free()
     if world > 1 or args.dist_path:
         t = torch.tensor([dt], dtype=torch.float64, device=merge_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -559,7 +611,7 @@ def main() -> int:
     # of device time, seven per piece): the per-kernel sums of the SAME step are taken from three extra steps with
     # PHASM_PHASE_EVENTS=2 (events around the two big kernels and around each piece), outside the timed region.
     ev_steps = 3
-    if world == 1 and not args.dist_path and incl_last.get("streamed"):
+    if args.full and world == 1 and not args.dist_path and incl_last.get("streamed"):
         keep_pcie = dict(pcie)
         for k in acc:
             acc[k] = 0.0
@@ -576,14 +628,16 @@ def main() -> int:
     # the kernel pipeline alone (reads resident in HBM, rows left in HBM): an extra, never `value`
     for k in acc:
         acc[k] = 0.0
-    step(False, inclusive=False)
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True, inclusive=False)
-    fence()
-    dt_res = time.perf_counter() - t1
-    if world > 1:
+    dt_res = 0.0
+    if args.full:
+        step(False, inclusive=False)
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(True, inclusive=False)
+        fence()
+        dt_res = time.perf_counter() - t1
+    if args.full and world > 1:
         t = torch.tensor([dt_res], dtype=torch.float64, device=merge_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt_res = float(t.item())
@@ -632,129 +686,133 @@ def main() -> int:
             "dist_backend": (args.dist_backend if (world > 1 or args.dist_path) else None),
             "ranks": ranks_in_collective,
             "read_pairs_per_sec": n_oriented * (n_oriented - 1) / (dt / K),
-            "resident": {"overlaps_per_sec": n_rows / (dt_res / K), "ms_per_step": dt_res / K * 1e3,
-                         "stage_ms": {k: round(v, 4) for k, v in avg_res.items()},
-                         "index_reused": int(last.get("index_reused", 0)),
-                         "note": "same step with the packed reads already in HBM and the rows left in HBM; index_reused = 1: the anchor index of the "
-                                 "unchanged upload is kept across these calls (ms_index is then the reset only; PHASM_NO_INDEX_REUSE=1 rebuilds it per call: "
-                                 "0.06 ms narrow, 2.9 / 16 ms for the wide index of configs 3 / 5)"},
             "candidates_per_step": int(last["n_candidates"]),
-            "stage_ms": {k: round(v, 4) for k, v in avg.items()},
             "load_seconds": round(t_load, 1),
         }
-        # ---- roofline.  The contract's figure -- SURVEY.md section 8d's algorithmic bytes / launch time -- is kept as
-        # `algorithmic_GBps`, but it is not a fraction of anything for these kernels: the verify reads a from LDS and b
-        # from L2, compares a strand-mirror pair once and emits it twice.  Each kernel is priced instead against the
-        # four things it can saturate, with peaks MEASURED on this box (tools/ubench.hip, run live below):
-        #   hbm   bytes on the memory side of L2 (PMC FETCH_SIZE / WRITE_SIZE, profiles/traffic.json) vs 8 TB/s
-        #   l2    bytes the kernel loads from L2 vs the measured L2-hit rate of global_load_dwordx4
-        #   lds   bytes it reads from LDS vs the measured rate of random ds_read_b64
-        #   valu  VALU wave-instructions (PMC SQ_INSTS_VALU) vs the measured issue rate of 2-operand integer ops
-        # `bound` = the largest fraction; every fraction is <= 1 by construction.
-        bits = last["bits_per_base"]
-        scan_bytes = last["shard_bases"] * bits // 8
-        exec_bytes = last["verify_bytes_exec"]          # both sides of every VERIFIED CANDIDATE, once
-        sharded = "true" if world > 1 else "false"
-        # (kernel names as rocprofv3 prints them; the trailing `false` = not the streamed step's instantiation: the resident
-        # loop and the --pmc passes run whole-set launches)
-        scan_name = ("k_wide_scan<%d, false>" % bits) if last["wide_index"] else ("k_scan_probe<%d, true, false>" % bits)
-        ver_name = "k_verify_a<%d, %s, true, false>" % (bits, sharded)
-        peaks = measured_peaks() if world == 1 else {}
-        try:
-            with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-                tj = json.load(f) if not args.reads and world == 1 else {}
-        except (OSError, ValueError):
-            tj = {}
-        pmc_traffic = tj.get(args.config, {})
-        pmc_ctr = tj.get(args.config + "_counters", {})
-        try:   # the VALU model: cycles per instruction class (calibrated), static mix per kernel, padding sensitivity
-            with open(os.path.join(ROOT, "profiles", "r03_valu_model.json")) as f:
-                valu_model = json.load(f)["kernels"] if args.config == "cfg2" and world == 1 else {}
-        except (OSError, ValueError, KeyError):
-            valu_model = {}
-        positions = last["shard_bases"]                  # one filter lookup (8 B of LDS) per position of the scan
-        # (timed_region_sum_ms: summed over the pieces of a host-to-host step of the same form, taken with PHASM_PHASE_EVENTS=2
-        # in three extra steps right behind the timed loop -- the timed steps themselves record no per-kernel events)
-        # Launch durations: HIP events around the kernel in the RESIDENT loop (one whole-set launch per step, the same
-        # launches the rocprofv3 --pmc passes profile); inside the host-to-host region the same work runs as 4 chunk
-        # launches, whose summed duration is reported next to it (`timed_region_sum_ms`).
-        kern = {
-            scan_name: {"avg_launch_ms": avg_res["ms_scan_probe"], "timed_region_sum_ms": avg["ms_scan_probe"],
-                        "algorithmic_bytes_per_launch": int(scan_bytes),
-                        "l2_bytes": None if last["wide_index"] else int(scan_bytes),   # (+ the table groups, counted on the hbm side)
-                        "lds_bytes": None if last["wide_index"] else int(positions * 8)},
-            ver_name: {"avg_launch_ms": avg_res["ms_verify_kernel"], "timed_region_sum_ms": avg["ms_verify_kernel"],
-                       "algorithmic_bytes_per_launch": int(ver_bytes),
-                       "executed_compare_bytes": int(exec_bytes),
-                       "l2_bytes": int(exec_bytes // 2),             # the b side streams from L2 (locality order)
-                       "lds_bytes": int(exec_bytes // 2 * 5 // 4)},  # the a side: 5 dwords read per 4 compared
-        }
-        for name, v in kern.items():
-            t = v["avg_launch_ms"] * 1e-3
-            v["algorithmic_GBps"] = v["algorithmic_bytes_per_launch"] / t / 1e9 if t > 0 else 0.0
-            v["traffic"] = pmc_traffic.get(name)
-            lim = {}
-            if v["traffic"] and t > 0:
-                lim["hbm"] = {"GBps": v["traffic"] / t / 1e9, "peak_GBps": HBM_PEAK_GBS}
-            sp = tj.get(args.config + "_split", {}).get(name)
-            rl = peaks.get("random_lines_G_per_s") if isinstance(peaks, dict) else None
-            if sp and rl and t > 0:
-                # the scan's table probes that miss L2 are random 64-byte line requests (calibrated split of FETCH_SIZE,
-                # tools/pmc_to_traffic.py): priced against the rate this memory system gives such requests, measured above
-                # (the narrow table's misses are served by the Infinity Cache, the wide index's by HBM)
-                pk = rl["2048_MB"] if last["wide_index"] else rl["64_MB"]
-                lim["fabric_lines"] = {"G_lines_per_s": sp["random_64B_lines"] / t / 1e9, "peak_G_lines_per_s": pk,
-                                       "random_64B_lines_per_launch": sp["random_64B_lines"], "stream_bytes": sp["stream_bytes"]}
-                v["traffic_uncalibrated_2x_rule"] = sp.get("uncalibrated_2x_rule_bytes")
-            if v.get("l2_bytes") and peaks.get("l2_hit_TBps") and t > 0:
-                lim["l2"] = {"GBps": v["l2_bytes"] / t / 1e9, "peak_GBps": peaks["l2_hit_TBps"] * 1e3}
-            if v.get("lds_bytes") and peaks.get("lds_random_b64_TBps") and t > 0:
-                lim["lds"] = {"GBps": v["lds_bytes"] / t / 1e9, "peak_GBps": peaks["lds_random_b64_TBps"] * 1e3}
-            ctr = pmc_ctr.get(name, {})
-            vm = valu_model.get(name, {})
-            if ctr.get("SQ_INSTS_VALU") and ctr.get("SQ_BUSY_CU_CYCLES") and vm.get("static_mean_cycles_per_valu_inst"):
-                # VALU busy = instructions x their issue cost / SIMD-cycles of the launch.  The cost per instruction is the
-                # kernel's static mix priced with the cycles tools/valu_calib.py measured (2.15 for VOP1/VOP2 forms, 4.05 for
-                # VOP3 integer forms -- SQ_ACTIVE_INST_VALU turned out to count instructions, not cycles, so it cannot say).
-                # In units of G SIMD-cycles per second: the peak is every SIMD busy every cycle of the launch.
-                simd_cycles = 4.0 * ctr["SQ_BUSY_CU_CYCLES"]
-                busy_cycles = ctr["SQ_INSTS_VALU"] * vm["static_mean_cycles_per_valu_inst"]
-                lim["valu"] = {"G_simd_cycles_per_s": busy_cycles / t / 1e9, "peak_G_simd_cycles_per_s": simd_cycles / t / 1e9,
-                               "wave_insts_per_launch": ctr["SQ_INSTS_VALU"],
-                               "mean_cycles_per_inst_static_mix": vm["static_mean_cycles_per_valu_inst"],
-                               "sensitivity": vm.get("valu_sensitivity"),
-                               "sensitivity_note": "tools/pad_probe.sh: kernel cycles gained per full-rate VALU cycle added to the hot loop "
-                                                   "(1 = VALU issue is what the kernel waits for, 0 = the pipe had room)"}
-            for k2, x in lim.items():
-                ach = x.get("GBps", x.get("G_simd_cycles_per_s", x.get("G_lines_per_s")))
-                pk = x.get("peak_GBps", x.get("peak_G_simd_cycles_per_s", x.get("peak_G_lines_per_s")))
-                x["frac"] = ach / pk
-            v["limits"] = lim
-            if lim:
-                v["bound"] = max(lim, key=lambda k2: lim[k2]["frac"])
-                v["frac"] = lim[v["bound"]]["frac"]
-        dom = max(kern, key=lambda k: kern[k]["avg_launch_ms"])
-        d = kern[dom]
-        bl = d["limits"].get(d.get("bound", ""), {})
-        out["roofline"] = {"bound": d.get("bound"), "kernel": dom,
-                           "achieved": bl.get("GBps", bl.get("G_simd_cycles_per_s", bl.get("G_lines_per_s"))),
-                           "peak": bl.get("peak_GBps", bl.get("peak_G_simd_cycles_per_s", bl.get("peak_G_lines_per_s"))),
-                           "unit": ("G SIMD-cycles/s (VALU busy)" if d.get("bound") == "valu" else
-                                    "G random 64-B lines/s" if d.get("bound") == "fabric_lines" else "GB/s"),
-                           "valu_sensitivity": bl.get("sensitivity"),
-                           "frac": d.get("frac"), "traffic": d["traffic"],
-                           "hbm_frac": d["limits"].get("hbm", {}).get("frac"),
-                           "avg_launch_ms": d["avg_launch_ms"],
-                           "algorithmic_bytes_per_launch": d["algorithmic_bytes_per_launch"],
-                           "algorithmic_GBps": d["algorithmic_GBps"],
-                           "algorithmic_note": "SURVEY 8d bytes / launch time; above the HBM peak because a comes from LDS, b from L2, and a "
-                                               "strand-mirror pair is compared once and emitted twice -- not a roofline fraction",
-                           "measured_peaks": peaks,
-                           "pmc_source": "profiles/traffic.json (rocprofv3 --pmc passes, tools/collect_pmc.sh + tools/pmc_to_traffic.py) and "
-                                         "profiles/r03_valu_model.json (tools/valu_calib.py, tools/isa_mix.py, tools/pad_probe.sh): `traffic`, the VALU "
-                                         "instruction and CU-cycle counts and the VALU model are replayed from there, everything else is measured in this run",
-                           "kernels": kern,
-                           "job_algorithmic_bytes": int(job_bytes), "job_algorithmic_GBps": job_gbs}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if args.full:
+            out["resident"] = {"overlaps_per_sec": n_rows / (dt_res / K), "ms_per_step": dt_res / K * 1e3,
+                               "stage_ms": {k: round(v, 4) for k, v in avg_res.items()},
+                               "index_reused": int(last.get("index_reused", 0)),
+                               "note": "same step with the packed reads already in HBM and the rows left in HBM; index_reused = 1: the anchor index of the "
+                                       "unchanged upload is kept across these calls (ms_index is then the reset only; PHASM_NO_INDEX_REUSE=1 rebuilds it per call: "
+                                       "0.06 ms narrow, 2.9 / 16 ms for the wide index of configs 3 / 5)"}
+            out["stage_ms"] = {k: round(v, 4) for k, v in avg.items()}
+        if args.full:
+            # ---- roofline.  The contract's figure -- SURVEY.md section 8d's algorithmic bytes / launch time -- is kept as
+            # `algorithmic_GBps`, but it is not a fraction of anything for these kernels: the verify reads a from LDS and b
+            # from L2, compares a strand-mirror pair once and emits it twice.  Each kernel is priced instead against the
+            # four things it can saturate, with peaks MEASURED on this box (tools/ubench.hip, run live below):
+            #   hbm   bytes on the memory side of L2 (PMC FETCH_SIZE / WRITE_SIZE, profiles/traffic.json) vs 8 TB/s
+            #   l2    bytes the kernel loads from L2 vs the measured L2-hit rate of global_load_dwordx4
+            #   lds   bytes it reads from LDS vs the measured rate of random ds_read_b64
+            #   valu  VALU wave-instructions (PMC SQ_INSTS_VALU) vs the measured issue rate of 2-operand integer ops
+            # `bound` = the largest fraction; every fraction is <= 1 by construction.
+            bits = last["bits_per_base"]
+            scan_bytes = last["shard_bases"] * bits // 8
+            exec_bytes = last["verify_bytes_exec"]          # both sides of every VERIFIED CANDIDATE, once
+            sharded = "true" if world > 1 else "false"
+            # (kernel names as rocprofv3 prints them; the trailing `false` = not the streamed step's instantiation: the resident
+            # loop and the --pmc passes run whole-set launches)
+            scan_name = ("k_wide_scan<%d, false>" % bits) if last["wide_index"] else ("k_scan_probe<%d, true, false>" % bits)
+            ver_name = "k_verify_a<%d, %s, true, false>" % (bits, sharded)
+            peaks = measured_peaks() if world == 1 else {}
+            try:
+                with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                    tj = json.load(f) if not args.reads and world == 1 else {}
+            except (OSError, ValueError):
+                tj = {}
+            pmc_traffic = tj.get(args.config, {})
+            pmc_ctr = tj.get(args.config + "_counters", {})
+            try:   # the VALU model: cycles per instruction class (calibrated), static mix per kernel, padding sensitivity
+                with open(os.path.join(ROOT, "profiles", "r03_valu_model.json")) as f:
+                    valu_model = json.load(f)["kernels"] if args.config == "cfg2" and world == 1 else {}
+            except (OSError, ValueError, KeyError):
+                valu_model = {}
+            positions = last["shard_bases"]                  # one filter lookup (8 B of LDS) per position of the scan
+            # (timed_region_sum_ms: summed over the pieces of a host-to-host step of the same form, taken with PHASM_PHASE_EVENTS=2
+            # in three extra steps right behind the timed loop -- the timed steps themselves record no per-kernel events)
+            # Launch durations: HIP events around the kernel in the RESIDENT loop (one whole-set launch per step, the same
+            # launches the rocprofv3 --pmc passes profile); inside the host-to-host region the same work runs as 4 chunk
+            # launches, whose summed duration is reported next to it (`timed_region_sum_ms`).
+            kern = {
+                scan_name: {"avg_launch_ms": avg_res["ms_scan_probe"], "timed_region_sum_ms": avg["ms_scan_probe"],
+                            "algorithmic_bytes_per_launch": int(scan_bytes),
+                            "l2_bytes": None if last["wide_index"] else int(scan_bytes),   # (+ the table groups, counted on the hbm side)
+                            "lds_bytes": None if last["wide_index"] else int(positions * 8)},
+                ver_name: {"avg_launch_ms": avg_res["ms_verify_kernel"], "timed_region_sum_ms": avg["ms_verify_kernel"],
+                           "algorithmic_bytes_per_launch": int(ver_bytes),
+                           "executed_compare_bytes": int(exec_bytes),
+                           "l2_bytes": int(exec_bytes // 2),             # the b side streams from L2 (locality order)
+                           "lds_bytes": int(exec_bytes // 2 * 5 // 4)},  # the a side: 5 dwords read per 4 compared
+            }
+            for name, v in kern.items():
+                t = v["avg_launch_ms"] * 1e-3
+                v["algorithmic_GBps"] = v["algorithmic_bytes_per_launch"] / t / 1e9 if t > 0 else 0.0
+                v["traffic"] = pmc_traffic.get(name)
+                lim = {}
+                if v["traffic"] and t > 0:
+                    lim["hbm"] = {"GBps": v["traffic"] / t / 1e9, "peak_GBps": HBM_PEAK_GBS}
+                sp = tj.get(args.config + "_split", {}).get(name)
+                rl = peaks.get("random_lines_G_per_s") if isinstance(peaks, dict) else None
+                if sp and rl and t > 0:
+                    # the scan's table probes that miss L2 are random 64-byte line requests (calibrated split of FETCH_SIZE,
+                    # tools/pmc_to_traffic.py): priced against the rate this memory system gives such requests, measured above
+                    # (the narrow table's misses are served by the Infinity Cache, the wide index's by HBM)
+                    pk = rl["2048_MB"] if last["wide_index"] else rl["64_MB"]
+                    lim["fabric_lines"] = {"G_lines_per_s": sp["random_64B_lines"] / t / 1e9, "peak_G_lines_per_s": pk,
+                                           "random_64B_lines_per_launch": sp["random_64B_lines"], "stream_bytes": sp["stream_bytes"]}
+                    v["traffic_uncalibrated_2x_rule"] = sp.get("uncalibrated_2x_rule_bytes")
+                if v.get("l2_bytes") and peaks.get("l2_hit_TBps") and t > 0:
+                    lim["l2"] = {"GBps": v["l2_bytes"] / t / 1e9, "peak_GBps": peaks["l2_hit_TBps"] * 1e3}
+                if v.get("lds_bytes") and peaks.get("lds_random_b64_TBps") and t > 0:
+                    lim["lds"] = {"GBps": v["lds_bytes"] / t / 1e9, "peak_GBps": peaks["lds_random_b64_TBps"] * 1e3}
+                ctr = pmc_ctr.get(name, {})
+                vm = valu_model.get(name, {})
+                if ctr.get("SQ_INSTS_VALU") and ctr.get("SQ_BUSY_CU_CYCLES") and vm.get("static_mean_cycles_per_valu_inst"):
+                    # VALU busy = instructions x their issue cost / SIMD-cycles of the launch.  The cost per instruction is the
+                    # kernel's static mix priced with the cycles tools/valu_calib.py measured (2.15 for VOP1/VOP2 forms, 4.05 for
+                    # VOP3 integer forms -- SQ_ACTIVE_INST_VALU turned out to count instructions, not cycles, so it cannot say).
+                    # In units of G SIMD-cycles per second: the peak is every SIMD busy every cycle of the launch.
+                    simd_cycles = 4.0 * ctr["SQ_BUSY_CU_CYCLES"]
+                    busy_cycles = ctr["SQ_INSTS_VALU"] * vm["static_mean_cycles_per_valu_inst"]
+                    lim["valu"] = {"G_simd_cycles_per_s": busy_cycles / t / 1e9, "peak_G_simd_cycles_per_s": simd_cycles / t / 1e9,
+                                   "wave_insts_per_launch": ctr["SQ_INSTS_VALU"],
+                                   "mean_cycles_per_inst_static_mix": vm["static_mean_cycles_per_valu_inst"],
+                                   "sensitivity": vm.get("valu_sensitivity"),
+                                   "sensitivity_note": "tools/pad_probe.sh: kernel cycles gained per full-rate VALU cycle added to the hot loop "
+                                                       "(1 = VALU issue is what the kernel waits for, 0 = the pipe had room)"}
+                for k2, x in lim.items():
+                    ach = x.get("GBps", x.get("G_simd_cycles_per_s", x.get("G_lines_per_s")))
+                    pk = x.get("peak_GBps", x.get("peak_G_simd_cycles_per_s", x.get("peak_G_lines_per_s")))
+                    x["frac"] = ach / pk
+                v["limits"] = lim
+                if lim:
+                    v["bound"] = max(lim, key=lambda k2: lim[k2]["frac"])
+                    v["frac"] = lim[v["bound"]]["frac"]
+            dom = max(kern, key=lambda k: kern[k]["avg_launch_ms"])
+            d = kern[dom]
+            bl = d["limits"].get(d.get("bound", ""), {})
+            out["roofline"] = {"bound": d.get("bound"), "kernel": dom,
+                               "achieved": bl.get("GBps", bl.get("G_simd_cycles_per_s", bl.get("G_lines_per_s"))),
+                               "peak": bl.get("peak_GBps", bl.get("peak_G_simd_cycles_per_s", bl.get("peak_G_lines_per_s"))),
+                               "unit": ("G SIMD-cycles/s (VALU busy)" if d.get("bound") == "valu" else
+                                        "G random 64-B lines/s" if d.get("bound") == "fabric_lines" else "GB/s"),
+                               "valu_sensitivity": bl.get("sensitivity"),
+                               "frac": d.get("frac"), "traffic": d["traffic"],
+                               "hbm_frac": d["limits"].get("hbm", {}).get("frac"),
+                               "avg_launch_ms": d["avg_launch_ms"],
+                               "algorithmic_bytes_per_launch": d["algorithmic_bytes_per_launch"],
+                               "algorithmic_GBps": d["algorithmic_GBps"],
+                               "algorithmic_note": "SURVEY 8d bytes / launch time; above the HBM peak because a comes from LDS, b from L2, and a "
+                                                   "strand-mirror pair is compared once and emitted twice -- not a roofline fraction",
+                               "measured_peaks": peaks,
+                               "pmc_source": "profiles/traffic.json (rocprofv3 --pmc passes, tools/collect_pmc.sh + tools/pmc_to_traffic.py) and "
+                                             "profiles/r03_valu_model.json (tools/valu_calib.py, tools/isa_mix.py, tools/pad_probe.sh): `traffic`, the VALU "
+                                             "instruction and CU-cycle counts and the VALU model are replayed from there, everything else is measured in this run",
+                               "kernels": kern,
+                               "job_algorithmic_bytes": int(job_bytes), "job_algorithmic_GBps": job_gbs}
         if world == 1:
             h2d_bytes = float(last["upload_bytes"])   # (half the packed set when the odd reads are rebuilt on the device)
             d2h_bytes = 24.0 * n_rows
@@ -787,38 +845,39 @@ def main() -> int:
             if pcie.get("streamed_steps"):
                 out["pcie"]["kernels_plus_d2h_ms"] = None
                 out["pcie"]["after_upload_ms"] = dt / K * 1e3 - pcie["h2d_s"] / K * 1e3   # what is left of a step once the last piece has landed
-            if not args.no_tuples:
-                # what the reference API returns: a list of (id_a, id_b, astart, aend, bstart, bend) tuples
-                t1 = time.perf_counter()
-                tup = ov.overlaps(m)
-                dt_t = time.perf_counter() - t1
-                out["python_tuples"] = {"seconds": dt_t, "tuples": len(tup), "tuples_per_sec": len(tup) / dt_t,
-                                        "note": "ExactOverlapper.overlaps(): one step + building the list of Python tuples"}
-                del tup
-            out["roofline"]["hbm_copy_measured"] = measured_hbm_gbs(device)   # GB/s of a d2d copy on this box
-            out["layout_stage1"] = layout_leg(ov, m, not args.no_cpu_baseline)
-            if not args.no_cold:
-                cc = cold_call_leg(dev_idx, oriented_once, m)
-                out["cold_call_ms"] = cc["cold_call_ms"]
-                out["cold_call"] = cc
-                out["cold_over_steady"] = cc["cold_call_ms"] / ms_step
-            if cli_leg is not None:
-                out["cli_overlap_seconds"] = cli_leg.get("cli_overlap_seconds")
-                out["cli_overlap"] = cli_leg
-            if not args.no_cfg4 and not args.reads:
-                out["cfg4_extension"] = cfg4_leg(dev_idx, m, 400, 8)
-            if not args.no_cpu_baseline:
-                out["cpu_baseline"] = cpu_baseline(m, args.cpu_sample_reads)
-            if args.other_configs and not args.reads:
-                # (last: the headline's handle is closed first so that the big configs have the GPU's memory to themselves)
-                ov.close()
-                del oriented_once
-                out["other_configs"] = {}
-                for name in [x.strip() for x in args.other_configs.split(",") if x.strip()]:
-                    try:
-                        out["other_configs"][name] = other_config_leg(dev_idx, name, m)
-                    except Exception as e:  # noqa: BLE001 -- the headline line must come out
-                        out["other_configs"][name] = {"error": repr(e)}
+            if args.full:
+                if not args.no_tuples:
+                    # what the reference API returns: a list of (id_a, id_b, astart, aend, bstart, bend) tuples
+                    t1 = time.perf_counter()
+                    tup = ov.overlaps(m)
+                    dt_t = time.perf_counter() - t1
+                    out["python_tuples"] = {"seconds": dt_t, "tuples": len(tup), "tuples_per_sec": len(tup) / dt_t,
+                                            "note": "ExactOverlapper.overlaps(): one step + building the list of Python tuples"}
+                    del tup
+                out["roofline"]["hbm_copy_measured"] = measured_hbm_gbs(device)   # GB/s of a d2d copy on this box
+                out["layout_stage1"] = layout_leg(ov, m, not args.no_cpu_baseline)
+                if not args.no_cold:
+                    cc = cold_call_leg(dev_idx, oriented_once, m)
+                    out["cold_call_ms"] = cc["cold_call_ms"]
+                    out["cold_call"] = cc
+                    out["cold_over_steady"] = cc["cold_call_ms"] / ms_step
+                if cli_leg is not None:
+                    out["cli_overlap_seconds"] = cli_leg.get("cli_overlap_seconds")
+                    out["cli_overlap"] = cli_leg
+                if not args.no_cfg4 and not args.reads:
+                    out["cfg4_extension"] = cfg4_leg(dev_idx, m, 400, 8)
+                if not args.no_cpu_baseline:
+                    out["cpu_baseline"] = cpu_baseline(m, args.cpu_sample_reads)
+                if args.other_configs and not args.reads:
+                    # (last: the headline's handle is closed first so that the big configs have the GPU's memory to themselves)
+                    ov.close()
+                    del oriented_once
+                    out["other_configs"] = {}
+                    for name in [x.strip() for x in args.other_configs.split(",") if x.strip()]:
+                        try:
+                            out["other_configs"][name] = other_config_leg(dev_idx, name, m)
+                        except Exception as e:  # noqa: BLE001 -- the headline line must come out
+                            out["other_configs"][name] = {"error": repr(e)}
     if world > 1 or args.dist_path:
         dist.barrier()
         dist.destroy_process_group()

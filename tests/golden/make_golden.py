@@ -18,6 +18,8 @@ Fixtures
                       "longest only" rule and many occurrences per pair
   ladder_*.npz        seeded synthetic read sets (phasm_amd.synth), both strands added as the
                       CLI does (assembler.py:38-40)
+  fresh_*.npz         two more synthetic sets in the ladder's format (golden_utils.FRESH_CASES)
+  live_random.npz     golden_utils.random_small_inputs(): 60 seeded random small read sets
 """
 import hashlib
 import json
@@ -32,6 +34,9 @@ sys.path.insert(0, ROOT)
 
 from oracle import overlap_oracle as oo  # noqa: E402
 from phasm_amd import synth  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(HERE))
+import golden_utils as gu  # noqa: E402
 
 
 def ref_rows(seqs, m):
@@ -178,8 +183,8 @@ def ladder_reads(cfg):
     return [s for _, s in synth.oriented(synth.generate_reads(cfg))]
 
 
-def ladder(only=None):
-    for name, (cfg, m) in LADDER.items():
+def ladder(only=None, cases=None):
+    for name, (cfg, m) in (cases or LADDER).items():
         if only and name not in only:
             continue
         seqs = ladder_reads(cfg)
@@ -191,11 +196,28 @@ def ladder(only=None):
         print(name, "oriented reads", len(seqs), "rows", len(rows), "ref %.1fs" % secs)
 
 
+def fresh_fixtures():
+    ladder(cases={name: gu.fresh_config(name) for name in gu.FRESH_CASES})
+
+
+def random_fixture(n_cases=60, seed=99):
+    out = {"n_cases": np.array(n_cases), "seed": np.array(seed)}
+    for t, (reads, m) in enumerate(gu.random_small_inputs(n_cases, seed)):
+        out["rows_%d" % t] = ref_rows(reads, m).astype(np.int32)
+        out["sha256_%d" % t] = np.array(sha(reads))
+        out["min_length_%d" % t] = np.array(m)
+    np.savez_compressed(os.path.join(HERE, "live_random.npz"), **out)
+    print("live_random.npz rows:", sum(len(v) for k, v in out.items() if k.startswith("rows_")))
+
+
 def main():
     if not oo.have_reference():
         sys.exit("oracle/_ref/ref_overlapper missing: run `make -C oracle ref` first")
-    if len(sys.argv) > 1:   # only the named ladder cases (the others are left as committed)
+    if len(sys.argv) > 1:   # only the named ladder / fresh cases, or "live_random" (the others are left as committed)
         ladder(set(sys.argv[1:]))
+        ladder(set(sys.argv[1:]), {name: gu.fresh_config(name) for name in gu.FRESH_CASES})
+        if "live_random" in sys.argv[1:]:
+            random_fixture()
         return
     with open(os.path.join(HERE, "toy_cases.json"), "w") as f:
         json.dump(toy_cases(), f, indent=0)
@@ -205,6 +227,8 @@ def main():
     print("adversarial rows:", sum(len(c["rows"]) for c in adv))
     repeats_fixture()
     ladder()
+    fresh_fixtures()
+    random_fixture()
 
 
 if __name__ == "__main__":

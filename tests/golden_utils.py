@@ -57,3 +57,47 @@ def ladder_case(name):
 
 def all_small_cases():
     return json_cases("toy_cases.json") + json_cases("adversarial.json")
+
+
+def random_small_inputs(n_cases=60, seed=99):
+    """Seeded random read sets (substrings of a random genome, half of them with their reverse complement) and a
+    min_length each: the inputs of live_random.npz."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n_cases):
+        glen = int(rng.integers(50, 400))
+        genome = bytes(b"ACGT"[i] for i in rng.integers(0, 4, size=glen))
+        reads = []
+        for _ in range(int(rng.integers(2, 30))):
+            ln = int(rng.integers(1, min(120, glen)))
+            st = int(rng.integers(0, glen - ln + 1))
+            r = genome[st:st + ln]
+            reads.append(r)
+            if rng.random() < 0.5:
+                reads.append(r.translate(bytes.maketrans(b"ACGT", b"TGCA"))[::-1])
+        out.append((reads, int(rng.integers(1, 40))))
+    return out
+
+
+def random_small_cases():
+    """random_small_inputs() with the reference's rows for each (tests/golden/live_random.npz)."""
+    z = np.load(os.path.join(GOLDEN, "live_random.npz"))
+    cases = []
+    for t, (reads, m) in enumerate(random_small_inputs(int(z["n_cases"]), int(z["seed"]))):
+        assert sha(reads) == str(z["sha256_%d" % t]) and m == int(z["min_length_%d" % t]), "random inputs drifted from the golden"
+        cases.append(("random%d" % t, reads, m, _rows(z["rows_%d" % t])))
+    return cases
+
+
+# read sets the ladder does not cover: config-2 density on a seed of its own, and a variable-length diploid set with
+# containments (stored in the ladder's format, loaded with ladder_case)
+FRESH_CASES = {
+    "fresh_cfg2_700": (dict(synth.scaled(synth.CONFIGS["cfg2"], 700).__dict__, seed=4242), 1000),
+    "fresh_varlen_500": (dict(n_reads=500, read_len=6000, genome_len=150_000, ploidy=2, snp=0.004, seed=909,
+                              len_sd=2500.0, len_min=800, len_max=15000), 600),
+}
+
+
+def fresh_config(name):
+    kw, m = FRESH_CASES[name]
+    return synth.SynthConfig(**kw), m

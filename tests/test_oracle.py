@@ -1,6 +1,6 @@
 """The oracle is pinned here: both CPU restatements must reproduce every golden vector that
 was produced by the compiled reference (tests/golden/make_golden.py), and -- where the
-reference binary is present (build container) -- agree with it live on fresh random cases."""
+reference binary is present -- agree with it live on the seeded random cases as well."""
 import numpy as np
 import pytest
 
@@ -64,23 +64,16 @@ def test_strand_mirror_closure_on_golden():
     assert np.array_equal(oo.sort_rows(mirrored), rows)
 
 
-@pytest.mark.skipif(not oo.have_reference(), reason="oracle/_ref not built (needs /root/reference)")
 def test_c_oracle_matches_live_reference_random():
-    rng = np.random.default_rng(99)
-    for t in range(60):
-        glen = int(rng.integers(50, 400))
-        genome = bytes(b"ACGT"[i] for i in rng.integers(0, 4, size=glen))
-        reads = []
-        for _ in range(int(rng.integers(2, 30))):
-            ln = int(rng.integers(1, min(120, glen)))
-            st = int(rng.integers(0, glen - ln + 1))
-            r = genome[st:st + ln]
-            reads.append(r)
-            if rng.random() < 0.5:
-                reads.append(r.translate(bytes.maketrans(b"ACGT", b"TGCA"))[::-1])
-        m = int(rng.integers(1, 40))
-        want, _, _ = oo.reference_overlaps(reads, m)
-        assert np.array_equal(oo.oracle_overlaps(reads, m), want), t
+    """60 seeded random cases against the reference's rows (tests/golden/live_random.npz), and against the compiled
+    reference itself where oracle/_ref has been built."""
+    live = oo.have_reference()
+    cases = gu.random_small_cases()
+    assert len(cases) == 60
+    for name, reads, m, want in cases:
+        assert np.array_equal(oo.oracle_overlaps(reads, m), want), name
+        if live:
+            assert np.array_equal(oo.reference_overlaps(reads, m)[0], want), name
 
 
 def test_extension_oracle_with_zero_differences_is_the_exact_contract():
