@@ -4,8 +4,9 @@ Counterpart of ``overlap(args)`` in the reference CLI (/root/reference/phasm/cli
 parser at :436-452): same positional FASTA argument, ``-l/--min-length`` (default 1000),
 ``-o/--output`` (default stdout), and byte-identical ``H`` / ``S`` / ``E`` lines for identical
 rows -- all ``S`` lines first, then the ``E`` lines.  Row order differs from the reference
-(whose order is an artefact of ``std::unordered_map`` iteration, overlapper.cpp:30,:68): here
-rows are a-major in FASTA order, then by start position.
+(whose order is an artefact of ``std::unordered_map`` iteration, overlapper.cpp:30,:68) and is
+not specified here either: the ``E`` lines come in the order the device emits the rows, which
+depends on the path a call takes (strand-paired 2-bit reads, 8-bit reads, pieces).
 
     python -m phasm_amd.cli overlap reads.fasta -l 1000 -o overlaps.gfa
 

@@ -264,6 +264,10 @@ try:
     rx = ReadExchange(ov)
     assert rx.upload(parts=3) is True and rx.n_collectives == 3     # each rank uploaded its share in three parts, the rest came over the wire
     assert rx.upload() is True                                      # (default: one part for a piece this small)
+    os.environ["PHASM_UPLOAD_PARTS"] = "2"                          # the part count asked for by the environment
+    rx2 = ReadExchange(ov)
+    assert rx2.upload() is True and rx2.n_collectives == 2
+    del os.environ["PHASM_UPLOAD_PARTS"]
     ex = CandidateExchange(ov, device=torch.device("cpu"))          # gloo carries the collectives, one GPU runs both ranks
     for step in range(2):
         res = ex.rows(m)
