@@ -283,20 +283,6 @@ struct po_handle {
     // beside whatever the handle's stream is doing for the piece before: ev_rc[k] = piece k is complete, both strands
     hipStream_t rc_stream = nullptr;
     hipEvent_t ev_rc[PO_MAX_PIECES] = {};
-    // Two-stream pieces (round 4): with the rows going home as records the streamed step is paced by the DEVICE, and a piece
-    // is two halves that need different things -- the counting pass (k_scan_probe, k_scan_fixup, the tile prefix sum) needs
-    // the piece's own reads and the index, everything behind it (fill, locality order, verify, select, tail) the candidate
-    // buffers.  The counting pass of piece k + 1 runs on scan_stream beside the second half of piece k on the handle's
-    // stream: ev_s1[k & 1] = piece k's counting pass is done; the small per-piece state both halves touch (scalars,
-    // tile offsets) exists twice, by the piece's parity.
-    hipStream_t scan_stream = nullptr;
-    hipEvent_t ev_s1[2] = {};
-    hipEvent_t ev_idx = nullptr;     // the step's index (and everything queued before it on the handle's stream) is complete
-    int two_stream = 0;              // this streamed step runs its pieces that way: 1 = on scan_stream; 2 = on rc_stream, and the
-                                     // counting pass of piece k + 1 does not start before the verify kernel of piece k has
-    hipEvent_t ev_gate[2] = {};      // (ev_gate[k & 1]: recorded on the handle's stream right in front of piece k's verify kernel)
-    int want_two = 0;                // what the step asked for (stream_begin queues no reverse complements up front for 2)
-    uint32_t st_k = 0;               // the piece run_overlaps is working on (its event in ev_rc)
     hipEvent_t ev_meta = nullptr;
     hipEvent_t ev_first = nullptr;   // the first words of the later pieces are in place
     // first two packed words of every read, appended as the reads are added (registered memory: the streamed step sends
@@ -510,7 +496,6 @@ void quiesce_store(po_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     if (h->rc_stream) (void)hipStreamSynchronize(h->rc_stream);
-    if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
 }
 
 // Pinned result pool, sized WHILE THE READS ARE ADDED.  A fresh 170 MB page-locked array costs 8 ms (hipHostMalloc maps
@@ -581,8 +566,7 @@ void result_pool_grow(po_handle* h, uint64_t bases = 0) {
 // buys nothing, and ~1 ms of a fresh handle's first call.  A kit is idle when it is put back (every stream synchronised).
 struct DevKit {
     int device = -1;
-    hipStream_t stream = nullptr, copy_stream = nullptr, up_stream = nullptr, rc_stream = nullptr, scan_stream = nullptr;
-    hipEvent_t ev_s1[2] = {}, ev_idx = nullptr;
+    hipStream_t stream = nullptr, copy_stream = nullptr, up_stream = nullptr, rc_stream = nullptr;
     hipEvent_t ev_sets[2][EV_N] = {};
     hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr, ev_meta = nullptr, ev_first = nullptr;
     hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[4] = {};
@@ -604,10 +588,6 @@ bool kit_take(po_handle* h) {
         h->copy_stream = k.copy_stream;
         h->up_stream = k.up_stream;
         h->rc_stream = k.rc_stream;
-        h->scan_stream = k.scan_stream;
-        h->ev_s1[0] = k.ev_s1[0];
-        h->ev_s1[1] = k.ev_s1[1];
-        h->ev_idx = k.ev_idx;
         std::memcpy(h->ev_sets, k.ev_sets, sizeof(k.ev_sets));
         h->ev_up0 = k.ev_up0;
         h->ev_up1 = k.ev_up1;
@@ -627,8 +607,7 @@ bool kit_take(po_handle* h) {
 bool kit_give(po_handle* h) {
     if (getenv("PHASM_NO_KIT_POOL") || !h->stream || !h->copy_stream || !h->up_stream || !h->rc_stream || !h->pinned) return false;
     if (hipStreamSynchronize(h->stream) != hipSuccess || hipStreamSynchronize(h->copy_stream) != hipSuccess ||
-        hipStreamSynchronize(h->up_stream) != hipSuccess || hipStreamSynchronize(h->rc_stream) != hipSuccess ||
-        (h->scan_stream && hipStreamSynchronize(h->scan_stream) != hipSuccess)) {
+        hipStreamSynchronize(h->up_stream) != hipSuccess || hipStreamSynchronize(h->rc_stream) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
@@ -638,10 +617,6 @@ bool kit_give(po_handle* h) {
     k.copy_stream = h->copy_stream;
     k.up_stream = h->up_stream;
     k.rc_stream = h->rc_stream;
-    k.scan_stream = h->scan_stream;
-    k.ev_s1[0] = h->ev_s1[0];
-    k.ev_s1[1] = h->ev_s1[1];
-    k.ev_idx = h->ev_idx;
     std::memcpy(k.ev_sets, h->ev_sets, sizeof(k.ev_sets));
     k.ev_up0 = h->ev_up0;
     k.ev_up1 = h->ev_up1;
@@ -715,12 +690,9 @@ struct Job {
     // hipEventQuery takes the runtime's locks on every call).  flag == nullptr: the records are there already.
     const volatile uint32_t* flag = nullptr;
     uint32_t want = 0;
-    // A piece may arrive in several copies (the LAST piece of a step does: its rows are what the call ends with, and its
-    // first part is expanded while the rest is still crossing PCIe).  A part knows its rows only when the pool has counted
-    // them: cont = this part's rows start where the previous part's ended; n_rows = 0 for every part but the last, which
-    // carries the piece's total for the check.
-    bool cont = false;
-    bool more = false;               // further parts of the same piece follow
+    // the read set's form: strand-mirror pairs (rows_of_rec), bits per base (the byte counters).  Per job, so that the
+    // caller never writes state the threads may still be reading for the piece before
+    uint32_t paired = 0, bits = 2;
 };
 
 struct Pool {
@@ -734,13 +706,11 @@ struct Pool {
     std::atomic<int> error{0};       // 1: counts disagree, 2: a record names an unknown read
     // the call's read set
     const uint32_t* len = nullptr;
-    uint32_t n_reads = 0, paired = 0, bits = 2;
+    uint32_t n_reads = 0;
     // byte counters of po_stats over the call's records (k_emit / k_tail sum them on the device for rows emitted there)
     std::atomic<uint64_t> sum_l{0}, sum_b{0}, sum_e{0};
     // the piece being expanded
     Job cur;
-    po_row* part_next = nullptr;     // where the next part of the current piece starts
-    uint64_t part_rows = 0;          // rows of the piece's parts so far
     uint64_t job_seq = 0;            // (under mu) pieces published so far
     uint32_t n_chunks = 0;
     std::vector<uint64_t> chunk_off;
@@ -800,7 +770,7 @@ bool expand_records(Pool& P, uint64_t lo, uint64_t hi, po_row* out) {
     uint64_t* o = reinterpret_cast<uint64_t*>(out);
     const Job& job = P.cur;
     const uint32_t* len = P.len;
-    const uint32_t paired = P.paired, n_reads = P.n_reads, bits = P.bits;
+    const uint32_t paired = job.paired, n_reads = P.n_reads, bits = job.bits;
     auto pb = [bits](uint32_t l) -> uint64_t { return bits == 8u ? l : (l >> 2) + ((l & 3u) != 0u); };
     uint64_t sl = 0, sb = 0, se = 0;
     for (uint64_t i = lo; i < hi; ++i) {
@@ -840,7 +810,7 @@ void run_phases(Pool& P, bool lead) {
         if (c >= nc) break;
         const uint64_t lo = (uint64_t)c * CHUNK, hi = std::min<uint64_t>(P.cur.n_rec, lo + CHUNK);
         uint64_t n = 0;
-        const uint32_t paired = P.paired;
+        const uint32_t paired = P.cur.paired;
         for (uint64_t i = lo; i < hi; ++i) n += rows_of_rec(load_rec(P.cur, i), paired);
         P.chunk_off[c + 1] = n;
         P.done_count.fetch_add(1, std::memory_order_release);
@@ -849,9 +819,7 @@ void run_phases(Pool& P, bool lead) {
         spin_until([&] { return P.done_count.load(std::memory_order_acquire) >= nc; });
         P.chunk_off[0] = 0;
         for (uint32_t c = 0; c < nc; ++c) P.chunk_off[c + 1] += P.chunk_off[c];
-        P.part_rows += P.chunk_off[nc];
-        if (!P.cur.more && P.part_rows != P.cur.n_rows) P.error.store(1);   // (the device counted differently: nothing is written)
-        P.part_next = P.cur.out + P.chunk_off[nc];
+        if (P.chunk_off[nc] != P.cur.n_rows) P.error.store(1);   // (the device counted differently: nothing is written)
         P.phase.store(P.error.load() ? 0 : 2, std::memory_order_release);
     } else {
         spin_until([&] { return P.phase.load(std::memory_order_acquire) != 1; });
@@ -901,8 +869,6 @@ void leader(Pool* Pp) {
         if (P.error.load() == 0 && j.n_rec) {
             // (no helper is inside the previous piece's loops any more: the counters may be reset)
             spin_until([&] { return P.inside.load(std::memory_order_acquire) == 0; });
-            if (j.cont) j.out = P.part_next;
-            else P.part_rows = 0;
             P.cur = j;
             P.n_chunks = (uint32_t)((j.n_rec + CHUNK - 1) / CHUNK);
             if (P.chunk_off.size() < (size_t)P.n_chunks + 1) P.chunk_off.resize((size_t)P.n_chunks + 1);
@@ -961,7 +927,6 @@ void begin(Pool* P, const uint32_t* len, uint32_t n_reads, bool tracing) {
     else g_spin_limit.store(4096);
     P->len = len;
     P->n_reads = n_reads;
-    P->paired = 0;
     P->error.store(0);
     P->submitted.store(0);
     P->finished.store(0);
@@ -1038,11 +1003,8 @@ po_status init_device(po_handle* h) {
     HIP_TRY(h, hipStreamCreateWithFlags(&h->rc_stream, hipStreamNonBlocking));
     // (four streams = the runtime's four hardware queues, one each.  A fifth stream shares a queue with one of these, and
     // whatever it launches waits behind everything queued there -- rc_stream's kernels are all queued up front behind the
-    // pieces' arrival events: profiles/r04_two_stream.txt.  The opt-in two-stream pieces make theirs when first asked for.)
+    // pieces' arrival events: profiles/r04_two_stream.txt.)
     imark("other streams made");
-    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_s1[0], hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_s1[1], hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_idx, hipEventDisableTiming));
     for (int k = 0; k < PO_MAX_PIECES; ++k) {
         HIP_TRY(h, hipEventCreate(&h->ev_piece[k]));
         HIP_TRY(h, hipEventCreateWithFlags(&h->ev_rc[k], hipEventDisableTiming));
@@ -1067,13 +1029,11 @@ po_status init_device(po_handle* h) {
             hipLaunchKernelGGL(po::k_fill_u32, dim3(1), dim3(64), 0, h->up_stream, wd + 8, (uint64_t)1, 0u);
             (void)hipMemcpyAsync(wd + 16, h->pinned + 62, 8, hipMemcpyHostToDevice, h->stream);
             hipLaunchKernelGGL(po::k_fill_u32, dim3(1), dim3(64), 0, h->rc_stream, wd + 24, (uint64_t)1, 0u);
-            if (h->scan_stream) hipLaunchKernelGGL(po::k_fill_u32, dim3(1), dim3(64), 0, h->scan_stream, wd + 40, (uint64_t)1, 0u);
             hipLaunchKernelGGL(po::k_fill_u32, dim3(1), dim3(64), 0, h->copy_stream, wd + 32, (uint64_t)1, 0u);
             (void)hipMemcpyAsync(h->pinned + 61, wd + 32, 8, hipMemcpyDeviceToHost, h->copy_stream);
             (void)hipMemcpyAsync(h->pinned + 60, wd + 16, 8, hipMemcpyDeviceToHost, h->stream);
             (void)hipStreamSynchronize(h->up_stream);
             (void)hipStreamSynchronize(h->rc_stream);
-            if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
             (void)hipStreamSynchronize(h->copy_stream);
             (void)hipStreamSynchronize(h->stream);
             (void)hipFree(w);
@@ -1725,12 +1685,6 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     const uint32_t paired = (BITS == 2 && h->paired && dpE == 0) ? (streamed ? po::PAIRED_STREAM_ALL : nshards > 1 ? 2u : 1u) : 0u;
     const uint32_t paired_ver = streamed ? po::paired_stream(h->st_r_end) : paired;
     if (streamed && (!paired || want_cands)) return fail(h, PO_ERR_INVALID, "streamed step without strand pairs");
-    // two-stream pieces (po_handle::scan_stream): the counting pass of this piece runs on s1, beside the second half of the
-    // piece before it on st
-    const bool two = streamed && h->two_stream && !h->idx_only;
-    const bool gated = two && h->two_stream == 2;
-    bool gate_recorded = false;
-    const hipStream_t s1 = two ? (gated ? h->rc_stream : h->scan_stream) : st;
     S.paired = paired ? 1u : 0u;
     S.max_diff = dpE;
     S.band = dpW;
@@ -1847,8 +1801,8 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     uint32_t* chain = h->d_chain.as<uint32_t>();
     uint32_t* bloom = h->d_bloom.as<uint32_t>();
     uint32_t* selfrep = h->d_selfrep.as<uint32_t>();
-    // The small state both halves of a piece touch exists twice, by the piece's parity: while the second half of piece k reads
-    // its candidate count and tile offsets, the counting pass of piece k + 1 writes its own (two-stream pieces, see po_handle)
+    // the small per-piece state (candidate count, emit counters, tile offsets) exists twice, by the piece's parity, like the
+    // piece's slots of the landing zone (`zone`, below)
     const uint32_t parity = streamed ? (shard & 1u) : 0u;
     unsigned long long* scalars = h->d_scalars.as<unsigned long long>() + 8 * parity;  // [0] scan total, [1] n_long, [3] rows, [4..7] emit counters
     uint32_t* const tile_off_p = h->d_tile_off.as<uint32_t>() + (size_t)parity * ((size_t)h->n_tiles + 2);
@@ -1883,7 +1837,7 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     const bool fold_clear = reuse_index && !wide;
     if (fold_clear) {
     } else if (reuse_index || ext_idx) {
-        hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(n, 16u), 256)), dim3(256), 0, s1, selfrep, n, scalars, 8u,
+        hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(n, 16u), 256)), dim3(256), 0, st, selfrep, n, scalars, 8u,
                            (uint32_t*)nullptr, 0u, (uint32_t*)nullptr, 0u);
     } else {
         const uint32_t bloom_words = (uint32_t)(bloom_bytes / 4);
@@ -1949,7 +1903,6 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     if (h->idx_only) {
         // (streamed step: the index is built from the first words of every read while piece 0 is still on the wire; the
         // pieces find it valid -- same upload, min_length, flavour -- and reuse it)
-        if (h->ev_idx) HIP_TRY(h, hipEventRecord(h->ev_idx, st));
         h->idx_valid = true;
         h->idx_gen = h->upload_gen;
         h->idx_m = m;
@@ -1967,31 +1920,6 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     h->idx_bits = (uint32_t)BITS;
     h->idx_ww = ww;
 
-    if (two) {
-        // the counting pass needs the index (and the per-read tables and tiles queued before it), this piece's reads with their
-        // reverse complements, and the parity's small state free again: the second half of the piece two before this one
-        HIP_TRY(h, hipStreamWaitEvent(s1, h->ev_idx, 0));
-        if (gated) {
-            // (this stream IS the one that writes the odd reads: piece k's reverse complements are queued here, in front of
-            // its counting pass, not all up front -- a stream's commands run in order, and the pass of piece k must not sit
-            // behind the reverse complements of pieces that have not landed)
-            const uint32_t p0 = r_begin / 2, p1 = r_end / 2;
-            HIP_TRY(h, hipStreamWaitEvent(s1, h->ev_piece[h->st_k], 0));
-            if (p1 > p0)
-                hipLaunchKernelGGL(po::k_revcomp_store, dim3(cdiv((uint64_t)(p1 - p0) * 64, 256)), dim3(256), 0, s1, h->d_words.as<uint64_t>(),
-                                   h->d_woff.as<uint64_t>(), h->d_len.as<uint32_t>(), p0, p1,
-                                   h->n_exc_uploaded ? h->d_exc_off.as<uint32_t>() : nullptr, h->d_exc_pos.as<uint32_t>());
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipEventRecord(h->ev_rc[h->st_k], s1));
-            // ... and the pass starts when the verify kernel of the piece before does: its one persistent workgroup per CU
-            // needs a whole CU, so it moves in as the verify workgroups drain -- the tail of one big kernel under the start
-            // of the next -- instead of taking the chip away from the small kernels in front of that verify kernel
-            if (h->st_k >= 1) HIP_TRY(h, hipStreamWaitEvent(s1, h->ev_gate[(h->st_k - 1) & 1], 0));
-        } else {
-            HIP_TRY(h, hipStreamWaitEvent(s1, h->ev_rc[h->st_k], 0));
-        }
-        if (h->st_k >= 2) HIP_TRY(h, hipStreamWaitEvent(s1, h->ev[EV_DONE], 0));
-    }
     // ---- scan, counting pass
     po::ScanArgs A = {};
     A.words = words;
@@ -2043,11 +1971,11 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     WA.lane_slot = A.truemask;
     WA.tile_off = A.tile_off;
     if (wide) {
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], s1));
+        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], st));
         auto wscan = streamed ? (ww == 4 ? po::k_wide_scan<BITS, false, BITS == 2, 4> : po::k_wide_scan<BITS, false, BITS == 2, 1>)
                      : ww == 16 ? po::k_wide_scan<BITS, false, false, 16> : ww == 4 ? po::k_wide_scan<BITS, false, false, 4> : po::k_wide_scan<BITS, false, false, 1>;
-        hipLaunchKernelGGL(wscan, dim3(cdiv(ntiles, 4)), dim3(256), 0, s1, WA, po::CandGuard{nullptr, 0u});
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], s1));
+        hipLaunchKernelGGL(wscan, dim3(cdiv(ntiles, 4)), dim3(256), 0, st, WA, po::CandGuard{nullptr, 0u});
+        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], st));
     } else {
         const size_t scan_lds = (size_t)scan_waves * po::SCAN_LDS_PER_WAVE + bloom_bytes;
         if (scan_lds > h->lds_max) return fail(h, PO_ERR_HIP, "device LDS too small for the scan kernel");
@@ -2069,26 +1997,26 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
         } else if (fold_clear) {
             const uint32_t te0 = self_clean ? 0u : tile_begin, ten = self_clean ? h->n_tiles : ntiles;
             // (a self-cleaning step's first piece zeroes both parities' scalars; any other reset only its own block)
-            hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(std::max(n, 16u), std::max(n_scan_waves, ten)), 256)), dim3(256), 0, s1,
+            hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(std::max(n, 16u), std::max(n_scan_waves, ten)), 256)), dim3(256), 0, st,
                                selfrep, n, self_clean ? h->d_scalars.as<unsigned long long>() : scalars, self_clean ? 16u : 8u,
                                h->d_left_cnt.as<uint32_t>(), n_scan_waves, h->d_tile_extra.as<uint32_t>() + te0, ten);
         } else {
-            HIP_TRY(h, hipMemsetAsync(h->d_left_cnt.p, 0, (size_t)n_scan_waves * 4, s1));
-            HIP_TRY(h, hipMemsetAsync(h->d_tile_extra.as<uint32_t>() + tile_begin, 0, (size_t)ntiles * 4, s1));
+            HIP_TRY(h, hipMemsetAsync(h->d_left_cnt.p, 0, (size_t)n_scan_waves * 4, st));
+            HIP_TRY(h, hipMemsetAsync(h->d_tile_extra.as<uint32_t>() + tile_begin, 0, (size_t)ntiles * 4, st));
         }
         A.left = h->d_left.as<uint2>();
         A.left_cnt = h->d_left_cnt.as<uint32_t>();
         A.tile_extra = h->d_tile_extra.as<uint32_t>();
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], s1));
-        hipLaunchKernelGGL(K == W ? probe_full : probe_part, dim3(scan_grid), dim3(scan_waves * 64), scan_lds, s1, A);
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], s1));
+        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], st));
+        hipLaunchKernelGGL(K == W ? probe_full : probe_part, dim3(scan_grid), dim3(scan_waves * 64), scan_lds, st, A);
+        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], st));
         auto fixup = streamed ? po::k_scan_fixup<BITS, CAN_STREAM> : po::k_scan_fixup<BITS, false>;
-        hipLaunchKernelGGL(fixup, dim3(n_scan_waves), dim3(256), 0, s1, A, n_scan_waves, self_clean ? 1u : 0u);
+        hipLaunchKernelGGL(fixup, dim3(n_scan_waves), dim3(256), 0, st, A, n_scan_waves, self_clean ? 1u : 0u);
         // (the leftover counts, tile_extra, are added to the tile counts by the prefix sum below)
         if (getenv("PHASM_DEBUG_LEFT")) {  // how many positions did the scan waves defer to k_scan_fixup?
             PO_TRY(ensure_host(h, h->scratch_host, (size_t)n_scan_waves * 4));
-            HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_left_cnt.p, (size_t)n_scan_waves * 4, hipMemcpyDeviceToHost, s1));
-            HIP_TRY(h, hipStreamSynchronize(s1));
+            HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_left_cnt.p, (size_t)n_scan_waves * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
             const uint32_t* lc = static_cast<const uint32_t*>(h->scratch_host.p);
             uint64_t sum = 0;
             uint32_t mx = 0;
@@ -2124,7 +2052,6 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
         const uint64_t worst = cap * 4u;
         bool order = pred >= 400000 && (r_end - r_begin) >= 4096;
         if (const char* e = getenv("PHASM_VERIFY_ORDER")) order = atoi(e) != 0;
-        if (const char* e = getenv("PHASM_PIECE_ORDER")) order = order && atoi(e) != 0;   // (A/B: pieces without the locality order)
         pred_order = order;
         auto fits = [](const DevBuf& b, uint64_t bytes) { return b.p && b.cap >= bytes; };
         async_count = pred > 0 && cap < (16u << 20) && cdiv(cap, po::TAIL_TILE) <= po::TAIL_MAX_TILES &&
@@ -2140,17 +2067,13 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     if (ntiles <= po::PS_SMALL_MAX) {
         PO_TRY(prefix_sum_small(h, A.tile_count + tile_begin, wide ? nullptr : A.tile_extra + tile_begin, ntiles,
                                 tile_off_p + tile_begin, count_slot,
-                                reinterpret_cast<const uint64_t*>(scalars + 2), also_slot, s1, reinterpret_cast<uint64_t*>(scalars)));
+                                reinterpret_cast<const uint64_t*>(scalars + 2), also_slot, st, reinterpret_cast<uint64_t*>(scalars)));
     } else {
         PO_TRY(prefix_sum<uint32_t>(h, A.tile_count + tile_begin, ntiles, tile_off_p + tile_begin, count_slot,
                                     reinterpret_cast<const uint64_t*>(scalars + 2), also_slot,
-                                    wide ? nullptr : A.tile_extra + tile_begin, s1, reinterpret_cast<uint64_t*>(scalars)));
+                                    wide ? nullptr : A.tile_extra + tile_begin, st, reinterpret_cast<uint64_t*>(scalars)));
     }
-    if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_COUNT], s1));
-    if (two) {   // everything behind the counting pass runs on the handle's stream, after it
-        HIP_TRY(h, hipEventRecord(h->ev_s1[parity], s1));
-        HIP_TRY(h, hipStreamWaitEvent(st, h->ev_s1[parity], 0));
-    }
+    if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_COUNT], st));
     po::CandGuard G = {nullptr, 0u};
     uint64_t n_cand64;
     uint32_t n_selfrep_reads;
@@ -2169,7 +2092,7 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
             HIP_TRY(h, hipEventSynchronize(h->st_pend.ev[EV_DONE]));
             PO_TRY(h->st_harvest());
         }
-        HIP_TRY(h, hipStreamSynchronize(s1));
+        HIP_TRY(h, hipStreamSynchronize(st));
         n_cand64 = h->pinned[1];
         n_selfrep_reads = (uint32_t)h->pinned[8];
     }
@@ -2216,8 +2139,6 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
         const bool use_order_early = [&]() {
             bool u = n_cand >= 400000 && (r_end - r_begin) >= 4096;
             if (const char* e = getenv("PHASM_VERIFY_ORDER")) u = atoi(e) != 0;
-            if (streamed)
-                if (const char* e = getenv("PHASM_PIECE_ORDER")) u = u && atoi(e) != 0;
             if (async_count) u = pred_order;   // (decided from the predicted count, before anything was launched)
             return u && !dp;
         }();
@@ -2313,7 +2234,7 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
         } else {
             // a's words live in LDS (read length + 3 guard words); reads too long for 64 KB use the global path
             const uint64_t need_words = ((uint64_t)h->max_len + W - 1) / W + 3;
-            const uint32_t lds_words_raw = (uint32_t)std::min<uint64_t>(need_words, 8192 - 1100 - (PO_VER_LDS_SWZ ? 256 : 0));  // (room for the records in 64 KB)
+            const uint32_t lds_words_raw = (uint32_t)std::min<uint64_t>(need_words, 8192 - 1100);  // (room for the records in 64 KB)
             const uint32_t n_a = r_end - r_begin;
             const uint32_t* perm = nullptr;
             // (sharded calls too: 0.65 -> 0.51 ms at 2 shards, 0.19 -> 0.17 at 8 -- once the label of a read ranked by
@@ -2358,14 +2279,10 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
                                        : (staged ? po::k_verify_a<BITS, false, true> : po::k_verify_a<BITS, false, false>);
             if (streamed) verify = staged ? po::k_verify_a<BITS, false, true, BITS == 2> : po::k_verify_a<BITS, false, false, BITS == 2>;
             const uint32_t lds_words = (lds_words_raw + 1u) & ~1u;  // even: the records behind a sit on a 16-byte boundary
-            const size_t ver_lds = (size_t)po::ver_a_words(lds_words) * 8 + (size_t)po::VREC_CAP * sizeof(po::VRec) + 16;
+            const size_t ver_lds = (size_t)lds_words * 8 + (size_t)po::VREC_CAP * sizeof(po::VRec) + 16;
             if (ver_lds > 48 * 1024)
                 HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(verify), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ver_lds));
             if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER0], st));
-            if (gated) {
-                HIP_TRY(h, hipEventRecord(h->ev_gate[h->st_k & 1], st));
-                gate_recorded = true;
-            }
             hipLaunchKernelGGL(verify, dim3(ver_grid), dim3(po::VER_BLOCK), ver_lds, st,
                                words, woff, len, h->d_read_tile0.as<uint32_t>(), tile_off_p, A.cand_p,
                                A.cand_b, r_begin, lds_words, paired_ver,
@@ -2591,7 +2508,6 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
     uint64_t* counters = h->pinned + 4;
     if (!used_tail) HIP_TRY(h, hipMemcpyAsync(counters, scalars + 4, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     res->unique_twins = !want_cands && paired != 0 && !dpE;
-    if (gated && !gate_recorded) HIP_TRY(h, hipEventRecord(h->ev_gate[h->st_k & 1], st));   // (a piece without candidates: nothing to wait behind)
     HIP_TRY(h, hipEventRecord(h->ev[EV_DONE], st));
     h->st_selfclean = streamed && self_clean && used_tail && !wide;   // (the next piece of this step may skip its reset)
     if (async_count && h->st_pend.valid) {
@@ -3261,7 +3177,6 @@ void po_destroy(po_handle* h) {
         if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
         if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
         if (h->rc_stream) (void)hipStreamSynchronize(h->rc_stream);
-        if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
         for (DevBuf* b : bufs) b->release();
         const bool pooled = kit_give(h);
         if (!pooled) {
@@ -3285,11 +3200,6 @@ void po_destroy(po_handle* h) {
         h->stage_host.release();
         for (void* c : h->arena_chunks) (void)hipFree(c);
         h->arena_chunks.clear();
-        for (hipEvent_t& e : h->ev_gate)   // (the handle's own, never part of the pooled kit)
-            if (e) {
-                (void)hipEventDestroy(e);
-                e = nullptr;
-            }
         if (!pooled) {
         if (h->up_stream) {
             (void)hipStreamSynchronize(h->up_stream);
@@ -3302,17 +3212,9 @@ void po_destroy(po_handle* h) {
         if (h->ev_meta) (void)hipEventDestroy(h->ev_meta);
         if (h->rc_stream) {
             (void)hipStreamSynchronize(h->rc_stream);
-            if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
             (void)hipStreamDestroy(h->rc_stream);
         }
         if (h->ev_first) (void)hipEventDestroy(h->ev_first);
-        if (h->scan_stream) {
-            (void)hipStreamSynchronize(h->scan_stream);
-            (void)hipStreamDestroy(h->scan_stream);
-        }
-        for (hipEvent_t e : h->ev_s1)
-            if (e) (void)hipEventDestroy(e);
-        if (h->ev_idx) (void)hipEventDestroy(h->ev_idx);
         if (h->copy_stream) {
             (void)hipStreamSynchronize(h->copy_stream);
             (void)hipStreamDestroy(h->copy_stream);
@@ -3796,47 +3698,34 @@ po_status append_home(po_handle* h, HostRows& R, const DevBuf& dev, uint64_t n_r
         if (bytes > h->home_stage.cap)
             PO_TRY(ensure_host(h, h->home_stage, std::max<size_t>({bytes * 2, (size_t)(h->home_last_bytes + h->home_last_bytes / 8), (size_t)8 << 20})));
     }
-    // behind a copy, on the same stream: a one-thread kernel writes a number into a page-locked word of the handle's landing
-    // zone (slots 96 ..) -- what the pool's first thread polls.  The LAST piece of a call can travel in parts, so that its
-    // first rows are being written while its last records are still on the wire.
-    uint32_t n_parts = 1;
-    // (measured, round 4: interleaved A/B at config 2, 4.68 ms with the split against 4.64 without -- the three extra copies
-    // and their words cost what the overlap gains; PHASM_HOME_SPLIT=n asks for n parts)
-    if (const char* e = getenv("PHASM_HOME_SPLIT"))
-        if (k + 1 == n_chunks && n_rec >= 65536) n_parts = (uint32_t)std::max(1, std::min(8, atoi(e)));
-    if (h->home_seq % N_EV + n_parts > N_EV) n_parts = 1;   // (not enough unused flag words left in this round)
-    P->paired = (h->bits == 2 && h->paired) ? 1u : 0u;
-    P->bits = (uint32_t)h->bits;
-    char* dst0 = static_cast<char*>(h->home_stage.p) + h->home_used;
-    for (uint32_t part = 0; part < n_parts; ++part) {
-        const uint64_t lo = n_rec * part / n_parts, hi = n_rec * (part + 1) / n_parts;
-        const uint32_t slot = (uint32_t)(h->home_seq % N_EV);
-        const uint32_t want = ++h->home_gen;
-        char* dst = dst0 + lo * elem;
-        // (Measured and not kept, round 4 -- profiles/r04_copy_kernels.txt.  Under the tracer the counting pass of the NEXT
-        // piece shows 200-230 us instead of 90 while this copy is in flight (the runtime copies with a kernel of its own);
-        // the HIP events of an untraced step do not (91 us per piece), and tools/copy_beside_kernel.py finds x 1.04-1.08.
-        // A copy kernel of ours writing the page-locked block with 1 .. 256 workgroups: 5.1, 5.0, 5.1, 5.3, 5.4, 5.5 ms per step
-        // against 4.7 -- the fewer waves the better, and the runtime's copy better than all of them; the same for the upload,
-        // 6.8-7.8 ms.  Copying 50 % / 10 % of the bytes (timing only, the host reading the previous step's identical records):
-        // 4.57 / 4.49 ms -- all of the interference is worth 0.2 ms, 8-byte records would buy 0.13.)
-        HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const char*>(dev.p) + lo * elem, (hi - lo) * elem, hipMemcpyDeviceToHost, h->copy_stream));
-        hipLaunchKernelGGL(po::k_fill_u32, dim3(1), dim3(64), 0, h->copy_stream, reinterpret_cast<uint32_t*>(h->pinned_dev + 96 + slot), (uint64_t)1, want);
-        HIP_TRY(h, hipGetLastError());
-        home::Job j;
-        j.rec = dst;
-        j.sh_b = h->home_sh_b;
-        j.sh_p = h->home_sh_p;
-        j.n_rec = hi - lo;
-        j.out = static_cast<po_row*>(R.hb.p) + R.total;
-        j.n_rows = nk;
-        j.flag = reinterpret_cast<const volatile uint32_t*>(h->pinned + 96 + slot);
-        j.want = want;
-        j.cont = part > 0;
-        j.more = part + 1 < n_parts;
-        home::submit(P, j);
-        ++h->home_seq;
-    }
+    // behind the copy, on the same stream: a one-thread kernel writes a number into a page-locked word of the handle's landing
+    // zone (slots 96 ..) -- what the pool's first thread polls
+    const uint32_t slot = (uint32_t)(h->home_seq % N_EV);
+    const uint32_t want = ++h->home_gen;
+    char* dst = static_cast<char*>(h->home_stage.p) + h->home_used;
+    // (Measured and not kept, round 4 -- profiles/r04_copy_kernels.txt.  Under the tracer the counting pass of the NEXT
+    // piece shows 200-230 us instead of 90 while this copy is in flight (the runtime copies with a kernel of its own);
+    // the HIP events of an untraced step do not (91 us per piece), and tools/copy_beside_kernel.py finds x 1.04-1.08.
+    // A copy kernel of ours writing the page-locked block with 1 .. 256 workgroups: 5.1, 5.0, 5.1, 5.3, 5.4, 5.5 ms per step
+    // against 4.7 -- the fewer waves the better, and the runtime's copy better than all of them; the same for the upload,
+    // 6.8-7.8 ms.  Copying 50 % / 10 % of the bytes (timing only, the host reading the previous step's identical records):
+    // 4.57 / 4.49 ms -- all of the interference is worth 0.2 ms, 8-byte records would buy 0.13.)
+    HIP_TRY(h, hipMemcpyAsync(dst, dev.p, bytes, hipMemcpyDeviceToHost, h->copy_stream));
+    hipLaunchKernelGGL(po::k_fill_u32, dim3(1), dim3(64), 0, h->copy_stream, reinterpret_cast<uint32_t*>(h->pinned_dev + 96 + slot), (uint64_t)1, want);
+    HIP_TRY(h, hipGetLastError());
+    home::Job j;
+    j.rec = dst;
+    j.sh_b = h->home_sh_b;
+    j.sh_p = h->home_sh_p;
+    j.n_rec = n_rec;
+    j.out = static_cast<po_row*>(R.hb.p) + R.total;
+    j.n_rows = nk;
+    j.flag = reinterpret_cast<const volatile uint32_t*>(h->pinned + 96 + slot);
+    j.want = want;
+    j.paired = (h->bits == 2 && h->paired) ? 1u : 0u;
+    j.bits = (uint32_t)h->bits;
+    home::submit(P, j);
+    ++h->home_seq;
     h->home_used += (bytes + 255) & ~size_t(255);
     h->home_last_bytes += bytes;
     R.total += nk;
@@ -3969,7 +3858,6 @@ po_status stream_begin(po_handle* h, const std::vector<uint32_t>& bounds) {
     if (!h->up_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
     for (uint32_t k = 0; k < P; ++k)
         if (!h->ev_piece[k]) HIP_TRY(h, hipEventCreate(&h->ev_piece[k]));
-    uint64_t piece0_bytes = 0;
     auto queue_piece = [&](uint32_t k) -> po_status {
         uint64_t* dw = h->d_words.as<uint64_t>();
         const uint64_t wb = bounds[k] < n ? h->woff[bounds[k]] : h->words[0].size();
@@ -3977,41 +3865,23 @@ po_status stream_begin(po_handle* h, const std::vector<uint32_t>& bounds) {
         if (we > wb) {
             HIP_TRY(h, hipMemcpyAsync(dw + wb, h->words[0].data() + wb, (we - wb) * 8, hipMemcpyHostToDevice, h->up_stream));
             h->upload_bytes += (we - wb) * 8;
-            if (k == 0) piece0_bytes = (we - wb) * 8;
         }
         HIP_TRY(h, hipEventRecord(h->ev_piece[k], h->up_stream));
         return PO_OK;
     };
     // (Measured and not kept, round 4: the first piece on the wire BEFORE the step's preparation.  The per-read tables and the
     // first words are host->device copies too and queue behind the piece's 20 MB on the same engine, so the index -- built
-    // from them while piece 0 is on the wire -- is late by what the piece takes to land.  PHASM_EARLY_PIECE0=1 brings it back.)
-    bool early0 = false;
-    if (getenv("PHASM_EARLY_PIECE0")) {
-        const uint64_t base1 = (h->words[0].size() + 1) & ~uint64_t(1);
-        const uint64_t nwords = base1 + h->words[1].size() + 72;
-        if (h->poison < 0 && h->d_words.p && h->d_words.cap >= nwords * 8 && h->bits == 2 && h->all_pairs_rcx && !getenv("PHASM_FULL_UPLOAD")) {
-            HIP_TRY(h, hipEventRecord(h->ev_up0, h->up_stream));
-            PO_TRY(queue_piece(0));
-            early0 = true;
-        }
-    }
+    // from them while piece 0 is on the wire -- is late by what the piece takes to land.)
     PO_TRY(upload_meta(h, &generate));   // (sets upload_bytes to what the tables weigh)
-    if (!generate) {
-        if (early0) (void)hipStreamSynchronize(h->up_stream);
-        return fail(h, PO_ERR_INVALID, "streamed step on reads that are not (x, reverse complement of x) pairs");
-    }
+    if (!generate) return fail(h, PO_ERR_INVALID, "streamed step on reads that are not (x, reverse complement of x) pairs");
     uint64_t* dw = h->d_words.as<uint64_t>();
     if (h->poison >= 0) {
         // (PHASM_POISON fills a fresh device buffer on the handle's stream: the pieces must not land under that fill)
         HIP_TRY(h, hipEventRecord(h->ev_up1, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->up_stream, h->ev_up1, 0));
     }
-    if (early0) {
-        h->upload_bytes += piece0_bytes;
-    } else {
-        HIP_TRY(h, hipEventRecord(h->ev_up0, h->up_stream));
-        PO_TRY(queue_piece(0));
-    }
+    HIP_TRY(h, hipEventRecord(h->ev_up0, h->up_stream));
+    PO_TRY(queue_piece(0));
     if (P > 1) {
         // first words of the reads of the later pieces (both strands: the host packed the odd store too, it just does
         // not travel), put in place on the handle's stream while piece 0 is crossing; the later pieces' copies are
@@ -4054,7 +3924,6 @@ po_status stream_begin(po_handle* h, const std::vector<uint32_t>& bounds) {
     HIP_TRY(h, hipStreamWaitEvent(h->rc_stream, h->ev_meta, 0));
     for (uint32_t k = 0; k < P; ++k) {
         if (!h->ev_rc[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_rc[k], hipEventDisableTiming));
-        if (h->want_two == 2) continue;   // (gated two-stream pieces queue their reverse complements themselves: run_overlaps)
         HIP_TRY(h, hipStreamWaitEvent(h->rc_stream, h->ev_piece[k], 0));
         const uint32_t p0 = bounds[k] / 2, p1 = bounds[k + 1] / 2;
         if (p1 > p0)
@@ -4095,8 +3964,6 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
     // the index ahead of piece 0: it needs every read's first word(s) only, and at 400 k reads (wide index, 2.9 ms; 16 ms at
     // 2 M reads) building it inside piece 0 -- after the piece has landed -- kept every later piece 2-3 ms behind its data
     h->st_selfclean = false;
-    h->two_stream = 0;
-    h->want_two = 0;
     h->st_early_index = P > 1 && h->poison < 0 && !getenv("PHASM_NO_INDEX_REUSE") && !getenv("PHASM_LATE_INDEX");
     {
         // words per read that travel ahead of the pieces: two, or five where the step will take the wide index and min_length
@@ -4107,30 +3974,8 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
         const bool wide = (idx && !strcmp(idx, "wide")) || (!(idx && !strcmp(idx, "narrow")) && count_eligible(h, m) > 160000);
         h->st_lead = (h->bits == 2 && wide && m >= 32u * 4u + 31u && !(win && atoi(win) < 4) && !getenv("PHASM_STREAM_LEAD2")) ? LEAD_WORDS : 2u;
     }
-    {
-        // PHASM_TWO_STREAM=1: counting passes on a stream of their own (scan_stream); 2: on rc_stream, gated by the verify kernel
-        // of the piece before.  Both need the index built ahead of piece 0 (its event is what the first pass waits for).
-        const char* e2 = getenv("PHASM_TWO_STREAM");
-        const int asked = e2 ? atoi(e2) : 0;
-        h->want_two = (h->st_early_index && h->ev_idx && (asked == 1 || asked == 2)) ? asked : 0;
-        for (int g = 0; g < 2 && h->want_two == 2; ++g)
-            if (!h->ev_gate[g] && hipEventCreateWithFlags(&h->ev_gate[g], hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError();
-                h->want_two = 0;
-            }
-    }
     PO_TRY(stream_begin(h, bounds));
     if (trace) std::fprintf(stderr, "[stream] %u pieces queued at %.3f ms\n", P, since());
-    // (two-stream pieces need the index built ahead -- its event is what the first counting pass waits for -- and no poison
-    // fills; PHASM_TWO_STREAM=0 keeps every piece on the handle's stream)
-    // Measured, round 4 (config 2): 7.1-7.2 ms per step against 4.5 on one stream -- the persistent scan kernel takes every CU's
-    // LDS and registers, the verify workgroups of the piece before wait behind it, and both run slower side by side than one
-    // after the other.  Off unless PHASM_TWO_STREAM=1 asks for it.
-    if (h->want_two == 1 && !h->scan_stream && hipStreamCreateWithFlags(&h->scan_stream, hipStreamNonBlocking) != hipSuccess) {
-        h->scan_stream = nullptr;
-        (void)hipGetLastError();
-    }
-    h->two_stream = h->want_two == 2 ? 2 : (h->want_two == 1 && h->scan_stream) ? 1 : 0;
     if (h->st_early_index) {
         po_result part;
         part.h = h;
@@ -4146,7 +3991,6 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
             (void)hipStreamSynchronize(h->stream);
             (void)hipStreamSynchronize(h->up_stream);
             (void)hipStreamSynchronize(h->rc_stream);
-            if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
             h->dirty = true;
             return ist;
         }
@@ -4185,11 +4029,8 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
     if (getenv("PHASM_STREAM_SYNC")) h->st_harvest = nullptr;   // (developer switch: every piece waits for its own end)
     for (uint32_t k = 0; k < P && st == PO_OK; ++k) {
         // piece k has landed and its odd reads (reverse complements) have been written next to it (rc_stream, stream_begin)
-        // (gated two-stream pieces: the reverse complements are queued inside run_overlaps, in front of the counting pass the
-        // handle's stream then waits for -- ev_rc[k] has not been recorded yet at this point)
-        if (h->two_stream != 2 && hipStreamWaitEvent(h->stream, h->ev_rc[k], 0) != hipSuccess) { st = fail(h, PO_ERR_HIP, "hipStreamWaitEvent"); break; }
+        if (hipStreamWaitEvent(h->stream, h->ev_rc[k], 0) != hipSuccess) { st = fail(h, PO_ERR_HIP, "hipStreamWaitEvent"); break; }
         h->st_on = true;
-        h->st_k = k;
         h->st_r_begin = bounds[k];
         h->st_r_end = bounds[k + 1];
         // per-piece workspaces: sized for the largest piece when they are first needed.  A piece keeps the candidates
@@ -4228,7 +4069,6 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->up_stream);
         (void)hipStreamSynchronize(h->rc_stream);
-        if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
         h->dirty = true;
         h->st_tail_gave_up = true;
         h->st_pred_valid = false;
@@ -4238,7 +4078,6 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
     if (st != PO_OK) {
         (void)hipStreamSynchronize(h->up_stream);
         (void)hipStreamSynchronize(h->rc_stream);
-        if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
         h->dirty = true;   // (a piece may be missing on the device)
         h->st_pred_valid = false;
         return st;
@@ -4375,7 +4214,6 @@ po_status po_overlaps_to_host(po_handle* h, uint32_t min_length, po_result** out
     if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     if (h->rc_stream) (void)hipStreamSynchronize(h->rc_stream);
-    if (h->scan_stream) (void)hipStreamSynchronize(h->scan_stream);
     if (h->copy_stream && hipStreamSynchronize(h->copy_stream) != hipSuccess && st == PO_OK) st = fail(h, PO_ERR_HIP, "row copy device->host");
     {
         // the helper threads have written every piece's rows before the array is handed out (or released)
@@ -5112,20 +4950,13 @@ int po_debug_expand_records(const po_cand* records, uint64_t n, const uint32_t* 
     if (!P) return -1;
     std::lock_guard<std::mutex> call(P->call_mu);
     home::begin(P, lengths, n_reads, false);
-    P->paired = paired ? 1u : 0u;
-    // (as the last piece of a streamed step travels: up to five parts of ONE piece, each part's rows behind the part before)
-    const uint64_t n_jobs = n ? std::min<uint64_t>(5, (n + 2999) / 3000) : 0;
-    for (uint64_t jn = 0; jn < n_jobs; ++jn) {
-        const uint64_t lo = n * jn / n_jobs, hi = n * (jn + 1) / n_jobs;
-        home::Job j;
-        j.rec = reinterpret_cast<const po::Cand*>(records) + lo;
-        j.n_rec = hi - lo;
-        j.out = rows_out;
-        j.n_rows = n_rows_expected;
-        j.cont = jn > 0;
-        j.more = jn + 1 < n_jobs;
-        home::submit(P, j);
-    }
+    home::Job j;
+    j.rec = records;
+    j.n_rec = n;
+    j.out = rows_out;
+    j.n_rows = n_rows_expected;
+    j.paired = paired ? 1u : 0u;
+    home::submit(P, j);
     home::wait_all(P);
     return P->error.load();
 }
@@ -5138,21 +4969,15 @@ int po_debug_expand_packed(const uint64_t* records, uint64_t n, uint32_t sh_b, u
     if (!P) return -1;
     std::lock_guard<std::mutex> call(P->call_mu);
     home::begin(P, lengths, n_reads, false);
-    P->paired = paired ? 1u : 0u;
-    const uint64_t n_jobs = n ? std::min<uint64_t>(5, (n + 2999) / 3000) : 0;
-    for (uint64_t jn = 0; jn < n_jobs; ++jn) {
-        const uint64_t lo = n * jn / n_jobs, hi = n * (jn + 1) / n_jobs;
-        home::Job j;
-        j.rec = records + lo;
-        j.sh_b = sh_b;
-        j.sh_p = sh_p;
-        j.n_rec = hi - lo;
-        j.out = rows_out;
-        j.n_rows = n_rows_expected;
-        j.cont = jn > 0;
-        j.more = jn + 1 < n_jobs;
-        home::submit(P, j);
-    }
+    home::Job j;
+    j.rec = records;
+    j.sh_b = sh_b;
+    j.sh_p = sh_p;
+    j.n_rec = n;
+    j.out = rows_out;
+    j.n_rows = n_rows_expected;
+    j.paired = paired ? 1u : 0u;
+    home::submit(P, j);
     home::wait_all(P);
     return P->error.load();
 }

@@ -173,7 +173,6 @@ TABLE = [
     ("select_kernel_wide_8bit", {"PHASM_SELECT_KERNEL": "1", "PHASM_INDEX": "wide"}, "ladder_varlen_sc", whole, kernel("k_select_local")),
     ("piece_reset", dict(STREAM, PHASM_PIECE_RESET="1"), "cfg2_1k", to_host, kernel("k_call_reset once per piece: 12 launches in 3 calls, 3 without the switch")),
     ("sync_count", dict(STREAM, PHASM_SYNC_COUNT="1"), "cfg2_1k", to_host, never_predicts),
-    ("piece_order_off", dict(STREAM, PHASM_PIECE_ORDER="0"), "cfg2_1k", to_host, kernel("k_read_label / k_read_sort / k_read_invert: none, 12 without the switch")),
     ("stream_lead2", dict(STREAM, PHASM_STREAM_LEAD2="1", PHASM_INDEX="wide"), "cfg3_1k", to_host, stat("upload_bytes", DIFFERENT, [0])),
     ("late_index", dict(STREAM, PHASM_LATE_INDEX="1"), "cfg2_1k", to_host, stat("upload_bytes", DIFFERENT)),
     ("no_index_reuse_whole", {"PHASM_NO_INDEX_REUSE": "1"}, "ladder_varlen", whole, stat("index_reused", lambda a, b: a == 0 and b == 1, [1])),
@@ -182,8 +181,6 @@ TABLE = [
     ("stream_max_pieces_2", {"PHASM_STREAM": "1", "PHASM_STREAM_MAX_PIECES": "2", "PHASM_STREAM_TRACE": "1"}, "big_pairs", to_host,
      pieces(2)),
     ("stream_sync", dict(STREAM, PHASM_STREAM_SYNC="1"), "cfg2_1k", to_host, never_predicts),
-    ("home_split_3", {"PHASM_HOME_SPLIT": "3", "PHASM_HOST_CHUNKS": "1", "PHASM_HOME_TRACE": "1"}, "cfg2_1k", to_host,
-     trace(r"^\[home\] piece \d+:", lambda a, b: a > b)),
     ("no_kit_pool", {"PHASM_NO_KIT_POOL": "1", "PHASM_ALLOC_TRACE": "1"}, "ladder_varlen", whole,
      trace(r"^\[init\] streams and events made", lambda a, b: a > b)),
     ("no_pin", {"PHASM_NO_PIN": "1"}, "cfg2_1k", whole, registered_stores(lambda a, b: a == 0 and b > 0)),
@@ -198,8 +195,6 @@ TABLE = [
 # check rows only and prove nothing about the switch; tests/test_switch_inventory.py lists each of them as an explicit,
 # reasoned exemption instead of counting it as covered.  (id, environment, input, entry point, why there is no proof)
 ROWS_ONLY = [
-    ("early_piece0", dict(STREAM, PHASM_EARLY_PIECE0="1"), "cfg2_1k", to_host,
-     "only moves piece 0's host->device copy ahead of the read tables' copies on the same engine"),
     ("compact_sync", {"PHASM_COMPACT_SYNC": "1"}, "ladder_cfg2_mini", cands_into,
      "only makes the host wait for the candidate count before the compaction, which writes to the same places"),
     ("home_spin_0", {"PHASM_HOME_SPIN": "0", "PHASM_HOST_CHUNKS": "2"}, "cfg2_1k", to_host,
@@ -297,9 +292,9 @@ def test_every_entry_names_its_proof():
     proven = proven_switches()
     for sid, env, name, entry, why in ROWS_ONLY:
         assert why.strip() and switch_of(env) not in proven, sid
-    for must in ("PHASM_VERIFY_STAGED", "PHASM_SELECT_KERNEL", "PHASM_PIECE_RESET", "PHASM_SYNC_COUNT", "PHASM_PIECE_ORDER",
+    for must in ("PHASM_VERIFY_STAGED", "PHASM_SELECT_KERNEL", "PHASM_PIECE_RESET", "PHASM_SYNC_COUNT",
                  "PHASM_STREAM_LEAD2", "PHASM_LATE_INDEX", "PHASM_NO_INDEX_REUSE", "PHASM_STREAM_MAX_PIECES",
-                 "PHASM_STREAM_SYNC", "PHASM_HOME_SPLIT", "PHASM_NO_KIT_POOL", "PHASM_NO_PIN", "PHASM_NO_POOL", "PHASM_NO_WARM"):
+                 "PHASM_STREAM_SYNC", "PHASM_NO_KIT_POOL", "PHASM_NO_PIN", "PHASM_NO_POOL", "PHASM_NO_WARM"):
         assert must in proven, must
 
 

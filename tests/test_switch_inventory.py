@@ -26,7 +26,6 @@ _DIAGNOSTIC = re.compile(r"_TRACE$|^PHASM_PHASE_EVENTS$")
 # switches whose only test checks rows, because nothing in the process shows whether they acted (test_gpu_switches.py
 # ROWS_ONLY): name -> why no test can prove more.  Not coverage: an exemption, stated one by one.
 ROWS_ONLY_EXEMPT = {
-    "PHASM_EARLY_PIECE0": "reorders two host->device copies on one engine; rows, statistics and kernel launches are unchanged",
     "PHASM_COMPACT_SYNC": "adds a host wait before the candidate compaction; rows, statistics and kernel launches are unchanged",
     "PHASM_HOME_SPIN": "changes how long host pool threads spin before sleeping; nothing else changes",
     "PHASM_NO_ARENA": "changes how small device buffers are allocated; rows, statistics and kernel launches are unchanged",
