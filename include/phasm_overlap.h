@@ -339,6 +339,47 @@ po_status po_layout_edges(po_handle* h, po_result* rows, const po_layout_params*
                           uint8_t* removed_reads_out, po_result** edges_out);
 po_status po_get_layout_stats(const po_handle* h, po_layout_stats* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * The first two operations of stage 2 of `phasm layout` (phasm/cli/assembler.py:145-159) on the
+ * edges po_layout_edges left on the device: transitive reduction, then the symmetry pass.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    int32_t length_fuzz;         /* remove_transitive_edges(g, length_fuzz); CLI default 1000, assembler.py:504 */
+    uint32_t reserved;           /* must be 0                                                         */
+} po_reduce_params;
+
+typedef struct {
+    uint64_t n_edges_in;         /* edges of the stage-1 graph                                        */
+    uint64_t n_transitive;       /* "Removing %d transitive edges...", assembler.py:157                */
+    uint64_t n_asymmetric;       /* edges make_symmetric removed after that, assembler.py:159         */
+    uint64_t n_edges_out;        /* edges left                                                        */
+    uint64_t max_out_degree;     /* longest adjacency list of the stage-1 graph                       */
+    float ms_csr, ms_mark, ms_symmetric, ms_emit, ms_total;
+} po_reduce_stats;
+
+/* `edges` is a po_layout_edges result of this handle; it stays valid and unchanged (reduce it again with
+ * another fuzz).  In order:
+ *   1. sort_adjacency_lists (phasm/assembly_graph.py:48-55, :211): every adjacency list ascending by weight,
+ *      ties in the order the reference's OrderedDict holds them -- by the FIRST input row that wrote the edge
+ *      (networkx's add_edge on an existing edge keeps its position);
+ *   2. remove_transitive_edges (assembly_graph.py:215-262) per node v: all neighbours IN_PLAY; sequentially over
+ *      w in adj[v], skipping a w that is no longer IN_PLAY, every IN_PLAY x in adj[w] with
+ *      weight(v,w) + weight(w,x) <= weight(v, last neighbour) + length_fuzz is ELIMINATED; then for every w the
+ *      first entry of adj[w] and every x with weight(w,x) < length_fuzz is ELIMINATED; (v, w) is transitive iff
+ *      w ended ELIMINATED.  Plain signed integers; weights may be <= 0;
+ *   3. g.remove_edges_from (assembler.py:158);
+ *   4. make_symmetric (assembly_graph.py:429-443): one pass, (u, v) goes iff (v^1, u^1) is no longer an edge.
+ * edge_flags_out (may be NULL): po_result_count(edges) bytes, one per stage-1 edge in its order -- 0 kept,
+ * 1 transitive (the reference's TransitiveReduction metadata record, assembler.py:147-155), 2 removed by the
+ * symmetry pass.  kept_out holds the kept po_edge entries in stage-1 order, an edge result like its input.
+ * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
+ * is not a po_layout_edges result, reserved != 0 or length_fuzz < 0: PO_ERR_INVALID.  Tips, bubbles and merging
+ * (assembler.py:161 on) are not part of this library. */
+po_status po_layout_reduce(po_handle* h, po_result* edges, const po_reduce_params* params, uint8_t* edge_flags_out,
+                           po_result** kept_out);
+po_status po_get_reduce_stats(const po_handle* h, po_reduce_stats* out);
+
 /* Diagnostics for the test suite (no reference counterpart: addSequence copies its argument and
  * never touches it again, src/overlapper.cpp:22-26 -- these two calls let a test PROVE that of this library).
  * po_debug_host_ranges: every range of host memory the library has made visible to the GPU in this process, ever

@@ -45,6 +45,20 @@ class PoLayoutStats(ctypes.Structure):
         return d
 
 
+class PoReduceParams(ctypes.Structure):
+    _fields_ = [("length_fuzz", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class PoReduceStats(ctypes.Structure):
+    _fields_ = [("n_edges_in", ctypes.c_uint64), ("n_transitive", ctypes.c_uint64), ("n_asymmetric", ctypes.c_uint64),
+                ("n_edges_out", ctypes.c_uint64), ("max_out_degree", ctypes.c_uint64),
+                ("ms_csr", ctypes.c_float), ("ms_mark", ctypes.c_float), ("ms_symmetric", ctypes.c_float),
+                ("ms_emit", ctypes.c_float), ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoStats(ctypes.Structure):
     _fields_ = [
         ("bits_per_base", ctypes.c_uint32), ("kmer", ctypes.c_uint32),
@@ -123,6 +137,8 @@ SYMBOLS = [
     ("po_add_gfa", ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_P)]),
     ("po_layout_edges", ctypes.c_int, [_P, _P, ctypes.POINTER(PoLayoutParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
     ("po_get_layout_stats", ctypes.c_int, [_P, ctypes.POINTER(PoLayoutStats)]),
+    ("po_layout_reduce", ctypes.c_int, [_P, _P, ctypes.POINTER(PoReduceParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
+    ("po_get_reduce_stats", ctypes.c_int, [_P, ctypes.POINTER(PoReduceStats)]),
     ("po_get_stats", ctypes.c_int, [_P, ctypes.POINTER(PoStats)]),
     ("po_last_error", ctypes.c_char_p, [_P]),
     ("po_debug_fault_backtrace", ctypes.c_int, [ctypes.c_int]),

@@ -189,6 +189,14 @@ def layout_edges(args) -> int:
         logger.info("%d contained reads removed; %d alignments pass the filters; graph has %d edges.",
                     st["n_contained_reads"], st["n_pass"], st["n_edges"])
         try:
+            if getattr(args, "transitive_reduction", False):
+                # assembler.py:145-159: remove_transitive_edges, remove_edges_from, make_symmetric
+                kept = ov.layout_reduce(edges, args.length_fuzz)
+                edges.free()
+                edges = kept
+                rs = ov.reduce_stats()
+                logger.info("Removing %d transitive edges...", rs["n_transitive"])
+                logger.info("Removed %d asymmetric edges; graph has %d edges.", rs["n_asymmetric"], rs["n_edges_out"])
             return write_stage1_graph(args.output, ov.ids(), ov.lengths(), edges.rows(), edges)
         finally:
             edges.free()
@@ -223,6 +231,11 @@ def main(argv=None) -> int:
     q.add_argument("-a", "--max-overhang-abs", type=int, default=1000)
     q.add_argument("-r", "--max-overhang-rel", type=float, default=0.8)
     q.add_argument("-o", "--output", type=argparse.FileType("w"), default=sys.stdout)
+    q.add_argument("--transitive-reduction", action="store_true",
+                   help="also remove the transitive edges and make the graph symmetric (the first two operations of "
+                        "graph cleaning, `phasm layout` stage 2) before writing it")
+    q.add_argument("-F", "--length-fuzz", type=int, default=1000,
+                   help="with --transitive-reduction: length fuzz of the transitive reduction (default: 1000)")
     q.add_argument("--device", type=int, default=None)
     q.add_argument("--las", default=None, metavar="LADUMP",
                    help="read the positional file as DBdump text and the alignments from this LAdump text")

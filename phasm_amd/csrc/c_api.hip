@@ -36,6 +36,7 @@
 #include "kernels.hip.h"
 #include "extend.hip.h"
 #include "layout.hip.h"
+#include "reduce.hip.h"
 
 namespace {
 
@@ -366,9 +367,15 @@ struct po_handle {
     // layout stage 1 (po_layout_edges)
     bool segments_only = false;  // reads were added by po_add_segment: lengths and names, no sequence
     int ids_paired = -1;         // -1 unknown, 0/1: ids come in (name+"+", name+"-") pairs
-    hipEvent_t ev_lay[4] = {};
+    hipEvent_t ev_lay[9] = {};   // [0..3] po_layout_edges, [4..8] po_layout_reduce
     DevBuf d_lay_len, d_lay_cnt, d_rflag, d_removed, d_ekey, d_ecnt, d_ewin, d_eoff;
+    DevBuf d_efirst;             // table path: first writer row per winning row (the edges' rank, po_result::d_rank)
     po_layout_stats lstats = {};
+
+    // transitive reduction + symmetry pass (po_layout_reduce, reduce.hip.h)
+    DevBuf d_red_cnt, d_red_deg, d_red_off, d_red_cur, d_red_tkey, d_red_ttgt, d_red_teid, d_red_ctgt, d_red_cw, d_red_ceid,
+        d_red_cidpos, d_red_stgt, d_red_seid, d_red_state, d_red_flag1, d_red_flags, d_red_keep, d_red_koff;
+    po_reduce_stats rstats = {};
 };
 
 struct po_result {
@@ -383,6 +390,9 @@ struct po_result {
     // rows written by this library's paired-strand emission: every (row, strand mirror) group is the only writer of
     // its twin edge pair -- po_layout_edges needs no dedupe table for them (layout.hip.h, k_layout_winner_adjacent)
     bool unique_twins = false;
+    // po_layout_edges through the table: the first writer row of every edge, its place in the reference's adjacency
+    // OrderedDict (po_layout_reduce orders by it; empty = the emission order is that order already)
+    DevBuf d_rank;
     // po_candidates_shard_into: the caller's buffer the candidates go to when they fit
     void* ext_dst = nullptr;
     uint64_t ext_cap = 0;
@@ -569,7 +579,7 @@ struct DevKit {
     hipStream_t stream = nullptr, copy_stream = nullptr, up_stream = nullptr, rc_stream = nullptr;
     hipEvent_t ev_sets[2][EV_N] = {};
     hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr, ev_meta = nullptr, ev_first = nullptr;
-    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[4] = {};
+    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[9] = {};
 
     uint64_t* pinned = nullptr;
     uint64_t* pinned_dev = nullptr;
@@ -2741,7 +2751,7 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
         if (n_edges) {
             hipLaunchKernelGGL(po::k_layout_emit, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, d_rows, n_rows, d_len,
                                h->d_rflag.as<uint8_t>(), h->d_ewin.as<uint8_t>(), h->d_eoff.as<uint32_t>(),
-                               res->d_rows.as<po::Edge>());
+                               res->d_rows.as<po::Edge>(), (const uint32_t*)nullptr, (uint32_t*)nullptr);
             HIP_TRY(h, hipGetLastError());
         }
     } else if (L.n_pass) {
@@ -2753,12 +2763,13 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
         PO_TRY(ensure(h, h->d_ecnt, (size_t)n_rows));
         PO_TRY(ensure(h, h->d_ewin, (size_t)n_rows));
         PO_TRY(ensure(h, h->d_eoff, ((size_t)n_rows + 1) * 4));
+        PO_TRY(ensure(h, h->d_efirst, (size_t)n_rows * 4));
         HIP_TRY(h, hipMemsetAsync(h->d_ekey.p, 0xFF, (size_t)n_slots * sizeof(po::EdgeSlot), st));
         hipLaunchKernelGGL(po::k_layout_insert, dim3(stride_grid), dim3(256), 0, st, d_rows, n_rows, d_len, h->d_rflag.as<uint8_t>(),
                            h->d_removed.as<uint8_t>(), h->d_ekey.as<po::EdgeSlot>(), n_slots);
         hipLaunchKernelGGL(po::k_layout_winner, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, d_rows, n_rows, d_len,
                            h->d_rflag.as<uint8_t>(), h->d_removed.as<uint8_t>(), h->d_ekey.as<po::EdgeSlot>(), n_slots,
-                           h->d_ecnt.as<uint8_t>(), h->d_ewin.as<uint8_t>());
+                           h->d_ecnt.as<uint8_t>(), h->d_ewin.as<uint8_t>(), h->d_efirst.as<uint32_t>());
         HIP_TRY(h, hipGetLastError());
         PO_TRY(prefix_sum<uint8_t>(h, h->d_ecnt.as<uint8_t>(), n_rows, h->d_eoff.as<uint32_t>(), &h->pinned[2]));
         HIP_TRY(h, hipEventRecord(h->ev_lay[2], st));
@@ -2769,10 +2780,11 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
             h->spare_edges = DevBuf();
         }
         PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_edges * sizeof(po_edge), 256), 1.0, false));
+        PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_edges * 4, 256), 1.0, false));
         if (n_edges) {
             hipLaunchKernelGGL(po::k_layout_emit, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, d_rows, n_rows, d_len,
                                h->d_rflag.as<uint8_t>(), h->d_ewin.as<uint8_t>(), h->d_eoff.as<uint32_t>(),
-                               res->d_rows.as<po::Edge>());
+                               res->d_rows.as<po::Edge>(), h->d_efirst.as<uint32_t>(), res->d_rank.as<uint32_t>());
             HIP_TRY(h, hipGetLastError());
         }
     } else {
@@ -2791,6 +2803,113 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
     (void)hipEventElapsedTime(&L.ms_dedupe, h->ev_lay[1], h->ev_lay[2]);
     (void)hipEventElapsedTime(&L.ms_emit, h->ev_lay[2], h->ev_lay[3]);
     (void)hipEventElapsedTime(&L.ms_total, h->ev_lay[0], h->ev_lay[3]);
+    return PO_OK;
+}
+
+// ---- transitive reduction + make_symmetric (po_layout_reduce): edges -> flags + kept edges ------
+
+po_status run_reduce(po_handle* h, po_result* edges, const po_reduce_params& prm, uint8_t* flags_out, po_result* res) {
+    hipStream_t st = h->stream;
+    po_reduce_stats& R = h->rstats;
+    R = po_reduce_stats();
+    res->count = 0;
+    res->elem = sizeof(po_edge);
+    res->kind_edges = true;
+    const uint32_t n_nodes = (uint32_t)h->len.size();
+    if (edges->count >= 0xFFFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_reduce: too many edges for one call");
+    const uint32_t n = (uint32_t)edges->count;
+    R.n_edges_in = n;
+    for (hipEvent_t& e : h->ev_lay)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    hipEvent_t* ev = h->ev_lay + 4;
+    PO_TRY(rows_to_device(h, edges));
+    if (n == 0 || n_nodes == 0) {
+        if (n) return fail(h, PO_ERR_INVALID, "po_layout_reduce: edges on a handle without reads");
+        PO_TRY(ensure(h, res->d_rows, 256, 1.0, false));
+        return PO_OK;
+    }
+    const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, h->d_red_cnt, 128));
+    PO_TRY(ensure(h, h->d_red_deg, nn * 4));
+    PO_TRY(ensure(h, h->d_red_off, nn * 4));
+    PO_TRY(ensure(h, h->d_red_cur, nn * 4));
+    PO_TRY(ensure(h, h->d_red_tkey, ne * 8));
+    DevBuf* u32s[] = {&h->d_red_ttgt, &h->d_red_teid, &h->d_red_ctgt, &h->d_red_cw, &h->d_red_ceid, &h->d_red_cidpos,
+                      &h->d_red_stgt, &h->d_red_seid};
+    for (DevBuf* b : u32s) PO_TRY(ensure(h, *b, ne * 4));
+    PO_TRY(ensure(h, h->d_red_koff, (ne + 1) * 4));
+    DevBuf* u8s[] = {&h->d_red_state, &h->d_red_flag1, &h->d_red_flags, &h->d_red_keep};
+    for (DevBuf* b : u8s) PO_TRY(ensure(h, *b, ne));
+    const po::Edge* d_edges = edges->d_rows.as<po::Edge>();
+    const uint32_t* d_rank = edges->d_rank.p ? edges->d_rank.as<uint32_t>() : nullptr;
+    unsigned long long* cnt = h->d_red_cnt.as<unsigned long long>();
+    uint32_t *deg = h->d_red_deg.as<uint32_t>(), *off = h->d_red_off.as<uint32_t>(), *cur = h->d_red_cur.as<uint32_t>();
+    const uint32_t stride_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    HIP_TRY(h, hipMemsetAsync(deg, 0, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(cur, 0, nn * 4, st));
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(po::k_reduce_degree, dim3(stride_grid), dim3(256), 0, st, d_edges, n, n_nodes, deg, cnt);
+    hipLaunchKernelGGL(po::k_reduce_maxdeg, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_nodes, 256), 256u))), dim3(256), 0, st,
+                       deg, n_nodes, cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::RC_N * 8, hipMemcpyDeviceToHost, st));
+    PO_TRY(prefix_sum<uint32_t>(h, deg, n_nodes, off, &h->pinned[2]));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    // (an edge that names a node the handle does not hold would index out of the CSR: nothing is scattered then)
+    if (h->pinned[16 + po::RC_INVALID]) return fail(h, PO_ERR_INVALID, "po_layout_reduce: an edge names a read the handle does not hold");
+    R.max_out_degree = h->pinned[16 + po::RC_MAXDEG];
+    hipLaunchKernelGGL(po::k_reduce_scatter, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, off, cur,
+                       h->d_red_tkey.as<unsigned long long>(), h->d_red_ttgt.as<uint32_t>(), h->d_red_teid.as<uint32_t>());
+    hipLaunchKernelGGL(po::k_reduce_order, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, n, off, deg,
+                       h->d_red_tkey.as<unsigned long long>(), h->d_red_ttgt.as<uint32_t>(), h->d_red_teid.as<uint32_t>(),
+                       h->d_red_ctgt.as<uint32_t>(), h->d_red_cw.as<int32_t>(), h->d_red_ceid.as<uint32_t>(),
+                       h->d_red_cidpos.as<uint32_t>(), h->d_red_stgt.as<uint32_t>(), h->d_red_seid.as<uint32_t>());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    hipLaunchKernelGGL(po::k_reduce_mark, dim3(n_nodes), dim3(po::WAVE), 0, st, n_nodes, prm.length_fuzz, off, deg,
+                       h->d_red_ctgt.as<uint32_t>(), h->d_red_cw.as<int32_t>(), h->d_red_ceid.as<uint32_t>(),
+                       h->d_red_cidpos.as<uint32_t>(), h->d_red_stgt.as<uint32_t>(), h->d_red_state.as<uint8_t>(),
+                       h->d_red_flag1.as<uint8_t>());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(po::k_reduce_symmetric, dim3(stride_grid), dim3(256), 0, st, d_edges, n, off, deg, h->d_red_stgt.as<uint32_t>(),
+                       h->d_red_seid.as<uint32_t>(), h->d_red_flag1.as<uint8_t>(), h->d_red_flags.as<uint8_t>(),
+                       h->d_red_keep.as<uint8_t>(), cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::RC_N * 8, hipMemcpyDeviceToHost, st));
+    PO_TRY(prefix_sum<uint8_t>(h, h->d_red_keep.as<uint8_t>(), n, h->d_red_koff.as<uint32_t>(), &h->pinned[2]));
+    if (flags_out) {
+        PO_TRY(ensure_host(h, h->scratch_host, ne));
+        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_red_flags.p, ne, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_kept = h->pinned[2];
+    R.n_transitive = h->pinned[16 + po::RC_TRANSITIVE];
+    R.n_asymmetric = h->pinned[16 + po::RC_ASYMMETRIC];
+    R.n_edges_out = n_kept;
+    if (flags_out) std::memcpy(flags_out, h->scratch_host.p, ne);
+    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
+        res->d_rows = h->spare_edges;
+        h->spare_edges = DevBuf();
+    }
+    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
+    if (d_rank) PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_kept * 4, 256), 1.0, false));
+    if (n_kept) {
+        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, h->d_red_keep.as<uint8_t>(),
+                           h->d_red_koff.as<uint32_t>(), res->d_rows.as<po::Edge>(), d_rank ? res->d_rank.as<uint32_t>() : nullptr);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(ev[4], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    res->count = n_kept;
+    (void)hipEventElapsedTime(&R.ms_csr, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&R.ms_mark, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&R.ms_symmetric, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&R.ms_emit, ev[3], ev[4]);
+    (void)hipEventElapsedTime(&R.ms_total, ev[0], ev[4]);
     return PO_OK;
 }
 
@@ -3172,7 +3291,10 @@ void po_destroy(po_handle* h) {
                           &h->d_ps_blocks, &h->d_scalars, &h->d_cand_a, &h->d_cand_p, &h->d_cand_b, &h->d_type,
                           &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key, &h->d_pair_min, &h->spare_rows, &h->spare_cands, &h->spare_edges,
                           &h->d_vlabel, &h->d_vrank, &h->d_vperm, &h->d_end_a, &h->d_end_b, &h->d_dpcnt, &h->d_lay_len, &h->d_lay_cnt, &h->d_rflag, &h->d_removed, &h->d_ekey, &h->d_ecnt,
-                          &h->d_ewin, &h->d_eoff, &h->d_chain_state, &h->d_tail_state};
+                          &h->d_ewin, &h->d_eoff, &h->d_chain_state, &h->d_tail_state, &h->d_efirst,
+                          &h->d_red_cnt, &h->d_red_deg, &h->d_red_off, &h->d_red_cur, &h->d_red_tkey, &h->d_red_ttgt, &h->d_red_teid,
+                          &h->d_red_ctgt, &h->d_red_cw, &h->d_red_ceid, &h->d_red_cidpos, &h->d_red_stgt, &h->d_red_seid, &h->d_red_state,
+                          &h->d_red_flag1, &h->d_red_flags, &h->d_red_keep, &h->d_red_koff};
         // every stream idle before anything the device (or a copy) may still touch is given back
         if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
         if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
@@ -4495,6 +4617,7 @@ void po_result_free(po_result* r) {
         }
     }
     r->d_rows.release();
+    r->d_rank.release();
     delete r;
 }
 
@@ -4909,11 +5032,50 @@ po_status po_layout_edges(po_handle* h, po_result* rows, const po_layout_params*
     if (st != PO_OK) {
         if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
         r->d_rows.release();
+        r->d_rank.release();
         delete r;
         return st;
     }
     ++h->live_results;
     *edges_out = r;
+    return PO_OK;
+}
+
+po_status po_layout_reduce(po_handle* h, po_result* edges, const po_reduce_params* params, uint8_t* edge_flags_out,
+                           po_result** kept_out) {
+    if (!h || !edges || !params || !kept_out) return PO_ERR_INVALID;
+    *kept_out = nullptr;
+    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_reduce: the edges belong to another handle");
+    if (params->reserved != 0 || params->length_fuzz < 0) return fail(h, PO_ERR_INVALID, "po_layout_reduce: bad parameters");
+    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
+    const po_status dev = init_device(h);
+    if (dev != PO_OK) return dev;
+    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
+        return fail(h, PO_ERR_INVALID, "po_layout_reduce needs a po_layout_edges result");
+    po_result* r = new (std::nothrow) po_result();
+    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
+    r->h = h;
+    po_status st;
+    try {
+        st = run_reduce(h, edges, *params, edge_flags_out, r);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_reduce");
+    }
+    if (st != PO_OK) {
+        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
+        r->d_rows.release();
+        r->d_rank.release();
+        delete r;
+        return st;
+    }
+    ++h->live_results;
+    *kept_out = r;
+    return PO_OK;
+}
+
+po_status po_get_reduce_stats(const po_handle* h, po_reduce_stats* out) {
+    if (!h || !out) return PO_ERR_INVALID;
+    *out = h->rstats;
     return PO_OK;
 }
 

@@ -47,8 +47,8 @@ constexpr unsigned long long EDGE_EMPTY = ~0ull;
 struct __attribute__((aligned(16))) EdgeSlot {
     unsigned long long key;  // u << 32 | v; EDGE_EMPTY = free (memset 0xFF)
     uint32_t writer;         // ~row: memset 0xFF = "no writer"; the smallest complement = the last row
-    uint32_t pad;
-};
+    uint32_t first;          // the FIRST writer row (memset 0xFF, atomicMin): the edge's place in its adjacency list
+};                           // (add_edge on an existing edge keeps its position; reduce.hip.h orders by it)
 
 template <int N>
 __device__ inline void block_add(const uint64_t (&v)[N], unsigned long long* __restrict__ counters) {
@@ -192,6 +192,17 @@ __global__ __launch_bounds__(256) void k_layout_insert(const Row* __restrict__ r
             if (++s == n_slots) s = 0;
         }
         atomicMin(&table[s].writer, ~i);
+        // the first row of this row's run of adjacent writers (the rows before it that stayed out of the table)
+        uint32_t j = i;
+        while (j > 0 && (rflag[j - 1] & RF_PASS)) {
+            const Row r0 = rows[j - 1];
+            Edge g1, g2;
+            row_edges(r0, rflag[j - 1] & RF_TYPE, len[r0.a_idx], len[r0.b_idx], g1, g2);
+            bool st0;
+            if (pair_key(g1, g2, st0) != key) break;
+            --j;
+        }
+        atomicMin(&table[s].first, j);
     }
 }
 
@@ -201,7 +212,8 @@ __global__ __launch_bounds__(256) void k_layout_winner(const Row* __restrict__ r
                                                        const uint8_t* __restrict__ rflag,
                                                        const uint8_t* __restrict__ removed,
                                                        const EdgeSlot* __restrict__ table, uint32_t n_slots,
-                                                       uint8_t* __restrict__ ecnt, uint8_t* __restrict__ ewin) {
+                                                       uint8_t* __restrict__ ecnt, uint8_t* __restrict__ ewin,
+                                                       uint32_t* __restrict__ efirst) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rows) return;
     const uint32_t f = rflag[i];
@@ -217,7 +229,10 @@ __global__ __launch_bounds__(256) void k_layout_winner(const Row* __restrict__ r
             for (;;) {  // k_layout_insert put the key there
                 const uint4 q = *reinterpret_cast<const uint4*>(&table[s]);
                 if ((((unsigned long long)q.y << 32) | q.x) == key) {
-                    if (q.z == ~i) win = self_twin ? 2u : 3u;
+                    if (q.z == ~i) {
+                        win = self_twin ? 2u : 3u;
+                        efirst[i] = q.w;
+                    }
                     break;
                 }
                 if (++s == n_slots) s = 0;
@@ -267,12 +282,14 @@ __global__ __launch_bounds__(256) void k_layout_winner_adjacent(const Row* __res
     ecnt[i] = (uint8_t)__popc(win);
 }
 
-// Pass 4: edges of row i at edges[eoff[i]...], edge 1 before edge 2.
+// Pass 4: edges of row i at edges[eoff[i]...], edge 1 before edge 2; with the table, rank[] receives the first
+// writer row of each edge (efirst, k_layout_winner) -- without it the emission order itself is that order.
 __global__ __launch_bounds__(256) void k_layout_emit(const Row* __restrict__ rows, uint32_t n_rows,
                                                      const uint32_t* __restrict__ len,
                                                      const uint8_t* __restrict__ rflag,
                                                      const uint8_t* __restrict__ ewin,
-                                                     const uint32_t* __restrict__ eoff, Edge* __restrict__ edges) {
+                                                     const uint32_t* __restrict__ eoff, Edge* __restrict__ edges,
+                                                     const uint32_t* __restrict__ efirst, uint32_t* __restrict__ rank) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rows) return;
     const uint32_t win = ewin[i];
@@ -281,8 +298,14 @@ __global__ __launch_bounds__(256) void k_layout_emit(const Row* __restrict__ row
     Edge e1, e2;
     row_edges(r, rflag[i] & RF_TYPE, len[r.a_idx], len[r.b_idx], e1, e2);
     uint32_t o = eoff[i];
-    if (win & 1u) edges[o++] = e1;
-    if (win & 2u) edges[o] = e2;
+    if (win & 1u) {
+        if (rank) rank[o] = efirst[i];
+        edges[o++] = e1;
+    }
+    if (win & 2u) {
+        if (rank) rank[o] = efirst[i];
+        edges[o] = e2;
+    }
 }
 
 // number of removed reads (bytes set in removed[])

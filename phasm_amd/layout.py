@@ -9,7 +9,10 @@ through ``ContainedReads`` / ``MinReadLength`` / ``MinOverlapLength`` / ``MaxOve
 (assembler.py:136) -- comes from ``po_layout_edges`` on the device, either straight from the rows of
 ``po_overlaps`` (no file in between) or from a GFA2 file read natively (``po_add_gfa``).
 
-Graph cleaning after that point (transitive reduction, tips, bubbles, merging) is out of scope.
+The first two operations of graph cleaning follow on request (``reduce=True`` / ``reduce_assembly_graph``):
+``remove_transitive_edges`` (Myers' reduction, phasm/assembly_graph.py:182-264) and ``make_symmetric``
+(assembly_graph.py:429-443) as `phasm layout` applies them (assembler.py:145-159), by ``po_layout_reduce`` on
+the edges still in HBM.  Cleaning after that point (tips, bubbles, merging, assembler.py:161 on) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -29,11 +32,15 @@ DEFAULTS = dict(min_read_length=0, min_overlap_length=0, max_overhang_abs=1000, 
 class AssemblyEdges:
     """Edges of the assembly graph after stage 1: ``edges`` is a structured array (u, v, weight,
     overlap_len) with u, v oriented-read indices into ``ids``; ``contained[i]`` tells that read i (nodes 2i,
-    2i+1) was contained in another read and left the graph."""
+    2i+1) was contained in another read and left the graph.  After ``reduce_assembly_graph``: ``edges`` are the
+    edges left, ``flags`` has one byte per stage-1 edge in stage-1 order (0 kept, 1 transitive, 2 removed by the
+    symmetry pass) and ``reduce_stats`` the counts and times of ``po_layout_reduce``."""
     edges: np.ndarray
     contained: np.ndarray
     ids: List[str]
     stats: dict
+    flags: Optional[np.ndarray] = None
+    reduce_stats: Optional[dict] = None
 
     def edge_tuples(self) -> List[Tuple[str, str, int, int]]:
         ids = self.ids
@@ -50,25 +57,43 @@ class AssemblyEdges:
         return g
 
 
+def reduce_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, length_fuzz: int = 1000,
+                          contained: Optional[np.ndarray] = None, stats: Optional[dict] = None) -> AssemblyEdges:
+    """``remove_transitive_edges(g, length_fuzz)`` + removal + ``make_symmetric`` on a ``layout_edges`` result of
+    ``ov`` (which stays valid): the edges left, plus the flag byte of every stage-1 edge."""
+    kept, flags = ov.layout_reduce(edges_result, length_fuzz, want_flags=True)
+    try:
+        edges = kept.rows()
+    finally:
+        kept.free()
+    if contained is None:
+        contained = np.zeros(len(ov) // 2, dtype=bool)
+    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(), flags, ov.reduce_stats())
+
+
 def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_length: int = 0,
                          min_overlap_length: int = 0, max_overhang_abs: int = 1000,
-                         max_overhang_rel: float = 0.8) -> AssemblyEdges:
-    """Filters + ``build_assembly_graph`` + contained-read removal on a row result of ``ov``."""
+                         max_overhang_rel: float = 0.8, reduce: bool = False, length_fuzz: int = 1000) -> AssemblyEdges:
+    """Filters + ``build_assembly_graph`` + contained-read removal on a row result of ``ov``; with ``reduce`` the
+    transitive reduction and the symmetry pass as well."""
     res, removed = ov.layout_edges(rows, min_read_length, min_overlap_length, max_overhang_abs, max_overhang_rel)
     try:
+        if reduce:
+            return reduce_assembly_graph(ov, res, length_fuzz, removed.astype(bool), ov.layout_stats())
         edges = res.rows()
     finally:
         res.free()
     return AssemblyEdges(edges, removed.astype(bool), ov.ids(), ov.layout_stats())
 
 
-def layout_from_gfa(path: str, device: Optional[int] = None, **params) -> AssemblyEdges:
+def layout_from_gfa(path: str, device: Optional[int] = None, reduce: bool = False, length_fuzz: int = 1000,
+                    **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 from an overlap file: native GFA2 read, then the device passes."""
     ov = ExactOverlapper(device=device)
     try:
         _, rows = ov.add_gfa(path)
         try:
-            return build_assembly_graph(ov, rows, **{**DEFAULTS, **params})
+            return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -85,23 +110,25 @@ def load_daligner(ov: ExactOverlapper, db_input, las_input, translations=None) -
     return ov.result_from_rows(rows)
 
 
-def layout_from_daligner(db_input, las_input, translations=None, device: Optional[int] = None, **params) -> AssemblyEdges:
+def layout_from_daligner(db_input, las_input, translations=None, device: Optional[int] = None, reduce: bool = False,
+                         length_fuzz: int = 1000, **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 straight from DAZZ_DB / DALIGNER dump text."""
     ov = ExactOverlapper(device=device)
     try:
         rows = load_daligner(ov, db_input, las_input, translations)
         try:
-            return build_assembly_graph(ov, rows, **{**DEFAULTS, **params})
+            return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
         ov.close()
 
 
-def layout_from_overlaps(ov: ExactOverlapper, min_length: int, **params) -> AssemblyEdges:
+def layout_from_overlaps(ov: ExactOverlapper, min_length: int, reduce: bool = False, length_fuzz: int = 1000,
+                         **params) -> AssemblyEdges:
     """Overlap + layout stage 1 without the file in between: the rows never leave HBM."""
     rows = ov.overlaps_result(min_length)
     try:
-        return build_assembly_graph(ov, rows, **{**DEFAULTS, **params})
+        return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, **{**DEFAULTS, **params})
     finally:
         rows.free()

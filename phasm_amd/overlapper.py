@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoStats
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoReduceParams, PoReduceStats, PoStats
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -394,6 +394,26 @@ class ExactOverlapper:
     def layout_stats(self) -> dict:
         s = PoLayoutStats()
         _check(self._h, self._lib.po_get_layout_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def layout_reduce(self, edges: OverlapResult, length_fuzz: int = 1000, want_flags: bool = False):
+        """``po_layout_reduce``: transitive reduction (``remove_transitive_edges``) and ``make_symmetric`` on a
+        ``layout_edges`` result, which stays valid.  Returns the kept edges (EDGE_DTYPE result), or with
+        ``want_flags`` the pair (kept edges, one byte per input edge: 0 kept, 1 transitive, 2 asymmetric)."""
+        if not -2**31 <= int(length_fuzz) < 2**31:
+            raise ValueError("length_fuzz does not fit 32 bits")
+        prm = PoReduceParams(int(length_fuzz), 0)
+        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
+        r = ctypes.c_void_p()
+        _check(self._h, self._lib.po_layout_reduce(
+            self._h, edges._ptr, ctypes.byref(prm),
+            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
+        kept = OverlapResult(self, r, EDGE_DTYPE)
+        return (kept, flags) if want_flags else kept
+
+    def reduce_stats(self) -> dict:
+        s = PoReduceStats()
+        _check(self._h, self._lib.po_get_reduce_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def __len__(self) -> int:
