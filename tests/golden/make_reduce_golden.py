@@ -18,7 +18,11 @@ functions themselves are imported and run, not restated.
 
 Per-branch totals: the reference logs every elimination at DEBUG level; a handler counts the records by the source
 line that wrote them (step 2, step 3 "smallest", step 3 "< fuzz"), for neighbours of the node in work.  What it does not log (skipped w, tied weights) is
-counted by tests/reduce_utils.py, whose three logged totals must equal the reference's here."""
+counted by tests/reduce_utils.py, whose three logged totals must equal the reference's here.
+
+After the first 73 cases come the ones that vary the out-degree (dense lines, hubs of exact degrees, staggered hubs), and
+for a few cases a SECOND PASS: the same three calls run again on the graph the first run left ("second_pass" in the
+file, beside the cases, as is every case's largest out-degree: the records of the first cases stay as they were)."""
 import io
 import json
 import logging
@@ -125,6 +129,11 @@ FULL_STAGE1_MAX = 400   # larger cases keep a digest of their stage-1 edges (the
 STEP_LINES = {240: "step2_eliminations", 250: "step3_first", 254: "step3_fuzz"}   # logger.debug calls of remove_transitive_edges
 
 
+# the read sets that vary the out-degree: (reads, fuzz values, branches counted from the reference's log, second pass)
+# (a second pass = (fuzz of the first, fuzz of the second); with a larger second fuzz it finds something to remove)
+DENSE = [(260, [0, 150, 1000], True, [(150, 150), (0, 1000)]), (450, [0, 150, 1000], True, []), (600, [150, 0], False, [])]
+HUB_DEGREES = [63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2049]
+
 NODE_LINE = 218   # "Processing node %s ...": names the node v the records after it belong to
 
 
@@ -174,7 +183,7 @@ def edge_list(g, node_index):
     return [[node_index[str(u)], node_index[str(v)], int(d[g.edge_len]), int(d[g.overlap_len])] for u, v, d in g.edges_iter(data=True)]
 
 
-def run_case(name, text, params, fuzzes, full_stage1, source, totals, count_branches):
+def run_case(name, text, params, fuzzes, full_stage1, source, totals, count_branches, second_pass=(), second=None, max_deg=None):
     log = logging.getLogger("phasm.assembly_graph")
     out = dict(source, name=name, params=params)
     results = {}
@@ -213,10 +222,36 @@ def run_case(name, text, params, fuzzes, full_stage1, source, totals, count_bran
                 assert counts[k] == v, (name, fuzz, k, counts[k], v)
             for k, v in counts.items():
                 totals[k] += v
+        for fuzz2 in [f2 for f1, f2 in second_pass if f1 == fuzz]:
+            # the same three calls once more (length fuzz ``fuzz2``) on the graph they left, whose adjacency lists stand
+            # in the first pass's sorted order; flags per kept edge of the first pass, by (u, v)
+            if g is None:
+                g, _ = stage1_graph(text, params)
+                g.remove_edges_from(ag.remove_transitive_edges(g, fuzz))
+                ag.make_symmetric(g)
+            transitive2 = ag.remove_transitive_edges(g, fuzz2)
+            g.remove_edges_from(transitive2)
+            n_asym2 = ag.make_symmetric(g)
+            kept2 = {(node_index[str(u)], node_index[str(v)]) for u, v in g.edges_iter()}
+            tset2 = {(node_index[str(u)], node_index[str(v)]) for u, v in transitive2}
+            g = None
+            k1 = ru.sort_edges(s1[flags == 0])
+            flags2 = np.array([1 if (u, v) in tset2 else (0 if (u, v) in kept2 else 2) for u, v in k1[:, :2].tolist()], dtype=np.uint8)
+            assert tset2 <= kept and kept2 <= kept and n_asym2 == int((flags2 == 2).sum())
+            second.append({"case": name, "fuzz": fuzz, "fuzz2": fuzz2, "n_in": len(k1), "n_transitive": len(tset2),
+                           "n_asymmetric": int(n_asym2), "n_kept": len(kept2), "flags_by_uv": ru.pack_flags(flags2),
+                           "kept_sha256": ru.edge_digest(k1[flags2 == 0])})
+            # the restatement: the kept edges with the rank they had in the first pass
+            keep_idx = np.flatnonzero(flags == 0)
+            mine2 = ru.reduce_edges(s1[keep_idx], fuzz2, rank=keep_idx)
+            assert np.array_equal(mine2[np.lexsort((s1[keep_idx, 1], s1[keep_idx, 0]))], flags2), (name, fuzz, fuzz2)
+            print("%-28s second pass F%d -> F%d: %d/%d/%d" % (name, fuzz, fuzz2, len(tset2), n_asym2, len(kept2)))
     if len(set(flag_sets)) > 1:
         totals["fuzz_sensitive_cases"] += 1
     totals["edges_weight_le0"] += int((s1[:, 2] <= 0).sum()) if len(s1) else 0
     out["n_stage1"] = len(s1)
+    if max_deg is not None:
+        max_deg[name] = int(np.bincount(s1[:, 0]).max()) if len(s1) else 0
     if full_stage1 and len(s1) <= FULL_STAGE1_MAX:
         out["stage1"] = s1.tolist()
     else:
@@ -230,28 +265,48 @@ def run_case(name, text, params, fuzzes, full_stage1, source, totals, count_bran
 def main():
     import layout_utils as lu
     totals = dict(ru.new_counts(), fuzz_sensitive_cases=0, edges_weight_le0=0)
-    cases = []
+    cases, max_deg = [], {}
     default = ru.DEFAULT_PARAMS
     for lad, seed, fuzzes in [("ladder_small", None, [1000, 10]), ("ladder_varlen", None, [1000, 10]),
                               ("ladder_varlen", 7, [1000]), ("ladder_cfg1_mini", None, [1000, 10]),
                               ("ladder_cfg2_mini", None, [1000, 10]), ("cfg2_1k", None, [1000, 10])]:
         src = {"ladder": lad, "shuffle_seed": seed}
         name = lad + ("" if seed is None else "_shuffled%d" % seed)
-        cases.append(run_case(name, ru.case_text(src), default, fuzzes, False, src, totals, False))
+        cases.append(run_case(name, ru.case_text(src), default, fuzzes, False, src, totals, False, max_deg=max_deg))
     for c in lu.load_cases():
         if c["digests"]:
             continue
-        cases.append(run_case("layout_" + c["name"], c["text"], c["params"], [1000, 10, 0], True, {"layout_case": c["name"]}, totals, True))
+        cases.append(run_case("layout_" + c["name"], c["text"], c["params"], [1000, 10, 0], True, {"layout_case": c["name"]}, totals, True, max_deg=max_deg))
     big_fuzz = 10 ** 6
     for seed in range(12):
         src = {"synth": {"kind": "line", "seed": 100 + seed, "n": 24 + 4 * seed}}
         src["text_sha256"] = ru.text_digest(ru.case_text(src))
-        cases.append(run_case("line_%d" % (100 + seed), ru.case_text(src), default, [0, 150, 1000, big_fuzz], True, src, totals, True))
+        cases.append(run_case("line_%d" % (100 + seed), ru.case_text(src), default, [0, 150, 1000, big_fuzz], True, src, totals, True, max_deg=max_deg))
     src = {"synth": {"kind": "hub", "seed": 5}}
     src["text_sha256"] = ru.text_digest(ru.case_text(src))
-    cases.append(run_case("hub_5200", ru.case_text(src), default, [1000, 0], True, src, totals, False))
+    cases.append(run_case("hub_5200", ru.case_text(src), default, [1000, 0], True, src, totals, False, max_deg=max_deg))
+    # (everything above is as the file first had it; what follows varies the out-degree: DESIGN.md section 3.9b)
+    second = []
+
+    def synth(name, kw, fuzzes, counted, second_pass=()):
+        src = {"synth": kw, "counted": counted}
+        src["text_sha256"] = ru.text_digest(ru.case_text(src))
+        cases.append(run_case(name, ru.case_text(src), default, fuzzes, True, src, totals, counted, second_pass, second, max_deg))
+
+    for n, fuzzes, counted, twice in DENSE:
+        synth("dense_%d" % n, {"kind": "line", "seed": 300 + n, "n": n, "span": 1200, "n_false": n // 9}, fuzzes, counted, twice)
+    for deg in HUB_DEGREES:
+        synth("hub_%d" % deg, {"kind": "hub", "seed": deg, "n_nb": deg, "n_cross": 200}, [0, 1000], True, [(0, 0), (0, 1000)] if deg == 1025 else [])
+    synth("stagger_1100", {"kind": "stagger", "seed": 11}, [0, 150, 1000], True, [(0, 0), (150, 150), (0, 1000)])
+    # tied weights whose order -- the rank the first pass hands on -- decides the second pass (reduce_utils.tie_case)
+    synth("tie_8", {"kind": "tie", "seed": 2}, [0, 150], True, [(0, 150), (0, 0), (150, 150)])
+    for name in ("line_105", "line_108"):       # a second pass of two of the first cases, recorded beside them
+        c = next(x for x in cases if x["name"] == name)
+        scrap = dict(ru.new_counts(), fuzz_sensitive_cases=0, edges_weight_le0=0)
+        again = run_case(name, ru.case_text(c), default, [0, 150], True, {}, scrap, False, [(150, 150), (0, 150), (0, 1000)], second)
+        assert all(again["results"][f] == c["results"][f] for f in ("0", "150"))
     path = ru.GOLDEN_FILE
-    ru.save_golden({"branch_totals": totals, "cases": cases}, path)
+    ru.save_golden({"branch_totals": totals, "cases": cases, "second_pass": second, "max_out_degree": max_deg}, path)
     print("totals", totals)
     print("wrote", path, len(cases), "cases", os.path.getsize(path), "bytes")
 

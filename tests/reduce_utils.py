@@ -15,7 +15,10 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DEFAULT_PARAMS = {"min_read_length": 0, "min_overlap_length": 0, "max_overhang_abs": 1000, "max_overhang_rel": 0.8}
-BRANCHES = ("step2_eliminations", "step3_first", "step3_fuzz", "step2_skips", "tied_nodes", "asymmetric")
+# the last four: comparisons that land on or next to their bound, counted for x that is an IN_PLAY neighbour of v at that moment:
+# weight(v,w) + weight(w,x) == limit / == limit + 1 in step 2, weight(w,x) == fuzz / == fuzz - 1 behind position 0 in step 3
+BRANCHES = ("step2_eliminations", "step3_first", "step3_fuzz", "step2_skips", "tied_nodes", "asymmetric",
+            "step2_at_limit", "step2_just_over", "step3_at_fuzz", "step3_just_under")
 
 
 # ---- the contract ------------------------------------------------------------------------------------------------
@@ -46,13 +49,20 @@ def mark_node(v, adj, fuzz, counts=None):
                 counts["step2_skips"] += 1
             continue
         for x, wx in adj.get(w, ()):
-            if x in in_play and x not in eliminated and vw + wx <= limit:
-                eliminated.add(x)
+            if x in in_play and x not in eliminated:
                 if counts is not None:
-                    counts["step2_eliminations"] += 1
+                    counts["step2_at_limit"] += vw + wx == limit
+                    counts["step2_just_over"] += vw + wx == limit + 1
+                if vw + wx <= limit:
+                    eliminated.add(x)
+                    if counts is not None:
+                        counts["step2_eliminations"] += 1
     for w, _ in nb:                                     # every w, whatever became of it
         for pos, (x, wx) in enumerate(adj.get(w, ())):
             if x in in_play and x not in eliminated:
+                if counts is not None and pos > 0:
+                    counts["step3_at_fuzz"] += wx == fuzz
+                    counts["step3_just_under"] += wx == fuzz - 1
                 if pos == 0:
                     if counts is not None:
                         counts["step3_first"] += 1
@@ -92,6 +102,38 @@ def reduce_edges(edges, fuzz, rank=None, nodes=None, counts=None):
 
 def new_counts():
     return {b: 0 for b in BRANCHES}
+
+
+def degree_profile(edges, fuzz):
+    """How the out-degrees of a case meet the thresholds the device code branches on (a wave strides over adj[w] 64
+    entries at a time; a node's states leave LDS above 1024 out-edges).  Whatever the fuzz:
+    the nodes with 129..1023 out-edges that have a neighbour w with len(adj[w]) > 64; the nodes with more than 1024
+    out-edges that have a neighbour w with more than 1024 out-edges, over 64 of whose targets are neighbours too.
+    For ``fuzz``: the (v, w) with len(adj[w]) > 128, w IN_PLAY when its turn comes, whose ascending walk meets at least
+    one sum within the limit and at least one above it."""
+    e3 = [(int(e[0]), int(e[1]), int(e[2])) for e in edges]
+    adj = sorted_adjacency(e3)
+    out = {"mid_long_w": 0, "wide_pairs": 0, "partial_walks": 0}
+    for v, nb in adj.items():
+        d = len(nb)
+        if d <= 128:
+            continue
+        in_play = {w for w, _ in nb}
+        if d <= 1023:
+            out["mid_long_w"] += any(len(adj.get(w, ())) > 64 for w in in_play)
+        if d > 1024:
+            out["wide_pairs"] += sum(1 for w in in_play if len(adj.get(w, ())) > 1024
+                                     and sum(x in in_play for x, _ in adj[w]) > 64)
+        eliminated = set()
+        limit = nb[-1][1] + fuzz
+        for w, vw in nb:
+            if w in eliminated:
+                continue
+            aw = adj.get(w, ())
+            within = sum(vw + wx <= limit for _, wx in aw)
+            out["partial_walks"] += len(aw) > 128 and 0 < within < len(aw)
+            eliminated.update(x for x, wx in aw if x in in_play and vw + wx <= limit)
+    return out
 
 
 # ---- seeded synthetic row sets -------------------------------------------------------------------------------------
@@ -177,6 +219,94 @@ def hub_case(seed, n_nb=5200, n_cross=400):
     return names, length, rows
 
 
+def stagger_case(seed, n_hubs=3, n_nb=1100, n_cross=300, n_sloppy=80, n_plant=24, plant_fuzz=150):
+    """n_hubs long reads three bases apart, each ending ten bases behind the one before, and n_nb neighbours to their
+    right as in hub_case: every hub has a row to every later hub and to the neighbours, so an earlier hub v finds a later
+    hub w among its neighbours whose list is as long as its own and eliminates nearly all of it.  Not all: every later
+    hub claims a larger offset than the true one for n_sloppy of its neighbours (sums above v's limit behind a long run
+    within it, one of them by exactly 1 for the last neighbour), and has no row at all to the targets of n_plant rows
+    among the neighbours whose weight is plant_fuzz or plant_fuzz - 1 (they survive step 2 and meet step 3's bound)."""
+    rng = random.Random(seed)
+    hub_len = 400_000
+    names = ["hub%d" % h for h in range(n_hubs)]
+    length = [hub_len + 7 * h for h in range(n_hubs)]          # hub h lies at 3 h and ends at hub_len + 10 h
+    pos, p = [], 3 * n_hubs
+    for k in range(n_nb):
+        if k % 7 != 3:
+            p += rng.randrange(1, 60)
+        pos.append(p)
+        names.append("n%d" % k)
+        length.append(hub_len - p + 1000 + 13 * k)
+
+    def cross(i, j, shift=0):
+        ovl = pos[i] + length[n_hubs + i] - pos[j] - shift
+        return (2 * (n_hubs + i), 2 * (n_hubs + j), length[n_hubs + i] - ovl, length[n_hubs + i], 0, ovl)
+
+    rows, orphans, planted = [], set(), set()
+    for t in range(n_plant):                                   # w -> x at plant_fuzz - (t & 1), behind a shorter row of w
+        for _ in range(1000):
+            i = rng.randrange(n_nb - 2)
+            want = pos[i] + plant_fuzz - (t & 1)
+            j = next((j for j in range(i + 2, n_nb) if pos[j] >= want), None)
+            if j is not None and pos[j] == want and pos[i + 1] > pos[i] and not {i, i + 1, j} & (orphans | planted):
+                break
+        else:
+            raise AssertionError("no pair of neighbours %d apart" % plant_fuzz)
+        rows += [cross(i, i + 1), cross(i, j)]
+        planted |= {i, i + 1}
+        orphans.add(j)
+    for h in range(n_hubs):
+        for g in range(h + 1, n_hubs):
+            rows.append((2 * h, 2 * g, 3 * (g - h), length[h], 0, length[h] - 3 * (g - h)))
+        free = [k for k in range(n_nb - 1) if k not in orphans and k not in planted]
+        sloppy = {k: rng.choice([1, 2, 40, rng.randrange(1, 300)]) for k in rng.sample(free, n_sloppy)} if h else {}
+        if h:
+            sloppy[n_nb - 1] = 1
+        for k in range(n_nb):
+            if h and k in orphans:
+                continue
+            a = pos[k] - 3 * h + sloppy.get(k, 0)
+            rows.append((2 * h, 2 * (n_hubs + k), a, length[h], 0, length[h] - a))
+    for _ in range(n_cross):
+        i, j = sorted(rng.sample(range(n_nb), 2))
+        if pos[i] == pos[j]:
+            continue
+        rows.append(cross(i, j, rng.choice([0, 0, 0, rng.randrange(200)])))
+    rng.shuffle(rows)
+    return names, length, rows
+
+
+def tie_case(seed, n=8):
+    """n groups of reads v, w1, w2, x (and four bystanders): w1 and w2 start at the same place (equal weights from v),
+    a sloppy row w1 -> w2 and a sloppy row w2 -> x claim offsets too large for a reduction with fuzz 0 to use, so all
+    of v's edges stay.  Reduced AGAIN with a larger fuzz both rows fit under v's limit, and which of the tied w1, w2
+    comes first in adj[v] -- the order the graph first saw the two edges, nothing else -- decides whether w2 still
+    gets to eliminate x or has been eliminated by w1 before its turn.  (The bystanders y1, y2, z1, z2 take position 0
+    of the lists of w1, w2 and of their reverse strands, which step 3 would otherwise use.)"""
+    rng = random.Random(seed)
+    names, length, rows = [], [], []
+    for g in range(n):
+        a = rng.randrange(60, 140)
+        reads = ("v", "w1", "w2", "x", "y1", "y2", "z1", "z2")
+        pos = dict(v=0, w1=a, w2=a, x=a + rng.randrange(280, 320), y1=a + rng.randrange(30, 50), y2=a + rng.randrange(50, 70),
+                   z1=rng.randrange(10, 30), z2=rng.randrange(30, 50))
+        end = dict(v=1000, w1=1100 + rng.randrange(9), w2=1110 + rng.randrange(9), x=1400, y1=1200, y2=1210, z1=1040, z2=1060)
+        base = len(names)
+        names += ["t%d_%s" % (g, r) for r in reads]
+        length += [end[r] - pos[r] for r in reads]
+        for i, j, shift in (("v", "w1", 0), ("v", "w2", 0), ("v", "x", 0), ("w1", "y1", 0), ("w2", "y2", 0), ("z1", "w1", 0),
+                            ("z2", "w2", 0), ("w1", "w2", rng.randrange(310, 330)), ("w2", "x", 50)):
+            ovl = end[i] - pos[j] - shift
+            ni, nj = base + reads.index(i), base + reads.index(j)
+            rows.append((2 * ni, 2 * nj, length[ni] - ovl, length[ni], 0, ovl))
+            rows.append((2 * nj + 1, 2 * ni + 1, length[nj] - ovl, length[nj], 0, ovl))
+    rng.shuffle(rows)
+    return names, length, rows
+
+
+SYNTH = {"line": line_case, "hub": hub_case, "stagger": stagger_case, "tie": tie_case}
+
+
 # ---- golden file ---------------------------------------------------------------------------------------------------
 
 def pack_flags(flags):
@@ -213,7 +343,7 @@ def case_text(c):
     if "synth" in c:            # a seeded row set of this module; the digest proves it is the one the reference saw
         kw = dict(c["synth"])
         kind = kw.pop("kind")
-        text = gfa_text(*(line_case(**kw) if kind == "line" else hub_case(**kw)))
+        text = gfa_text(*SYNTH[kind](**kw))
         assert c.get("text_sha256") in (None, text_digest(text)), "synthetic rows drifted from the golden inputs"
         return text
     _, seqs, _, grows = golden_utils.ladder_case(c["ladder"])

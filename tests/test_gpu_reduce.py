@@ -69,8 +69,7 @@ def test_reduce_from_gfa_text_equals_the_reference(case, tmp_path):
     edges_res, _ = ov.layout_edges(rows, **case["params"])
     rows.free()
     s1 = check_against_golden(case, ov, edges_res)
-    if case["name"].startswith("hub"):
-        assert ov.reduce_stats()["max_out_degree"] >= 5000      # beyond what the wave keeps in LDS
+    assert ov.reduce_stats()["max_out_degree"] == GOLDEN["max_out_degree"][case["name"]]   # (5200, 1024, 1025, ...: as recorded)
     edges_res.free()
     ov.close()
     assert len(s1) == case["n_stage1"]
@@ -126,6 +125,71 @@ def test_same_answer_twice_and_after_another_fuzz(tmp_path):
     for r in (again, kept, edges_res, rows):
         r.free()
     other.close()
+    ov.close()
+
+
+def edges_from_text(case, tmp_path):
+    p = tmp_path / "in.gfa"
+    p.write_text(ru.case_text(case))
+    ov = ExactOverlapper()
+    _, rows = ov.add_gfa(str(p))
+    edges_res, _ = ov.layout_edges(rows, **case["params"])
+    rows.free()
+    return ov, edges_res
+
+
+SECOND_CASES = sorted({r["case"] for r in GOLDEN["second_pass"]}, key=[c["name"] for c in CASES].index)
+
+
+@pytest.mark.parametrize("name", SECOND_CASES)
+def test_reducing_a_kept_result_equals_the_reference_second_pass(name, tmp_path):
+    """Reduced again, a kept result gives what the reference's three calls give on the graph their first run left,
+    flag for flag.  Only tie_8 makes that depend on the hidden rank the kept result carries (k_reduce_emit): see
+    test_a_second_pass_depends_on_the_rank_the_first_hands_on in tests/test_reduce_oracle.py."""
+    case = next(c for c in CASES if c["name"] == name)
+    ov, edges_res = edges_from_text(case, tmp_path)
+    for rec in (r for r in GOLDEN["second_pass"] if r["case"] == name):
+        kept_res, flags = ov.layout_reduce(edges_res, rec["fuzz"], want_flags=True)
+        kept = edge_array(kept_res.rows())
+        assert np.array_equal(flags[by_uv(edge_array(edges_res.rows()))],
+                              ru.unpack_flags(case["results"][str(rec["fuzz"])]["flags_by_uv"], case["n_stage1"]))
+        assert len(kept) == rec["n_in"]
+        again_res, flags2 = ov.layout_reduce(kept_res, rec["fuzz2"], want_flags=True)
+        again = edge_array(again_res.rows())
+        st = ov.reduce_stats()
+        assert np.array_equal(flags2[by_uv(kept)], ru.unpack_flags(rec["flags_by_uv"], len(kept))), (name, rec["fuzz"], rec["fuzz2"])
+        assert again.tolist() == kept[flags2 == 0].tolist()
+        assert ru.edge_digest(ru.sort_edges(again)) == rec["kept_sha256"]
+        assert (st["n_edges_in"], st["n_transitive"], st["n_asymmetric"], st["n_edges_out"]) == \
+               (rec["n_in"], rec["n_transitive"], rec["n_asymmetric"], rec["n_kept"])
+        assert edge_array(kept_res.rows()).tolist() == kept.tolist()
+        again_res.free()
+        kept_res.free()
+    edges_res.free()
+    ov.close()
+
+
+@pytest.mark.parametrize("name", ["dense_600", "stagger_1100", "hub_1025"])
+def test_same_bytes_from_five_calls_between_calls_with_another_fuzz(name, tmp_path):
+    """Out-degrees in the hundreds and above 1024: k_reduce_scatter's atomics hand out the slots of a long list in a
+    new order every call, and many lanes store into one state array at once; neither may show in the answer.  From
+    the second call on the global state workspace of the nodes above 1024 out-edges holds what the call before left
+    (on a fresh handle it holds anything), so a state that a call does not set again shows here."""
+    case = next(c for c in CASES if c["name"] == name)
+    fuzz, other = (int(f) for f in list(case["results"])[:2])
+    ov, edges_res = edges_from_text(case, tmp_path)
+    seen = {}
+    for f in (fuzz, other) * 5:
+        kept, flags = ov.layout_reduce(edges_res, f, want_flags=True)
+        key = (flags.tobytes(), kept.rows().tobytes())
+        kept.free()
+        assert seen.setdefault(f, key) == key
+    assert seen[fuzz][0] != seen[other][0] or name.startswith("hub")    # (the hubs' two values give the same flags)
+    s1 = edge_array(edges_res.rows())
+    for f in (fuzz, other):
+        got = np.frombuffer(seen[f][0], dtype=np.uint8)
+        assert np.array_equal(got[by_uv(s1)], ru.unpack_flags(case["results"][str(f)]["flags_by_uv"], len(s1)))
+    edges_res.free()
     ov.close()
 
 

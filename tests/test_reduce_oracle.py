@@ -3,6 +3,9 @@ the reference's own remove_transitive_edges / make_symmetric produced (tests/gol
 tests/golden/make_reduce_golden.py), the fixture conditions of that file, and the host side of the new C ABI calls.
 Everything is exact equality of integers."""
 import ctypes
+import functools
+import hashlib
+import json
 
 import numpy as np
 import pytest
@@ -17,7 +20,30 @@ from phasm_amd.overlapper import ExactOverlapper
 GOLDEN = ru.load_golden()
 CASES = GOLDEN["cases"]
 # the cases whose branches the generator counted (reference's debug log): every inline case
-COUNTED = [c for c in CASES if "layout_case" in c or c.get("synth", {}).get("kind") == "line"]
+# (the cases added for their out-degrees say so themselves)
+COUNTED = [c for c in CASES if c.get("counted", "layout_case" in c or c.get("synth", {}).get("kind") == "line")]
+BY_NAME = {c["name"]: c for c in CASES}
+N_FIRST = 73          # the cases the file had before the out-degree cases came
+FIRST_SHA256 = "d3f51c4dcf2bd3952b6370d2ef84b5dd21dc794a9d207858f8d040549ccd5d3f"
+
+
+@functools.lru_cache(maxsize=None)
+def stage1_of(name):
+    """(stage-1 edges in insertion order, their (u, v) order): computed once per case, shared, never written to."""
+    s1 = stage1_in_insertion_order(BY_NAME[name])
+    order = np.lexsort((s1[:, 1], s1[:, 0])) if len(s1) else np.empty(0, dtype=np.int64)
+    s1.setflags(write=False)
+    order.setflags(write=False)
+    return s1, order
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name, fuzz):
+    """(flags, branch counts) of the restatement: computed once per (case, fuzz), shared between the tests."""
+    counts = ru.new_counts()
+    flags = ru.reduce_edges(stage1_of(name)[0], fuzz, counts=counts)
+    flags.setflags(write=False)
+    return flags, counts
 
 
 def stage1_in_insertion_order(c):
@@ -39,10 +65,9 @@ def stage1_in_insertion_order(c):
 
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_restatement_equals_the_reference_on_every_golden_case(case):
-    s1 = stage1_in_insertion_order(case)
-    order = np.lexsort((s1[:, 1], s1[:, 0])) if len(s1) else np.empty(0, dtype=np.int64)
+    s1, order = stage1_of(case["name"])
     for fuzz, exp in case["results"].items():
-        flags = ru.reduce_edges(s1, int(fuzz))
+        flags = restated(case["name"], int(fuzz))[0]
         assert np.array_equal(flags[order], ru.unpack_flags(exp["flags_by_uv"], len(s1))), fuzz
         assert int((flags == 1).sum()) == exp["n_transitive"]
         assert int((flags == 2).sum()) == exp["n_asymmetric"]
@@ -68,23 +93,89 @@ def test_the_fixtures_reach_every_branch():
     counts = ru.new_counts()
     sensitive = 0
     for c in CASES:
-        s1 = stage1_in_insertion_order(c) if c in COUNTED else None
         seen = set()
         for fuzz, exp in c["results"].items():
             seen.add(exp["flags_by_uv"])
-            if s1 is not None:
-                ru.reduce_edges(s1, int(fuzz), counts=counts)
+            if c in COUNTED:
+                for k, n in restated(c["name"], int(fuzz))[1].items():
+                    counts[k] += n
         sensitive += len(seen) > 1
     assert counts == {k: t[k] for k in ru.BRANCHES}
     assert sensitive == t["fuzz_sensitive_cases"]
     assert max(c["n_stage1"] for c in CASES if c.get("synth", {}).get("kind") == "hub") > 2 * 5000
     assert {"0", "1000000"} <= {f for c in CASES for f in c["results"]}
+    # the out-degrees the kernels branch on (a wave strides over adj[w] by 64; the states leave LDS above 1024)
+    degrees = set()
+    for c in CASES[N_FIRST:]:
+        degrees |= set(np.bincount(stage1_of(c["name"])[0][:, 0]).tolist())
+    assert {63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2049} <= degrees
+    prof = {n: ru.degree_profile(stage1_of(n)[0], f) for n, f in (("dense_260", 0), ("dense_450", 0), ("stagger_1100", 0))}
+    # nodes with 129..1023 out-edges that have a neighbour w with len(adj[w]) > 64
+    assert prof["dense_260"]["mid_long_w"] + prof["dense_450"]["mid_long_w"] >= 100
+    # a node above 1024 with a neighbour w above 1024, more than 64 of whose targets are its neighbours
+    assert prof["stagger_1100"]["wide_pairs"] >= 1
+    # (v, w) with len(adj[w]) > 128 whose walk over adj[w] accepts at least one entry and stops before the end
+    assert prof["stagger_1100"]["partial_walks"] >= 1 and prof["dense_450"]["partial_walks"] >= 1
+
+
+def test_the_first_cases_are_as_they_were():
+    """The cases added later leave the records of the first 73 alone: the digest below was taken from the file as it
+    stood before them (canonical JSON of load_golden()["cases"][:73])."""
+    text = json.dumps(CASES[:N_FIRST], sort_keys=True, separators=(",", ":"))
+    assert hashlib.sha256(text.encode()).hexdigest() == FIRST_SHA256
+    assert len(CASES) > N_FIRST
+
+
+def test_the_golden_file_is_small_enough_to_commit():
+    import os
+    assert os.path.getsize(ru.GOLDEN_FILE) < 1 << 20
+
+
+SECOND = GOLDEN["second_pass"]
+
+
+def second_pass_flags(rec, rank_of):
+    """Flags of the second pass by (u, v); rank_of(keep) -> the rank given to the kept edges (keep = their indices in
+    the first pass's insertion order, ascending)."""
+    s1, _ = stage1_of(rec["case"])
+    keep = np.flatnonzero(restated(rec["case"], rec["fuzz"])[0] == 0)
+    kept = s1[keep]
+    flags = ru.reduce_edges(kept, rec["fuzz2"], rank=rank_of(keep))
+    return flags[np.lexsort((kept[:, 1], kept[:, 0]))]
+
+
+def test_a_second_pass_depends_on_the_rank_the_first_hands_on():
+    """A condition on the golden file: at least one recorded second pass comes out differently when the kept edges are
+    given another order than the one they had in the first pass -- reversed, none at all (every rank 0), or their
+    (u, v) order.  Without such a record a kept result with a wrong or missing hidden rank would pass every test."""
+    rec = next(r for r in SECOND if r["case"] == "tie_8" and (r["fuzz"], r["fuzz2"]) == (0, 150))
+    want = ru.unpack_flags(rec["flags_by_uv"], rec["n_in"])
+    assert rec["n_transitive"] > 0
+    assert np.array_equal(second_pass_flags(rec, lambda keep: keep), want)
+    s1, _ = stage1_of("tie_8")
+    for wrong in (lambda keep: -keep, lambda keep: np.zeros(len(keep), dtype=np.int64),
+                  lambda keep: np.argsort(np.lexsort((s1[keep, 1], s1[keep, 0])))):
+        assert not np.array_equal(second_pass_flags(rec, wrong), want)
+
+
+@pytest.mark.parametrize("rec", SECOND, ids=["%s-F%d-F%d" % (r["case"], r["fuzz"], r["fuzz2"]) for r in SECOND])
+def test_restatement_of_a_second_pass_equals_the_reference(rec):
+    """Reducing the kept edges again: the reference ran its three calls a second time on the graph the first pass left
+    (adjacency lists in the first pass's order), the restatement takes the kept edges with their first-pass rank."""
+    s1, _ = stage1_of(rec["case"])
+    keep = np.flatnonzero(restated(rec["case"], rec["fuzz"])[0] == 0)
+    kept = s1[keep]
+    assert len(kept) == rec["n_in"]
+    flags = ru.reduce_edges(kept, rec["fuzz2"], rank=keep)
+    order = np.lexsort((kept[:, 1], kept[:, 0]))
+    assert np.array_equal(flags[order], ru.unpack_flags(rec["flags_by_uv"], len(kept)))
+    assert (int((flags == 1).sum()), int((flags == 2).sum())) == (rec["n_transitive"], rec["n_asymmetric"])
+    assert ru.edge_digest(ru.sort_edges(kept[flags == 0])) == rec["kept_sha256"]
 
 
 def test_restatement_on_a_node_subset_equals_the_whole():
-    c = next(x for x in CASES if x["name"] == "line_105")
-    s1 = stage1_in_insertion_order(c)
-    whole = ru.reduce_edges(s1, 150)
+    s1 = stage1_of("line_105")[0]
+    whole = restated("line_105", 150)[0]
     nodes = sorted(set(s1[:, 0].tolist()))[::3]
     part = ru.reduce_edges(s1, 150, nodes=nodes)
     sel = np.isin(s1[:, 0], nodes)

@@ -38,7 +38,8 @@ int main(int argc, char** argv) {
     for (uint32_t i = 0; i < n; ++i) { if (scanf("%u %u %d %u", &e[i].u, &e[i].v, &e[i].weight, &rank[i]) != 4) return 1; e[i].overlap_len = 0; }
     std::vector<uint32_t> deg(n_nodes + 1, 0), off(n_nodes + 1, 0), cur(n_nodes + 1, 0), ttgt(n), teid(n), ctgt(n), ceid(n), cidpos(n), stgt(n), seid(n), koff(n + 1);
     std::vector<int32_t> cw(n); std::vector<unsigned long long> tkey(n); unsigned long long cnt[16] = {};
-    std::vector<uint8_t> gstate(n, 77), flag1(n, 99), flags(n, 99), keep(n);
+    // (the workspace starts as a call before could have left it: a state that is not set again reads ELIMINATED)
+    std::vector<uint8_t> gstate(n, NS_ELIMINATED), flag1(n, 99), flags(n, 99), keep(n);
     LAUNCH(3, 4, k_reduce_degree(e.data(), n, n_nodes, deg.data(), cnt));
     LAUNCH(2, 4, k_reduce_maxdeg(deg.data(), n_nodes, cnt));
     for (uint32_t i = 0, s = 0; i < n_nodes; ++i) { off[i] = s; s += deg[i]; }
