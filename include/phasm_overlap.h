@@ -374,11 +374,75 @@ typedef struct {
  * 1 transitive (the reference's TransitiveReduction metadata record, assembler.py:147-155), 2 removed by the
  * symmetry pass.  kept_out holds the kept po_edge entries in stage-1 order, an edge result like its input.
  * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
- * is not a po_layout_edges result, reserved != 0 or length_fuzz < 0: PO_ERR_INVALID.  Tips, bubbles and merging
- * (assembler.py:161 on) are not part of this library. */
+ * is not a po_layout_edges result, reserved != 0 or length_fuzz < 0: PO_ERR_INVALID.  kept_out carries the node order
+ * of its input on (po_result_node_order).  Tip removal follows with po_layout_tips. */
 po_status po_layout_reduce(po_handle* h, po_result* edges, const po_reduce_params* params, uint8_t* edge_flags_out,
                            po_result** kept_out);
 po_status po_get_reduce_stats(const po_handle* h, po_reduce_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The next three calls of stage 2 (phasm/cli/assembler.py:161-167, and again :177-179):
+ * remove_tips, make_symmetric, clean_graph, on an edge result of this handle.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t max_tip_len;        /* remove_tips(g, max_tip_len, ...); CLI default 4, assembler.py -t            */
+    int32_t max_tip_len_bases;   /* ... max_tip_len_bases; CLI and function default 5000                         */
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_tips_params;
+
+typedef struct {
+    uint64_t n_edges_in;         /* edges of the input graph                                                     */
+    uint64_t n_in_tip_edges;     /* edges remove_incoming_tips removed (assembly_graph.py:326-381)                */
+    uint64_t n_out_tip_edges;    /* edges remove_outgoing_tips removed (:267-323)                                 */
+    uint64_t n_asymmetric;       /* edges make_symmetric removed after that                                      */
+    uint64_t n_edges_out;        /* edges left                                                                   */
+    uint64_t n_nodes;            /* nodes of the input graph (those in its node order)                           */
+    uint64_t n_isolated_nodes;   /* nodes clean_graph removed: no edge left                                      */
+    uint64_t n_candidates_in;    /* nodes with in-degree 0 and out-degree 1 at the start of the incoming pass    */
+    uint64_t n_candidates_out;   /* nodes with out-degree 0 and in-degree 1 at the start of the outgoing pass    */
+    uint64_t n_rounds_in;        /* rounds the device needed to settle the candidates in node order              */
+    uint64_t n_rounds_out;
+    float ms_setup, ms_incoming, ms_outgoing, ms_symmetric, ms_emit, ms_total;
+} po_tips_stats;
+
+/* `edges` is an edge result of this handle -- from po_layout_edges, the kept_out of po_layout_reduce or the kept_out
+ * of this call; it stays valid and unchanged.  The graph's nodes are those in the result's node order (below); a
+ * node without edges is a node until this call counts it as isolated.  In order:
+ *   1. remove_incoming_tips: tips = the nodes with in-degree 0 at the start, in node order.  For each tip s with
+ *      out-degree 1, on the graph as the tips before it left it: path = [s]; while out(curr) == 1 and in(curr) <= 1
+ *      the one successor is appended and becomes curr, and the edge's weight joins a signed 64-bit sum; a path of more
+ *      than max_tip_len + 1 nodes, or a sum above max_tip_len_bases, is no tip.  If the loop ends by its own condition
+ *      every edge of the path goes, the last one into the junction or dead end included;
+ *   2. remove_outgoing_tips: the same on the reversed graph (tips = nodes with out-degree 0, predecessors walked);
+ *   3. make_symmetric: one pass, (u, v) goes iff (v^1, u^1) is no longer an edge;
+ *   4. clean_graph: the nodes left without an edge are counted and leave the node order of kept_out.
+ * The result depends on the node order, as the reference's does; the device reproduces it exactly.
+ * edge_flags_out (may be NULL): po_result_count(edges) bytes in input order -- 0 kept, 1 incoming-tip edge,
+ * 2 outgoing-tip edge, 3 removed by the symmetry pass.  kept_out holds the kept edges in input order.
+ * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
+ * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips, merging of unambiguous paths, coverage and
+ * bubbles (assembler.py:173 on) are not part of this library. */
+po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
+                         po_result** kept_out);
+po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
+
+/* The nodes of an edge result's graph in the reference's order (`for n in g`: the order in which add_edge first saw
+ * each node, phasm/assembly_graph.py:136-179, without the nodes of contained reads), computed by po_layout_edges from
+ * the rows: a row reaches build_assembly_graph iff it passes the filters and no earlier row has marked one of its
+ * oriented reads contained (ContainedReads is stateful, phasm/filter.py:90-101); it inserts a, b, b^1, a^1
+ * (OVERLAP_AB) or b, a, a^1, b^1 (OVERLAP_BA).  *n_out = number of nodes; up to `cap` of them go to nodes_out. */
+po_status po_result_node_order(po_result* r, uint32_t* nodes_out, uint64_t cap, uint64_t* n_out);
+
+/* What the node order cost the last po_layout_edges call: two passes over the rows that run on every call, behind the
+ * times of po_layout_stats (whose ms_total does not include them). */
+typedef struct {
+    uint64_t n_rows;
+    float ms_first_contained;    /* first containing row per oriented node (with the memsets)                     */
+    float ms_rank;               /* first reaching (row, slot) per node                                           */
+    float ms_total;
+} po_node_order_stats;
+po_status po_get_node_order_stats(const po_handle* h, po_node_order_stats* out);
 
 /* Diagnostics for the test suite (no reference counterpart: addSequence copies its argument and
  * never touches it again, src/overlapper.cpp:22-26 -- these two calls let a test PROVE that of this library).

@@ -59,6 +59,30 @@ class PoReduceStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoTipsParams(ctypes.Structure):
+    _fields_ = [("max_tip_len", ctypes.c_uint32), ("max_tip_len_bases", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class PoTipsStats(ctypes.Structure):
+    _fields_ = [("n_edges_in", ctypes.c_uint64), ("n_in_tip_edges", ctypes.c_uint64), ("n_out_tip_edges", ctypes.c_uint64),
+                ("n_asymmetric", ctypes.c_uint64), ("n_edges_out", ctypes.c_uint64), ("n_nodes", ctypes.c_uint64),
+                ("n_isolated_nodes", ctypes.c_uint64), ("n_candidates_in", ctypes.c_uint64), ("n_candidates_out", ctypes.c_uint64),
+                ("n_rounds_in", ctypes.c_uint64), ("n_rounds_out", ctypes.c_uint64),
+                ("ms_setup", ctypes.c_float), ("ms_incoming", ctypes.c_float), ("ms_outgoing", ctypes.c_float),
+                ("ms_symmetric", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PoNodeOrderStats(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
+                ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoStats(ctypes.Structure):
     _fields_ = [
         ("bits_per_base", ctypes.c_uint32), ("kmer", ctypes.c_uint32),
@@ -139,6 +163,10 @@ SYMBOLS = [
     ("po_get_layout_stats", ctypes.c_int, [_P, ctypes.POINTER(PoLayoutStats)]),
     ("po_layout_reduce", ctypes.c_int, [_P, _P, ctypes.POINTER(PoReduceParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
     ("po_get_reduce_stats", ctypes.c_int, [_P, ctypes.POINTER(PoReduceStats)]),
+    ("po_layout_tips", ctypes.c_int, [_P, _P, ctypes.POINTER(PoTipsParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
+    ("po_get_tips_stats", ctypes.c_int, [_P, ctypes.POINTER(PoTipsStats)]),
+    ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),
     ("po_get_stats", ctypes.c_int, [_P, ctypes.POINTER(PoStats)]),
     ("po_last_error", ctypes.c_char_p, [_P]),
     ("po_debug_fault_backtrace", ctypes.c_int, [ctypes.c_int]),

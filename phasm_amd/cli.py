@@ -170,6 +170,19 @@ def daligner2gfa(args) -> int:
     return n_e
 
 
+def _int_in(lo: int, hi: int):
+    """argparse type: an integer in [lo, hi] (what the library's 32-bit parameters hold)."""
+    def parse(text: str) -> int:
+        try:
+            value = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError("%r is not an integer" % text)
+        if not lo <= value <= hi:
+            raise argparse.ArgumentTypeError("%d is not in [%d, %d]" % (value, lo, hi))
+        return value
+    return parse
+
+
 def layout_edges(args) -> int:
     ov = ExactOverlapper(device=getattr(args, "device", None))
     try:
@@ -197,6 +210,17 @@ def layout_edges(args) -> int:
                 rs = ov.reduce_stats()
                 logger.info("Removing %d transitive edges...", rs["n_transitive"])
                 logger.info("Removed %d asymmetric edges; graph has %d edges.", rs["n_asymmetric"], rs["n_edges_out"])
+            if getattr(args, "remove_tips", False):
+                # assembler.py:161-171: remove_tips, make_symmetric, clean_graph
+                # (one device call does all three, so the reference's two progress lines come before it)
+                logger.info("Removing tips...")
+                logger.info("Removing isolated nodes...")
+                kept = ov.layout_tips(edges, args.max_tip_length, args.max_tip_length_bases)
+                edges.free()
+                edges = kept
+                ts = ov.tips_stats()
+                logger.info("Removed %d tip edges, %d isolated nodes, %d asymmetric edges.",
+                            ts["n_in_tip_edges"] + ts["n_out_tip_edges"], ts["n_isolated_nodes"], ts["n_asymmetric"])
             return write_stage1_graph(args.output, ov.ids(), ov.lengths(), edges.rows(), edges)
         finally:
             edges.free()
@@ -236,6 +260,13 @@ def main(argv=None) -> int:
                         "graph cleaning, `phasm layout` stage 2) before writing it")
     q.add_argument("-F", "--length-fuzz", type=int, default=1000,
                    help="with --transitive-reduction: length fuzz of the transitive reduction (default: 1000)")
+    q.add_argument("--remove-tips", action="store_true",
+                   help="also remove short tips, make the graph symmetric and drop the isolated nodes (the next three "
+                        "operations of graph cleaning; after the transitive reduction when both are given)")
+    q.add_argument("-t", "--max-tip-length", type=_int_in(0, 2**32 - 1), default=4,
+                   help="with --remove-tips: maximum number of edges of a tip (default: 4)")
+    q.add_argument("--max-tip-length-bases", type=_int_in(-2**31, 2**31 - 1), default=5000,
+                   help="with --remove-tips: maximum length of a tip in bases (default: 5000)")
     q.add_argument("--device", type=int, default=None)
     q.add_argument("--las", default=None, metavar="LADUMP",
                    help="read the positional file as DBdump text and the alignments from this LAdump text")

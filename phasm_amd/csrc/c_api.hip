@@ -37,8 +37,14 @@
 #include "extend.hip.h"
 #include "layout.hip.h"
 #include "reduce.hip.h"
+#include "tips.hip.h"
 
 namespace {
+
+// workspaces of po_layout_tips (po_handle::d_tip)
+enum { TB_CNT, TB_OUTDEG, TB_OUTSUM, TB_INDEG, TB_INSUM, TB_MARK, TB_CAND, TB_CSTATE, TB_EFLAG, TB_FLAGS, TB_KEEP, TB_KOFF,
+       TB_TKEY, TB_TVAL, TB_ALIVE, TB_RCNT, TB_N };
+constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
     void* p = nullptr;
@@ -243,6 +249,7 @@ struct po_handle {
     DevBuf spare_rows;   // device buffers of freed results, kept for the next call (hipFree / hipMalloc of a
     DevBuf spare_cands;  // 50-170 MB buffer costs ~0.2 ms each and synchronises the device)
     DevBuf spare_edges;
+    DevBuf spare_nrank;   // the node-order buffer of the last edge result that was freed (po_result::d_nrank)
     HostBuf spare_host;    // pinned row buffer of a freed result, kept for the next po_result_rows
     HostBuf scratch_host;  // pinned landing zone for small device->host copies into caller memory
     // pinned result pool sized while the reads are added (result_pool_grow): bytes of total_bases it was sized for
@@ -367,7 +374,7 @@ struct po_handle {
     // layout stage 1 (po_layout_edges)
     bool segments_only = false;  // reads were added by po_add_segment: lengths and names, no sequence
     int ids_paired = -1;         // -1 unknown, 0/1: ids come in (name+"+", name+"-") pairs
-    hipEvent_t ev_lay[9] = {};   // [0..3] po_layout_edges, [4..8] po_layout_reduce
+    hipEvent_t ev_lay[18] = {};  // [0..3] po_layout_edges, [4..8] po_layout_reduce, [9..14] po_layout_tips, [15..17] node order
     DevBuf d_lay_len, d_lay_cnt, d_rflag, d_removed, d_ekey, d_ecnt, d_ewin, d_eoff;
     DevBuf d_efirst;             // table path: first writer row per winning row (the edges' rank, po_result::d_rank)
     po_layout_stats lstats = {};
@@ -376,6 +383,12 @@ struct po_handle {
     DevBuf d_red_cnt, d_red_deg, d_red_off, d_red_cur, d_red_tkey, d_red_ttgt, d_red_teid, d_red_ctgt, d_red_cw, d_red_ceid,
         d_red_cidpos, d_red_stgt, d_red_seid, d_red_state, d_red_flag1, d_red_flags, d_red_keep, d_red_koff;
     po_reduce_stats rstats = {};
+
+    // the node order of the stage-1 graph (k_layout_node_rank) and tip removal (po_layout_tips, tips.hip.h)
+    DevBuf d_lay_firstc;
+    DevBuf d_tip[TB_N];
+    po_tips_stats tstats = {};
+    po_node_order_stats nostats = {};
 };
 
 struct po_result {
@@ -393,6 +406,9 @@ struct po_result {
     // po_layout_edges through the table: the first writer row of every edge, its place in the reference's adjacency
     // OrderedDict (po_layout_reduce orders by it; empty = the emission order is that order already)
     DevBuf d_rank;
+    // edge results: (first reaching row << 2 | slot) per node, the place of the node in the reference's graph order
+    // (layout.hip.h, k_layout_node_rank; all ones = the node is not in the graph); po_layout_tips walks in this order
+    DevBuf d_nrank;
     // po_candidates_shard_into: the caller's buffer the candidates go to when they fit
     void* ext_dst = nullptr;
     uint64_t ext_cap = 0;
@@ -579,7 +595,7 @@ struct DevKit {
     hipStream_t stream = nullptr, copy_stream = nullptr, up_stream = nullptr, rc_stream = nullptr;
     hipEvent_t ev_sets[2][EV_N] = {};
     hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr, ev_meta = nullptr, ev_first = nullptr;
-    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[9] = {};
+    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[18] = {};
 
     uint64_t* pinned = nullptr;
     uint64_t* pinned_dev = nullptr;
@@ -2676,6 +2692,15 @@ po_status rows_to_device(po_handle* h, po_result* r) {
     return PO_OK;
 }
 
+// the node-order buffer of a new edge result: the one a freed result left behind, if it is large enough
+po_status ensure_nrank(po_handle* h, po_result* res, size_t bytes) {
+    if (!res->d_nrank.p && h->spare_nrank.p && h->spare_nrank.cap >= bytes) {
+        res->d_nrank = h->spare_nrank;
+        h->spare_nrank = DevBuf();
+    }
+    return ensure(h, res->d_nrank, bytes, 1.0, false);
+}
+
 po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm, uint8_t* removed_out, po_result* res) {
     PO_TRY(init_device(h));
     hipStream_t st = h->stream;
@@ -2791,6 +2816,25 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
         HIP_TRY(h, hipEventRecord(h->ev_lay[2], st));
     }
     HIP_TRY(h, hipEventRecord(h->ev_lay[3], st));
+    // the node order of this graph, for po_layout_tips.  Outside the times above, which are stage 1 as it was; these two
+    // passes have times of their own (po_get_node_order_stats)
+    po_node_order_stats& NO = h->nostats;
+    NO = po_node_order_stats();
+    NO.n_rows = n_rows;
+    PO_TRY(ensure_nrank(h, res, std::max<size_t>((size_t)n_nodes * 8, 256)));
+    HIP_TRY(h, hipEventRecord(h->ev_lay[15], st));
+    HIP_TRY(h, hipMemsetAsync(res->d_nrank.p, 0xFF, std::max<size_t>((size_t)n_nodes * 8, 256), st));
+    if (L.n_pass) {
+        PO_TRY(ensure(h, h->d_lay_firstc, ((size_t)n_nodes + 1) * 4));
+        HIP_TRY(h, hipMemsetAsync(h->d_lay_firstc.p, 0xFF, ((size_t)n_nodes + 1) * 4, st));
+        hipLaunchKernelGGL(po::k_layout_first_contained, dim3(stride_grid), dim3(256), 0, st, d_rows, n_rows,
+                           h->d_rflag.as<uint8_t>(), h->d_lay_firstc.as<uint32_t>());
+        HIP_TRY(h, hipEventRecord(h->ev_lay[16], st));
+        hipLaunchKernelGGL(po::k_layout_node_rank, dim3(stride_grid), dim3(256), 0, st, d_rows, n_rows, h->d_rflag.as<uint8_t>(),
+                           h->d_removed.as<uint8_t>(), h->d_lay_firstc.as<uint32_t>(), res->d_nrank.as<unsigned long long>());
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(h->ev_lay[17], st));
     if (removed_out && n_names) {
         PO_TRY(ensure_host(h, h->scratch_host, n_names));
         HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_removed.p, n_names, hipMemcpyDeviceToHost, st));
@@ -2803,6 +2847,11 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
     (void)hipEventElapsedTime(&L.ms_dedupe, h->ev_lay[1], h->ev_lay[2]);
     (void)hipEventElapsedTime(&L.ms_emit, h->ev_lay[2], h->ev_lay[3]);
     (void)hipEventElapsedTime(&L.ms_total, h->ev_lay[0], h->ev_lay[3]);
+    if (L.n_pass) {
+        (void)hipEventElapsedTime(&NO.ms_first_contained, h->ev_lay[15], h->ev_lay[16]);
+        (void)hipEventElapsedTime(&NO.ms_rank, h->ev_lay[16], h->ev_lay[17]);
+    }
+    (void)hipEventElapsedTime(&NO.ms_total, h->ev_lay[15], h->ev_lay[17]);
     return PO_OK;
 }
 
@@ -2823,9 +2872,15 @@ po_status run_reduce(po_handle* h, po_result* edges, const po_reduce_params& prm
         if (!e) HIP_TRY(h, hipEventCreate(&e));
     hipEvent_t* ev = h->ev_lay + 4;
     PO_TRY(rows_to_device(h, edges));
+    if (edges->d_nrank.p) {   // the node order goes with the graph: the reduction removes edges, never nodes
+        const size_t nb = std::max<size_t>((size_t)n_nodes * 8, 256);
+        PO_TRY(ensure_nrank(h, res, nb));
+        HIP_TRY(h, hipMemcpyAsync(res->d_nrank.p, edges->d_nrank.p, nb, hipMemcpyDeviceToDevice, st));
+    }
     if (n == 0 || n_nodes == 0) {
         if (n) return fail(h, PO_ERR_INVALID, "po_layout_reduce: edges on a handle without reads");
         PO_TRY(ensure(h, res->d_rows, 256, 1.0, false));
+        HIP_TRY(h, hipStreamSynchronize(st));
         return PO_OK;
     }
     const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n;
@@ -2910,6 +2965,165 @@ po_status run_reduce(po_handle* h, po_result* edges, const po_reduce_params& prm
     (void)hipEventElapsedTime(&R.ms_symmetric, ev[2], ev[3]);
     (void)hipEventElapsedTime(&R.ms_emit, ev[3], ev[4]);
     (void)hipEventElapsedTime(&R.ms_total, ev[0], ev[4]);
+    return PO_OK;
+}
+
+// ---- tip removal + make_symmetric + clean_graph (po_layout_tips): edges -> flags + kept edges + node order ------
+
+po_status run_tips(po_handle* h, po_result* edges, const po_tips_params& prm, uint8_t* flags_out, po_result* res) {
+    hipStream_t st = h->stream;
+    po_tips_stats& T = h->tstats;
+    T = po_tips_stats();
+    res->count = 0;
+    res->elem = sizeof(po_edge);
+    res->kind_edges = true;
+    const uint32_t n_nodes = (uint32_t)h->len.size();
+    if (edges->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_tips: too many edges for one call");
+    const uint32_t n = (uint32_t)edges->count;
+    T.n_edges_in = n;
+    if (!edges->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_layout_tips: the edge result carries no node order");
+    if (n && n_nodes == 0) return fail(h, PO_ERR_INVALID, "po_layout_tips: edges on a handle without reads");
+    for (hipEvent_t& e : h->ev_lay)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    hipEvent_t* ev = h->ev_lay + 9;
+    PO_TRY(rows_to_device(h, edges));
+    const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n + 1;
+    const uint32_t n_slots = 2 * n + 64;
+    DevBuf* B = h->d_tip;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[TB_CNT], 128));
+    PO_TRY(ensure(h, B[TB_RCNT], TIP_BATCH * 8));
+    for (int k : {TB_OUTDEG, TB_OUTSUM, TB_INDEG, TB_INSUM, TB_CAND}) PO_TRY(ensure(h, B[k], nn * 4));
+    PO_TRY(ensure(h, B[TB_MARK], nn * 8));
+    for (int k : {TB_CSTATE, TB_ALIVE}) PO_TRY(ensure(h, B[k], nn));
+    for (int k : {TB_EFLAG, TB_FLAGS, TB_KEEP}) PO_TRY(ensure(h, B[k], ne));
+    PO_TRY(ensure(h, B[TB_KOFF], (ne + 1) * 4));
+    PO_TRY(ensure(h, B[TB_TKEY], (size_t)n_slots * 8));
+    PO_TRY(ensure(h, B[TB_TVAL], (size_t)n_slots * 4));
+    const size_t nrank_bytes = std::max<size_t>((size_t)n_nodes * 8, 256);
+    PO_TRY(ensure_nrank(h, res, nrank_bytes));
+    const po::Edge* d_edges = edges->d_rows.as<po::Edge>();
+    const uint32_t* d_rank = edges->d_rank.p ? edges->d_rank.as<uint32_t>() : nullptr;
+    const unsigned long long* nrank = edges->d_nrank.as<unsigned long long>();
+    unsigned long long *cnt = B[TB_CNT].as<unsigned long long>(), *rcnt = B[TB_RCNT].as<unsigned long long>();
+    uint32_t *outdeg = B[TB_OUTDEG].as<uint32_t>(), *outsum = B[TB_OUTSUM].as<uint32_t>(), *indeg = B[TB_INDEG].as<uint32_t>(),
+             *insum = B[TB_INSUM].as<uint32_t>(), *cand = B[TB_CAND].as<uint32_t>();
+    unsigned long long* mark = B[TB_MARK].as<unsigned long long>();
+    uint8_t *cstate = B[TB_CSTATE].as<uint8_t>(), *eflag = B[TB_EFLAG].as<uint8_t>(), *flags = B[TB_FLAGS].as<uint8_t>(),
+            *keep = B[TB_KEEP].as<uint8_t>(), *alive = B[TB_ALIVE].as<uint8_t>();
+    unsigned long long* tkey = B[TB_TKEY].as<unsigned long long>();
+    uint32_t* tval = B[TB_TVAL].as<uint32_t>();
+    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
+    const uint32_t node_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_nodes, 256), (uint32_t)h->n_cu * 8));
+    // No truncation of the caller's bound: a walk never visits a node twice (its start has no in-edge, and every later
+    // node has exactly one when the walk leaves it -- tips.hip.h), so it holds at most n_nodes
+    // nodes and any bound of n_nodes or more decides as n_nodes does.  The cap keeps `max_len + 2` from wrapping and
+    // the chains that k_tips_mark follows, which do not stop at a visited node, short.
+    const uint32_t max_len = std::min<uint32_t>(prm.max_tip_len, n_nodes);
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    for (uint32_t* p : {outdeg, outsum, indeg, insum}) HIP_TRY(h, hipMemsetAsync(p, 0, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(alive, 0, nn, st));
+    HIP_TRY(h, hipMemsetAsync(tkey, 0xFF, (size_t)n_slots * 8, st));
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    if (n) {
+        hipLaunchKernelGGL(po::k_tips_degree, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_nodes, outdeg, outsum, indeg, insum,
+                           eflag, cnt);
+        hipLaunchKernelGGL(po::k_tips_insert, dim3(edge_grid), dim3(256), 0, st, d_edges, n, tkey, tval, n_slots);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::TC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    // (an edge that names a node the handle does not hold would index out of the degree arrays: nothing walks then)
+    if (h->pinned[16 + po::TC_INVALID]) return fail(h, PO_ERR_INVALID, "po_layout_tips: an edge names a read the handle does not hold");
+    // one pass of remove_incoming_tips (rev = 0) or remove_outgoing_tips (rev = 1): rounds until every candidate is resolved
+    auto pass = [&](int rev, uint8_t which, uint64_t& n_cand_out, uint64_t& rounds_out) -> po_status {
+        po::TipSide g = rev ? po::TipSide{indeg, insum, outdeg, outsum} : po::TipSide{outdeg, outsum, indeg, insum};
+        n_cand_out = rounds_out = 0;
+        if (n == 0) return PO_OK;
+        HIP_TRY(h, hipMemsetAsync(mark, 0xFF, nn * 8, st));
+        HIP_TRY(h, hipMemsetAsync(cnt + po::TC_CAND, 0, 8, st));
+        hipLaunchKernelGGL(po::k_tips_candidates, dim3(cdiv(n_nodes, 256)), dim3(256), 0, st, n_nodes, nrank, g.fdeg, g.bdeg, cand,
+                           cstate, cnt);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt + po::TC_CAND, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        const uint32_t n_cand = (uint32_t)h->pinned[16];
+        n_cand_out = n_cand;
+        // Rounds go out in batches, one readback per batch: round j of a batch counts the candidates it leaves unresolved
+        // in word j.  A round launched after the last candidate has resolved finds nothing to do.
+        uint32_t round = 0;
+        for (uint64_t unresolved = n_cand; unresolved;) {
+            const uint32_t batch = round == 0 ? 8u : (uint32_t)TIP_BATCH;
+            HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
+            for (uint32_t j = 0; j < batch; ++j) {
+                hipLaunchKernelGGL(po::k_tips_mark, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, rev, max_len, round + j,
+                                   cand, cstate, n_cand, nrank, g.fdeg, g.fsum, mark);
+                hipLaunchKernelGGL(po::k_tips_resolve, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, rev, max_len,
+                                   prm.max_tip_len_bases, round + j, which, cand, cstate, n_cand, nrank, g, mark, eflag, rcnt + j);
+            }
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            for (uint32_t j = 0; j < batch && unresolved; ++j, ++round) {
+                // (the unresolved candidate of the lowest rank holds its own key everywhere: a round that resolves none is a bug)
+                if (h->pinned[32 + j] >= unresolved) return fail(h, PO_ERR_HIP, "internal: a round of po_layout_tips resolved no candidate");
+                unresolved = h->pinned[32 + j];
+            }
+        }
+        rounds_out = round;
+        return PO_OK;
+    };
+    PO_TRY(pass(0, 1, T.n_candidates_in, T.n_rounds_in));
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    PO_TRY(pass(1, 2, T.n_candidates_out, T.n_rounds_out));
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    if (n) {
+        hipLaunchKernelGGL(po::k_tips_symmetric, dim3(edge_grid), dim3(256), 0, st, d_edges, n, tkey, tval, n_slots, eflag, flags,
+                           keep, cnt);
+        hipLaunchKernelGGL(po::k_tips_alive, dim3(edge_grid), dim3(256), 0, st, d_edges, n, keep, alive);
+    }
+    hipLaunchKernelGGL(po::k_tips_nodes, dim3(node_grid), dim3(256), 0, st, n_nodes, nrank, alive,
+                       res->d_nrank.as<unsigned long long>(), cnt);
+    HIP_TRY(h, hipGetLastError());
+    if ((size_t)n_nodes * 8 < nrank_bytes)   // (the tail of the smallest allocation: no node)
+        HIP_TRY(h, hipMemsetAsync(res->d_nrank.as<char>() + (size_t)n_nodes * 8, 0xFF, nrank_bytes - (size_t)n_nodes * 8, st));
+    HIP_TRY(h, hipEventRecord(ev[4], st));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::TC_N * 8, hipMemcpyDeviceToHost, st));
+    PO_TRY(prefix_sum<uint8_t>(h, keep, n, B[TB_KOFF].as<uint32_t>(), &h->pinned[2]));
+    if (flags_out && n) {
+        PO_TRY(ensure_host(h, h->scratch_host, n));
+        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, flags, n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_kept = h->pinned[2];
+    T.n_in_tip_edges = h->pinned[16 + po::TC_IN];
+    T.n_out_tip_edges = h->pinned[16 + po::TC_OUT];
+    T.n_asymmetric = h->pinned[16 + po::TC_ASYM];
+    T.n_nodes = h->pinned[16 + po::TC_NODES];
+    T.n_isolated_nodes = h->pinned[16 + po::TC_ISOLATED];
+    T.n_edges_out = n_kept;
+    if (flags_out && n) std::memcpy(flags_out, h->scratch_host.p, n);
+    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
+        res->d_rows = h->spare_edges;
+        h->spare_edges = DevBuf();
+    }
+    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
+    if (d_rank) PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_kept * 4, 256), 1.0, false));
+    if (n_kept) {
+        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, keep, B[TB_KOFF].as<uint32_t>(),
+                           res->d_rows.as<po::Edge>(), d_rank ? res->d_rank.as<uint32_t>() : nullptr);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(ev[5], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    res->count = n_kept;
+    (void)hipEventElapsedTime(&T.ms_setup, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&T.ms_incoming, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&T.ms_outgoing, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&T.ms_symmetric, ev[3], ev[4]);
+    (void)hipEventElapsedTime(&T.ms_emit, ev[4], ev[5]);
+    (void)hipEventElapsedTime(&T.ms_total, ev[0], ev[5]);
     return PO_OK;
 }
 
@@ -3289,17 +3503,18 @@ void po_destroy(po_handle* h) {
                           &h->d_table, &h->d_slot_cnt, &h->d_slot_cur, &h->d_slot_start, &h->d_read_slot, &h->d_chain,
                           &h->d_chain_tmp, &h->d_long_list, &h->d_entry_off, &h->d_bloom, &h->d_selfrep, &h->d_tile_count, &h->d_tile_off,
                           &h->d_ps_blocks, &h->d_scalars, &h->d_cand_a, &h->d_cand_p, &h->d_cand_b, &h->d_type,
-                          &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key, &h->d_pair_min, &h->spare_rows, &h->spare_cands, &h->spare_edges,
+                          &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key, &h->d_pair_min, &h->spare_rows, &h->spare_cands, &h->spare_edges, &h->spare_nrank,
                           &h->d_vlabel, &h->d_vrank, &h->d_vperm, &h->d_end_a, &h->d_end_b, &h->d_dpcnt, &h->d_lay_len, &h->d_lay_cnt, &h->d_rflag, &h->d_removed, &h->d_ekey, &h->d_ecnt,
                           &h->d_ewin, &h->d_eoff, &h->d_chain_state, &h->d_tail_state, &h->d_efirst,
                           &h->d_red_cnt, &h->d_red_deg, &h->d_red_off, &h->d_red_cur, &h->d_red_tkey, &h->d_red_ttgt, &h->d_red_teid,
                           &h->d_red_ctgt, &h->d_red_cw, &h->d_red_ceid, &h->d_red_cidpos, &h->d_red_stgt, &h->d_red_seid, &h->d_red_state,
-                          &h->d_red_flag1, &h->d_red_flags, &h->d_red_keep, &h->d_red_koff};
+                          &h->d_red_flag1, &h->d_red_flags, &h->d_red_keep, &h->d_red_koff, &h->d_lay_firstc};
         // every stream idle before anything the device (or a copy) may still touch is given back
         if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
         if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
         if (h->rc_stream) (void)hipStreamSynchronize(h->rc_stream);
         for (DevBuf* b : bufs) b->release();
+        for (DevBuf& b : h->d_tip) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -4616,8 +4831,14 @@ void po_result_free(po_result* r) {
             r->d_rows = DevBuf();
         }
     }
+    if (h && r->d_nrank.p && r->d_nrank.cap > h->spare_nrank.cap) {
+        h->spare_nrank.release();
+        h->spare_nrank = r->d_nrank;
+        r->d_nrank = DevBuf();
+    }
     r->d_rows.release();
     r->d_rank.release();
+    r->d_nrank.release();
     delete r;
 }
 
@@ -5033,6 +5254,7 @@ po_status po_layout_edges(po_handle* h, po_result* rows, const po_layout_params*
         if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
         r->d_rows.release();
         r->d_rank.release();
+        r->d_nrank.release();
         delete r;
         return st;
     }
@@ -5065,11 +5287,81 @@ po_status po_layout_reduce(po_handle* h, po_result* edges, const po_reduce_param
         if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
         r->d_rows.release();
         r->d_rank.release();
+        r->d_nrank.release();
         delete r;
         return st;
     }
     ++h->live_results;
     *kept_out = r;
+    return PO_OK;
+}
+
+po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
+                         po_result** kept_out) {
+    if (!h || !edges || !params || !kept_out) return PO_ERR_INVALID;
+    *kept_out = nullptr;
+    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_tips: the edges belong to another handle");
+    if (params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_tips: bad parameters");
+    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
+    const po_status dev = init_device(h);
+    if (dev != PO_OK) return dev;
+    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
+        return fail(h, PO_ERR_INVALID, "po_layout_tips needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips)");
+    po_result* r = new (std::nothrow) po_result();
+    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
+    r->h = h;
+    po_status st;
+    try {
+        st = run_tips(h, edges, *params, edge_flags_out, r);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_tips");
+    }
+    if (st != PO_OK) {
+        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
+        r->d_rows.release();
+        r->d_rank.release();
+        r->d_nrank.release();
+        delete r;
+        return st;
+    }
+    ++h->live_results;
+    *kept_out = r;
+    return PO_OK;
+}
+
+po_status po_get_node_order_stats(const po_handle* h, po_node_order_stats* out) {
+    if (!h || !out) return PO_ERR_INVALID;
+    *out = h->nostats;
+    return PO_OK;
+}
+
+po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out) {
+    if (!h || !out) return PO_ERR_INVALID;
+    *out = h->tstats;
+    return PO_OK;
+}
+
+po_status po_result_node_order(po_result* r, uint32_t* nodes_out, uint64_t cap, uint64_t* n_out) {
+    if (!r || !n_out || (!nodes_out && cap)) return PO_ERR_INVALID;
+    *n_out = 0;
+    po_handle* h = r->h;
+    if (!h) return PO_ERR_INVALID;
+    if (!r->kind_edges || !r->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_result_node_order needs an edge result");
+    const size_t n_nodes = h->len.size();
+    try {
+        std::vector<unsigned long long> rank(n_nodes);
+        (void)hipSetDevice(h->device);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (n_nodes) HIP_TRY(h, hipMemcpy(rank.data(), r->d_nrank.p, n_nodes * 8, hipMemcpyDeviceToHost));
+        std::vector<std::pair<unsigned long long, uint32_t>> order;
+        for (size_t i = 0; i < n_nodes; ++i)
+            if (rank[i] != po::NODE_NO_RANK) order.emplace_back(rank[i], (uint32_t)i);
+        std::sort(order.begin(), order.end());
+        *n_out = order.size();
+        for (size_t i = 0; i < order.size() && i < cap; ++i) nodes_out[i] = order[i].second;
+    } catch (const std::bad_alloc&) {
+        return fail(h, PO_ERR_NOMEM, "out of host memory in po_result_node_order");
+    }
     return PO_OK;
 }
 

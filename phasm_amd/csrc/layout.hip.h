@@ -308,6 +308,46 @@ __global__ __launch_bounds__(256) void k_layout_emit(const Row* __restrict__ row
     }
 }
 
+// The reference's NODE ORDER (`for n in g`: the order in which add_edge first saw each node), which its tip removal
+// visits the tips in (tips.hip.h).  It cannot be read off the edges: ContainedReads is stateful (filter.py:90-101), so a
+// row reaches build_assembly_graph iff it passes the stateless predicates and no EARLIER row has marked one of its two
+// oriented reads contained -- and it may bring in a node through an edge to a read that is found contained later.
+//   k_layout_first_contained   firstc[n] = the first row that marks node n contained (memset 0xFF = none)
+//   k_layout_node_rank         nrank[n] = the smallest (row << 2 | slot) over the reaching rows that name n, slots in the
+//                              order of the two add_edge calls (assembly_graph.py:146-176); nodes of contained reads, which
+//                              leave the graph in both orientations (assembler.py:113-126), keep no rank (memset 0xFF)
+__global__ __launch_bounds__(256) void k_layout_first_contained(const Row* __restrict__ rows, uint32_t n_rows,
+                                                                const uint8_t* __restrict__ rflag,
+                                                                uint32_t* __restrict__ firstc) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += gridDim.x * blockDim.x) {
+        const uint32_t f = rflag[i];
+        if (f & RF_INVALID) continue;
+        const uint32_t type = f & RF_TYPE;
+        if (type == LT_A_CONTAINED) atomicMin(&firstc[rows[i].a_idx], i);
+        else if (type == LT_B_CONTAINED) atomicMin(&firstc[rows[i].b_idx], i);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_layout_node_rank(const Row* __restrict__ rows, uint32_t n_rows,
+                                                          const uint8_t* __restrict__ rflag,
+                                                          const uint8_t* __restrict__ removed,
+                                                          const uint32_t* __restrict__ firstc,
+                                                          unsigned long long* __restrict__ nrank) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += gridDim.x * blockDim.x) {
+        const uint32_t f = rflag[i];
+        if ((f & RF_INVALID) || !(f & RF_PASS)) continue;
+        const Row r = rows[i];
+        if (firstc[r.a_idx] <= i || firstc[r.b_idx] <= i) continue;
+        const bool ab = (f & RF_TYPE) == LT_OVERLAP_AB;
+        // OVERLAP_AB: add_edge(a, b), add_edge(b^1, a^1); OVERLAP_BA: add_edge(b, a), add_edge(a^1, b^1)
+        const uint32_t n0 = ab ? r.a_idx : r.b_idx, n1 = ab ? r.b_idx : r.a_idx;
+        const uint32_t node[4] = {n0, n1, n1 ^ 1u, n0 ^ 1u};
+#pragma unroll
+        for (uint32_t s = 0; s < 4; ++s)
+            if (!removed[node[s] >> 1]) atomicMin(&nrank[node[s]], ((unsigned long long)i << 2) | s);
+    }
+}
+
 // number of removed reads (bytes set in removed[])
 __global__ __launch_bounds__(256) void k_count_bytes(const uint8_t* __restrict__ v, uint32_t n,
                                                      unsigned long long* __restrict__ out) {

@@ -12,7 +12,9 @@ through ``ContainedReads`` / ``MinReadLength`` / ``MinOverlapLength`` / ``MaxOve
 The first two operations of graph cleaning follow on request (``reduce=True`` / ``reduce_assembly_graph``):
 ``remove_transitive_edges`` (Myers' reduction, phasm/assembly_graph.py:182-264) and ``make_symmetric``
 (assembly_graph.py:429-443) as `phasm layout` applies them (assembler.py:145-159), by ``po_layout_reduce`` on
-the edges still in HBM.  Cleaning after that point (tips, bubbles, merging, assembler.py:161 on) is out of scope.
+the edges still in HBM, and then the next three (``tips=True`` / ``remove_tips``): ``remove_tips``, ``make_symmetric``
+and ``clean_graph`` (assembly_graph.py:267-394, :429-453; assembler.py:161-167) by ``po_layout_tips``, in the reference's
+node order.  Cleaning after that point (diamond tips, merging, coverage, bubbles, assembler.py:173 on) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -34,13 +36,18 @@ class AssemblyEdges:
     overlap_len) with u, v oriented-read indices into ``ids``; ``contained[i]`` tells that read i (nodes 2i,
     2i+1) was contained in another read and left the graph.  After ``reduce_assembly_graph``: ``edges`` are the
     edges left, ``flags`` has one byte per stage-1 edge in stage-1 order (0 kept, 1 transitive, 2 removed by the
-    symmetry pass) and ``reduce_stats`` the counts and times of ``po_layout_reduce``."""
+    symmetry pass) and ``reduce_stats`` the counts and times of ``po_layout_reduce``.  After ``remove_tips``: ``edges``
+    are the edges left, ``tip_flags`` has one byte per edge that went into tip removal, in that order (0 kept,
+    1 incoming-tip edge, 2 outgoing-tip edge, 3 removed by the symmetry pass) and ``tips_stats`` the counts, rounds and
+    times of ``po_layout_tips``."""
     edges: np.ndarray
     contained: np.ndarray
     ids: List[str]
     stats: dict
     flags: Optional[np.ndarray] = None
     reduce_stats: Optional[dict] = None
+    tip_flags: Optional[np.ndarray] = None
+    tips_stats: Optional[dict] = None
 
     def edge_tuples(self) -> List[Tuple[str, str, int, int]]:
         ids = self.ids
@@ -58,28 +65,55 @@ class AssemblyEdges:
 
 
 def reduce_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, length_fuzz: int = 1000,
-                          contained: Optional[np.ndarray] = None, stats: Optional[dict] = None) -> AssemblyEdges:
+                          contained: Optional[np.ndarray] = None, stats: Optional[dict] = None, tips: bool = False,
+                          max_tip_len: int = 4, max_tip_len_bases: int = 5000) -> AssemblyEdges:
     """``remove_transitive_edges(g, length_fuzz)`` + removal + ``make_symmetric`` on a ``layout_edges`` result of
-    ``ov`` (which stays valid): the edges left, plus the flag byte of every stage-1 edge."""
+    ``ov`` (which stays valid): the edges left, plus the flag byte of every stage-1 edge.  With ``tips`` the tip
+    removal follows on the reduced graph."""
     kept, flags = ov.layout_reduce(edges_result, length_fuzz, want_flags=True)
+    try:
+        if contained is None:
+            contained = np.zeros(len(ov) // 2, dtype=bool)
+        stats = stats if stats is not None else ov.layout_stats()
+        if tips:
+            out = remove_tips(ov, kept, max_tip_len, max_tip_len_bases, contained, stats)
+            out.flags, out.reduce_stats = flags, ov.reduce_stats()
+            return out
+        edges = kept.rows()
+    finally:
+        kept.free()
+    return AssemblyEdges(edges, contained, ov.ids(), stats, flags, ov.reduce_stats())
+
+
+def remove_tips(ov: ExactOverlapper, edges_result: OverlapResult, max_tip_len: int = 4, max_tip_len_bases: int = 5000,
+                contained: Optional[np.ndarray] = None, stats: Optional[dict] = None) -> AssemblyEdges:
+    """``remove_tips(g, max_tip_len, max_tip_len_bases)`` + ``make_symmetric`` + ``clean_graph`` on an edge result of
+    ``ov`` (which stays valid): the edges left, plus the flag byte of every input edge."""
+    kept, tip_flags = ov.layout_tips(edges_result, max_tip_len, max_tip_len_bases, want_flags=True)
     try:
         edges = kept.rows()
     finally:
         kept.free()
     if contained is None:
         contained = np.zeros(len(ov) // 2, dtype=bool)
-    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(), flags, ov.reduce_stats())
+    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
+                         tip_flags=tip_flags, tips_stats=ov.tips_stats())
 
 
 def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_length: int = 0,
                          min_overlap_length: int = 0, max_overhang_abs: int = 1000,
-                         max_overhang_rel: float = 0.8, reduce: bool = False, length_fuzz: int = 1000) -> AssemblyEdges:
+                         max_overhang_rel: float = 0.8, reduce: bool = False, length_fuzz: int = 1000, tips: bool = False,
+                         max_tip_len: int = 4, max_tip_len_bases: int = 5000) -> AssemblyEdges:
     """Filters + ``build_assembly_graph`` + contained-read removal on a row result of ``ov``; with ``reduce`` the
-    transitive reduction and the symmetry pass as well."""
+    transitive reduction and the symmetry pass as well; with ``tips`` the tip removal (after the reduction when both
+    are asked for)."""
     res, removed = ov.layout_edges(rows, min_read_length, min_overlap_length, max_overhang_abs, max_overhang_rel)
     try:
         if reduce:
-            return reduce_assembly_graph(ov, res, length_fuzz, removed.astype(bool), ov.layout_stats())
+            return reduce_assembly_graph(ov, res, length_fuzz, removed.astype(bool), ov.layout_stats(), tips, max_tip_len,
+                                         max_tip_len_bases)
+        if tips:
+            return remove_tips(ov, res, max_tip_len, max_tip_len_bases, removed.astype(bool), ov.layout_stats())
         edges = res.rows()
     finally:
         res.free()
@@ -87,13 +121,14 @@ def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_leng
 
 
 def layout_from_gfa(path: str, device: Optional[int] = None, reduce: bool = False, length_fuzz: int = 1000,
-                    **params) -> AssemblyEdges:
+                    tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 from an overlap file: native GFA2 read, then the device passes."""
     ov = ExactOverlapper(device=device)
     try:
         _, rows = ov.add_gfa(path)
         try:
-            return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, **{**DEFAULTS, **params})
+            return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
+                                        max_tip_len_bases=max_tip_len_bases, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -111,13 +146,15 @@ def load_daligner(ov: ExactOverlapper, db_input, las_input, translations=None) -
 
 
 def layout_from_daligner(db_input, las_input, translations=None, device: Optional[int] = None, reduce: bool = False,
-                         length_fuzz: int = 1000, **params) -> AssemblyEdges:
+                         length_fuzz: int = 1000, tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000,
+                         **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 straight from DAZZ_DB / DALIGNER dump text."""
     ov = ExactOverlapper(device=device)
     try:
         rows = load_daligner(ov, db_input, las_input, translations)
         try:
-            return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, **{**DEFAULTS, **params})
+            return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
+                                        max_tip_len_bases=max_tip_len_bases, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -125,10 +162,11 @@ def layout_from_daligner(db_input, las_input, translations=None, device: Optiona
 
 
 def layout_from_overlaps(ov: ExactOverlapper, min_length: int, reduce: bool = False, length_fuzz: int = 1000,
-                         **params) -> AssemblyEdges:
+                         tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, **params) -> AssemblyEdges:
     """Overlap + layout stage 1 without the file in between: the rows never leave HBM."""
     rows = ov.overlaps_result(min_length)
     try:
-        return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, **{**DEFAULTS, **params})
+        return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
+                                        max_tip_len_bases=max_tip_len_bases, **{**DEFAULTS, **params})
     finally:
         rows.free()

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoReduceParams, PoReduceStats, PoStats
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -129,6 +129,16 @@ class OverlapResult:
 
     def device_ptr(self) -> int:
         return int(self._lib.po_result_device_rows(self._ptr) or 0)
+
+    def node_order(self) -> np.ndarray:
+        """``po_result_node_order``: the nodes of an edge result's graph in the order the reference's graph holds
+        them (``for n in g``), which tip removal follows."""
+        n = ctypes.c_uint64()
+        _check(self._owner._h, self._lib.po_result_node_order(self._ptr, None, 0, ctypes.byref(n)))
+        out = np.zeros(int(n.value), dtype=np.uint32)
+        if len(out):
+            _check(self._owner._h, self._lib.po_result_node_order(self._ptr, out.ctypes.data_as(ctypes.c_void_p), len(out), ctypes.byref(n)))
+        return out
 
     def copy_to_device(self, dst_ptr: int, count: Optional[int] = None) -> None:
         """Device-to-device copy of the first ``count`` entries (default: all) to ``dst_ptr``."""
@@ -414,6 +424,35 @@ class ExactOverlapper:
     def reduce_stats(self) -> dict:
         s = PoReduceStats()
         _check(self._h, self._lib.po_get_reduce_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def layout_tips(self, edges: OverlapResult, max_tip_len: int = 4, max_tip_len_bases: int = 5000, want_flags: bool = False):
+        """``po_layout_tips``: ``remove_tips`` + ``make_symmetric`` + ``clean_graph`` on an edge result (of
+        ``layout_edges``, ``layout_reduce`` or this call), which stays valid.  Returns the kept edges (EDGE_DTYPE
+        result), or with ``want_flags`` the pair (kept edges, one byte per input edge: 0 kept, 1 incoming-tip edge,
+        2 outgoing-tip edge, 3 asymmetric)."""
+        if not 0 <= int(max_tip_len) < 2**32:
+            raise ValueError("max_tip_len does not fit 32 bits")
+        if not -2**31 <= int(max_tip_len_bases) < 2**31:
+            raise ValueError("max_tip_len_bases does not fit 32 bits")
+        prm = PoTipsParams(int(max_tip_len), int(max_tip_len_bases), 0)
+        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
+        r = ctypes.c_void_p()
+        _check(self._h, self._lib.po_layout_tips(
+            self._h, edges._ptr, ctypes.byref(prm),
+            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
+        kept = OverlapResult(self, r, EDGE_DTYPE)
+        return (kept, flags) if want_flags else kept
+
+    def node_order_stats(self) -> dict:
+        """Times of the two node-order passes of the last ``layout_edges`` call (not part of ``layout_stats``)."""
+        s = PoNodeOrderStats()
+        _check(self._h, self._lib.po_get_node_order_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def tips_stats(self) -> dict:
+        s = PoTipsStats()
+        _check(self._h, self._lib.po_get_tips_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def __len__(self) -> int:
