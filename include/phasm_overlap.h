@@ -421,11 +421,47 @@ typedef struct {
  * edge_flags_out (may be NULL): po_result_count(edges) bytes in input order -- 0 kept, 1 incoming-tip edge,
  * 2 outgoing-tip edge, 3 removed by the symmetry pass.  kept_out holds the kept edges in input order.
  * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
- * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips, merging of unambiguous paths, coverage and
- * bubbles (assembler.py:173 on) are not part of this library. */
+ * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds; merging of
+ * unambiguous paths, coverage and bubbles (assembler.py:185 on) are not part of this library. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The call between the two tip blocks of stage 2 (phasm/cli/assembler.py:173): remove_diamond_tips
+ * (phasm/assembly_graph.py:721-743) on an edge result of this handle.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_diamond_params;
+
+typedef struct {
+    uint64_t n_edges_in;         /* edges of the input graph                                                     */
+    uint64_t n_edges_out;        /* edges left: n_edges_in - 3 * n_diamonds                                      */
+    uint64_t n_nodes;            /* nodes of the input graph (those in its node order)                           */
+    uint64_t n_nodes_removed;    /* end nodes and pred1 nodes that left the graph: 2 * n_diamonds                */
+    uint64_t n_candidates;       /* nodes with out-degree 0 and in-degree 2 at the start                         */
+    uint64_t n_diamonds;         /* "Removed %d diamond tips", assembler.py:174                                  */
+    uint64_t n_rounds;           /* rounds the device needed to settle the candidates in node order              */
+    uint64_t n_invalid;          /* edges that name a read the handle does not hold (the call fails then)        */
+    float ms_setup, ms_rounds, ms_emit, ms_total;
+} po_diamond_stats;
+
+/* `edges` is an edge result of this handle -- from po_layout_edges, po_layout_reduce, po_layout_tips or this call; it
+ * stays valid and unchanged, its node order too.  end_nodes = the nodes with out-degree 0 and in-degree 2 at the start,
+ * in node order.  For each end node E, on the graph as the end nodes before it left it: among its two predecessors,
+ * pred1 is one with out-degree 1 and in-degree 1 and gt1 one with out-degree > 1; if both exist, E and pred1 are removed
+ * as NODES (one diamond): the two in-edges of E and the in-edge of pred1 go.  No symmetry pass and no clean_graph follow:
+ * a node left without an edge stays in the node order of kept_out (the next po_layout_tips counts it as isolated).  The
+ * result depends on the node order, as the reference's does; the device reproduces it exactly.
+ * params may be NULL.  edge_flags_out (may be NULL): po_result_count(edges) bytes in input order -- 0 kept, 1 in-edge of
+ * a removed end node, 2 the in-edge of a removed pred1.  kept_out holds the kept edges in input order and the node order
+ * of the input without the removed nodes.  There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result
+ * of another handle, a result that is no edge result, reserved != 0: PO_ERR_INVALID. */
+po_status po_layout_diamonds(po_handle* h, po_result* edges, const po_diamond_params* params, uint8_t* edge_flags_out,
+                             po_result** kept_out);
+po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out);
 
 /* The nodes of an edge result's graph in the reference's order (`for n in g`: the order in which add_edge first saw
  * each node, phasm/assembly_graph.py:136-179, without the nodes of contained reads), computed by po_layout_edges from

@@ -75,6 +75,20 @@ class PoTipsStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoDiamondParams(ctypes.Structure):
+    _fields_ = [("reserved", ctypes.c_uint32)]
+
+
+class PoDiamondStats(ctypes.Structure):
+    _fields_ = [("n_edges_in", ctypes.c_uint64), ("n_edges_out", ctypes.c_uint64), ("n_nodes", ctypes.c_uint64),
+                ("n_nodes_removed", ctypes.c_uint64), ("n_candidates", ctypes.c_uint64), ("n_diamonds", ctypes.c_uint64),
+                ("n_rounds", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64),
+                ("ms_setup", ctypes.c_float), ("ms_rounds", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -165,6 +179,8 @@ SYMBOLS = [
     ("po_get_reduce_stats", ctypes.c_int, [_P, ctypes.POINTER(PoReduceStats)]),
     ("po_layout_tips", ctypes.c_int, [_P, _P, ctypes.POINTER(PoTipsParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
     ("po_get_tips_stats", ctypes.c_int, [_P, ctypes.POINTER(PoTipsStats)]),
+    ("po_layout_diamonds", ctypes.c_int, [_P, _P, ctypes.POINTER(PoDiamondParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
+    ("po_get_diamond_stats", ctypes.c_int, [_P, ctypes.POINTER(PoDiamondStats)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),
     ("po_get_stats", ctypes.c_int, [_P, ctypes.POINTER(PoStats)]),

@@ -202,7 +202,8 @@ def layout_edges(args) -> int:
         logger.info("%d contained reads removed; %d alignments pass the filters; graph has %d edges.",
                     st["n_contained_reads"], st["n_pass"], st["n_edges"])
         try:
-            if getattr(args, "transitive_reduction", False):
+            clean = getattr(args, "clean", False)
+            if clean or getattr(args, "transitive_reduction", False):
                 # assembler.py:145-159: remove_transitive_edges, remove_edges_from, make_symmetric
                 kept = ov.layout_reduce(edges, args.length_fuzz)
                 edges.free()
@@ -210,12 +211,28 @@ def layout_edges(args) -> int:
                 rs = ov.reduce_stats()
                 logger.info("Removing %d transitive edges...", rs["n_transitive"])
                 logger.info("Removed %d asymmetric edges; graph has %d edges.", rs["n_asymmetric"], rs["n_edges_out"])
-            if getattr(args, "remove_tips", False):
+            if clean or getattr(args, "remove_tips", False):
                 # assembler.py:161-171: remove_tips, make_symmetric, clean_graph
                 # (one device call does all three, so the reference's two progress lines come before it)
                 logger.info("Removing tips...")
                 logger.info("Removing isolated nodes...")
                 kept = ov.layout_tips(edges, args.max_tip_length, args.max_tip_length_bases)
+                edges.free()
+                edges = kept
+                ts = ov.tips_stats()
+                logger.info("Removed %d tip edges, %d isolated nodes, %d asymmetric edges.",
+                            ts["n_in_tip_edges"] + ts["n_out_tip_edges"], ts["n_isolated_nodes"], ts["n_asymmetric"])
+            if clean or getattr(args, "remove_diamond_tips", False):
+                # assembler.py:173-174: remove_diamond_tips (no symmetry pass, no clean_graph)
+                kept = ov.layout_diamonds(edges)
+                edges.free()
+                edges = kept
+                logger.info("Removed %d diamond tips", ov.diamond_stats()["n_diamonds"])
+            if clean:
+                # assembler.py:176-182: remove_tips(g, max_tip_length) -- the base bound is the function's default --,
+                # make_symmetric, clean_graph; the counts are this block's own
+                logger.info("Removing tips (stage 2)...")
+                kept = ov.layout_tips(edges, args.max_tip_length, 5000)
                 edges.free()
                 edges = kept
                 ts = ov.tips_stats()
@@ -267,6 +284,13 @@ def main(argv=None) -> int:
                    help="with --remove-tips: maximum number of edges of a tip (default: 4)")
     q.add_argument("--max-tip-length-bases", type=_int_in(-2**31, 2**31 - 1), default=5000,
                    help="with --remove-tips: maximum length of a tip in bases (default: 5000)")
+    q.add_argument("--remove-diamond-tips", action="store_true",
+                   help="also remove the diamond tips (the call between the two tip blocks of graph cleaning; after "
+                        "--remove-tips when both are given)")
+    q.add_argument("--clean", action="store_true",
+                   help="graph cleaning as `phasm layout` runs it up to the merging of paths: transitive reduction, tips, "
+                        "diamond tips, tips again; -F, -t and --max-tip-length-bases apply (the last to the first tip "
+                        "block only, as in the reference)")
     q.add_argument("--device", type=int, default=None)
     q.add_argument("--las", default=None, metavar="LADUMP",
                    help="read the positional file as DBdump text and the alignments from this LAdump text")

@@ -38,6 +38,7 @@
 #include "layout.hip.h"
 #include "reduce.hip.h"
 #include "tips.hip.h"
+#include "diamond.hip.h"
 
 namespace {
 
@@ -374,7 +375,8 @@ struct po_handle {
     // layout stage 1 (po_layout_edges)
     bool segments_only = false;  // reads were added by po_add_segment: lengths and names, no sequence
     int ids_paired = -1;         // -1 unknown, 0/1: ids come in (name+"+", name+"-") pairs
-    hipEvent_t ev_lay[18] = {};  // [0..3] po_layout_edges, [4..8] po_layout_reduce, [9..14] po_layout_tips, [15..17] node order
+    hipEvent_t ev_lay[22] = {};  // [0..3] po_layout_edges, [4..8] po_layout_reduce, [9..14] po_layout_tips, [15..17] node order,
+                                 // [18..21] po_layout_diamonds
     DevBuf d_lay_len, d_lay_cnt, d_rflag, d_removed, d_ekey, d_ecnt, d_ewin, d_eoff;
     DevBuf d_efirst;             // table path: first writer row per winning row (the edges' rank, po_result::d_rank)
     po_layout_stats lstats = {};
@@ -388,6 +390,7 @@ struct po_handle {
     DevBuf d_lay_firstc;
     DevBuf d_tip[TB_N];
     po_tips_stats tstats = {};
+    po_diamond_stats dstats = {};   // po_layout_diamonds (diamond.hip.h) works in the buffers of d_tip: one call at a time
     po_node_order_stats nostats = {};
 };
 
@@ -595,7 +598,7 @@ struct DevKit {
     hipStream_t stream = nullptr, copy_stream = nullptr, up_stream = nullptr, rc_stream = nullptr;
     hipEvent_t ev_sets[2][EV_N] = {};
     hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr, ev_meta = nullptr, ev_first = nullptr;
-    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[18] = {};
+    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[22] = {};
 
     uint64_t* pinned = nullptr;
     uint64_t* pinned_dev = nullptr;
@@ -3127,6 +3130,138 @@ po_status run_tips(po_handle* h, po_result* edges, const po_tips_params& prm, ui
     return PO_OK;
 }
 
+// ---- remove_diamond_tips (po_layout_diamonds): edges -> flags + kept edges + node order ---------------------------
+
+po_status run_diamonds(po_handle* h, po_result* edges, uint8_t* flags_out, po_result* res) {
+    hipStream_t st = h->stream;
+    po_diamond_stats& D = h->dstats;
+    D = po_diamond_stats();
+    res->count = 0;
+    res->elem = sizeof(po_edge);
+    res->kind_edges = true;
+    const uint32_t n_nodes = (uint32_t)h->len.size();
+    if (edges->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_diamonds: too many edges for one call");
+    const uint32_t n = (uint32_t)edges->count;
+    D.n_edges_in = n;
+    if (!edges->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: the edge result carries no node order");
+    if (n && n_nodes == 0) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: edges on a handle without reads");
+    for (hipEvent_t& e : h->ev_lay)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    hipEvent_t* ev = h->ev_lay + 18;
+    PO_TRY(rows_to_device(h, edges));
+    // the workspaces of po_layout_tips under other names (grow-only, on the handle): OUTSUM / INSUM hold the min / max id
+    // of a node's in-edges, ALIVE the removed byte per node
+    const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n + 1;
+    DevBuf* B = h->d_tip;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[TB_CNT], 128));
+    PO_TRY(ensure(h, B[TB_RCNT], TIP_BATCH * 8));
+    for (int k : {TB_OUTDEG, TB_OUTSUM, TB_INDEG, TB_INSUM, TB_CAND}) PO_TRY(ensure(h, B[k], nn * 4));
+    PO_TRY(ensure(h, B[TB_MARK], nn * 8));
+    for (int k : {TB_CSTATE, TB_ALIVE}) PO_TRY(ensure(h, B[k], nn));
+    for (int k : {TB_EFLAG, TB_KEEP}) PO_TRY(ensure(h, B[k], ne));
+    PO_TRY(ensure(h, B[TB_KOFF], (ne + 1) * 4));
+    const size_t nrank_bytes = std::max<size_t>((size_t)n_nodes * 8, 256);
+    PO_TRY(ensure_nrank(h, res, nrank_bytes));
+    const po::Edge* d_edges = edges->d_rows.as<po::Edge>();
+    const uint32_t* d_rank = edges->d_rank.p ? edges->d_rank.as<uint32_t>() : nullptr;
+    const unsigned long long* nrank = edges->d_nrank.as<unsigned long long>();
+    unsigned long long *cnt = B[TB_CNT].as<unsigned long long>(), *rcnt = B[TB_RCNT].as<unsigned long long>();
+    uint32_t *outdeg = B[TB_OUTDEG].as<uint32_t>(), *indeg = B[TB_INDEG].as<uint32_t>(), *inmin = B[TB_OUTSUM].as<uint32_t>(),
+             *inmax = B[TB_INSUM].as<uint32_t>(), *cand = B[TB_CAND].as<uint32_t>();
+    unsigned long long* mark = B[TB_MARK].as<unsigned long long>();
+    uint8_t *cstate = B[TB_CSTATE].as<uint8_t>(), *eflag = B[TB_EFLAG].as<uint8_t>(), *keep = B[TB_KEEP].as<uint8_t>(),
+            *removed = B[TB_ALIVE].as<uint8_t>();
+    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
+    const uint32_t both_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(std::max(n, n_nodes), 256), (uint32_t)h->n_cu * 8));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    for (uint32_t* p : {outdeg, indeg, inmax}) HIP_TRY(h, hipMemsetAsync(p, 0, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(inmin, 0xFF, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(mark, 0xFF, nn * 8, st));
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    if (n) {
+        hipLaunchKernelGGL(po::k_diamond_degree, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_nodes, outdeg, indeg, inmin, inmax,
+                           eflag, cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (n_nodes) {
+        // (in stream order behind the degrees; with an invalid edge the degrees are incomplete and nothing is decided on them)
+        hipLaunchKernelGGL(po::k_diamond_candidates, dim3(cdiv(n_nodes, 256)), dim3(256), 0, st, n_nodes, nrank, outdeg, indeg, cand,
+                           cstate, removed, cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::DC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    D.n_invalid = h->pinned[16 + po::DC_INVALID];
+    // (an edge that names a node the handle does not hold would index out of the degree arrays: nothing is decided then)
+    if (D.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: an edge names a read the handle does not hold");
+    const uint32_t n_cand = (uint32_t)h->pinned[16 + po::DC_CAND];
+    D.n_candidates = n_cand;
+    // Rounds go out in batches, one readback per batch, as in po_layout_tips: round j of a batch counts the candidates it
+    // leaves unresolved in word j.  A round launched after the last candidate has resolved finds nothing to do.
+    uint32_t round = 0;
+    for (uint64_t unresolved = n_cand; unresolved;) {
+        const uint32_t batch = round == 0 ? 4u : (uint32_t)TIP_BATCH;
+        HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
+        for (uint32_t j = 0; j < batch; ++j) {
+            hipLaunchKernelGGL(po::k_diamond_mark, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, round + j, cand, cstate,
+                               n_cand, nrank, indeg, inmin, inmax, mark);
+            hipLaunchKernelGGL(po::k_diamond_resolve, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, round + j, cand, cstate,
+                               n_cand, nrank, outdeg, indeg, inmin, inmax, mark, eflag, removed, rcnt + j, cnt);
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        for (uint32_t j = 0; j < batch && unresolved; ++j, ++round) {
+            // (the unresolved candidate of the lowest rank holds its own key everywhere: a round that resolves none is a bug)
+            if (h->pinned[32 + j] >= unresolved) return fail(h, PO_ERR_HIP, "internal: a round of po_layout_diamonds resolved no candidate");
+            unresolved = h->pinned[32 + j];
+        }
+    }
+    D.n_rounds = round;
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    if (n || n_nodes) {
+        hipLaunchKernelGGL(po::k_diamond_nodes, dim3(both_grid), dim3(256), 0, st, n, n_nodes, eflag, keep, nrank, removed,
+                           res->d_nrank.as<unsigned long long>(), cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if ((size_t)n_nodes * 8 < nrank_bytes)   // (the tail of the smallest allocation: no node)
+        HIP_TRY(h, hipMemsetAsync(res->d_nrank.as<char>() + (size_t)n_nodes * 8, 0xFF, nrank_bytes - (size_t)n_nodes * 8, st));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::DC_N * 8, hipMemcpyDeviceToHost, st));
+    PO_TRY(prefix_sum<uint8_t>(h, keep, n, B[TB_KOFF].as<uint32_t>(), &h->pinned[2]));
+    if (flags_out && n) {
+        PO_TRY(ensure_host(h, h->scratch_host, n));
+        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, eflag, n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_kept = h->pinned[2];
+    D.n_diamonds = h->pinned[16 + po::DC_DIAMONDS];
+    D.n_nodes = h->pinned[16 + po::DC_NODES];
+    D.n_nodes_removed = h->pinned[16 + po::DC_REMOVED];
+    D.n_edges_out = n_kept;
+    if (flags_out && n) std::memcpy(flags_out, h->scratch_host.p, n);
+    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
+        res->d_rows = h->spare_edges;
+        h->spare_edges = DevBuf();
+    }
+    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
+    if (d_rank) PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_kept * 4, 256), 1.0, false));
+    if (n_kept) {
+        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, keep, B[TB_KOFF].as<uint32_t>(),
+                           res->d_rows.as<po::Edge>(), d_rank ? res->d_rank.as<uint32_t>() : nullptr);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    res->count = n_kept;
+    (void)hipEventElapsedTime(&D.ms_setup, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&D.ms_rounds, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&D.ms_emit, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&D.ms_total, ev[0], ev[3]);
+    return PO_OK;
+}
+
 // ---- GFA2 reader for `phasm layout` (S and E lines) ---------------------------------------------
 
 struct Field {
@@ -5326,6 +5461,46 @@ po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* p
     }
     ++h->live_results;
     *kept_out = r;
+    return PO_OK;
+}
+
+po_status po_layout_diamonds(po_handle* h, po_result* edges, const po_diamond_params* params, uint8_t* edge_flags_out,
+                             po_result** kept_out) {
+    if (!h || !edges || !kept_out) return PO_ERR_INVALID;
+    *kept_out = nullptr;
+    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: the edges belong to another handle");
+    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: bad parameters");
+    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
+    const po_status dev = init_device(h);
+    if (dev != PO_OK) return dev;
+    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
+        return fail(h, PO_ERR_INVALID,
+                    "po_layout_diamonds needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds)");
+    po_result* r = new (std::nothrow) po_result();
+    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
+    r->h = h;
+    po_status st;
+    try {
+        st = run_diamonds(h, edges, edge_flags_out, r);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_diamonds");
+    }
+    if (st != PO_OK) {
+        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
+        r->d_rows.release();
+        r->d_rank.release();
+        r->d_nrank.release();
+        delete r;
+        return st;
+    }
+    ++h->live_results;
+    *kept_out = r;
+    return PO_OK;
+}
+
+po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out) {
+    if (!h || !out) return PO_ERR_INVALID;
+    *out = h->dstats;
     return PO_OK;
 }
 

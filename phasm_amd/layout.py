@@ -14,7 +14,10 @@ The first two operations of graph cleaning follow on request (``reduce=True`` / 
 (assembly_graph.py:429-443) as `phasm layout` applies them (assembler.py:145-159), by ``po_layout_reduce`` on
 the edges still in HBM, and then the next three (``tips=True`` / ``remove_tips``): ``remove_tips``, ``make_symmetric``
 and ``clean_graph`` (assembly_graph.py:267-394, :429-453; assembler.py:161-167) by ``po_layout_tips``, in the reference's
-node order.  Cleaning after that point (diamond tips, merging, coverage, bubbles, assembler.py:173 on) is out of scope.
+node order, and ``remove_diamond_tips`` (assembly_graph.py:721-743; assembler.py:173) by ``po_layout_diamonds``
+(``remove_diamond_tips`` here).  ``clean_assembly_graph`` / ``clean=True`` runs the whole sequence of assembler.py:145-182
+in one call -- reduction, tips, diamond tips, tips again -- and tells for every stage-1 edge which step removed it.
+Cleaning after that point (merging of unambiguous paths, coverage, bubbles, assembler.py:185 on) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -39,7 +42,11 @@ class AssemblyEdges:
     symmetry pass) and ``reduce_stats`` the counts and times of ``po_layout_reduce``.  After ``remove_tips``: ``edges``
     are the edges left, ``tip_flags`` has one byte per edge that went into tip removal, in that order (0 kept,
     1 incoming-tip edge, 2 outgoing-tip edge, 3 removed by the symmetry pass) and ``tips_stats`` the counts, rounds and
-    times of ``po_layout_tips``."""
+    times of ``po_layout_tips``.  After ``remove_diamond_tips``: ``diamond_flags`` has one byte per edge that went into
+    it (0 kept, 1 in-edge of a removed end node, 2 the in-edge of a removed pred1) and ``diamond_stats`` the counts, rounds
+    and times of ``po_layout_diamonds``.  After ``clean_assembly_graph``: ``edges`` are the edges left by the whole
+    chain, ``removed_by`` has one byte per stage-1 edge in stage-1 order (``REMOVED_BY``) and ``clean_stats`` the stats of
+    the four device calls in order (reduce, tips, diamonds, tips)."""
     edges: np.ndarray
     contained: np.ndarray
     ids: List[str]
@@ -48,6 +55,10 @@ class AssemblyEdges:
     reduce_stats: Optional[dict] = None
     tip_flags: Optional[np.ndarray] = None
     tips_stats: Optional[dict] = None
+    diamond_flags: Optional[np.ndarray] = None
+    diamond_stats: Optional[dict] = None
+    removed_by: Optional[np.ndarray] = None
+    clean_stats: Optional[List[dict]] = None
 
     def edge_tuples(self) -> List[Tuple[str, str, int, int]]:
         ids = self.ids
@@ -100,15 +111,73 @@ def remove_tips(ov: ExactOverlapper, edges_result: OverlapResult, max_tip_len: i
                          tip_flags=tip_flags, tips_stats=ov.tips_stats())
 
 
+def remove_diamond_tips(ov: ExactOverlapper, edges_result: OverlapResult, contained: Optional[np.ndarray] = None,
+                        stats: Optional[dict] = None) -> AssemblyEdges:
+    """``remove_diamond_tips(g)`` on an edge result of ``ov`` (which stays valid): the edges left, plus the flag byte of
+    every input edge.  Nodes the call leaves without an edge stay nodes (no ``clean_graph`` follows in the reference)."""
+    kept, diamond_flags = ov.layout_diamonds(edges_result, want_flags=True)
+    try:
+        edges = kept.rows()
+    finally:
+        kept.free()
+    if contained is None:
+        contained = np.zeros(len(ov) // 2, dtype=bool)
+    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
+                         diamond_flags=diamond_flags, diamond_stats=ov.diamond_stats())
+
+
+# ``AssemblyEdges.removed_by``: which step of assembler.py:145-182 removed a stage-1 edge
+REMOVED_BY = {0: "kept", 1: "transitive", 2: "asymmetric after the reduction", 3: "incoming tip", 4: "outgoing tip",
+              5: "asymmetric after the tips", 6: "in-edge of a diamond's end node", 7: "in-edge of a diamond's pred1",
+              8: "incoming tip (stage 2)", 9: "outgoing tip (stage 2)", 10: "asymmetric after the tips (stage 2)"}
+_REMOVED_BY_BASE = (0, 2, 5, 7)   # reduce flags 1-2, tips 1-3, diamonds 1-2, tips 1-3
+
+
+def clean_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, length_fuzz: int = 1000, max_tip_len: int = 4,
+                         max_tip_len_bases: int = 5000, contained: Optional[np.ndarray] = None,
+                         stats: Optional[dict] = None) -> AssemblyEdges:
+    """Graph cleaning as `phasm layout` runs it up to the merging of paths (assembler.py:145-182) on a ``layout_edges``
+    result of ``ov`` (which stays valid): reduction + symmetry, tips with both bounds + symmetry + isolated nodes, diamond
+    tips, tips again with ``max_tip_len`` and the function's own default of 5000 bases (the reference's second call
+    passes no base bound) + symmetry + isolated nodes.  Four device calls; the edges stay in HBM in between."""
+    steps = (lambda r: ov.layout_reduce(r, length_fuzz, want_flags=True), ov.reduce_stats), \
+            (lambda r: ov.layout_tips(r, max_tip_len, max_tip_len_bases, want_flags=True), ov.tips_stats), \
+            (lambda r: ov.layout_diamonds(r, want_flags=True), ov.diamond_stats), \
+            (lambda r: ov.layout_tips(r, max_tip_len, 5000, want_flags=True), ov.tips_stats)
+    removed_by = np.zeros(len(edges_result), dtype=np.uint8)
+    live = np.arange(len(edges_result))
+    clean_stats = []
+    cur = edges_result
+    try:
+        for (call, call_stats), base in zip(steps, _REMOVED_BY_BASE):
+            kept, flags = call(cur)
+            if cur is not edges_result:
+                cur.free()
+            cur = kept
+            clean_stats.append(call_stats())
+            removed_by[live[flags != 0]] = flags[flags != 0] + base
+            live = live[flags == 0]
+        edges = cur.rows()
+    finally:
+        if cur is not edges_result:
+            cur.free()
+    if contained is None:
+        contained = np.zeros(len(ov) // 2, dtype=bool)
+    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
+                         removed_by=removed_by, clean_stats=clean_stats)
+
+
 def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_length: int = 0,
                          min_overlap_length: int = 0, max_overhang_abs: int = 1000,
                          max_overhang_rel: float = 0.8, reduce: bool = False, length_fuzz: int = 1000, tips: bool = False,
-                         max_tip_len: int = 4, max_tip_len_bases: int = 5000) -> AssemblyEdges:
+                         max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False) -> AssemblyEdges:
     """Filters + ``build_assembly_graph`` + contained-read removal on a row result of ``ov``; with ``reduce`` the
     transitive reduction and the symmetry pass as well; with ``tips`` the tip removal (after the reduction when both
-    are asked for)."""
+    are asked for); with ``clean`` the whole of ``clean_assembly_graph`` instead of either."""
     res, removed = ov.layout_edges(rows, min_read_length, min_overlap_length, max_overhang_abs, max_overhang_rel)
     try:
+        if clean:
+            return clean_assembly_graph(ov, res, length_fuzz, max_tip_len, max_tip_len_bases, removed.astype(bool), ov.layout_stats())
         if reduce:
             return reduce_assembly_graph(ov, res, length_fuzz, removed.astype(bool), ov.layout_stats(), tips, max_tip_len,
                                          max_tip_len_bases)
@@ -121,14 +190,15 @@ def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_leng
 
 
 def layout_from_gfa(path: str, device: Optional[int] = None, reduce: bool = False, length_fuzz: int = 1000,
-                    tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, **params) -> AssemblyEdges:
+                    tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
+                    **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 from an overlap file: native GFA2 read, then the device passes."""
     ov = ExactOverlapper(device=device)
     try:
         _, rows = ov.add_gfa(path)
         try:
             return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -147,14 +217,14 @@ def load_daligner(ov: ExactOverlapper, db_input, las_input, translations=None) -
 
 def layout_from_daligner(db_input, las_input, translations=None, device: Optional[int] = None, reduce: bool = False,
                          length_fuzz: int = 1000, tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000,
-                         **params) -> AssemblyEdges:
+                         clean: bool = False, **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 straight from DAZZ_DB / DALIGNER dump text."""
     ov = ExactOverlapper(device=device)
     try:
         rows = load_daligner(ov, db_input, las_input, translations)
         try:
             return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -162,11 +232,12 @@ def layout_from_daligner(db_input, las_input, translations=None, device: Optiona
 
 
 def layout_from_overlaps(ov: ExactOverlapper, min_length: int, reduce: bool = False, length_fuzz: int = 1000,
-                         tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, **params) -> AssemblyEdges:
+                         tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
+                         **params) -> AssemblyEdges:
     """Overlap + layout stage 1 without the file in between: the rows never leave HBM."""
     rows = ov.overlaps_result(min_length)
     try:
         return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, **{**DEFAULTS, **params})
     finally:
         rows.free()

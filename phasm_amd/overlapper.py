@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -443,6 +443,25 @@ class ExactOverlapper:
             flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
         kept = OverlapResult(self, r, EDGE_DTYPE)
         return (kept, flags) if want_flags else kept
+
+    def layout_diamonds(self, edges: OverlapResult, want_flags: bool = False):
+        """``po_layout_diamonds``: ``remove_diamond_tips`` on an edge result (of ``layout_edges``, ``layout_reduce``,
+        ``layout_tips`` or this call), which stays valid.  Returns the kept edges (EDGE_DTYPE result), or with
+        ``want_flags`` the pair (kept edges, one byte per input edge: 0 kept, 1 in-edge of a removed end node, 2 the
+        in-edge of a removed pred1).  Nodes left without an edge stay in the result's node order."""
+        prm = PoDiamondParams(0)
+        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
+        r = ctypes.c_void_p()
+        _check(self._h, self._lib.po_layout_diamonds(
+            self._h, edges._ptr, ctypes.byref(prm),
+            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
+        kept = OverlapResult(self, r, EDGE_DTYPE)
+        return (kept, flags) if want_flags else kept
+
+    def diamond_stats(self) -> dict:
+        s = PoDiamondStats()
+        _check(self._h, self._lib.po_get_diamond_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
 
     def node_order_stats(self) -> dict:
         """Times of the two node-order passes of the last ``layout_edges`` call (not part of ``layout_stats``)."""
