@@ -421,8 +421,8 @@ typedef struct {
  * edge_flags_out (may be NULL): po_result_count(edges) bytes in input order -- 0 kept, 1 incoming-tip edge,
  * 2 outgoing-tip edge, 3 removed by the symmetry pass.  kept_out holds the kept edges in input order.
  * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
- * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds; merging of
- * unambiguous paths, coverage and bubbles (assembler.py:185 on) are not part of this library. */
+ * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds, the merging
+ * of unambiguous paths with po_layout_merge; coverage and bubbles (assembler.py:188 on) are not part of this library. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -462,6 +462,60 @@ typedef struct {
 po_status po_layout_diamonds(po_handle* h, po_result* edges, const po_diamond_params* params, uint8_t* edge_flags_out,
                              po_result** kept_out);
 po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The last call of stage 2 that changes the graph before `phasm layout` writes it (phasm/cli/assembler.py:184-186):
+ * merge_unambiguous_paths (phasm/assembly_graph.py:456-541) on an edge result of this handle.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_merge_params;
+
+typedef struct {
+    uint64_t n_edges_in;         /* edges of the input graph                                                     */
+    uint64_t n_edges_out;        /* edges left: n_edges_in - (n_nodes_merged - n_merged)                         */
+    uint64_t n_nodes;            /* nodes of the input graph (those in its node order)                           */
+    uint64_t n_merged;           /* merged nodes K                                                               */
+    uint64_t n_nodes_merged;     /* "Merged %d nodes.", assembler.py:186                                         */
+    uint64_t max_path_nodes;     /* nodes of the longest path                                                    */
+    uint64_t n_self_loops;       /* merged nodes that got a self-loop from the edge (last node -> head)          */
+    uint64_t n_cycle_nodes;      /* nodes with a link in and out that reached no head (they stay as they are)    */
+    uint64_t n_rounds;           /* pointer-jumping rounds run: at most ceil(log2(n_nodes)) + 1                  */
+    uint64_t n_overflow;         /* weights that do not fit int32 / ids that do not fit uint32 (the call fails)  */
+    uint64_t n_invalid;          /* edges that name a read the handle does not hold (the call fails then)        */
+    float ms_links, ms_rank, ms_number, ms_emit, ms_total;
+} po_merge_stats;
+
+/* `edges` is an edge result of this handle -- from po_layout_edges, po_layout_reduce, po_layout_tips or
+ * po_layout_diamonds; it stays valid and unchanged, its node order too.  With distinct edges (u, v, weight, overlap_len):
+ * link(u) = v iff u has one out-edge, into v, and v has one in-edge.  A head is a node with a link out and none in; its
+ * path is the head followed by its links (at least two nodes).  Nodes on cycles of links stay as they are.  Paths are
+ * numbered k = 0, 1, ... by the rank of their head in the node order (the reference's "merged%d", strand +).  An input
+ * edge that is a link of a path goes.  Every other edge (u, v) stays, in input order: u on a path (its last node) is
+ * renamed to the merged node and weight += the sum of the path's link weights; v on a path (its head) is renamed;
+ * overlap_len stays.  Merged node k is written as n_nodes + k, n_nodes = po_num_sequences(h).  An edge from a path's last
+ * node to its own head becomes a self-loop of the merged node.  The node order of merged_out: the unmerged nodes in their
+ * old order, then the merged nodes by k.
+ * params may be NULL.  edge_flags_out (may be NULL): po_result_count(edges) bytes in input order -- 0 kept as it is,
+ * 1 link of a path (gone), 2 kept with a renamed end or a raised weight.  merged_out is a MERGED GRAPH: po_result_count,
+ * po_result_rows and po_result_node_order work on it; po_layout_reduce, _tips, _diamonds and _merge refuse it with
+ * PO_ERR_INVALID (their kernels index by oriented read).  A weight that does not fit int32 or an id that does not fit
+ * uint32: PO_ERR_INVALID and n_overflow > 0, never a wrapped value.  There is no CPU fallback: without a GPU the call
+ * returns PO_ERR_HIP.  A result of another handle, a result that is no edge result, reserved != 0: PO_ERR_INVALID. */
+po_status po_layout_merge(po_handle* h, po_result* edges, const po_merge_params* params, uint8_t* edge_flags_out,
+                          po_result** merged_out);
+po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out);
+
+/* The merged nodes of a po_layout_merge result: *n_paths = K and *n_members = the nodes on paths; then, up to the caps,
+ * offsets_out[K + 1] (members of path k at [offsets[k], offsets[k + 1])), members_out (the path's nodes in order),
+ * prefix_out (one per member: the weight of the link out of it, 0 for the last) and lengths_out[K] (the sum of the
+ * prefixes plus the length of the last read).  Arrays are written only when the cap holds all of them (cap_paths >= K
+ * for offsets and lengths, cap_members >= n_members for members and prefixes); any of them may be NULL.  On anything
+ * but a merged graph: PO_ERR_INVALID. */
+po_status po_result_merged_paths(po_result* merged, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out,
+                                 uint64_t cap_paths, uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members,
+                                 int64_t* lengths_out);
 
 /* The nodes of an edge result's graph in the reference's order (`for n in g`: the order in which add_edge first saw
  * each node, phasm/assembly_graph.py:136-179, without the nodes of contained reads), computed by po_layout_edges from

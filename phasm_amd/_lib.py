@@ -89,6 +89,22 @@ class PoDiamondStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoMergeParams(ctypes.Structure):
+    _fields_ = [("reserved", ctypes.c_uint32)]
+
+
+class PoMergeStats(ctypes.Structure):
+    _fields_ = [("n_edges_in", ctypes.c_uint64), ("n_edges_out", ctypes.c_uint64), ("n_nodes", ctypes.c_uint64),
+                ("n_merged", ctypes.c_uint64), ("n_nodes_merged", ctypes.c_uint64), ("max_path_nodes", ctypes.c_uint64),
+                ("n_self_loops", ctypes.c_uint64), ("n_cycle_nodes", ctypes.c_uint64), ("n_rounds", ctypes.c_uint64),
+                ("n_overflow", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64),
+                ("ms_links", ctypes.c_float), ("ms_rank", ctypes.c_float), ("ms_number", ctypes.c_float), ("ms_emit", ctypes.c_float),
+                ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -181,6 +197,10 @@ SYMBOLS = [
     ("po_get_tips_stats", ctypes.c_int, [_P, ctypes.POINTER(PoTipsStats)]),
     ("po_layout_diamonds", ctypes.c_int, [_P, _P, ctypes.POINTER(PoDiamondParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
     ("po_get_diamond_stats", ctypes.c_int, [_P, ctypes.POINTER(PoDiamondStats)]),
+    ("po_layout_merge", ctypes.c_int, [_P, _P, ctypes.POINTER(PoMergeParams), ctypes.c_void_p, ctypes.POINTER(_P)]),
+    ("po_get_merge_stats", ctypes.c_int, [_P, ctypes.POINTER(PoMergeStats)]),
+    ("po_result_merged_paths", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),
     ("po_get_stats", ctypes.c_int, [_P, ctypes.POINTER(PoStats)]),

@@ -202,7 +202,8 @@ def layout_edges(args) -> int:
         logger.info("%d contained reads removed; %d alignments pass the filters; graph has %d edges.",
                     st["n_contained_reads"], st["n_pass"], st["n_edges"])
         try:
-            clean = getattr(args, "clean", False)
+            merge = getattr(args, "merge", False)
+            clean = getattr(args, "clean", False) or merge
             if clean or getattr(args, "transitive_reduction", False):
                 # assembler.py:145-159: remove_transitive_edges, remove_edges_from, make_symmetric
                 kept = ov.layout_reduce(edges, args.length_fuzz)
@@ -238,6 +239,13 @@ def layout_edges(args) -> int:
                 ts = ov.tips_stats()
                 logger.info("Removed %d tip edges, %d isolated nodes, %d asymmetric edges.",
                             ts["n_in_tip_edges"] + ts["n_out_tip_edges"], ts["n_isolated_nodes"], ts["n_asymmetric"])
+            if merge:
+                # assembler.py:184-186 and the file of :195-212 (gfa2_write_graph): S lines in node order, F lines behind
+                # a merged node's S line, E lines in the result's own order
+                logger.info("Merging unambiguous paths...")
+                g = layout_mod.merge_unambiguous_paths(ov, edges)
+                logger.info("Merged %d nodes.", g.merge_stats["n_nodes_merged"])
+                return layout_mod.write_merged_graph(args.output, g)
             return write_stage1_graph(args.output, ov.ids(), ov.lengths(), edges.rows(), edges)
         finally:
             edges.free()
@@ -291,6 +299,9 @@ def main(argv=None) -> int:
                    help="graph cleaning as `phasm layout` runs it up to the merging of paths: transitive reduction, tips, "
                         "diamond tips, tips again; -F, -t and --max-tip-length-bases apply (the last to the first tip "
                         "block only, as in the reference)")
+    q.add_argument("--merge", action="store_true",
+                   help="graph cleaning as --clean, then merge the unambiguous paths and write the graph file of `phasm "
+                        "layout`: S lines in node order, F lines for the reads of every merged node, E lines")
     q.add_argument("--device", type=int, default=None)
     q.add_argument("--las", default=None, metavar="LADUMP",
                    help="read the positional file as DBdump text and the alignments from this LAdump text")

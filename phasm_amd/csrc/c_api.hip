@@ -39,12 +39,19 @@
 #include "reduce.hip.h"
 #include "tips.hip.h"
 #include "diamond.hip.h"
+#include "merge.hip.h"
 
 namespace {
 
 // workspaces of po_layout_tips (po_handle::d_tip)
 enum { TB_CNT, TB_OUTDEG, TB_OUTSUM, TB_INDEG, TB_INSUM, TB_MARK, TB_CAND, TB_CSTATE, TB_EFLAG, TB_FLAGS, TB_KEEP, TB_KOFF,
        TB_TKEY, TB_TVAL, TB_ALIVE, TB_RCNT, TB_N };
+// workspaces of po_layout_merge (merge.hip.h)
+enum { MB_CNT, MB_RCNT, MB_OUTDEG, MB_INDEG, MB_OUTE, MB_INE, MB_LINK, MB_BACK, MB_JB0, MB_JB1, MB_HOPS0, MB_HOPS1, MB_WS0, MB_WS1,
+       MB_HKEY, MB_HVAL, MB_HLEN, MB_HSUM, MB_PATHK, MB_LENS, MB_PSUM, MB_NPATH, MB_NPOS, MB_EFLAG, MB_KEEP, MB_KOFF, MB_TMP, MB_LEN,
+       MB_N };
+// events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
+constexpr int EV_LAY_N = 27;
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -375,8 +382,8 @@ struct po_handle {
     // layout stage 1 (po_layout_edges)
     bool segments_only = false;  // reads were added by po_add_segment: lengths and names, no sequence
     int ids_paired = -1;         // -1 unknown, 0/1: ids come in (name+"+", name+"-") pairs
-    hipEvent_t ev_lay[22] = {};  // [0..3] po_layout_edges, [4..8] po_layout_reduce, [9..14] po_layout_tips, [15..17] node order,
-                                 // [18..21] po_layout_diamonds
+    hipEvent_t ev_lay[EV_LAY_N] = {};  // [0..3] po_layout_edges, [4..8] po_layout_reduce, [9..14] po_layout_tips, [15..17] node order,
+                                 // [18..21] po_layout_diamonds, [22..26] po_layout_merge
     DevBuf d_lay_len, d_lay_cnt, d_rflag, d_removed, d_ekey, d_ecnt, d_ewin, d_eoff;
     DevBuf d_efirst;             // table path: first writer row per winning row (the edges' rank, po_result::d_rank)
     po_layout_stats lstats = {};
@@ -392,6 +399,10 @@ struct po_handle {
     po_tips_stats tstats = {};
     po_diamond_stats dstats = {};   // po_layout_diamonds (diamond.hip.h) works in the buffers of d_tip: one call at a time
     po_node_order_stats nostats = {};
+
+    // merging of unambiguous paths (po_layout_merge, merge.hip.h)
+    DevBuf d_mrg[MB_N];
+    po_merge_stats mstats = {};
 };
 
 struct po_result {
@@ -412,6 +423,11 @@ struct po_result {
     // edge results: (first reaching row << 2 | slot) per node, the place of the node in the reference's graph order
     // (layout.hip.h, k_layout_node_rank; all ones = the node is not in the graph); po_layout_tips walks in this order
     DevBuf d_nrank;
+    // po_layout_merge: a merged graph -- node ids >= the handle's reads name merged nodes (d_nrank holds their ranks too);
+    // the tables of po_result_merged_paths
+    bool merged = false;
+    uint64_t n_merged = 0, n_members = 0;
+    DevBuf d_moff, d_member, d_prefix, d_mlen;
     // po_candidates_shard_into: the caller's buffer the candidates go to when they fit
     void* ext_dst = nullptr;
     uint64_t ext_cap = 0;
@@ -598,11 +614,12 @@ struct DevKit {
     hipStream_t stream = nullptr, copy_stream = nullptr, up_stream = nullptr, rc_stream = nullptr;
     hipEvent_t ev_sets[2][EV_N] = {};
     hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr, ev_meta = nullptr, ev_first = nullptr;
-    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[22] = {};
+    hipEvent_t ev_piece[PO_MAX_PIECES] = {}, ev_rc[PO_MAX_PIECES] = {}, ev_lay[EV_LAY_N] = {};
 
     uint64_t* pinned = nullptr;
     uint64_t* pinned_dev = nullptr;
 };
+static_assert(sizeof(DevKit::ev_lay) == sizeof(po_handle::ev_lay), "a kit carries every layout event of a handle");
 std::mutex g_kit_mu;
 std::vector<DevKit> g_kits;
 constexpr size_t KIT_POOL_MAX = 8;
@@ -3262,6 +3279,203 @@ po_status run_diamonds(po_handle* h, po_result* edges, uint8_t* flags_out, po_re
     return PO_OK;
 }
 
+// ---- merge_unambiguous_paths (po_layout_merge): edges -> flags + renamed kept edges + merged-node tables + node order ----
+
+po_status run_merge(po_handle* h, po_result* edges, uint8_t* flags_out, po_result* res) {
+    hipStream_t st = h->stream;
+    po_merge_stats& M = h->mstats;
+    M = po_merge_stats();
+    res->count = 0;
+    res->elem = sizeof(po_edge);
+    res->kind_edges = true;
+    res->merged = true;
+    const uint32_t n_nodes = (uint32_t)h->len.size();
+    if (edges->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_merge: too many edges for one call");
+    const uint32_t n = (uint32_t)edges->count;
+    M.n_edges_in = n;
+    if (!edges->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_layout_merge: the edge result carries no node order");
+    if (n && n_nodes == 0) return fail(h, PO_ERR_INVALID, "po_layout_merge: edges on a handle without reads");
+    for (hipEvent_t& e : h->ev_lay)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    hipEvent_t* ev = h->ev_lay + 22;
+    PO_TRY(rows_to_device(h, edges));
+    const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n + 1;
+    DevBuf* B = h->d_mrg;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[MB_CNT], 128));
+    PO_TRY(ensure(h, B[MB_RCNT], po::MERGE_BATCH * 8));
+    for (int k : {MB_OUTDEG, MB_INDEG, MB_OUTE, MB_INE, MB_LINK, MB_BACK, MB_JB0, MB_JB1, MB_HOPS0, MB_HOPS1, MB_HLEN, MB_PATHK, MB_NPATH,
+                  MB_NPOS, MB_LEN})
+        PO_TRY(ensure(h, B[k], nn * 4));
+    for (int k : {MB_WS0, MB_WS1, MB_HSUM}) PO_TRY(ensure(h, B[k], nn * 8));
+    for (int k : {MB_EFLAG, MB_KEEP}) PO_TRY(ensure(h, B[k], ne));
+    PO_TRY(ensure(h, B[MB_KOFF], (ne + 1) * 4));
+    PO_TRY(ensure(h, B[MB_TMP], ne * sizeof(po_edge)));
+    const po::Edge* d_edges = edges->d_rows.as<po::Edge>();
+    const unsigned long long* nrank = edges->d_nrank.as<unsigned long long>();
+    unsigned long long *cnt = B[MB_CNT].as<unsigned long long>(), *rcnt = B[MB_RCNT].as<unsigned long long>();
+    uint32_t *outdeg = B[MB_OUTDEG].as<uint32_t>(), *indeg = B[MB_INDEG].as<uint32_t>(), *oute = B[MB_OUTE].as<uint32_t>(),
+             *ine = B[MB_INE].as<uint32_t>(), *link = B[MB_LINK].as<uint32_t>(), *back = B[MB_BACK].as<uint32_t>(),
+             *hlen = B[MB_HLEN].as<uint32_t>(), *pathk = B[MB_PATHK].as<uint32_t>(), *npath = B[MB_NPATH].as<uint32_t>(),
+             *npos = B[MB_NPOS].as<uint32_t>(), *d_len = B[MB_LEN].as<uint32_t>();
+    uint32_t* jb[2] = {B[MB_JB0].as<uint32_t>(), B[MB_JB1].as<uint32_t>()};
+    uint32_t* hops[2] = {B[MB_HOPS0].as<uint32_t>(), B[MB_HOPS1].as<uint32_t>()};
+    unsigned long long* ws[2] = {B[MB_WS0].as<unsigned long long>(), B[MB_WS1].as<unsigned long long>()};
+    unsigned long long* hsum = B[MB_HSUM].as<unsigned long long>();
+    uint8_t *eflag = B[MB_EFLAG].as<uint8_t>(), *keep = B[MB_KEEP].as<uint8_t>();
+    po::Edge* renamed = B[MB_TMP].as<po::Edge>();
+    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
+    const uint32_t node_blocks = std::max<uint32_t>(1u, cdiv(n_nodes, 256));
+    // a head has a link out, into a node that is no head: at most every second node is one
+    const uint32_t max_heads = n_nodes / 2 + 1;
+    uint32_t pad_cap = 1;
+    while (pad_cap < max_heads) pad_cap <<= 1;
+    PO_TRY(ensure(h, B[MB_HKEY], (size_t)pad_cap * 8));
+    PO_TRY(ensure(h, B[MB_HVAL], (size_t)pad_cap * 4));
+    unsigned long long* hkey = B[MB_HKEY].as<unsigned long long>();
+    uint32_t* hval = B[MB_HVAL].as<uint32_t>();
+    // (the memsets and the lengths are work of every call: inside ms_links and ms_total.  The lengths go up again
+    // because the copy po_layout_edges left on the handle is as old as that call: reads may have been added since.)
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    for (uint32_t* p : {outdeg, indeg}) HIP_TRY(h, hipMemsetAsync(p, 0, nn * 4, st));
+    for (uint32_t* p : {oute, ine}) HIP_TRY(h, hipMemsetAsync(p, 0xFF, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(hkey, 0xFF, (size_t)pad_cap * 8, st));   // (the sort's padding: behind every rank word)
+    if (n_nodes) HIP_TRY(h, hipMemcpyAsync(d_len, h->len.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, st));
+    if (n) {
+        hipLaunchKernelGGL(po::k_merge_degree, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_nodes, outdeg, indeg, oute, ine, cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::MC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    M.n_invalid = h->pinned[16 + po::MC_INVALID];
+    // (an edge that names a node the handle does not hold would index out of the degree arrays: nothing is linked then)
+    if (M.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_merge: an edge names a read the handle does not hold");
+    if (n_nodes) {
+        hipLaunchKernelGGL(po::k_merge_links, dim3(node_blocks), dim3(256), 0, st, d_edges, n, n_nodes, nrank, outdeg, indeg, oute, ine,
+                           link, back, jb[0], hops[0], ws[0], hlen, hkey, hval, cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::MC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    M.n_nodes = h->pinned[16 + po::MC_NODES];
+    const uint64_t K64 = h->pinned[16 + po::MC_HEADS];
+    if (K64 > max_heads) return fail(h, PO_ERR_HIP, "internal: po_layout_merge counted more heads than nodes allow");
+    const uint32_t K = (uint32_t)K64;
+    M.n_merged = K;
+    if ((uint64_t)n_nodes + K > 0xFFFFFFFFull) {
+        M.n_overflow = 1;
+        return fail(h, PO_ERR_INVALID, "po_layout_merge: the merged nodes do not fit 32-bit node ids");
+    }
+    // List ranking.  A node sits fewer than n_nodes links behind its head, so ceil(log2(n_nodes)) rounds reach every
+    // head; the bound is the host's (po::merge_round_cap), no kernel follows links.  Rounds go out in batches, one readback
+    // per batch: round j of a batch counts the nodes that reached a root in it in word j, and the first round that counts
+    // none ends the ranking (later rounds of its batch change nothing on a path).
+    const uint32_t max_rounds = po::merge_round_cap(M.n_nodes);
+    uint32_t launched = 0, rounds = 0;
+    for (bool done = K == 0; !done && launched < max_rounds;) {
+        const uint32_t batch = std::min<uint32_t>(po::MERGE_BATCH, max_rounds - launched);
+        HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
+        for (uint32_t j = 0; j < batch; ++j, ++launched) {
+            const int a = po::merge_final_buffer(launched), b = a ^ 1;
+            hipLaunchKernelGGL(po::k_merge_jump, dim3(node_blocks), dim3(256), 0, st, n_nodes, back, jb[a], hops[a], ws[a], jb[b],
+                               hops[b], ws[b], rcnt + j);
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        done = po::merge_rounds_done(h->pinned + 32, batch, rounds);
+    }
+    M.n_rounds = rounds;
+    const int fin = po::merge_final_buffer(launched);   // the triple the last launch wrote
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    const uint32_t pad = po::merge_sort_pad(K);
+    if (n_nodes) {
+        hipLaunchKernelGGL(po::k_merge_tails, dim3(node_blocks), dim3(256), 0, st, n_nodes, link, back, jb[fin], hops[fin], ws[fin], hlen,
+                           hsum, cnt);
+        // heads by rank: bitonic sort of the K rank words, padded with all ones to a power of two
+        po::merge_sort_steps(K, [&](uint32_t j, uint32_t k) {
+            hipLaunchKernelGGL(po::k_merge_bitonic, dim3(cdiv(pad, 256)), dim3(256), 0, st, hkey, hval, pad, j, k);
+        });
+        HIP_TRY(h, hipGetLastError());
+    }
+    PO_TRY(ensure(h, B[MB_LENS], ((size_t)K + 1) * 4));
+    PO_TRY(ensure(h, B[MB_PSUM], ((size_t)K + 1) * 8));
+    PO_TRY(ensure(h, res->d_moff, std::max<size_t>(((size_t)K + 2) * 4, 256), 1.0, false));
+    PO_TRY(ensure(h, res->d_mlen, std::max<size_t>((size_t)K * 8, 256), 1.0, false));
+    uint32_t *lens = B[MB_LENS].as<uint32_t>(), *moff = res->d_moff.as<uint32_t>();
+    long long* psum = B[MB_PSUM].as<long long>();
+    if (K) {
+        hipLaunchKernelGGL(po::k_merge_number, dim3(cdiv(K, 256)), dim3(256), 0, st, K, n_nodes, hval, hlen, hsum, pathk, lens, psum);
+        HIP_TRY(h, hipGetLastError());
+    }
+    PO_TRY(prefix_sum<uint32_t>(h, lens, K, moff, &h->pinned[3]));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::MC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_members = h->pinned[3];
+    M.n_nodes_merged = h->pinned[16 + po::MC_MERGED];
+    M.n_cycle_nodes = h->pinned[16 + po::MC_CYCLE];
+    M.max_path_nodes = h->pinned[16 + po::MC_MAXPATH];
+    // (every node that reached a head is a member of that head's path: the lengths the last nodes wrote add up to them)
+    if (n_members != M.n_nodes_merged) return fail(h, PO_ERR_HIP, "internal: the path lengths of po_layout_merge do not add up");
+    PO_TRY(ensure(h, res->d_member, std::max<size_t>(n_members * 4, 256), 1.0, false));
+    PO_TRY(ensure(h, res->d_prefix, std::max<size_t>(n_members * 4, 256), 1.0, false));
+    const size_t n_out_nodes = (size_t)n_nodes + K;
+    const size_t nrank_bytes = std::max<size_t>(n_out_nodes * 8, 256);
+    PO_TRY(ensure_nrank(h, res, nrank_bytes));
+    if (n_nodes) {
+        hipLaunchKernelGGL(po::k_merge_tables, dim3(node_blocks), dim3(256), 0, st, d_edges, n, n_nodes, d_len, link, back, jb[fin],
+                           hops[fin], ws[fin], oute, pathk, moff, K, (uint32_t)n_members, res->d_member.as<uint32_t>(),
+                           res->d_prefix.as<int32_t>(), res->d_mlen.as<long long>(), npath, npos);
+        hipLaunchKernelGGL(po::k_merge_ranks, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(node_blocks, (uint32_t)h->n_cu * 8))), dim3(256),
+                           0, st, n_nodes, K, nrank, npath, cnt, res->d_nrank.as<unsigned long long>());
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (n_out_nodes * 8 < nrank_bytes)   // (the tail of the smallest allocation: no node)
+        HIP_TRY(h, hipMemsetAsync(res->d_nrank.as<char>() + n_out_nodes * 8, 0xFF, nrank_bytes - n_out_nodes * 8, st));
+    if (n) {
+        hipLaunchKernelGGL(po::k_merge_edges, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_nodes, link, npath, psum, renamed, eflag,
+                           keep, cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::MC_N * 8, hipMemcpyDeviceToHost, st));
+    PO_TRY(prefix_sum<uint8_t>(h, keep, n, B[MB_KOFF].as<uint32_t>(), &h->pinned[2]));
+    if (flags_out && n) {
+        PO_TRY(ensure_host(h, h->scratch_host, n));
+        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, eflag, n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_kept = h->pinned[2];
+    M.n_self_loops = h->pinned[16 + po::MC_SELF];
+    M.n_overflow = h->pinned[16 + po::MC_OVERFLOW];
+    M.n_edges_out = n_kept;
+    if (M.n_overflow) return fail(h, PO_ERR_INVALID, "po_layout_merge: the weight of an edge out of a merged node does not fit 32 bits");
+    if (flags_out && n) std::memcpy(flags_out, h->scratch_host.p, n);
+    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
+        res->d_rows = h->spare_edges;
+        h->spare_edges = DevBuf();
+    }
+    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
+    if (n_kept) {
+        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, renamed, (const uint32_t*)nullptr, n, keep,
+                           B[MB_KOFF].as<uint32_t>(), res->d_rows.as<po::Edge>(), (uint32_t*)nullptr);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(ev[4], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    res->count = n_kept;
+    res->n_merged = K;
+    res->n_members = n_members;
+    (void)hipEventElapsedTime(&M.ms_links, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&M.ms_rank, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&M.ms_number, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&M.ms_emit, ev[3], ev[4]);
+    (void)hipEventElapsedTime(&M.ms_total, ev[0], ev[4]);
+    return PO_OK;
+}
+
 // ---- GFA2 reader for `phasm layout` (S and E lines) ---------------------------------------------
 
 struct Field {
@@ -3650,6 +3864,7 @@ void po_destroy(po_handle* h) {
         if (h->rc_stream) (void)hipStreamSynchronize(h->rc_stream);
         for (DevBuf* b : bufs) b->release();
         for (DevBuf& b : h->d_tip) b.release();
+        for (DevBuf& b : h->d_mrg) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -4974,6 +5189,7 @@ void po_result_free(po_result* r) {
     r->d_rows.release();
     r->d_rank.release();
     r->d_nrank.release();
+    for (DevBuf* b : {&r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen}) b->release();
     delete r;
 }
 
@@ -5409,6 +5625,7 @@ po_status po_layout_reduce(po_handle* h, po_result* edges, const po_reduce_param
     if (dev != PO_OK) return dev;
     if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
         return fail(h, PO_ERR_INVALID, "po_layout_reduce needs a po_layout_edges result");
+    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_reduce: a merged graph (po_layout_merge) cannot be cleaned again");
     po_result* r = new (std::nothrow) po_result();
     if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
     r->h = h;
@@ -5442,6 +5659,7 @@ po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* p
     if (dev != PO_OK) return dev;
     if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
         return fail(h, PO_ERR_INVALID, "po_layout_tips needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips)");
+    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_tips: a merged graph (po_layout_merge) cannot be cleaned again");
     po_result* r = new (std::nothrow) po_result();
     if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
     r->h = h;
@@ -5476,6 +5694,7 @@ po_status po_layout_diamonds(po_handle* h, po_result* edges, const po_diamond_pa
     if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
         return fail(h, PO_ERR_INVALID,
                     "po_layout_diamonds needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds)");
+    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: a merged graph (po_layout_merge) cannot be cleaned again");
     po_result* r = new (std::nothrow) po_result();
     if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
     r->h = h;
@@ -5504,6 +5723,73 @@ po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out) {
     return PO_OK;
 }
 
+po_status po_layout_merge(po_handle* h, po_result* edges, const po_merge_params* params, uint8_t* edge_flags_out,
+                          po_result** merged_out) {
+    if (!h || !edges || !merged_out) return PO_ERR_INVALID;
+    *merged_out = nullptr;
+    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_merge: the edges belong to another handle");
+    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_merge: bad parameters");
+    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
+    const po_status dev = init_device(h);
+    if (dev != PO_OK) return dev;
+    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
+        return fail(h, PO_ERR_INVALID,
+                    "po_layout_merge needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds)");
+    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_merge: the graph is merged already");
+    po_result* r = new (std::nothrow) po_result();
+    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
+    r->h = h;
+    po_status st;
+    try {
+        st = run_merge(h, edges, edge_flags_out, r);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_merge");
+    }
+    if (st != PO_OK) {
+        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
+        for (DevBuf* b : {&r->d_rows, &r->d_rank, &r->d_nrank, &r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen}) b->release();
+        delete r;
+        return st;
+    }
+    ++h->live_results;
+    *merged_out = r;
+    return PO_OK;
+}
+
+po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out) {
+    if (!h || !out) return PO_ERR_INVALID;
+    *out = h->mstats;
+    return PO_OK;
+}
+
+po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
+                                 uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {
+    if (!r || !n_paths || !n_members) return PO_ERR_INVALID;
+    *n_paths = *n_members = 0;
+    po_handle* h = r->h;
+    if (!h) return PO_ERR_INVALID;
+    if (!r->merged) return fail(h, PO_ERR_INVALID, "po_result_merged_paths needs a po_layout_merge result");
+    const uint64_t K = r->n_merged, m = r->n_members;
+    *n_paths = K;
+    *n_members = m;
+    try {
+        (void)hipSetDevice(h->device);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (offsets_out && cap_paths >= K) {
+            std::vector<uint32_t> off(K);
+            if (K) HIP_TRY(h, hipMemcpy(off.data(), r->d_moff.p, K * 4, hipMemcpyDeviceToHost));
+            for (uint64_t k = 0; k < K; ++k) offsets_out[k] = off[k];
+            offsets_out[K] = m;
+        }
+        if (lengths_out && cap_paths >= K && K) HIP_TRY(h, hipMemcpy(lengths_out, r->d_mlen.p, K * 8, hipMemcpyDeviceToHost));
+        if (members_out && cap_members >= m && m) HIP_TRY(h, hipMemcpy(members_out, r->d_member.p, m * 4, hipMemcpyDeviceToHost));
+        if (prefix_out && cap_members >= m && m) HIP_TRY(h, hipMemcpy(prefix_out, r->d_prefix.p, m * 4, hipMemcpyDeviceToHost));
+    } catch (const std::bad_alloc&) {
+        return fail(h, PO_ERR_NOMEM, "out of host memory in po_result_merged_paths");
+    }
+    return PO_OK;
+}
+
 po_status po_get_node_order_stats(const po_handle* h, po_node_order_stats* out) {
     if (!h || !out) return PO_ERR_INVALID;
     *out = h->nostats;
@@ -5522,7 +5808,7 @@ po_status po_result_node_order(po_result* r, uint32_t* nodes_out, uint64_t cap, 
     po_handle* h = r->h;
     if (!h) return PO_ERR_INVALID;
     if (!r->kind_edges || !r->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_result_node_order needs an edge result");
-    const size_t n_nodes = h->len.size();
+    const size_t n_nodes = h->len.size() + (r->merged ? (size_t)r->n_merged : 0);   // (merged node k is node reads + k)
     try {
         std::vector<unsigned long long> rank(n_nodes);
         (void)hipSetDevice(h->device);

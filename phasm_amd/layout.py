@@ -17,7 +17,10 @@ and ``clean_graph`` (assembly_graph.py:267-394, :429-453; assembler.py:161-167) 
 node order, and ``remove_diamond_tips`` (assembly_graph.py:721-743; assembler.py:173) by ``po_layout_diamonds``
 (``remove_diamond_tips`` here).  ``clean_assembly_graph`` / ``clean=True`` runs the whole sequence of assembler.py:145-182
 in one call -- reduction, tips, diamond tips, tips again -- and tells for every stage-1 edge which step removed it.
-Cleaning after that point (merging of unambiguous paths, coverage, bubbles, assembler.py:185 on) is out of scope.
+``merge_unambiguous_paths`` / ``merge=True`` adds the last call that changes the graph before `phasm layout` writes it
+(assembly_graph.py:456-541; assembler.py:184-186) by ``po_layout_merge``: every non-branching path becomes one ``merged%d``
+node, and the result describes the GFA2 file the command writes (``S``, ``F`` and ``E`` lines, phasm/io/gfa.py:281-326).
+What follows that point (coverage per edge, bubbles, GraphML and GFA1 output, `phasm chain`) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -46,7 +49,13 @@ class AssemblyEdges:
     it (0 kept, 1 in-edge of a removed end node, 2 the in-edge of a removed pred1) and ``diamond_stats`` the counts, rounds
     and times of ``po_layout_diamonds``.  After ``clean_assembly_graph``: ``edges`` are the edges left by the whole
     chain, ``removed_by`` has one byte per stage-1 edge in stage-1 order (``REMOVED_BY``) and ``clean_stats`` the stats of
-    the four device calls in order (reduce, tips, diamonds, tips)."""
+    the four device calls in order (reduce, tips, diamonds, tips).  After ``merge_unambiguous_paths``: ``edges`` are the
+    edges of the merged graph (a node id >= ``len(ids)`` names merged node ``id - len(ids)``), ``merge_flags`` has one
+    byte per edge that went into the merge (0 kept as it is, 1 link of a path, 2 kept with a renamed end or a raised
+    weight), ``merged_paths`` the tables ``(offsets, members, prefix_lengths, lengths)`` of the merged nodes,
+    ``merge_stats`` the counts, rounds and times of ``po_layout_merge``, ``node_order`` the nodes of the merged graph in
+    the reference's order and ``node_lengths`` the length of every oriented read.  These five fields are set only by the
+    merge (``merge_unambiguous_paths`` or ``merge=True``) and stay ``None`` otherwise."""
     edges: np.ndarray
     contained: np.ndarray
     ids: List[str]
@@ -59,10 +68,33 @@ class AssemblyEdges:
     diamond_stats: Optional[dict] = None
     removed_by: Optional[np.ndarray] = None
     clean_stats: Optional[List[dict]] = None
+    merge_flags: Optional[np.ndarray] = None
+    merged_paths: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]] = None
+    merge_stats: Optional[dict] = None
+    node_order: Optional[np.ndarray] = None
+    node_lengths: Optional[np.ndarray] = None
+
+    def node_name(self, n: int) -> str:
+        """The reference's ``str(node)``: the oriented read's id, or ``merged%d+`` for a merged node."""
+        n = int(n)
+        return self.ids[n] if n < len(self.ids) else "merged%d+" % (n - len(self.ids))
+
+    def node_length(self, n: int) -> int:
+        """The reference's ``len(node)`` (needs ``node_lengths``, which ``merge_unambiguous_paths`` fills in)."""
+        n = int(n)
+        if n < len(self.ids):
+            if self.node_lengths is None:
+                raise ValueError("this AssemblyEdges carries no read lengths")
+            return int(self.node_lengths[n])
+        if self.merged_paths is None or n - len(self.ids) >= len(self.merged_paths[3]):
+            raise ValueError("node %d is no node of this graph" % n)
+        return int(self.merged_paths[3][n - len(self.ids)])
 
     def edge_tuples(self) -> List[Tuple[str, str, int, int]]:
         ids = self.ids
         e = self.edges
+        if self.merged_paths is not None:
+            ids = [self.node_name(n) for n in range(len(ids) + len(self.merged_paths[3]))]
         return [(ids[u], ids[v], w, o) for u, v, w, o in
                 zip(e["u"].tolist(), e["v"].tolist(), e["weight"].tolist(), e["overlap_len"].tolist())]
 
@@ -126,6 +158,62 @@ def remove_diamond_tips(ov: ExactOverlapper, edges_result: OverlapResult, contai
                          diamond_flags=diamond_flags, diamond_stats=ov.diamond_stats())
 
 
+def _merge_into(out: AssemblyEdges, ov: ExactOverlapper, edges_result: OverlapResult) -> AssemblyEdges:
+    merged, flags = ov.layout_merge(edges_result, want_flags=True)
+    try:
+        out.edges, out.merge_flags, out.merge_stats = merged.rows(), flags, ov.merge_stats()
+        out.merged_paths, out.node_order, out.node_lengths = merged.merged_paths(), merged.node_order(), ov.lengths()
+    finally:
+        merged.free()
+    return out
+
+
+def merge_unambiguous_paths(ov: ExactOverlapper, edges_result: OverlapResult, contained: Optional[np.ndarray] = None,
+                            stats: Optional[dict] = None) -> AssemblyEdges:
+    """``merge_unambiguous_paths(g)`` on an edge result of ``ov`` (which stays valid): the merged graph's edges, the flag
+    byte of every input edge, the tables of the merged nodes and the node order."""
+    if contained is None:
+        contained = np.zeros(len(ov) // 2, dtype=bool)
+    out = AssemblyEdges(np.empty(0), contained, ov.ids(), stats if stats is not None else ov.layout_stats())
+    return _merge_into(out, ov, edges_result)
+
+
+def write_merged_graph(f, g: AssemblyEdges) -> int:
+    """What the reference's ``gfa2_write_graph`` (phasm/io/gfa.py:281-326) writes for the merged graph ``g`` (a result of
+    ``merge_unambiguous_paths`` or of ``merge=True``): the header; for every node in node order one ``S`` line per segment
+    name at its first occurrence, followed for a merged node by its ``F`` lines; then the ``E`` lines, in the result's own
+    order (the reference's adjacency order is not reproduced).  Returns the number of ``E`` lines."""
+    from .io import gfa
+    if g.merged_paths is None or g.node_order is None:
+        raise ValueError("write_merged_graph needs the result of merge_unambiguous_paths")
+    offsets, members, prefix, lengths = g.merged_paths
+    n_ids = len(g.ids)
+    f.write(gfa.gfa_header())
+    segments = set()
+    for n in g.node_order.tolist():
+        name = g.node_name(n)[:-1]
+        if name in segments:
+            continue
+        segments.add(name)
+        f.write(gfa.gfa_line("S", name, g.node_length(n), "*"))
+        if n >= n_ids:
+            k = n - n_ids
+            lo, hi = int(offsets[k]), int(offsets[k + 1])
+            total, cur, length = int(prefix[lo:hi].sum()), 0, int(lengths[k])
+            # The reference takes a falsy prefix for the last read (gfa.py:301-307).  Stage 1 never emits a weight <= 0,
+            # so the prefix of every read but a path's last is positive and the two tests agree.
+            for read, p in zip(members[lo:hi].tolist(), prefix[lo:hi].tolist()):
+                f.write(gfa.gfa_line("F", name, g.ids[read], cur, cur + p if p else length, 0, p if p else length - total, "*"))
+                cur += p
+    e = g.edges
+    node_len = np.concatenate([np.asarray(g.node_lengths, dtype=np.int64), np.asarray(lengths, dtype=np.int64)])
+    names = [g.node_name(n) for n in range(n_ids + len(lengths))]
+    f.write("".join("E\t*\t%s\t%s\t%d\t%d\t0\t%d\t*\n" % t for t in
+                    zip([names[u] for u in e["u"].tolist()], [names[v] for v in e["v"].tolist()], e["weight"].tolist(),
+                        node_len[e["u"]].tolist() if len(e) else [], e["overlap_len"].tolist())))
+    return len(e)
+
+
 # ``AssemblyEdges.removed_by``: which step of assembler.py:145-182 removed a stage-1 edge
 REMOVED_BY = {0: "kept", 1: "transitive", 2: "asymmetric after the reduction", 3: "incoming tip", 4: "outgoing tip",
               5: "asymmetric after the tips", 6: "in-edge of a diamond's end node", 7: "in-edge of a diamond's pred1",
@@ -135,11 +223,14 @@ _REMOVED_BY_BASE = (0, 2, 5, 7)   # reduce flags 1-2, tips 1-3, diamonds 1-2, ti
 
 def clean_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, length_fuzz: int = 1000, max_tip_len: int = 4,
                          max_tip_len_bases: int = 5000, contained: Optional[np.ndarray] = None,
-                         stats: Optional[dict] = None) -> AssemblyEdges:
+                         stats: Optional[dict] = None, merge: bool = False) -> AssemblyEdges:
     """Graph cleaning as `phasm layout` runs it up to the merging of paths (assembler.py:145-182) on a ``layout_edges``
     result of ``ov`` (which stays valid): reduction + symmetry, tips with both bounds + symmetry + isolated nodes, diamond
     tips, tips again with ``max_tip_len`` and the function's own default of 5000 bases (the reference's second call
-    passes no base bound) + symmetry + isolated nodes.  Four device calls; the edges stay in HBM in between."""
+    passes no base bound) + symmetry + isolated nodes.  Four device calls; the edges stay in HBM in between.  With
+    ``merge`` the merging of unambiguous paths follows as a fifth (assembler.py:184-186): ``removed_by`` stays what the
+    cleaning made it -- a link of a path is not removed by cleaning -- and ``merge_flags`` refers to the edges that went
+    into the merge, those with ``removed_by == 0`` in stage-1 order."""
     steps = (lambda r: ov.layout_reduce(r, length_fuzz, want_flags=True), ov.reduce_stats), \
             (lambda r: ov.layout_tips(r, max_tip_len, max_tip_len_bases, want_flags=True), ov.tips_stats), \
             (lambda r: ov.layout_diamonds(r, want_flags=True), ov.diamond_stats), \
@@ -157,27 +248,34 @@ def clean_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, lengt
             clean_stats.append(call_stats())
             removed_by[live[flags != 0]] = flags[flags != 0] + base
             live = live[flags == 0]
-        edges = cur.rows()
+        if contained is None:
+            contained = np.zeros(len(ov) // 2, dtype=bool)
+        out = AssemblyEdges(np.empty(0), contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
+                            removed_by=removed_by, clean_stats=clean_stats)
+        if merge:
+            _merge_into(out, ov, cur)
+        else:
+            out.edges = cur.rows()
     finally:
         if cur is not edges_result:
             cur.free()
-    if contained is None:
-        contained = np.zeros(len(ov) // 2, dtype=bool)
-    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
-                         removed_by=removed_by, clean_stats=clean_stats)
+    return out
 
 
 def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_length: int = 0,
                          min_overlap_length: int = 0, max_overhang_abs: int = 1000,
                          max_overhang_rel: float = 0.8, reduce: bool = False, length_fuzz: int = 1000, tips: bool = False,
-                         max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False) -> AssemblyEdges:
+                         max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
+                         merge: bool = False) -> AssemblyEdges:
     """Filters + ``build_assembly_graph`` + contained-read removal on a row result of ``ov``; with ``reduce`` the
     transitive reduction and the symmetry pass as well; with ``tips`` the tip removal (after the reduction when both
-    are asked for); with ``clean`` the whole of ``clean_assembly_graph`` instead of either."""
+    are asked for); with ``clean`` the whole of ``clean_assembly_graph`` instead of either; with ``merge`` (which implies
+    ``clean``) the merging of unambiguous paths after it."""
     res, removed = ov.layout_edges(rows, min_read_length, min_overlap_length, max_overhang_abs, max_overhang_rel)
     try:
-        if clean:
-            return clean_assembly_graph(ov, res, length_fuzz, max_tip_len, max_tip_len_bases, removed.astype(bool), ov.layout_stats())
+        if clean or merge:
+            return clean_assembly_graph(ov, res, length_fuzz, max_tip_len, max_tip_len_bases, removed.astype(bool), ov.layout_stats(),
+                                        merge=merge)
         if reduce:
             return reduce_assembly_graph(ov, res, length_fuzz, removed.astype(bool), ov.layout_stats(), tips, max_tip_len,
                                          max_tip_len_bases)
@@ -191,14 +289,14 @@ def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_leng
 
 def layout_from_gfa(path: str, device: Optional[int] = None, reduce: bool = False, length_fuzz: int = 1000,
                     tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
-                    **params) -> AssemblyEdges:
+                    merge: bool = False, **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 from an overlap file: native GFA2 read, then the device passes."""
     ov = ExactOverlapper(device=device)
     try:
         _, rows = ov.add_gfa(path)
         try:
             return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, clean=clean, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -217,14 +315,14 @@ def load_daligner(ov: ExactOverlapper, db_input, las_input, translations=None) -
 
 def layout_from_daligner(db_input, las_input, translations=None, device: Optional[int] = None, reduce: bool = False,
                          length_fuzz: int = 1000, tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000,
-                         clean: bool = False, **params) -> AssemblyEdges:
+                         clean: bool = False, merge: bool = False, **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 straight from DAZZ_DB / DALIGNER dump text."""
     ov = ExactOverlapper(device=device)
     try:
         rows = load_daligner(ov, db_input, las_input, translations)
         try:
             return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, clean=clean, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -233,11 +331,11 @@ def layout_from_daligner(db_input, las_input, translations=None, device: Optiona
 
 def layout_from_overlaps(ov: ExactOverlapper, min_length: int, reduce: bool = False, length_fuzz: int = 1000,
                          tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
-                         **params) -> AssemblyEdges:
+                         merge: bool = False, **params) -> AssemblyEdges:
     """Overlap + layout stage 1 without the file in between: the rows never leave HBM."""
     rows = ov.overlaps_result(min_length)
     try:
         return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, clean=clean, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, **{**DEFAULTS, **params})
     finally:
         rows.free()

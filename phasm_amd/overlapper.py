@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -139,6 +139,22 @@ class OverlapResult:
         if len(out):
             _check(self._owner._h, self._lib.po_result_node_order(self._ptr, out.ctypes.data_as(ctypes.c_void_p), len(out), ctypes.byref(n)))
         return out
+
+    def merged_paths(self):
+        """``po_result_merged_paths`` of a ``layout_merge`` result: ``(offsets, members, prefix_lengths, lengths)`` --
+        merged node k (node id ``len(owner) + k``) holds the reads ``members[offsets[k]:offsets[k + 1]]`` in path order,
+        ``prefix_lengths`` has the weight of the link out of each member (0 for a path's last) and ``lengths[k]`` is the
+        merged node's length."""
+        k, m = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._owner._h, self._lib.po_result_merged_paths(self._ptr, ctypes.byref(k), ctypes.byref(m), None, 0, None, None, 0, None))
+        offsets = np.zeros(int(k.value) + 1, dtype=np.uint64)
+        lengths = np.zeros(int(k.value), dtype=np.int64)
+        members = np.zeros(int(m.value), dtype=np.uint32)
+        prefix = np.zeros(int(m.value), dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
+        _check(self._owner._h, self._lib.po_result_merged_paths(self._ptr, ctypes.byref(k), ctypes.byref(m), ptr(offsets), len(lengths),
+                                                                 ptr(members), ptr(prefix), len(members), ptr(lengths)))
+        return offsets, members, prefix, lengths
 
     def copy_to_device(self, dst_ptr: int, count: Optional[int] = None) -> None:
         """Device-to-device copy of the first ``count`` entries (default: all) to ``dst_ptr``."""
@@ -461,6 +477,26 @@ class ExactOverlapper:
     def diamond_stats(self) -> dict:
         s = PoDiamondStats()
         _check(self._h, self._lib.po_get_diamond_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def layout_merge(self, edges: OverlapResult, want_flags: bool = False):
+        """``po_layout_merge``: ``merge_unambiguous_paths`` on an edge result (of ``layout_edges``, ``layout_reduce``,
+        ``layout_tips`` or ``layout_diamonds``), which stays valid.  Returns the merged graph (EDGE_DTYPE result: the
+        kept edges in input order, merged node k written as ``len(self) + k``; ``merged_paths()`` and ``node_order()``
+        describe its nodes), or with ``want_flags`` the pair (merged graph, one byte per input edge: 0 kept as it is,
+        1 link of a path, 2 kept with a renamed end or a raised weight)."""
+        prm = PoMergeParams(0)
+        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
+        r = ctypes.c_void_p()
+        _check(self._h, self._lib.po_layout_merge(
+            self._h, edges._ptr, ctypes.byref(prm),
+            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
+        merged = OverlapResult(self, r, EDGE_DTYPE)
+        return (merged, flags) if want_flags else merged
+
+    def merge_stats(self) -> dict:
+        s = PoMergeStats()
+        _check(self._h, self._lib.po_get_merge_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def node_order_stats(self) -> dict:
