@@ -422,7 +422,8 @@ typedef struct {
  * 2 outgoing-tip edge, 3 removed by the symmetry pass.  kept_out holds the kept edges in input order.
  * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
  * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds, the merging
- * of unambiguous paths with po_layout_merge; coverage and bubbles (assembler.py:188 on) are not part of this library. */
+ * of unambiguous paths with po_layout_merge, the average coverage per edge with po_layout_coverage; bubbles and what follows
+ * them (`phasm chain`, phasing) are not part of this library. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -516,6 +517,51 @@ po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out);
 po_status po_result_merged_paths(po_result* merged, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out,
                                  uint64_t cap_paths, uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members,
                                  int64_t* lengths_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The last computation of `phasm layout` before it writes the graph (phasm/cli/assembler.py:190-193):
+ * average_coverage_path(g, read_alignments, [u, v]) (phasm/assembly_graph.py:544-591) for every edge.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_coverage_params;
+
+typedef struct {
+    uint64_t read_length_sum;    /* sum of len(r) over the distinct reads r aligning to a member of u or of v      */
+    int64_t path_length;         /* weight + len(v)                                                              */
+} po_edge_coverage;              /* 16 bytes; avg_coverage = read_length_sum / path_length                        */
+
+typedef struct {
+    uint64_t n_rows, n_edges;
+    uint64_t n_nodes;            /* nodes with at least one edge                                                 */
+    uint64_t n_pairs;            /* distinct (node, aligning read) pairs                                         */
+    uint64_t max_set;            /* the largest per-node set                                                     */
+    uint64_t n_zero_path;        /* edges with path_length == 0 (the reference raises ZeroDivisionError)         */
+    uint64_t n_invalid;          /* edges or rows that name a read the handle does not hold (the call fails then) */
+    float ms_sets, ms_edges, ms_total;
+} po_coverage_stats;
+
+/* `graph` is an edge result of this handle -- from po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds
+ * -- or a merged graph from po_layout_merge; `rows` is a row result of this handle (po_overlaps*, po_add_gfa,
+ * po_result_from_rows; a host-only result is copied up).  Both stay valid and unchanged.  With
+ *   A(x) = { b : some row (x, b, ...) } + { a : some row (a, x, ...) } over ALL rows -- those the filters of stage 1
+ *          drop and those of contained reads included (alignment_recorder, assembler.py:65-76, sees every line);
+ *          duplicates count once, a row present on one strand only counts as given, a row (x, x) puts x into A(x),
+ *          x+ and x- are different elements;
+ *   members of a node = the node itself, or the reads of the path of a merged node;
+ * the entry of edge (u, v, weight, overlap_len), in the graph's edge order, is
+ *   read_length_sum = the sum of len(r) over the union of A(m), m a member of u or of v;  path_length = weight + len(v)
+ * (len of a merged node: its merged length), both exact 64-bit integers: the IEEE double quotient of the two equals the
+ * reference's `read_length_sum / path_length` bit for bit.  A self-loop (U, U) takes U's members once.  A v of length 0
+ * adds neither its length nor its aligning reads (the reference tests `bool(last)`).  An edge with path_length == 0 is
+ * reported as it is and counted in n_zero_path.  Device memory beyond the inputs is linear: 40 bytes per row, 28 per
+ * node, 16 per edge.  params may be NULL.  A graph without edges: PO_OK, nothing written.  There is no CPU fallback:
+ * without a GPU the call returns PO_ERR_HIP.  A result of another handle, the wrong kind of result in either position,
+ * reserved != 0, coverage_out NULL with edges present: PO_ERR_INVALID. */
+po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, const po_coverage_params* params,
+                             po_edge_coverage* coverage_out /* host, po_result_count(graph) entries */);
+po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out);
 
 /* The nodes of an edge result's graph in the reference's order (`for n in g`: the order in which add_edge first saw
  * each node, phasm/assembly_graph.py:136-179, without the nodes of contained reads), computed by po_layout_edges from

@@ -183,6 +183,17 @@ def _int_in(lo: int, hi: int):
     return parse
 
 
+def _write_coverage(graphml, g) -> None:
+    """The log line of the coverage and, with --graphml, the file (assembler.py:208-209)."""
+    if g.coverage_stats is None:
+        return
+    cs = g.coverage_stats
+    logger.info("Average coverage of %d edges from %d (node, aligning read) pairs; largest set %d reads.",
+                cs["n_edges"], cs["n_pairs"], cs["max_set"])
+    if graphml is not None:
+        layout_mod.write_graphml(graphml, g)
+
+
 def layout_edges(args) -> int:
     ov = ExactOverlapper(device=getattr(args, "device", None))
     try:
@@ -193,11 +204,14 @@ def layout_edges(args) -> int:
         else:
             nseg, rows = ov.add_gfa(args.gfa_file)
         logger.info("Read %d reads and %d local alignments from the GFA2 file.", nseg, len(rows))
+        graphml = getattr(args, "graphml", None)
+        coverage = getattr(args, "coverage", False) or graphml is not None
         try:
             edges, _removed = ov.layout_edges(rows, args.min_read_length, args.min_overlap_length,
                                               args.max_overhang_abs, args.max_overhang_rel)
         finally:
-            rows.free()
+            if not coverage:
+                rows.free()   # (the coverage reads every row again: with it they live until it is done)
         st = ov.layout_stats()
         logger.info("%d contained reads removed; %d alignments pass the filters; graph has %d edges.",
                     st["n_contained_reads"], st["n_pass"], st["n_edges"])
@@ -243,12 +257,21 @@ def layout_edges(args) -> int:
                 # assembler.py:184-186 and the file of :195-212 (gfa2_write_graph): S lines in node order, F lines behind
                 # a merged node's S line, E lines in the result's own order
                 logger.info("Merging unambiguous paths...")
-                g = layout_mod.merge_unambiguous_paths(ov, edges)
+                if coverage:   # assembler.py:190-193, on the merged graph while it is still on the device
+                    logger.info("Calculating average coverage for each edge...")
+                g = layout_mod.merge_unambiguous_paths(ov, edges, coverage_rows=rows if coverage else None)
                 logger.info("Merged %d nodes.", g.merge_stats["n_nodes_merged"])
+                _write_coverage(graphml, g)
                 return layout_mod.write_merged_graph(args.output, g)
+            if coverage:
+                logger.info("Calculating average coverage for each edge...")
+                g = layout_mod.AssemblyEdges(edges.rows(), None, ov.ids(), st)
+                _write_coverage(graphml, layout_mod._coverage_into(g, ov, edges, rows))
             return write_stage1_graph(args.output, ov.ids(), ov.lengths(), edges.rows(), edges)
         finally:
             edges.free()
+            if coverage:
+                rows.free()
     finally:
         ov.close()
 
@@ -302,6 +325,12 @@ def main(argv=None) -> int:
     q.add_argument("--merge", action="store_true",
                    help="graph cleaning as --clean, then merge the unambiguous paths and write the graph file of `phasm "
                         "layout`: S lines in node order, F lines for the reads of every merged node, E lines")
+    q.add_argument("--coverage", action="store_true",
+                   help="also calculate the average coverage of every edge of the graph the command ends with (the last "
+                        "computation of `phasm layout` before it writes the graph), from every alignment of the input")
+    q.add_argument("--graphml", type=argparse.FileType("w"), default=None, metavar="FILE",
+                   help="also write the graph as GraphML with the edge attributes weight, overlap_len and avg_coverage "
+                        "(implies --coverage)")
     q.add_argument("--device", type=int, default=None)
     q.add_argument("--las", default=None, metavar="LADUMP",
                    help="read the positional file as DBdump text and the alignments from this LAdump text")
@@ -324,7 +353,7 @@ def main(argv=None) -> int:
     logging.basicConfig(level=[logging.WARNING, logging.INFO, logging.DEBUG][min(args.verbose, 2)],
                         stream=sys.stderr)
     args.func(args)
-    for name in ("output", "out"):   # (the command may end with os._exit: nothing may be left in a Python buffer)
+    for name in ("output", "out", "graphml"):   # (the command may end with os._exit: nothing may be left in a Python buffer)
         f = getattr(args, name, None)
         if f is not None and f not in (sys.stdout, sys.stderr):
             f.close()

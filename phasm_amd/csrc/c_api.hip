@@ -40,6 +40,7 @@
 #include "tips.hip.h"
 #include "diamond.hip.h"
 #include "merge.hip.h"
+#include "coverage.hip.h"
 
 namespace {
 
@@ -50,8 +51,10 @@ enum { TB_CNT, TB_OUTDEG, TB_OUTSUM, TB_INDEG, TB_INSUM, TB_MARK, TB_CAND, TB_CS
 enum { MB_CNT, MB_RCNT, MB_OUTDEG, MB_INDEG, MB_OUTE, MB_INE, MB_LINK, MB_BACK, MB_JB0, MB_JB1, MB_HOPS0, MB_HOPS1, MB_WS0, MB_WS1,
        MB_HKEY, MB_HVAL, MB_HLEN, MB_HSUM, MB_PATHK, MB_LENS, MB_PSUM, MB_NPATH, MB_NPOS, MB_EFLAG, MB_KEEP, MB_KOFF, MB_TMP, MB_LEN,
        MB_N };
+// workspaces of po_layout_coverage (coverage.hip.h)
+enum { VB_CNT, VB_USED, VB_NODEOF, VB_LEN, VB_TABLE, VB_SUM, VB_SETCNT, VB_OFF, VB_CUR, VB_LIST, VB_OUT, VB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 27;
+constexpr int EV_LAY_N = 30;
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -383,7 +386,7 @@ struct po_handle {
     bool segments_only = false;  // reads were added by po_add_segment: lengths and names, no sequence
     int ids_paired = -1;         // -1 unknown, 0/1: ids come in (name+"+", name+"-") pairs
     hipEvent_t ev_lay[EV_LAY_N] = {};  // [0..3] po_layout_edges, [4..8] po_layout_reduce, [9..14] po_layout_tips, [15..17] node order,
-                                 // [18..21] po_layout_diamonds, [22..26] po_layout_merge
+                                 // [18..21] po_layout_diamonds, [22..26] po_layout_merge, [27..29] po_layout_coverage
     DevBuf d_lay_len, d_lay_cnt, d_rflag, d_removed, d_ekey, d_ecnt, d_ewin, d_eoff;
     DevBuf d_efirst;             // table path: first writer row per winning row (the edges' rank, po_result::d_rank)
     po_layout_stats lstats = {};
@@ -403,6 +406,10 @@ struct po_handle {
     // merging of unambiguous paths (po_layout_merge, merge.hip.h)
     DevBuf d_mrg[MB_N];
     po_merge_stats mstats = {};
+
+    // average coverage per edge (po_layout_coverage, coverage.hip.h)
+    DevBuf d_cov[VB_N];
+    po_coverage_stats cstats = {};
 };
 
 struct po_result {
@@ -3476,6 +3483,101 @@ po_status run_merge(po_handle* h, po_result* edges, uint8_t* flags_out, po_resul
     return PO_OK;
 }
 
+// ---- average_coverage_path per edge (po_layout_coverage): edges + all rows -> (read_length_sum, path_length) per edge ----
+
+po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_coverage* out) {
+    hipStream_t st = h->stream;
+    po_coverage_stats& C = h->cstats;
+    C = po_coverage_stats();
+    const uint32_t n_ids = (uint32_t)h->len.size();
+    if (graph->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_coverage: too many edges for one call");
+    // (the pair table has 4 slots per row and is indexed with 32 bits)
+    if (rows->count >= 0x3FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_coverage: more than 2^30 rows in one call");
+    const uint32_t n = (uint32_t)graph->count, n_rows = (uint32_t)rows->count;
+    C.n_edges = n;
+    C.n_rows = n_rows;
+    if (n == 0) return PO_OK;
+    const uint32_t K = graph->merged ? (uint32_t)graph->n_merged : 0u, n_members = graph->merged ? (uint32_t)graph->n_members : 0u;
+    if ((uint64_t)n_ids + K > 0xFFFFFFFEull) return fail(h, PO_ERR_CAPACITY, "po_layout_coverage: the nodes do not fit 32-bit node ids");
+    const uint32_t n_total = n_ids + K;
+    for (hipEvent_t& e : h->ev_lay)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    hipEvent_t* ev = h->ev_lay + 27;
+    PO_TRY(rows_to_device(h, graph));
+    PO_TRY(rows_to_device(h, rows));
+    const uint32_t n_slots = po::cov_table_slots(n_rows);
+    const size_t nn = (size_t)n_total + 1, n_list = 2 * (size_t)n_rows + 1;
+    DevBuf* B = h->d_cov;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[VB_CNT], 128));
+    for (int k : {VB_USED, VB_NODEOF, VB_LEN, VB_SETCNT, VB_OFF, VB_CUR}) PO_TRY(ensure(h, B[k], nn * 4));
+    PO_TRY(ensure(h, B[VB_SUM], nn * 8));
+    PO_TRY(ensure(h, B[VB_TABLE], (size_t)n_slots * 8));
+    PO_TRY(ensure(h, B[VB_LIST], n_list * 4));
+    PO_TRY(ensure(h, B[VB_OUT], (size_t)n * sizeof(po::EdgeCoverage)));
+    unsigned long long *cnt = B[VB_CNT].as<unsigned long long>(), *table = B[VB_TABLE].as<unsigned long long>(),
+                       *sum = B[VB_SUM].as<unsigned long long>();
+    uint32_t *used = B[VB_USED].as<uint32_t>(), *node_of = B[VB_NODEOF].as<uint32_t>(), *d_len = B[VB_LEN].as<uint32_t>(),
+             *setcnt = B[VB_SETCNT].as<uint32_t>(), *off = B[VB_OFF].as<uint32_t>(), *cur = B[VB_CUR].as<uint32_t>(),
+             *list = B[VB_LIST].as<uint32_t>();
+    po::EdgeCoverage* d_out = B[VB_OUT].as<po::EdgeCoverage>();
+    const po::Edge* d_edges = graph->d_rows.as<po::Edge>();
+    const po::Row* d_rows = rows->d_rows.as<po::Row>();
+    const uint32_t cap = (uint32_t)h->n_cu * 8;
+    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), cap));
+    const uint32_t row_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_rows, 256), cap));
+    const uint32_t node_blocks = std::max<uint32_t>(1u, cdiv(n_total, 256));
+    // (the memsets and the lengths are work of every call: inside ms_sets and ms_total)
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    for (uint32_t* p : {used, setcnt, cur}) HIP_TRY(h, hipMemsetAsync(p, 0, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(node_of, 0xFF, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(sum, 0, nn * 8, st));
+    HIP_TRY(h, hipMemsetAsync(table, 0xFF, (size_t)n_slots * 8, st));
+    if (n_ids) HIP_TRY(h, hipMemcpyAsync(d_len, h->len.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(po::k_cov_mark, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_total, used, cnt);
+    hipLaunchKernelGGL(po::k_cov_nodes, dim3(node_blocks), dim3(256), 0, st, n_ids, n_total, used, node_of, cnt);
+    if (n_members && K)
+        hipLaunchKernelGGL(po::k_cov_members, dim3(cdiv(n_members, 256)), dim3(256), 0, st, graph->d_member.as<uint32_t>(), n_members,
+                           graph->d_moff.as<uint32_t>(), K, n_ids, used, node_of, cnt);
+    if (n_rows)
+        hipLaunchKernelGGL(po::k_cov_insert, dim3(row_grid), dim3(256), 0, st, d_rows, n_rows, n_ids, d_len, node_of, table, n_slots, sum,
+                           setcnt, cnt);
+    hipLaunchKernelGGL(po::k_cov_max, dim3(std::min<uint32_t>(node_blocks, cap)), dim3(256), 0, st, setcnt, n_total, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, setcnt, n_total, off, &h->pinned[2]));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::CC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    C.n_invalid = h->pinned[16 + po::CC_INVALID];
+    C.n_nodes = h->pinned[16 + po::CC_NODES];
+    C.n_pairs = h->pinned[16 + po::CC_PAIRS];
+    C.max_set = h->pinned[16 + po::CC_MAXSET];
+    if (C.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_coverage: an edge or a row names a read the handle does not hold");
+    if (h->pinned[2] != C.n_pairs || C.n_pairs >= n_list)
+        return fail(h, PO_ERR_HIP, "internal: the set sizes of po_layout_coverage do not add up");
+    const uint32_t n_pairs = (uint32_t)C.n_pairs;
+    if (n_pairs)
+        hipLaunchKernelGGL(po::k_cov_fill, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_slots, 256), cap))), dim3(256), 0, st,
+                           table, n_slots, n_total, off, cur, list, n_pairs);
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    // one wave per edge, four to a workgroup
+    hipLaunchKernelGGL(po::k_cov_edges, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 4), cap * 4))), dim3(256), 0, st, d_edges,
+                       n, n_ids, n_total, d_len, graph->merged ? graph->d_mlen.as<long long>() : (const long long*)nullptr, table, n_slots,
+                       sum, setcnt, off, list, n_pairs, d_out, cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    PO_TRY(ensure_host(h, h->scratch_host, (size_t)n * sizeof(po_edge_coverage)));
+    HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, d_out, (size_t)n * sizeof(po_edge_coverage), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::CC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    C.n_zero_path = h->pinned[16 + po::CC_ZERO];
+    std::memcpy(out, h->scratch_host.p, (size_t)n * sizeof(po_edge_coverage));
+    (void)hipEventElapsedTime(&C.ms_sets, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&C.ms_edges, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&C.ms_total, ev[0], ev[2]);
+    return PO_OK;
+}
+
 // ---- GFA2 reader for `phasm layout` (S and E lines) ---------------------------------------------
 
 struct Field {
@@ -3865,6 +3967,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf* b : bufs) b->release();
         for (DevBuf& b : h->d_tip) b.release();
         for (DevBuf& b : h->d_mrg) b.release();
+        for (DevBuf& b : h->d_cov) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -5759,6 +5862,34 @@ po_status po_layout_merge(po_handle* h, po_result* edges, const po_merge_params*
 po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out) {
     if (!h || !out) return PO_ERR_INVALID;
     *out = h->mstats;
+    return PO_OK;
+}
+
+po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, const po_coverage_params* params,
+                             po_edge_coverage* coverage_out) {
+    if (!h || !graph || !rows) return PO_ERR_INVALID;
+    if (graph->h != h || rows->h != h) return fail(h, PO_ERR_INVALID, "po_layout_coverage: a result belongs to another handle");
+    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_coverage: bad parameters");
+    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
+    const po_status dev = init_device(h);
+    if (dev != PO_OK) return dev;
+    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
+        return fail(h, PO_ERR_INVALID, "po_layout_coverage needs an edge result or a merged graph in the first position");
+    if (rows->elem != sizeof(po_row) || rows->kind_edges) return fail(h, PO_ERR_INVALID, "po_layout_coverage needs a row result in the second position");
+    if (graph->count && !coverage_out) return fail(h, PO_ERR_INVALID, "po_layout_coverage: no room for the coverage of the edges");
+    po_status st;
+    try {
+        st = run_coverage(h, graph, rows, coverage_out);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_coverage");
+    }
+    if (st != PO_OK && h->dev_ready) (void)hipStreamSynchronize(h->stream);
+    return st;
+}
+
+po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out) {
+    if (!h || !out) return PO_ERR_INVALID;
+    *out = h->cstats;
     return PO_OK;
 }
 

@@ -20,7 +20,10 @@ in one call -- reduction, tips, diamond tips, tips again -- and tells for every 
 ``merge_unambiguous_paths`` / ``merge=True`` adds the last call that changes the graph before `phasm layout` writes it
 (assembly_graph.py:456-541; assembler.py:184-186) by ``po_layout_merge``: every non-branching path becomes one ``merged%d``
 node, and the result describes the GFA2 file the command writes (``S``, ``F`` and ``E`` lines, phasm/io/gfa.py:281-326).
-What follows that point (coverage per edge, bubbles, GraphML and GFA1 output, `phasm chain`) is out of scope.
+``average_coverage`` / ``coverage=True`` computes what the command computes next, the average coverage of every edge
+(``average_coverage_path``, assembly_graph.py:544-591; assembler.py:190-193), by ``po_layout_coverage`` from all the rows
+still in HBM, and ``write_graphml`` writes the graph with that attribute (the counterpart of assembler.py:208-209).
+What follows that point (bubbles, GFA1 output, `phasm chain`, phasing) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -55,7 +58,10 @@ class AssemblyEdges:
     weight), ``merged_paths`` the tables ``(offsets, members, prefix_lengths, lengths)`` of the merged nodes,
     ``merge_stats`` the counts, rounds and times of ``po_layout_merge``, ``node_order`` the nodes of the merged graph in
     the reference's order and ``node_lengths`` the length of every oriented read.  These five fields are set only by the
-    merge (``merge_unambiguous_paths`` or ``merge=True``) and stay ``None`` otherwise."""
+    merge (``merge_unambiguous_paths`` or ``merge=True``) and stay ``None`` otherwise.  With ``coverage=True`` (or
+    ``coverage_rows``) three more, all in the order of ``edges``: ``coverage_sums`` (structured: ``read_length_sum``,
+    ``path_length``), ``avg_coverage`` (float64, the reference's ``avg_coverage`` edge attribute) and ``coverage_stats``
+    (``po_get_coverage_stats``); ``None`` unless asked for."""
     edges: np.ndarray
     contained: np.ndarray
     ids: List[str]
@@ -73,6 +79,9 @@ class AssemblyEdges:
     merge_stats: Optional[dict] = None
     node_order: Optional[np.ndarray] = None
     node_lengths: Optional[np.ndarray] = None
+    coverage_sums: Optional[np.ndarray] = None
+    avg_coverage: Optional[np.ndarray] = None
+    coverage_stats: Optional[dict] = None
 
     def node_name(self, n: int) -> str:
         """The reference's ``str(node)``: the oriented read's id, or ``merged%d+`` for a merged node."""
@@ -99,83 +108,150 @@ class AssemblyEdges:
                 zip(e["u"].tolist(), e["v"].tolist(), e["weight"].tolist(), e["overlap_len"].tolist())]
 
     def to_networkx(self):
-        """A ``networkx.DiGraph`` with the reference's edge attributes (``weight``, ``overlap_len``)."""
+        """A ``networkx.DiGraph`` with the reference's edge attributes (``weight``, ``overlap_len`` and, when the
+        coverage was asked for, ``avg_coverage``)."""
         import networkx
         g = networkx.DiGraph()
         for u, v, w, o in self.edge_tuples():
             g.add_edge(u, v, weight=w, overlap_len=o)
+        if self.avg_coverage is not None:
+            for (u, v, _, _), c in zip(self.edge_tuples(), self.avg_coverage.tolist()):
+                g[u][v]["avg_coverage"] = c
         return g
+
+
+def _quotients(sums: np.ndarray) -> np.ndarray:
+    """``read_length_sum / path_length`` per edge as the reference computes it: both are exact integers below 2**53, so
+    the IEEE double quotient is Python's ``int / int`` bit for bit.  A zero path length raises like the reference."""
+    if len(sums) and (sums["path_length"] == 0).any():
+        raise ZeroDivisionError("division by zero: an edge with path_length == 0")
+    return sums["read_length_sum"].astype(np.float64) / sums["path_length"].astype(np.float64)
+
+
+def _coverage_into(out: "AssemblyEdges", ov: ExactOverlapper, graph_res: OverlapResult,
+                   rows_res: Optional[OverlapResult]) -> "AssemblyEdges":
+    """Fills the three coverage fields of ``out`` for the graph ``graph_res`` (whose edges ``out.edges`` are) when rows are given."""
+    if rows_res is not None:
+        out.coverage_sums, out.coverage_stats = ov.layout_coverage(graph_res, rows_res), ov.coverage_stats()
+        out.avg_coverage = _quotients(out.coverage_sums)
+    return out
+
+
+def average_coverage(ov: ExactOverlapper, graph_res: OverlapResult, rows_res: OverlapResult) -> np.ndarray:
+    """The reference's ``average_coverage_path(g, read_alignments, [u, v])`` for every edge of ``graph_res`` (an edge result
+    or a merged graph of ``ov``), ``read_alignments`` being every row of ``rows_res``: float64, in the graph's edge order."""
+    return _quotients(ov.layout_coverage(graph_res, rows_res))
+
+
+def write_graphml(f, g: "AssemblyEdges") -> int:
+    """The graph ``g`` as GraphML with the reference's attribute names: nodes named by ``node_name`` (the nodes of
+    ``node_order`` where the result carries one, else the ends of the edges in order of appearance), edge data ``weight``,
+    ``overlap_len`` and, when present, ``avg_coverage`` (written with ``repr``: it reads back to the same double).
+    Returns the number of edges."""
+    from xml.sax.saxutils import escape, quoteattr
+    names = g.edge_tuples()
+    nodes = [g.node_name(n) for n in g.node_order.tolist()] if g.node_order is not None else []
+    seen = set(nodes)
+    for u, v, _, _ in names:
+        for n in (u, v):
+            if n not in seen:
+                seen.add(n)
+                nodes.append(n)
+    cov = g.avg_coverage.tolist() if g.avg_coverage is not None else None
+    f.write('<?xml version="1.0" encoding="utf-8"?>\n<graphml xmlns="http://graphml.graphdrawing.org/xmlns" '
+            'xmlns:xsi="http://www.w3.org/2001/XMLSchema-instance" xsi:schemaLocation="http://graphml.graphdrawing.org/xmlns '
+            'http://graphml.graphdrawing.org/xmlns/1.0/graphml.xsd">\n')
+    f.write('  <key id="d0" for="edge" attr.name="weight" attr.type="long" />\n'
+            '  <key id="d1" for="edge" attr.name="overlap_len" attr.type="long" />\n')
+    if cov is not None:
+        f.write('  <key id="d2" for="edge" attr.name="avg_coverage" attr.type="double" />\n')
+    f.write('  <graph edgedefault="directed">\n')
+    f.write("".join("    <node id=%s />\n" % quoteattr(n) for n in nodes))
+    for i, (u, v, w, o) in enumerate(names):
+        f.write('    <edge source=%s target=%s>\n      <data key="d0">%d</data>\n      <data key="d1">%d</data>\n'
+                % (quoteattr(u), quoteattr(v), w, o))
+        if cov is not None:
+            f.write('      <data key="d2">%s</data>\n' % escape(repr(cov[i])))
+        f.write("    </edge>\n")
+    f.write("  </graph>\n</graphml>\n")
+    return len(names)
 
 
 def reduce_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, length_fuzz: int = 1000,
                           contained: Optional[np.ndarray] = None, stats: Optional[dict] = None, tips: bool = False,
-                          max_tip_len: int = 4, max_tip_len_bases: int = 5000) -> AssemblyEdges:
+                          max_tip_len: int = 4, max_tip_len_bases: int = 5000,
+                          coverage_rows: Optional[OverlapResult] = None) -> AssemblyEdges:
     """``remove_transitive_edges(g, length_fuzz)`` + removal + ``make_symmetric`` on a ``layout_edges`` result of
     ``ov`` (which stays valid): the edges left, plus the flag byte of every stage-1 edge.  With ``tips`` the tip
-    removal follows on the reduced graph."""
+    removal follows on the reduced graph.  With ``coverage_rows`` (here and in the functions below: the row result the
+    graph came from) the coverage of every edge left is computed as well."""
     kept, flags = ov.layout_reduce(edges_result, length_fuzz, want_flags=True)
     try:
         if contained is None:
             contained = np.zeros(len(ov) // 2, dtype=bool)
         stats = stats if stats is not None else ov.layout_stats()
         if tips:
-            out = remove_tips(ov, kept, max_tip_len, max_tip_len_bases, contained, stats)
-            out.flags, out.reduce_stats = flags, ov.reduce_stats()
+            rstats = ov.reduce_stats()
+            out = remove_tips(ov, kept, max_tip_len, max_tip_len_bases, contained, stats, coverage_rows)
+            out.flags, out.reduce_stats = flags, rstats
             return out
-        edges = kept.rows()
+        out = AssemblyEdges(kept.rows(), contained, ov.ids(), stats, flags, ov.reduce_stats())
+        return _coverage_into(out, ov, kept, coverage_rows)
     finally:
         kept.free()
-    return AssemblyEdges(edges, contained, ov.ids(), stats, flags, ov.reduce_stats())
 
 
 def remove_tips(ov: ExactOverlapper, edges_result: OverlapResult, max_tip_len: int = 4, max_tip_len_bases: int = 5000,
-                contained: Optional[np.ndarray] = None, stats: Optional[dict] = None) -> AssemblyEdges:
+                contained: Optional[np.ndarray] = None, stats: Optional[dict] = None,
+                coverage_rows: Optional[OverlapResult] = None) -> AssemblyEdges:
     """``remove_tips(g, max_tip_len, max_tip_len_bases)`` + ``make_symmetric`` + ``clean_graph`` on an edge result of
     ``ov`` (which stays valid): the edges left, plus the flag byte of every input edge."""
     kept, tip_flags = ov.layout_tips(edges_result, max_tip_len, max_tip_len_bases, want_flags=True)
     try:
-        edges = kept.rows()
+        if contained is None:
+            contained = np.zeros(len(ov) // 2, dtype=bool)
+        out = AssemblyEdges(kept.rows(), contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
+                            tip_flags=tip_flags, tips_stats=ov.tips_stats())
+        return _coverage_into(out, ov, kept, coverage_rows)
     finally:
         kept.free()
-    if contained is None:
-        contained = np.zeros(len(ov) // 2, dtype=bool)
-    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
-                         tip_flags=tip_flags, tips_stats=ov.tips_stats())
 
 
 def remove_diamond_tips(ov: ExactOverlapper, edges_result: OverlapResult, contained: Optional[np.ndarray] = None,
-                        stats: Optional[dict] = None) -> AssemblyEdges:
+                        stats: Optional[dict] = None, coverage_rows: Optional[OverlapResult] = None) -> AssemblyEdges:
     """``remove_diamond_tips(g)`` on an edge result of ``ov`` (which stays valid): the edges left, plus the flag byte of
     every input edge.  Nodes the call leaves without an edge stay nodes (no ``clean_graph`` follows in the reference)."""
     kept, diamond_flags = ov.layout_diamonds(edges_result, want_flags=True)
     try:
-        edges = kept.rows()
+        if contained is None:
+            contained = np.zeros(len(ov) // 2, dtype=bool)
+        out = AssemblyEdges(kept.rows(), contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
+                            diamond_flags=diamond_flags, diamond_stats=ov.diamond_stats())
+        return _coverage_into(out, ov, kept, coverage_rows)
     finally:
         kept.free()
-    if contained is None:
-        contained = np.zeros(len(ov) // 2, dtype=bool)
-    return AssemblyEdges(edges, contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
-                         diamond_flags=diamond_flags, diamond_stats=ov.diamond_stats())
 
 
-def _merge_into(out: AssemblyEdges, ov: ExactOverlapper, edges_result: OverlapResult) -> AssemblyEdges:
+def _merge_into(out: AssemblyEdges, ov: ExactOverlapper, edges_result: OverlapResult,
+                coverage_rows: Optional[OverlapResult] = None) -> AssemblyEdges:
     merged, flags = ov.layout_merge(edges_result, want_flags=True)
     try:
         out.edges, out.merge_flags, out.merge_stats = merged.rows(), flags, ov.merge_stats()
         out.merged_paths, out.node_order, out.node_lengths = merged.merged_paths(), merged.node_order(), ov.lengths()
+        _coverage_into(out, ov, merged, coverage_rows)
     finally:
         merged.free()
     return out
 
 
 def merge_unambiguous_paths(ov: ExactOverlapper, edges_result: OverlapResult, contained: Optional[np.ndarray] = None,
-                            stats: Optional[dict] = None) -> AssemblyEdges:
+                            stats: Optional[dict] = None, coverage_rows: Optional[OverlapResult] = None) -> AssemblyEdges:
     """``merge_unambiguous_paths(g)`` on an edge result of ``ov`` (which stays valid): the merged graph's edges, the flag
     byte of every input edge, the tables of the merged nodes and the node order."""
     if contained is None:
         contained = np.zeros(len(ov) // 2, dtype=bool)
     out = AssemblyEdges(np.empty(0), contained, ov.ids(), stats if stats is not None else ov.layout_stats())
-    return _merge_into(out, ov, edges_result)
+    return _merge_into(out, ov, edges_result, coverage_rows)
 
 
 def write_merged_graph(f, g: AssemblyEdges) -> int:
@@ -223,14 +299,20 @@ _REMOVED_BY_BASE = (0, 2, 5, 7)   # reduce flags 1-2, tips 1-3, diamonds 1-2, ti
 
 def clean_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, length_fuzz: int = 1000, max_tip_len: int = 4,
                          max_tip_len_bases: int = 5000, contained: Optional[np.ndarray] = None,
-                         stats: Optional[dict] = None, merge: bool = False) -> AssemblyEdges:
+                         stats: Optional[dict] = None, merge: bool = False, coverage: bool = False,
+                         rows: Optional[OverlapResult] = None) -> AssemblyEdges:
     """Graph cleaning as `phasm layout` runs it up to the merging of paths (assembler.py:145-182) on a ``layout_edges``
     result of ``ov`` (which stays valid): reduction + symmetry, tips with both bounds + symmetry + isolated nodes, diamond
     tips, tips again with ``max_tip_len`` and the function's own default of 5000 bases (the reference's second call
     passes no base bound) + symmetry + isolated nodes.  Four device calls; the edges stay in HBM in between.  With
     ``merge`` the merging of unambiguous paths follows as a fifth (assembler.py:184-186): ``removed_by`` stays what the
     cleaning made it -- a link of a path is not removed by cleaning -- and ``merge_flags`` refers to the edges that went
-    into the merge, those with ``removed_by == 0`` in stage-1 order."""
+    into the merge, those with ``removed_by == 0`` in stage-1 order.  With ``coverage`` the average coverage of every
+    edge of the graph the call ends with follows (assembler.py:190-193); it needs ``rows``, the row result the stage-1
+    graph was built from."""
+    if coverage and rows is None:
+        raise ValueError("coverage=True needs the row result the graph was built from (rows=...)")
+    coverage_rows = rows if coverage else None
     steps = (lambda r: ov.layout_reduce(r, length_fuzz, want_flags=True), ov.reduce_stats), \
             (lambda r: ov.layout_tips(r, max_tip_len, max_tip_len_bases, want_flags=True), ov.tips_stats), \
             (lambda r: ov.layout_diamonds(r, want_flags=True), ov.diamond_stats), \
@@ -253,9 +335,10 @@ def clean_assembly_graph(ov: ExactOverlapper, edges_result: OverlapResult, lengt
         out = AssemblyEdges(np.empty(0), contained, ov.ids(), stats if stats is not None else ov.layout_stats(),
                             removed_by=removed_by, clean_stats=clean_stats)
         if merge:
-            _merge_into(out, ov, cur)
+            _merge_into(out, ov, cur, coverage_rows)
         else:
             out.edges = cur.rows()
+            _coverage_into(out, ov, cur, coverage_rows)
     finally:
         if cur is not edges_result:
             cur.free()
@@ -266,37 +349,39 @@ def build_assembly_graph(ov: ExactOverlapper, rows: OverlapResult, min_read_leng
                          min_overlap_length: int = 0, max_overhang_abs: int = 1000,
                          max_overhang_rel: float = 0.8, reduce: bool = False, length_fuzz: int = 1000, tips: bool = False,
                          max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
-                         merge: bool = False) -> AssemblyEdges:
+                         merge: bool = False, coverage: bool = False) -> AssemblyEdges:
     """Filters + ``build_assembly_graph`` + contained-read removal on a row result of ``ov``; with ``reduce`` the
     transitive reduction and the symmetry pass as well; with ``tips`` the tip removal (after the reduction when both
     are asked for); with ``clean`` the whole of ``clean_assembly_graph`` instead of either; with ``merge`` (which implies
-    ``clean``) the merging of unambiguous paths after it."""
+    ``clean``) the merging of unambiguous paths after it; with ``coverage`` the average coverage of every edge of the
+    graph the call ends with."""
     res, removed = ov.layout_edges(rows, min_read_length, min_overlap_length, max_overhang_abs, max_overhang_rel)
+    coverage_rows = rows if coverage else None
     try:
         if clean or merge:
             return clean_assembly_graph(ov, res, length_fuzz, max_tip_len, max_tip_len_bases, removed.astype(bool), ov.layout_stats(),
-                                        merge=merge)
+                                        merge=merge, coverage=coverage, rows=coverage_rows)
         if reduce:
             return reduce_assembly_graph(ov, res, length_fuzz, removed.astype(bool), ov.layout_stats(), tips, max_tip_len,
-                                         max_tip_len_bases)
+                                         max_tip_len_bases, coverage_rows)
         if tips:
-            return remove_tips(ov, res, max_tip_len, max_tip_len_bases, removed.astype(bool), ov.layout_stats())
-        edges = res.rows()
+            return remove_tips(ov, res, max_tip_len, max_tip_len_bases, removed.astype(bool), ov.layout_stats(), coverage_rows)
+        out = AssemblyEdges(res.rows(), removed.astype(bool), ov.ids(), ov.layout_stats())
+        return _coverage_into(out, ov, res, coverage_rows)
     finally:
         res.free()
-    return AssemblyEdges(edges, removed.astype(bool), ov.ids(), ov.layout_stats())
 
 
 def layout_from_gfa(path: str, device: Optional[int] = None, reduce: bool = False, length_fuzz: int = 1000,
                     tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
-                    merge: bool = False, **params) -> AssemblyEdges:
+                    merge: bool = False, coverage: bool = False, **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 from an overlap file: native GFA2 read, then the device passes."""
     ov = ExactOverlapper(device=device)
     try:
         _, rows = ov.add_gfa(path)
         try:
             return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, coverage=coverage, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -315,14 +400,14 @@ def load_daligner(ov: ExactOverlapper, db_input, las_input, translations=None) -
 
 def layout_from_daligner(db_input, las_input, translations=None, device: Optional[int] = None, reduce: bool = False,
                          length_fuzz: int = 1000, tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000,
-                         clean: bool = False, merge: bool = False, **params) -> AssemblyEdges:
+                         clean: bool = False, merge: bool = False, coverage: bool = False, **params) -> AssemblyEdges:
     """``phasm layout`` stage 1 straight from DAZZ_DB / DALIGNER dump text."""
     ov = ExactOverlapper(device=device)
     try:
         rows = load_daligner(ov, db_input, las_input, translations)
         try:
             return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, coverage=coverage, **{**DEFAULTS, **params})
         finally:
             rows.free()
     finally:
@@ -331,11 +416,11 @@ def layout_from_daligner(db_input, las_input, translations=None, device: Optiona
 
 def layout_from_overlaps(ov: ExactOverlapper, min_length: int, reduce: bool = False, length_fuzz: int = 1000,
                          tips: bool = False, max_tip_len: int = 4, max_tip_len_bases: int = 5000, clean: bool = False,
-                         merge: bool = False, **params) -> AssemblyEdges:
+                         merge: bool = False, coverage: bool = False, **params) -> AssemblyEdges:
     """Overlap + layout stage 1 without the file in between: the rows never leave HBM."""
     rows = ov.overlaps_result(min_length)
     try:
         return build_assembly_graph(ov, rows, reduce=reduce, length_fuzz=length_fuzz, tips=tips, max_tip_len=max_tip_len,
-                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, **{**DEFAULTS, **params})
+                                        max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, coverage=coverage, **{**DEFAULTS, **params})
     finally:
         rows.free()

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -497,6 +497,22 @@ class ExactOverlapper:
     def merge_stats(self) -> dict:
         s = PoMergeStats()
         _check(self._h, self._lib.po_get_merge_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def layout_coverage(self, graph: OverlapResult, rows: OverlapResult) -> np.ndarray:
+        """``po_layout_coverage``: the operands of the reference's ``average_coverage_path(g, read_alignments, [u, v])`` for
+        every edge of ``graph`` (an edge result or a merged graph) from ALL the rows of ``rows`` (a row result); both stay
+        valid.  Returns a structured array (``read_length_sum`` u8, ``path_length`` i8) in the graph's edge order; the
+        reference's value is ``read_length_sum / path_length``."""
+        prm = PoCoverageParams(0)
+        out = np.zeros(len(graph), dtype=COVERAGE_DTYPE)
+        _check(self._h, self._lib.po_layout_coverage(
+            self._h, graph._ptr, rows._ptr, ctypes.byref(prm), out.ctypes.data_as(ctypes.c_void_p) if len(out) else None))
+        return out
+
+    def coverage_stats(self) -> dict:
+        s = PoCoverageStats()
+        _check(self._h, self._lib.po_get_coverage_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def node_order_stats(self) -> dict:
