@@ -44,6 +44,9 @@
 
 namespace {
 
+// workspaces of po_layout_reduce (po_handle::d_red, reduce.hip.h)
+enum { RB_CNT, RB_DEG, RB_OFF, RB_CUR, RB_TKEY, RB_TTGT, RB_TEID, RB_CTGT, RB_CW, RB_CEID, RB_CIDPOS, RB_STGT, RB_SEID, RB_STATE,
+       RB_FLAG1, RB_FLAGS, RB_KEEP, RB_KOFF, RB_N };
 // workspaces of po_layout_tips (po_handle::d_tip)
 enum { TB_CNT, TB_OUTDEG, TB_OUTSUM, TB_INDEG, TB_INSUM, TB_MARK, TB_CAND, TB_CSTATE, TB_EFLAG, TB_FLAGS, TB_KEEP, TB_KOFF,
        TB_TKEY, TB_TVAL, TB_ALIVE, TB_RCNT, TB_N };
@@ -55,6 +58,9 @@ enum { MB_CNT, MB_RCNT, MB_OUTDEG, MB_INDEG, MB_OUTE, MB_INE, MB_LINK, MB_BACK, 
 enum { VB_CNT, VB_USED, VB_NODEOF, VB_LEN, VB_TABLE, VB_SUM, VB_SETCNT, VB_OFF, VB_CUR, VB_LIST, VB_OUT, VB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
 constexpr int EV_LAY_N = 30;
+// the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
+enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27 };
+static_assert(EV_COVERAGE + 3 == EV_LAY_N, "the three events of po_layout_coverage are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -385,15 +391,13 @@ struct po_handle {
     // layout stage 1 (po_layout_edges)
     bool segments_only = false;  // reads were added by po_add_segment: lengths and names, no sequence
     int ids_paired = -1;         // -1 unknown, 0/1: ids come in (name+"+", name+"-") pairs
-    hipEvent_t ev_lay[EV_LAY_N] = {};  // [0..3] po_layout_edges, [4..8] po_layout_reduce, [9..14] po_layout_tips, [15..17] node order,
-                                 // [18..21] po_layout_diamonds, [22..26] po_layout_merge, [27..29] po_layout_coverage
+    hipEvent_t ev_lay[EV_LAY_N] = {};  // one slice per layout call: EV_EDGES, EV_REDUCE, ... (the enum beside EV_LAY_N)
     DevBuf d_lay_len, d_lay_cnt, d_rflag, d_removed, d_ekey, d_ecnt, d_ewin, d_eoff;
     DevBuf d_efirst;             // table path: first writer row per winning row (the edges' rank, po_result::d_rank)
     po_layout_stats lstats = {};
 
     // transitive reduction + symmetry pass (po_layout_reduce, reduce.hip.h)
-    DevBuf d_red_cnt, d_red_deg, d_red_off, d_red_cur, d_red_tkey, d_red_ttgt, d_red_teid, d_red_ctgt, d_red_cw, d_red_ceid,
-        d_red_cidpos, d_red_stgt, d_red_seid, d_red_state, d_red_flag1, d_red_flags, d_red_keep, d_red_koff;
+    DevBuf d_red[RB_N];
     po_reduce_stats rstats = {};
 
     // the node order of the stage-1 graph (k_layout_node_rank) and tip removal (po_layout_tips, tips.hip.h)
@@ -2728,6 +2732,128 @@ po_status ensure_nrank(po_handle* h, po_result* res, size_t bytes) {
     return ensure(h, res->d_nrank, bytes, 1.0, false);
 }
 
+// the edge buffer of a new edge result, likewise (never less than the smallest allocation)
+po_status take_spare_edges(po_handle* h, po_result* res, size_t bytes) {
+    if (h->spare_edges.p && h->spare_edges.cap >= bytes) {
+        res->d_rows = h->spare_edges;
+        h->spare_edges = DevBuf();
+    }
+    return ensure(h, res->d_rows, std::max<size_t>(bytes, 256), 1.0, false);
+}
+
+// all ones behind the ranks of `n_nodes` nodes: the tail of the smallest allocation names no node
+po_status fill_nrank_tail(po_handle* h, po_result* res, size_t n_nodes, size_t nrank_bytes) {
+    if (n_nodes * 8 < nrank_bytes)
+        HIP_TRY(h, hipMemsetAsync(res->d_nrank.as<char>() + n_nodes * 8, 0xFF, nrank_bytes - n_nodes * 8, h->stream));
+    return PO_OK;
+}
+
+// every buffer a result may hold on the device (an empty one releases nothing)
+void release_device(po_result* r) {
+    for (DevBuf* b : {&r->d_rows, &r->d_rank, &r->d_nrank, &r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen}) b->release();
+}
+
+// the grid of a kernel that strides over n items: eight workgroups of 256 per CU at the most
+uint32_t stride_grid(const po_handle* h, uint64_t n) {
+    return std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
+}
+
+// the events of the layout calls, made by the first of them on a handle
+po_status lay_events(po_handle* h) {
+    for (hipEvent_t& e : h->ev_lay)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    return PO_OK;
+}
+
+// ---- what the stage-2 calls (po_layout_reduce, _tips, _diamonds, _merge) share --------------------------------------
+// A driver opens with stage2_open, works out one keep byte and one flag byte per input edge, and closes with
+// stage2_count and stage2_emit; between those two it reads its own counters from the landing zone.
+
+// what a stage has worked out per input edge when it closes: keep byte, flag byte, and room for the kept edges' places
+struct EdgeMarks {
+    const uint8_t* keep;
+    const uint8_t* flags;
+    uint32_t* koff;
+};
+
+// The open: an empty edge result, the bound on the edges (`limit`: what the stage's 32-bit indices allow), with
+// `need_order` the node order the stage walks in, the events, the edges on the device.
+po_status stage2_open(po_handle* h, po_result* edges, po_result* res, const char* name, uint64_t limit, bool need_order,
+                      uint64_t& n_edges_in) {
+    res->count = 0;
+    res->elem = sizeof(po_edge);
+    res->kind_edges = true;
+    if (edges->count >= limit) return fail(h, PO_ERR_CAPACITY, std::string(name) + ": too many edges for one call");
+    n_edges_in = (uint32_t)edges->count;
+    if (need_order) {
+        if (!edges->d_nrank.p) return fail(h, PO_ERR_INVALID, std::string(name) + ": the edge result carries no node order");
+        if (edges->count && h->len.empty()) return fail(h, PO_ERR_INVALID, std::string(name) + ": edges on a handle without reads");
+    }
+    PO_TRY(lay_events(h));
+    return rows_to_device(h, edges);
+}
+
+// The close, first step: the first `n_cnt` counters to words [16..] of the landing zone, the places of the kept edges,
+// the flags on their way to the host; waits for all of it.
+po_status stage2_count(po_handle* h, uint32_t n, const unsigned long long* cnt, int n_cnt, const EdgeMarks& m, bool want_flags,
+                       uint64_t& n_kept) {
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, (size_t)n_cnt * 8, hipMemcpyDeviceToHost, st));
+    PO_TRY(prefix_sum<uint8_t>(h, m.keep, n, m.koff, &h->pinned[2]));
+    if (want_flags && n) {
+        PO_TRY(ensure_host(h, h->scratch_host, n));
+        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, m.flags, n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    n_kept = h->pinned[2];
+    return PO_OK;
+}
+
+// The close, second step: the flags to the caller, the kept edges of `src` (and their ranks, where the input has them)
+// into the result's buffers -- the buffer of the previous call's result if it is large enough --, the closing event.
+po_status stage2_emit(po_handle* h, po_result* res, uint32_t n, uint64_t n_kept, const po::Edge* src, const uint32_t* src_rank,
+                      const EdgeMarks& m, uint8_t* flags_out, hipEvent_t done) {
+    hipStream_t st = h->stream;
+    if (flags_out && n) std::memcpy(flags_out, h->scratch_host.p, n);
+    PO_TRY(take_spare_edges(h, res, n_kept * sizeof(po_edge)));
+    if (src_rank) PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_kept * 4, 256), 1.0, false));
+    if (n_kept) {
+        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, src, src_rank, n, m.keep, m.koff,
+                           res->d_rows.as<po::Edge>(), src_rank ? res->d_rank.as<uint32_t>() : nullptr);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(done, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    res->count = n_kept;
+    return PO_OK;
+}
+
+// The rounds of po_layout_tips and po_layout_diamonds go out in batches (the first of `first_batch` rounds, the later
+// ones of TIP_BATCH), one readback per batch: `launch(r, word)` enqueues round r, which counts the candidates it leaves
+// unresolved in `word`.  A round launched after the last candidate has resolved finds nothing to do.
+template <class Launch>
+po_status batched_rounds(po_handle* h, uint32_t n_cand, uint32_t first_batch, const char* name, unsigned long long* rcnt,
+                         Launch&& launch, uint64_t& rounds_out) {
+    hipStream_t st = h->stream;
+    uint32_t round = 0;
+    for (uint64_t unresolved = n_cand; unresolved;) {
+        const uint32_t batch = round == 0 ? first_batch : (uint32_t)TIP_BATCH;
+        HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
+        for (uint32_t j = 0; j < batch; ++j) launch(round + j, rcnt + j);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        for (uint32_t j = 0; j < batch && unresolved; ++j, ++round) {
+            // (the unresolved candidate of the lowest rank holds its own key everywhere: a round that resolves none is a bug)
+            if (h->pinned[32 + j] >= unresolved)
+                return fail(h, PO_ERR_HIP, std::string("internal: a round of ") + name + " resolved no candidate");
+            unresolved = h->pinned[32 + j];
+        }
+    }
+    rounds_out = round;
+    return PO_OK;
+}
+
 po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm, uint8_t* removed_out, po_result* res) {
     PO_TRY(init_device(h));
     hipStream_t st = h->stream;
@@ -2742,8 +2868,8 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
     const uint32_t n_rows = (uint32_t)n_rows64;
     const uint32_t n_names = n_nodes / 2;
     L.n_rows = n_rows;
-    for (hipEvent_t& e : h->ev_lay)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    PO_TRY(lay_events(h));
+    hipEvent_t *ev = h->ev_lay + EV_EDGES, *ev_no = h->ev_lay + EV_NODE_ORDER;
     PO_TRY(rows_to_device(h, rows));
     PO_TRY(ensure(h, h->d_lay_len, ((size_t)n_nodes + 1) * 4));
     PO_TRY(ensure(h, h->d_lay_cnt, 128));
@@ -2762,16 +2888,16 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
     P.max_overhang_abs = prm.max_overhang_abs;
     P.pad = 0;
     P.max_overhang_rel = prm.max_overhang_rel;
-    const uint32_t stride_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_rows, 256), (uint32_t)h->n_cu * 8));
-    HIP_TRY(h, hipEventRecord(h->ev_lay[0], st));
+    const uint32_t row_grid = stride_grid(h, n_rows);
+    HIP_TRY(h, hipEventRecord(ev[0], st));
     if (n_rows) {
-        hipLaunchKernelGGL(po::k_layout_classify, dim3(stride_grid), dim3(256), 0, st, d_rows, n_rows, d_len, n_nodes, P,
+        hipLaunchKernelGGL(po::k_layout_classify, dim3(row_grid), dim3(256), 0, st, d_rows, n_rows, d_len, n_nodes, P,
                            h->d_rflag.as<uint8_t>(), h->d_removed.as<uint8_t>(), cnt);
         hipLaunchKernelGGL(po::k_count_bytes, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_names, 256), 256u))), dim3(256), 0,
                            st, h->d_removed.as<uint8_t>(), n_names, cnt + po::LC_N);
         HIP_TRY(h, hipGetLastError());
     }
-    HIP_TRY(h, hipEventRecord(h->ev_lay[1], st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
     HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, (po::LC_N + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     const uint64_t* c = h->pinned + 16;
@@ -2792,14 +2918,10 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
                            h->d_rflag.as<uint8_t>(), h->d_removed.as<uint8_t>(), h->d_ecnt.as<uint8_t>(), h->d_ewin.as<uint8_t>());
         HIP_TRY(h, hipGetLastError());
         PO_TRY(prefix_sum<uint8_t>(h, h->d_ecnt.as<uint8_t>(), n_rows, h->d_eoff.as<uint32_t>(), &h->pinned[2]));
-        HIP_TRY(h, hipEventRecord(h->ev_lay[2], st));
+        HIP_TRY(h, hipEventRecord(ev[2], st));
         HIP_TRY(h, hipStreamSynchronize(st));
         n_edges = h->pinned[2];
-        if (h->spare_edges.p && h->spare_edges.cap >= n_edges * sizeof(po_edge)) {
-            res->d_rows = h->spare_edges;
-            h->spare_edges = DevBuf();
-        }
-        PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_edges * sizeof(po_edge), 256), 1.0, false));
+        PO_TRY(take_spare_edges(h, res, n_edges * sizeof(po_edge)));
         if (n_edges) {
             hipLaunchKernelGGL(po::k_layout_emit, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, d_rows, n_rows, d_len,
                                h->d_rflag.as<uint8_t>(), h->d_ewin.as<uint8_t>(), h->d_eoff.as<uint32_t>(),
@@ -2817,21 +2939,17 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
         PO_TRY(ensure(h, h->d_eoff, ((size_t)n_rows + 1) * 4));
         PO_TRY(ensure(h, h->d_efirst, (size_t)n_rows * 4));
         HIP_TRY(h, hipMemsetAsync(h->d_ekey.p, 0xFF, (size_t)n_slots * sizeof(po::EdgeSlot), st));
-        hipLaunchKernelGGL(po::k_layout_insert, dim3(stride_grid), dim3(256), 0, st, d_rows, n_rows, d_len, h->d_rflag.as<uint8_t>(),
+        hipLaunchKernelGGL(po::k_layout_insert, dim3(row_grid), dim3(256), 0, st, d_rows, n_rows, d_len, h->d_rflag.as<uint8_t>(),
                            h->d_removed.as<uint8_t>(), h->d_ekey.as<po::EdgeSlot>(), n_slots);
         hipLaunchKernelGGL(po::k_layout_winner, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, d_rows, n_rows, d_len,
                            h->d_rflag.as<uint8_t>(), h->d_removed.as<uint8_t>(), h->d_ekey.as<po::EdgeSlot>(), n_slots,
                            h->d_ecnt.as<uint8_t>(), h->d_ewin.as<uint8_t>(), h->d_efirst.as<uint32_t>());
         HIP_TRY(h, hipGetLastError());
         PO_TRY(prefix_sum<uint8_t>(h, h->d_ecnt.as<uint8_t>(), n_rows, h->d_eoff.as<uint32_t>(), &h->pinned[2]));
-        HIP_TRY(h, hipEventRecord(h->ev_lay[2], st));
+        HIP_TRY(h, hipEventRecord(ev[2], st));
         HIP_TRY(h, hipStreamSynchronize(st));
         n_edges = h->pinned[2];
-        if (h->spare_edges.p && h->spare_edges.cap >= n_edges * sizeof(po_edge)) {
-            res->d_rows = h->spare_edges;
-            h->spare_edges = DevBuf();
-        }
-        PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_edges * sizeof(po_edge), 256), 1.0, false));
+        PO_TRY(take_spare_edges(h, res, n_edges * sizeof(po_edge)));
         PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_edges * 4, 256), 1.0, false));
         if (n_edges) {
             hipLaunchKernelGGL(po::k_layout_emit, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, d_rows, n_rows, d_len,
@@ -2840,28 +2958,28 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
             HIP_TRY(h, hipGetLastError());
         }
     } else {
-        HIP_TRY(h, hipEventRecord(h->ev_lay[2], st));
+        HIP_TRY(h, hipEventRecord(ev[2], st));
     }
-    HIP_TRY(h, hipEventRecord(h->ev_lay[3], st));
+    HIP_TRY(h, hipEventRecord(ev[3], st));
     // the node order of this graph, for po_layout_tips.  Outside the times above, which are stage 1 as it was; these two
     // passes have times of their own (po_get_node_order_stats)
     po_node_order_stats& NO = h->nostats;
     NO = po_node_order_stats();
     NO.n_rows = n_rows;
     PO_TRY(ensure_nrank(h, res, std::max<size_t>((size_t)n_nodes * 8, 256)));
-    HIP_TRY(h, hipEventRecord(h->ev_lay[15], st));
+    HIP_TRY(h, hipEventRecord(ev_no[0], st));
     HIP_TRY(h, hipMemsetAsync(res->d_nrank.p, 0xFF, std::max<size_t>((size_t)n_nodes * 8, 256), st));
     if (L.n_pass) {
         PO_TRY(ensure(h, h->d_lay_firstc, ((size_t)n_nodes + 1) * 4));
         HIP_TRY(h, hipMemsetAsync(h->d_lay_firstc.p, 0xFF, ((size_t)n_nodes + 1) * 4, st));
-        hipLaunchKernelGGL(po::k_layout_first_contained, dim3(stride_grid), dim3(256), 0, st, d_rows, n_rows,
+        hipLaunchKernelGGL(po::k_layout_first_contained, dim3(row_grid), dim3(256), 0, st, d_rows, n_rows,
                            h->d_rflag.as<uint8_t>(), h->d_lay_firstc.as<uint32_t>());
-        HIP_TRY(h, hipEventRecord(h->ev_lay[16], st));
-        hipLaunchKernelGGL(po::k_layout_node_rank, dim3(stride_grid), dim3(256), 0, st, d_rows, n_rows, h->d_rflag.as<uint8_t>(),
+        HIP_TRY(h, hipEventRecord(ev_no[1], st));
+        hipLaunchKernelGGL(po::k_layout_node_rank, dim3(row_grid), dim3(256), 0, st, d_rows, n_rows, h->d_rflag.as<uint8_t>(),
                            h->d_removed.as<uint8_t>(), h->d_lay_firstc.as<uint32_t>(), res->d_nrank.as<unsigned long long>());
         HIP_TRY(h, hipGetLastError());
     }
-    HIP_TRY(h, hipEventRecord(h->ev_lay[17], st));
+    HIP_TRY(h, hipEventRecord(ev_no[2], st));
     if (removed_out && n_names) {
         PO_TRY(ensure_host(h, h->scratch_host, n_names));
         HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_removed.p, n_names, hipMemcpyDeviceToHost, st));
@@ -2870,15 +2988,15 @@ po_status run_layout(po_handle* h, po_result* rows, const po_layout_params& prm,
     if (removed_out && n_names) std::memcpy(removed_out, h->scratch_host.p, n_names);
     res->count = n_edges;
     L.n_edges = n_edges;
-    (void)hipEventElapsedTime(&L.ms_classify, h->ev_lay[0], h->ev_lay[1]);
-    (void)hipEventElapsedTime(&L.ms_dedupe, h->ev_lay[1], h->ev_lay[2]);
-    (void)hipEventElapsedTime(&L.ms_emit, h->ev_lay[2], h->ev_lay[3]);
-    (void)hipEventElapsedTime(&L.ms_total, h->ev_lay[0], h->ev_lay[3]);
+    (void)hipEventElapsedTime(&L.ms_classify, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&L.ms_dedupe, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&L.ms_emit, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&L.ms_total, ev[0], ev[3]);
     if (L.n_pass) {
-        (void)hipEventElapsedTime(&NO.ms_first_contained, h->ev_lay[15], h->ev_lay[16]);
-        (void)hipEventElapsedTime(&NO.ms_rank, h->ev_lay[16], h->ev_lay[17]);
+        (void)hipEventElapsedTime(&NO.ms_first_contained, ev_no[0], ev_no[1]);
+        (void)hipEventElapsedTime(&NO.ms_rank, ev_no[1], ev_no[2]);
     }
-    (void)hipEventElapsedTime(&NO.ms_total, h->ev_lay[15], h->ev_lay[17]);
+    (void)hipEventElapsedTime(&NO.ms_total, ev_no[0], ev_no[2]);
     return PO_OK;
 }
 
@@ -2888,17 +3006,10 @@ po_status run_reduce(po_handle* h, po_result* edges, const po_reduce_params& prm
     hipStream_t st = h->stream;
     po_reduce_stats& R = h->rstats;
     R = po_reduce_stats();
-    res->count = 0;
-    res->elem = sizeof(po_edge);
-    res->kind_edges = true;
     const uint32_t n_nodes = (uint32_t)h->len.size();
-    if (edges->count >= 0xFFFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_reduce: too many edges for one call");
+    PO_TRY(stage2_open(h, edges, res, "po_layout_reduce", 0xFFFFFF00ull, false, R.n_edges_in));
     const uint32_t n = (uint32_t)edges->count;
-    R.n_edges_in = n;
-    for (hipEvent_t& e : h->ev_lay)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
-    hipEvent_t* ev = h->ev_lay + 4;
-    PO_TRY(rows_to_device(h, edges));
+    hipEvent_t* ev = h->ev_lay + EV_REDUCE;
     if (edges->d_nrank.p) {   // the node order goes with the graph: the reduction removes edges, never nodes
         const size_t nb = std::max<size_t>((size_t)n_nodes * 8, 256);
         PO_TRY(ensure_nrank(h, res, nb));
@@ -2912,27 +3023,29 @@ po_status run_reduce(po_handle* h, po_result* edges, const po_reduce_params& prm
     }
     const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n;
     PO_TRY(ensure(h, h->d_scalars, 128));
-    PO_TRY(ensure(h, h->d_red_cnt, 128));
-    PO_TRY(ensure(h, h->d_red_deg, nn * 4));
-    PO_TRY(ensure(h, h->d_red_off, nn * 4));
-    PO_TRY(ensure(h, h->d_red_cur, nn * 4));
-    PO_TRY(ensure(h, h->d_red_tkey, ne * 8));
-    DevBuf* u32s[] = {&h->d_red_ttgt, &h->d_red_teid, &h->d_red_ctgt, &h->d_red_cw, &h->d_red_ceid, &h->d_red_cidpos,
-                      &h->d_red_stgt, &h->d_red_seid};
-    for (DevBuf* b : u32s) PO_TRY(ensure(h, *b, ne * 4));
-    PO_TRY(ensure(h, h->d_red_koff, (ne + 1) * 4));
-    DevBuf* u8s[] = {&h->d_red_state, &h->d_red_flag1, &h->d_red_flags, &h->d_red_keep};
-    for (DevBuf* b : u8s) PO_TRY(ensure(h, *b, ne));
+    DevBuf* B = h->d_red;
+    PO_TRY(ensure(h, B[RB_CNT], 128));
+    for (int k : {RB_DEG, RB_OFF, RB_CUR}) PO_TRY(ensure(h, B[k], nn * 4));
+    PO_TRY(ensure(h, B[RB_TKEY], ne * 8));
+    for (int k : {RB_TTGT, RB_TEID, RB_CTGT, RB_CW, RB_CEID, RB_CIDPOS, RB_STGT, RB_SEID}) PO_TRY(ensure(h, B[k], ne * 4));
+    PO_TRY(ensure(h, B[RB_KOFF], (ne + 1) * 4));
+    for (int k : {RB_STATE, RB_FLAG1, RB_FLAGS, RB_KEEP}) PO_TRY(ensure(h, B[k], ne));
     const po::Edge* d_edges = edges->d_rows.as<po::Edge>();
     const uint32_t* d_rank = edges->d_rank.p ? edges->d_rank.as<uint32_t>() : nullptr;
-    unsigned long long* cnt = h->d_red_cnt.as<unsigned long long>();
-    uint32_t *deg = h->d_red_deg.as<uint32_t>(), *off = h->d_red_off.as<uint32_t>(), *cur = h->d_red_cur.as<uint32_t>();
-    const uint32_t stride_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
+    unsigned long long *cnt = B[RB_CNT].as<unsigned long long>(), *tkey = B[RB_TKEY].as<unsigned long long>();
+    uint32_t *deg = B[RB_DEG].as<uint32_t>(), *off = B[RB_OFF].as<uint32_t>(), *cur = B[RB_CUR].as<uint32_t>(),
+             *ttgt = B[RB_TTGT].as<uint32_t>(), *teid = B[RB_TEID].as<uint32_t>(), *ctgt = B[RB_CTGT].as<uint32_t>(),
+             *ceid = B[RB_CEID].as<uint32_t>(), *cidpos = B[RB_CIDPOS].as<uint32_t>(), *stgt = B[RB_STGT].as<uint32_t>(),
+             *seid = B[RB_SEID].as<uint32_t>(), *koff = B[RB_KOFF].as<uint32_t>();
+    int32_t* cw = B[RB_CW].as<int32_t>();
+    uint8_t *state = B[RB_STATE].as<uint8_t>(), *flag1 = B[RB_FLAG1].as<uint8_t>(), *flags = B[RB_FLAGS].as<uint8_t>(),
+            *keep = B[RB_KEEP].as<uint8_t>();
+    const uint32_t edge_grid = stride_grid(h, n);
     HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
     HIP_TRY(h, hipMemsetAsync(deg, 0, nn * 4, st));
     HIP_TRY(h, hipMemsetAsync(cur, 0, nn * 4, st));
     HIP_TRY(h, hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(po::k_reduce_degree, dim3(stride_grid), dim3(256), 0, st, d_edges, n, n_nodes, deg, cnt);
+    hipLaunchKernelGGL(po::k_reduce_degree, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_nodes, deg, cnt);
     hipLaunchKernelGGL(po::k_reduce_maxdeg, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_nodes, 256), 256u))), dim3(256), 0, st,
                        deg, n_nodes, cnt);
     HIP_TRY(h, hipGetLastError());
@@ -2942,51 +3055,26 @@ po_status run_reduce(po_handle* h, po_result* edges, const po_reduce_params& prm
     // (an edge that names a node the handle does not hold would index out of the CSR: nothing is scattered then)
     if (h->pinned[16 + po::RC_INVALID]) return fail(h, PO_ERR_INVALID, "po_layout_reduce: an edge names a read the handle does not hold");
     R.max_out_degree = h->pinned[16 + po::RC_MAXDEG];
-    hipLaunchKernelGGL(po::k_reduce_scatter, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, off, cur,
-                       h->d_red_tkey.as<unsigned long long>(), h->d_red_ttgt.as<uint32_t>(), h->d_red_teid.as<uint32_t>());
-    hipLaunchKernelGGL(po::k_reduce_order, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, n, off, deg,
-                       h->d_red_tkey.as<unsigned long long>(), h->d_red_ttgt.as<uint32_t>(), h->d_red_teid.as<uint32_t>(),
-                       h->d_red_ctgt.as<uint32_t>(), h->d_red_cw.as<int32_t>(), h->d_red_ceid.as<uint32_t>(),
-                       h->d_red_cidpos.as<uint32_t>(), h->d_red_stgt.as<uint32_t>(), h->d_red_seid.as<uint32_t>());
+    hipLaunchKernelGGL(po::k_reduce_scatter, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, off, cur, tkey, ttgt, teid);
+    hipLaunchKernelGGL(po::k_reduce_order, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, n, off, deg, tkey, ttgt, teid, ctgt, cw, ceid,
+                       cidpos, stgt, seid);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[1], st));
-    hipLaunchKernelGGL(po::k_reduce_mark, dim3(n_nodes), dim3(po::WAVE), 0, st, n_nodes, prm.length_fuzz, off, deg,
-                       h->d_red_ctgt.as<uint32_t>(), h->d_red_cw.as<int32_t>(), h->d_red_ceid.as<uint32_t>(),
-                       h->d_red_cidpos.as<uint32_t>(), h->d_red_stgt.as<uint32_t>(), h->d_red_state.as<uint8_t>(),
-                       h->d_red_flag1.as<uint8_t>());
+    hipLaunchKernelGGL(po::k_reduce_mark, dim3(n_nodes), dim3(po::WAVE), 0, st, n_nodes, prm.length_fuzz, off, deg, ctgt, cw, ceid,
+                       cidpos, stgt, state, flag1);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(po::k_reduce_symmetric, dim3(stride_grid), dim3(256), 0, st, d_edges, n, off, deg, h->d_red_stgt.as<uint32_t>(),
-                       h->d_red_seid.as<uint32_t>(), h->d_red_flag1.as<uint8_t>(), h->d_red_flags.as<uint8_t>(),
-                       h->d_red_keep.as<uint8_t>(), cnt);
+    hipLaunchKernelGGL(po::k_reduce_symmetric, dim3(edge_grid), dim3(256), 0, st, d_edges, n, off, deg, stgt, seid, flag1, flags, keep,
+                       cnt);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[3], st));
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::RC_N * 8, hipMemcpyDeviceToHost, st));
-    PO_TRY(prefix_sum<uint8_t>(h, h->d_red_keep.as<uint8_t>(), n, h->d_red_koff.as<uint32_t>(), &h->pinned[2]));
-    if (flags_out) {
-        PO_TRY(ensure_host(h, h->scratch_host, ne));
-        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_red_flags.p, ne, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    const uint64_t n_kept = h->pinned[2];
+    uint64_t n_kept = 0;
+    const EdgeMarks marks = {keep, flags, koff};
+    PO_TRY(stage2_count(h, n, cnt, po::RC_N, marks, flags_out != nullptr, n_kept));
     R.n_transitive = h->pinned[16 + po::RC_TRANSITIVE];
     R.n_asymmetric = h->pinned[16 + po::RC_ASYMMETRIC];
     R.n_edges_out = n_kept;
-    if (flags_out) std::memcpy(flags_out, h->scratch_host.p, ne);
-    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
-        res->d_rows = h->spare_edges;
-        h->spare_edges = DevBuf();
-    }
-    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
-    if (d_rank) PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_kept * 4, 256), 1.0, false));
-    if (n_kept) {
-        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, h->d_red_keep.as<uint8_t>(),
-                           h->d_red_koff.as<uint32_t>(), res->d_rows.as<po::Edge>(), d_rank ? res->d_rank.as<uint32_t>() : nullptr);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipEventRecord(ev[4], st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    res->count = n_kept;
+    PO_TRY(stage2_emit(h, res, n, n_kept, d_edges, d_rank, marks, flags_out, ev[4]));
     (void)hipEventElapsedTime(&R.ms_csr, ev[0], ev[1]);
     (void)hipEventElapsedTime(&R.ms_mark, ev[1], ev[2]);
     (void)hipEventElapsedTime(&R.ms_symmetric, ev[2], ev[3]);
@@ -3001,19 +3089,10 @@ po_status run_tips(po_handle* h, po_result* edges, const po_tips_params& prm, ui
     hipStream_t st = h->stream;
     po_tips_stats& T = h->tstats;
     T = po_tips_stats();
-    res->count = 0;
-    res->elem = sizeof(po_edge);
-    res->kind_edges = true;
     const uint32_t n_nodes = (uint32_t)h->len.size();
-    if (edges->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_tips: too many edges for one call");
+    PO_TRY(stage2_open(h, edges, res, "po_layout_tips", 0x7FFFFF00ull, true, T.n_edges_in));
     const uint32_t n = (uint32_t)edges->count;
-    T.n_edges_in = n;
-    if (!edges->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_layout_tips: the edge result carries no node order");
-    if (n && n_nodes == 0) return fail(h, PO_ERR_INVALID, "po_layout_tips: edges on a handle without reads");
-    for (hipEvent_t& e : h->ev_lay)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
-    hipEvent_t* ev = h->ev_lay + 9;
-    PO_TRY(rows_to_device(h, edges));
+    hipEvent_t* ev = h->ev_lay + EV_TIPS;
     const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n + 1;
     const uint32_t n_slots = 2 * n + 64;
     DevBuf* B = h->d_tip;
@@ -3039,9 +3118,8 @@ po_status run_tips(po_handle* h, po_result* edges, const po_tips_params& prm, ui
     uint8_t *cstate = B[TB_CSTATE].as<uint8_t>(), *eflag = B[TB_EFLAG].as<uint8_t>(), *flags = B[TB_FLAGS].as<uint8_t>(),
             *keep = B[TB_KEEP].as<uint8_t>(), *alive = B[TB_ALIVE].as<uint8_t>();
     unsigned long long* tkey = B[TB_TKEY].as<unsigned long long>();
-    uint32_t* tval = B[TB_TVAL].as<uint32_t>();
-    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
-    const uint32_t node_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_nodes, 256), (uint32_t)h->n_cu * 8));
+    uint32_t *tval = B[TB_TVAL].as<uint32_t>(), *koff = B[TB_KOFF].as<uint32_t>();
+    const uint32_t edge_grid = stride_grid(h, n), node_grid = stride_grid(h, n_nodes);
     // No truncation of the caller's bound: a walk never visits a node twice (its start has no in-edge, and every later
     // node has exactly one when the walk leaves it -- tips.hip.h), so it holds at most n_nodes
     // nodes and any bound of n_nodes or more decides as n_nodes does.  The cap keeps `max_len + 2` from wrapping and
@@ -3077,29 +3155,12 @@ po_status run_tips(po_handle* h, po_result* edges, const po_tips_params& prm, ui
         HIP_TRY(h, hipStreamSynchronize(st));
         const uint32_t n_cand = (uint32_t)h->pinned[16];
         n_cand_out = n_cand;
-        // Rounds go out in batches, one readback per batch: round j of a batch counts the candidates it leaves unresolved
-        // in word j.  A round launched after the last candidate has resolved finds nothing to do.
-        uint32_t round = 0;
-        for (uint64_t unresolved = n_cand; unresolved;) {
-            const uint32_t batch = round == 0 ? 8u : (uint32_t)TIP_BATCH;
-            HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
-            for (uint32_t j = 0; j < batch; ++j) {
-                hipLaunchKernelGGL(po::k_tips_mark, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, rev, max_len, round + j,
-                                   cand, cstate, n_cand, nrank, g.fdeg, g.fsum, mark);
-                hipLaunchKernelGGL(po::k_tips_resolve, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, rev, max_len,
-                                   prm.max_tip_len_bases, round + j, which, cand, cstate, n_cand, nrank, g, mark, eflag, rcnt + j);
-            }
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(h, hipStreamSynchronize(st));
-            for (uint32_t j = 0; j < batch && unresolved; ++j, ++round) {
-                // (the unresolved candidate of the lowest rank holds its own key everywhere: a round that resolves none is a bug)
-                if (h->pinned[32 + j] >= unresolved) return fail(h, PO_ERR_HIP, "internal: a round of po_layout_tips resolved no candidate");
-                unresolved = h->pinned[32 + j];
-            }
-        }
-        rounds_out = round;
-        return PO_OK;
+        return batched_rounds(h, n_cand, 8, "po_layout_tips", rcnt, [&](uint32_t r, unsigned long long* left) {
+            hipLaunchKernelGGL(po::k_tips_mark, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, rev, max_len, r, cand, cstate,
+                               n_cand, nrank, g.fdeg, g.fsum, mark);
+            hipLaunchKernelGGL(po::k_tips_resolve, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, rev, max_len,
+                               prm.max_tip_len_bases, r, which, cand, cstate, n_cand, nrank, g, mark, eflag, left);
+        }, rounds_out);
     };
     PO_TRY(pass(0, 1, T.n_candidates_in, T.n_rounds_in));
     HIP_TRY(h, hipEventRecord(ev[2], st));
@@ -3113,38 +3174,18 @@ po_status run_tips(po_handle* h, po_result* edges, const po_tips_params& prm, ui
     hipLaunchKernelGGL(po::k_tips_nodes, dim3(node_grid), dim3(256), 0, st, n_nodes, nrank, alive,
                        res->d_nrank.as<unsigned long long>(), cnt);
     HIP_TRY(h, hipGetLastError());
-    if ((size_t)n_nodes * 8 < nrank_bytes)   // (the tail of the smallest allocation: no node)
-        HIP_TRY(h, hipMemsetAsync(res->d_nrank.as<char>() + (size_t)n_nodes * 8, 0xFF, nrank_bytes - (size_t)n_nodes * 8, st));
+    PO_TRY(fill_nrank_tail(h, res, n_nodes, nrank_bytes));
     HIP_TRY(h, hipEventRecord(ev[4], st));
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::TC_N * 8, hipMemcpyDeviceToHost, st));
-    PO_TRY(prefix_sum<uint8_t>(h, keep, n, B[TB_KOFF].as<uint32_t>(), &h->pinned[2]));
-    if (flags_out && n) {
-        PO_TRY(ensure_host(h, h->scratch_host, n));
-        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, flags, n, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    const uint64_t n_kept = h->pinned[2];
+    uint64_t n_kept = 0;
+    const EdgeMarks marks = {keep, flags, koff};
+    PO_TRY(stage2_count(h, n, cnt, po::TC_N, marks, flags_out != nullptr, n_kept));
     T.n_in_tip_edges = h->pinned[16 + po::TC_IN];
     T.n_out_tip_edges = h->pinned[16 + po::TC_OUT];
     T.n_asymmetric = h->pinned[16 + po::TC_ASYM];
     T.n_nodes = h->pinned[16 + po::TC_NODES];
     T.n_isolated_nodes = h->pinned[16 + po::TC_ISOLATED];
     T.n_edges_out = n_kept;
-    if (flags_out && n) std::memcpy(flags_out, h->scratch_host.p, n);
-    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
-        res->d_rows = h->spare_edges;
-        h->spare_edges = DevBuf();
-    }
-    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
-    if (d_rank) PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_kept * 4, 256), 1.0, false));
-    if (n_kept) {
-        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, keep, B[TB_KOFF].as<uint32_t>(),
-                           res->d_rows.as<po::Edge>(), d_rank ? res->d_rank.as<uint32_t>() : nullptr);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipEventRecord(ev[5], st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    res->count = n_kept;
+    PO_TRY(stage2_emit(h, res, n, n_kept, d_edges, d_rank, marks, flags_out, ev[5]));
     (void)hipEventElapsedTime(&T.ms_setup, ev[0], ev[1]);
     (void)hipEventElapsedTime(&T.ms_incoming, ev[1], ev[2]);
     (void)hipEventElapsedTime(&T.ms_outgoing, ev[2], ev[3]);
@@ -3160,19 +3201,10 @@ po_status run_diamonds(po_handle* h, po_result* edges, uint8_t* flags_out, po_re
     hipStream_t st = h->stream;
     po_diamond_stats& D = h->dstats;
     D = po_diamond_stats();
-    res->count = 0;
-    res->elem = sizeof(po_edge);
-    res->kind_edges = true;
     const uint32_t n_nodes = (uint32_t)h->len.size();
-    if (edges->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_diamonds: too many edges for one call");
+    PO_TRY(stage2_open(h, edges, res, "po_layout_diamonds", 0x7FFFFF00ull, true, D.n_edges_in));
     const uint32_t n = (uint32_t)edges->count;
-    D.n_edges_in = n;
-    if (!edges->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: the edge result carries no node order");
-    if (n && n_nodes == 0) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: edges on a handle without reads");
-    for (hipEvent_t& e : h->ev_lay)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
-    hipEvent_t* ev = h->ev_lay + 18;
-    PO_TRY(rows_to_device(h, edges));
+    hipEvent_t* ev = h->ev_lay + EV_DIAMONDS;
     // the workspaces of po_layout_tips under other names (grow-only, on the handle): OUTSUM / INSUM hold the min / max id
     // of a node's in-edges, ALIVE the removed byte per node
     const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n + 1;
@@ -3192,12 +3224,11 @@ po_status run_diamonds(po_handle* h, po_result* edges, uint8_t* flags_out, po_re
     const unsigned long long* nrank = edges->d_nrank.as<unsigned long long>();
     unsigned long long *cnt = B[TB_CNT].as<unsigned long long>(), *rcnt = B[TB_RCNT].as<unsigned long long>();
     uint32_t *outdeg = B[TB_OUTDEG].as<uint32_t>(), *indeg = B[TB_INDEG].as<uint32_t>(), *inmin = B[TB_OUTSUM].as<uint32_t>(),
-             *inmax = B[TB_INSUM].as<uint32_t>(), *cand = B[TB_CAND].as<uint32_t>();
+             *inmax = B[TB_INSUM].as<uint32_t>(), *cand = B[TB_CAND].as<uint32_t>(), *koff = B[TB_KOFF].as<uint32_t>();
     unsigned long long* mark = B[TB_MARK].as<unsigned long long>();
     uint8_t *cstate = B[TB_CSTATE].as<uint8_t>(), *eflag = B[TB_EFLAG].as<uint8_t>(), *keep = B[TB_KEEP].as<uint8_t>(),
             *removed = B[TB_ALIVE].as<uint8_t>();
-    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
-    const uint32_t both_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(std::max(n, n_nodes), 256), (uint32_t)h->n_cu * 8));
+    const uint32_t edge_grid = stride_grid(h, n), both_grid = stride_grid(h, std::max(n, n_nodes));
     HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
     for (uint32_t* p : {outdeg, indeg, inmax}) HIP_TRY(h, hipMemsetAsync(p, 0, nn * 4, st));
     HIP_TRY(h, hipMemsetAsync(inmin, 0xFF, nn * 4, st));
@@ -3222,63 +3253,27 @@ po_status run_diamonds(po_handle* h, po_result* edges, uint8_t* flags_out, po_re
     if (D.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: an edge names a read the handle does not hold");
     const uint32_t n_cand = (uint32_t)h->pinned[16 + po::DC_CAND];
     D.n_candidates = n_cand;
-    // Rounds go out in batches, one readback per batch, as in po_layout_tips: round j of a batch counts the candidates it
-    // leaves unresolved in word j.  A round launched after the last candidate has resolved finds nothing to do.
-    uint32_t round = 0;
-    for (uint64_t unresolved = n_cand; unresolved;) {
-        const uint32_t batch = round == 0 ? 4u : (uint32_t)TIP_BATCH;
-        HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
-        for (uint32_t j = 0; j < batch; ++j) {
-            hipLaunchKernelGGL(po::k_diamond_mark, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, round + j, cand, cstate,
-                               n_cand, nrank, indeg, inmin, inmax, mark);
-            hipLaunchKernelGGL(po::k_diamond_resolve, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, round + j, cand, cstate,
-                               n_cand, nrank, outdeg, indeg, inmin, inmax, mark, eflag, removed, rcnt + j, cnt);
-        }
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        for (uint32_t j = 0; j < batch && unresolved; ++j, ++round) {
-            // (the unresolved candidate of the lowest rank holds its own key everywhere: a round that resolves none is a bug)
-            if (h->pinned[32 + j] >= unresolved) return fail(h, PO_ERR_HIP, "internal: a round of po_layout_diamonds resolved no candidate");
-            unresolved = h->pinned[32 + j];
-        }
-    }
-    D.n_rounds = round;
+    PO_TRY(batched_rounds(h, n_cand, 4, "po_layout_diamonds", rcnt, [&](uint32_t r, unsigned long long* left) {
+        hipLaunchKernelGGL(po::k_diamond_mark, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, r, cand, cstate, n_cand, nrank,
+                           indeg, inmin, inmax, mark);
+        hipLaunchKernelGGL(po::k_diamond_resolve, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, d_edges, n, r, cand, cstate, n_cand,
+                           nrank, outdeg, indeg, inmin, inmax, mark, eflag, removed, left, cnt);
+    }, D.n_rounds));
     HIP_TRY(h, hipEventRecord(ev[2], st));
     if (n || n_nodes) {
         hipLaunchKernelGGL(po::k_diamond_nodes, dim3(both_grid), dim3(256), 0, st, n, n_nodes, eflag, keep, nrank, removed,
                            res->d_nrank.as<unsigned long long>(), cnt);
         HIP_TRY(h, hipGetLastError());
     }
-    if ((size_t)n_nodes * 8 < nrank_bytes)   // (the tail of the smallest allocation: no node)
-        HIP_TRY(h, hipMemsetAsync(res->d_nrank.as<char>() + (size_t)n_nodes * 8, 0xFF, nrank_bytes - (size_t)n_nodes * 8, st));
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::DC_N * 8, hipMemcpyDeviceToHost, st));
-    PO_TRY(prefix_sum<uint8_t>(h, keep, n, B[TB_KOFF].as<uint32_t>(), &h->pinned[2]));
-    if (flags_out && n) {
-        PO_TRY(ensure_host(h, h->scratch_host, n));
-        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, eflag, n, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    const uint64_t n_kept = h->pinned[2];
+    PO_TRY(fill_nrank_tail(h, res, n_nodes, nrank_bytes));
+    uint64_t n_kept = 0;
+    const EdgeMarks marks = {keep, eflag, koff};
+    PO_TRY(stage2_count(h, n, cnt, po::DC_N, marks, flags_out != nullptr, n_kept));
     D.n_diamonds = h->pinned[16 + po::DC_DIAMONDS];
     D.n_nodes = h->pinned[16 + po::DC_NODES];
     D.n_nodes_removed = h->pinned[16 + po::DC_REMOVED];
     D.n_edges_out = n_kept;
-    if (flags_out && n) std::memcpy(flags_out, h->scratch_host.p, n);
-    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
-        res->d_rows = h->spare_edges;
-        h->spare_edges = DevBuf();
-    }
-    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
-    if (d_rank) PO_TRY(ensure(h, res->d_rank, std::max<size_t>(n_kept * 4, 256), 1.0, false));
-    if (n_kept) {
-        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, d_edges, d_rank, n, keep, B[TB_KOFF].as<uint32_t>(),
-                           res->d_rows.as<po::Edge>(), d_rank ? res->d_rank.as<uint32_t>() : nullptr);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipEventRecord(ev[3], st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    res->count = n_kept;
+    PO_TRY(stage2_emit(h, res, n, n_kept, d_edges, d_rank, marks, flags_out, ev[3]));
     (void)hipEventElapsedTime(&D.ms_setup, ev[0], ev[1]);
     (void)hipEventElapsedTime(&D.ms_rounds, ev[1], ev[2]);
     (void)hipEventElapsedTime(&D.ms_emit, ev[2], ev[3]);
@@ -3292,20 +3287,11 @@ po_status run_merge(po_handle* h, po_result* edges, uint8_t* flags_out, po_resul
     hipStream_t st = h->stream;
     po_merge_stats& M = h->mstats;
     M = po_merge_stats();
-    res->count = 0;
-    res->elem = sizeof(po_edge);
-    res->kind_edges = true;
     res->merged = true;
     const uint32_t n_nodes = (uint32_t)h->len.size();
-    if (edges->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_merge: too many edges for one call");
+    PO_TRY(stage2_open(h, edges, res, "po_layout_merge", 0x7FFFFF00ull, true, M.n_edges_in));
     const uint32_t n = (uint32_t)edges->count;
-    M.n_edges_in = n;
-    if (!edges->d_nrank.p) return fail(h, PO_ERR_INVALID, "po_layout_merge: the edge result carries no node order");
-    if (n && n_nodes == 0) return fail(h, PO_ERR_INVALID, "po_layout_merge: edges on a handle without reads");
-    for (hipEvent_t& e : h->ev_lay)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
-    hipEvent_t* ev = h->ev_lay + 22;
-    PO_TRY(rows_to_device(h, edges));
+    hipEvent_t* ev = h->ev_lay + EV_MERGE;
     const size_t nn = (size_t)n_nodes + 1, ne = (size_t)n + 1;
     DevBuf* B = h->d_mrg;
     PO_TRY(ensure(h, h->d_scalars, 128));
@@ -3330,8 +3316,9 @@ po_status run_merge(po_handle* h, po_result* edges, uint8_t* flags_out, po_resul
     unsigned long long* ws[2] = {B[MB_WS0].as<unsigned long long>(), B[MB_WS1].as<unsigned long long>()};
     unsigned long long* hsum = B[MB_HSUM].as<unsigned long long>();
     uint8_t *eflag = B[MB_EFLAG].as<uint8_t>(), *keep = B[MB_KEEP].as<uint8_t>();
+    uint32_t* koff = B[MB_KOFF].as<uint32_t>();
     po::Edge* renamed = B[MB_TMP].as<po::Edge>();
-    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
+    const uint32_t edge_grid = stride_grid(h, n);
     const uint32_t node_blocks = std::max<uint32_t>(1u, cdiv(n_nodes, 256));
     // a head has a link out, into a node that is no head: at most every second node is one
     const uint32_t max_heads = n_nodes / 2 + 1;
@@ -3436,43 +3423,24 @@ po_status run_merge(po_handle* h, po_result* edges, uint8_t* flags_out, po_resul
         hipLaunchKernelGGL(po::k_merge_tables, dim3(node_blocks), dim3(256), 0, st, d_edges, n, n_nodes, d_len, link, back, jb[fin],
                            hops[fin], ws[fin], oute, pathk, moff, K, (uint32_t)n_members, res->d_member.as<uint32_t>(),
                            res->d_prefix.as<int32_t>(), res->d_mlen.as<long long>(), npath, npos);
-        hipLaunchKernelGGL(po::k_merge_ranks, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(node_blocks, (uint32_t)h->n_cu * 8))), dim3(256),
-                           0, st, n_nodes, K, nrank, npath, cnt, res->d_nrank.as<unsigned long long>());
+        hipLaunchKernelGGL(po::k_merge_ranks, dim3(stride_grid(h, n_nodes)), dim3(256), 0, st, n_nodes, K, nrank, npath, cnt,
+                           res->d_nrank.as<unsigned long long>());
         HIP_TRY(h, hipGetLastError());
     }
-    if (n_out_nodes * 8 < nrank_bytes)   // (the tail of the smallest allocation: no node)
-        HIP_TRY(h, hipMemsetAsync(res->d_nrank.as<char>() + n_out_nodes * 8, 0xFF, nrank_bytes - n_out_nodes * 8, st));
+    PO_TRY(fill_nrank_tail(h, res, n_out_nodes, nrank_bytes));
     if (n) {
         hipLaunchKernelGGL(po::k_merge_edges, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_nodes, link, npath, psum, renamed, eflag,
                            keep, cnt);
         HIP_TRY(h, hipGetLastError());
     }
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::MC_N * 8, hipMemcpyDeviceToHost, st));
-    PO_TRY(prefix_sum<uint8_t>(h, keep, n, B[MB_KOFF].as<uint32_t>(), &h->pinned[2]));
-    if (flags_out && n) {
-        PO_TRY(ensure_host(h, h->scratch_host, n));
-        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, eflag, n, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    const uint64_t n_kept = h->pinned[2];
+    uint64_t n_kept = 0;
+    const EdgeMarks marks = {keep, eflag, koff};
+    PO_TRY(stage2_count(h, n, cnt, po::MC_N, marks, flags_out != nullptr, n_kept));
     M.n_self_loops = h->pinned[16 + po::MC_SELF];
     M.n_overflow = h->pinned[16 + po::MC_OVERFLOW];
     M.n_edges_out = n_kept;
     if (M.n_overflow) return fail(h, PO_ERR_INVALID, "po_layout_merge: the weight of an edge out of a merged node does not fit 32 bits");
-    if (flags_out && n) std::memcpy(flags_out, h->scratch_host.p, n);
-    if (h->spare_edges.p && h->spare_edges.cap >= n_kept * sizeof(po_edge)) {   // (the buffer of the previous call's result)
-        res->d_rows = h->spare_edges;
-        h->spare_edges = DevBuf();
-    }
-    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_kept * sizeof(po_edge), 256), 1.0, false));
-    if (n_kept) {
-        hipLaunchKernelGGL(po::k_reduce_emit, dim3(cdiv(n, 256)), dim3(256), 0, st, renamed, (const uint32_t*)nullptr, n, keep,
-                           B[MB_KOFF].as<uint32_t>(), res->d_rows.as<po::Edge>(), (uint32_t*)nullptr);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipEventRecord(ev[4], st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    res->count = n_kept;
+    PO_TRY(stage2_emit(h, res, n, n_kept, renamed, nullptr, marks, flags_out, ev[4]));
     res->n_merged = K;
     res->n_members = n_members;
     (void)hipEventElapsedTime(&M.ms_links, ev[0], ev[1]);
@@ -3500,9 +3468,8 @@ po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_
     const uint32_t K = graph->merged ? (uint32_t)graph->n_merged : 0u, n_members = graph->merged ? (uint32_t)graph->n_members : 0u;
     if ((uint64_t)n_ids + K > 0xFFFFFFFEull) return fail(h, PO_ERR_CAPACITY, "po_layout_coverage: the nodes do not fit 32-bit node ids");
     const uint32_t n_total = n_ids + K;
-    for (hipEvent_t& e : h->ev_lay)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
-    hipEvent_t* ev = h->ev_lay + 27;
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_COVERAGE;
     PO_TRY(rows_to_device(h, graph));
     PO_TRY(rows_to_device(h, rows));
     const uint32_t n_slots = po::cov_table_slots(n_rows);
@@ -3524,8 +3491,7 @@ po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_
     const po::Edge* d_edges = graph->d_rows.as<po::Edge>();
     const po::Row* d_rows = rows->d_rows.as<po::Row>();
     const uint32_t cap = (uint32_t)h->n_cu * 8;
-    const uint32_t edge_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), cap));
-    const uint32_t row_grid = std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_rows, 256), cap));
+    const uint32_t edge_grid = stride_grid(h, n), row_grid = stride_grid(h, n_rows);
     const uint32_t node_blocks = std::max<uint32_t>(1u, cdiv(n_total, 256));
     // (the memsets and the lengths are work of every call: inside ms_sets and ms_total)
     HIP_TRY(h, hipEventRecord(ev[0], st));
@@ -3557,8 +3523,8 @@ po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_
         return fail(h, PO_ERR_HIP, "internal: the set sizes of po_layout_coverage do not add up");
     const uint32_t n_pairs = (uint32_t)C.n_pairs;
     if (n_pairs)
-        hipLaunchKernelGGL(po::k_cov_fill, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n_slots, 256), cap))), dim3(256), 0, st,
-                           table, n_slots, n_total, off, cur, list, n_pairs);
+        hipLaunchKernelGGL(po::k_cov_fill, dim3(stride_grid(h, n_slots)), dim3(256), 0, st, table, n_slots, n_total, off, cur, list,
+                           n_pairs);
     HIP_TRY(h, hipEventRecord(ev[1], st));
     // one wave per edge, four to a workgroup
     hipLaunchKernelGGL(po::k_cov_edges, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 4), cap * 4))), dim3(256), 0, st, d_edges,
@@ -3575,6 +3541,55 @@ po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_
     (void)hipEventElapsedTime(&C.ms_sets, ev[0], ev[1]);
     (void)hipEventElapsedTime(&C.ms_edges, ev[1], ev[2]);
     (void)hipEventElapsedTime(&C.ms_total, ev[0], ev[2]);
+    return PO_OK;
+}
+
+// ---- what the po_layout_* entry points share ------------------------------------------------------------------------
+
+// Everything an edge-producing entry point does behind its checks: `run(result)` fills a new result of handle h, which
+// goes to *out; a failed call leaves nothing behind on the device and no result.
+template <class Run>
+po_status new_edge_result(po_handle* h, const char* name, po_result** out, Run&& run) {
+    po_result* r = new (std::nothrow) po_result();
+    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
+    r->h = h;
+    po_status st;
+    try {
+        st = run(r);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, std::string("out of host memory in ") + name);
+    }
+    if (st != PO_OK) {
+        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
+        release_device(r);
+        delete r;
+        return st;
+    }
+    ++h->live_results;
+    *out = r;
+    return PO_OK;
+}
+
+// A stage-2 entry point behind its null checks: the checks every stage makes, in the order the messages promise, then
+// the call.  `needs` and `merged_msg` end the two sentences that differ from stage to stage.
+template <class Run>
+po_status stage2_call(po_handle* h, po_result* edges, const char* name, bool params_ok, const char* needs, const char* merged_msg,
+                      po_result** out, Run&& run) {
+    if (edges->h != h) return fail(h, PO_ERR_INVALID, std::string(name) + ": the edges belong to another handle");
+    if (!params_ok) return fail(h, PO_ERR_INVALID, std::string(name) + ": bad parameters");
+    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
+    PO_TRY(init_device(h));
+    if (edges->elem != sizeof(po_edge) || !edges->kind_edges) return fail(h, PO_ERR_INVALID, std::string(name) + " needs " + needs);
+    if (edges->merged) return fail(h, PO_ERR_INVALID, std::string(name) + ": " + merged_msg);
+    return new_edge_result(h, name, out, run);
+}
+
+constexpr const char* CANNOT_CLEAN_AGAIN = "a merged graph (po_layout_merge) cannot be cleaned again";
+
+template <class S>
+po_status get_stats(const po_handle* h, S po_handle::*member, S* out) {
+    if (!h || !out) return PO_ERR_INVALID;
+    *out = h->*member;
     return PO_OK;
 }
 
@@ -3956,15 +3971,13 @@ void po_destroy(po_handle* h) {
                           &h->d_ps_blocks, &h->d_scalars, &h->d_cand_a, &h->d_cand_p, &h->d_cand_b, &h->d_type,
                           &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key, &h->d_pair_min, &h->spare_rows, &h->spare_cands, &h->spare_edges, &h->spare_nrank,
                           &h->d_vlabel, &h->d_vrank, &h->d_vperm, &h->d_end_a, &h->d_end_b, &h->d_dpcnt, &h->d_lay_len, &h->d_lay_cnt, &h->d_rflag, &h->d_removed, &h->d_ekey, &h->d_ecnt,
-                          &h->d_ewin, &h->d_eoff, &h->d_chain_state, &h->d_tail_state, &h->d_efirst,
-                          &h->d_red_cnt, &h->d_red_deg, &h->d_red_off, &h->d_red_cur, &h->d_red_tkey, &h->d_red_ttgt, &h->d_red_teid,
-                          &h->d_red_ctgt, &h->d_red_cw, &h->d_red_ceid, &h->d_red_cidpos, &h->d_red_stgt, &h->d_red_seid, &h->d_red_state,
-                          &h->d_red_flag1, &h->d_red_flags, &h->d_red_keep, &h->d_red_koff, &h->d_lay_firstc};
+                          &h->d_ewin, &h->d_eoff, &h->d_chain_state, &h->d_tail_state, &h->d_efirst, &h->d_lay_firstc};
         // every stream idle before anything the device (or a copy) may still touch is given back
         if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
         if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
         if (h->rc_stream) (void)hipStreamSynchronize(h->rc_stream);
         for (DevBuf* b : bufs) b->release();
+        for (DevBuf& b : h->d_red) b.release();
         for (DevBuf& b : h->d_tip) b.release();
         for (DevBuf& b : h->d_mrg) b.release();
         for (DevBuf& b : h->d_cov) b.release();
@@ -5289,10 +5302,7 @@ void po_result_free(po_result* r) {
         h->spare_nrank = r->d_nrank;
         r->d_nrank = DevBuf();
     }
-    r->d_rows.release();
-    r->d_rank.release();
-    r->d_nrank.release();
-    for (DevBuf* b : {&r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen}) b->release();
+    release_device(r);
     delete r;
 }
 
@@ -5695,174 +5705,43 @@ po_status po_layout_edges(po_handle* h, po_result* rows, const po_layout_params*
         return fail(h, PO_ERR_INVALID, "po_layout_edges: bad parameters");
     if (!ids_are_strand_pairs(h))
         return fail(h, PO_ERR_INVALID, "po_layout_edges needs reads added as name+\"+\" / name+\"-\" pairs");
-    po_result* r = new (std::nothrow) po_result();
-    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
-    r->h = h;
-    po_status st;
-    try {
-        st = run_layout(h, rows, *params, removed_reads_out, r);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_edges");
-    }
-    if (st != PO_OK) {
-        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
-        r->d_rows.release();
-        r->d_rank.release();
-        r->d_nrank.release();
-        delete r;
-        return st;
-    }
-    ++h->live_results;
-    *edges_out = r;
-    return PO_OK;
+    return new_edge_result(h, "po_layout_edges", edges_out,
+                           [&](po_result* r) { return run_layout(h, rows, *params, removed_reads_out, r); });
 }
 
 po_status po_layout_reduce(po_handle* h, po_result* edges, const po_reduce_params* params, uint8_t* edge_flags_out,
                            po_result** kept_out) {
     if (!h || !edges || !params || !kept_out) return PO_ERR_INVALID;
     *kept_out = nullptr;
-    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_reduce: the edges belong to another handle");
-    if (params->reserved != 0 || params->length_fuzz < 0) return fail(h, PO_ERR_INVALID, "po_layout_reduce: bad parameters");
-    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
-    const po_status dev = init_device(h);
-    if (dev != PO_OK) return dev;
-    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
-        return fail(h, PO_ERR_INVALID, "po_layout_reduce needs a po_layout_edges result");
-    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_reduce: a merged graph (po_layout_merge) cannot be cleaned again");
-    po_result* r = new (std::nothrow) po_result();
-    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
-    r->h = h;
-    po_status st;
-    try {
-        st = run_reduce(h, edges, *params, edge_flags_out, r);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_reduce");
-    }
-    if (st != PO_OK) {
-        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
-        r->d_rows.release();
-        r->d_rank.release();
-        r->d_nrank.release();
-        delete r;
-        return st;
-    }
-    ++h->live_results;
-    *kept_out = r;
-    return PO_OK;
+    return stage2_call(h, edges, "po_layout_reduce", params->reserved == 0 && params->length_fuzz >= 0, "a po_layout_edges result",
+                       CANNOT_CLEAN_AGAIN, kept_out, [&](po_result* r) { return run_reduce(h, edges, *params, edge_flags_out, r); });
 }
 
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out) {
     if (!h || !edges || !params || !kept_out) return PO_ERR_INVALID;
     *kept_out = nullptr;
-    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_tips: the edges belong to another handle");
-    if (params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_tips: bad parameters");
-    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
-    const po_status dev = init_device(h);
-    if (dev != PO_OK) return dev;
-    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
-        return fail(h, PO_ERR_INVALID, "po_layout_tips needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips)");
-    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_tips: a merged graph (po_layout_merge) cannot be cleaned again");
-    po_result* r = new (std::nothrow) po_result();
-    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
-    r->h = h;
-    po_status st;
-    try {
-        st = run_tips(h, edges, *params, edge_flags_out, r);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_tips");
-    }
-    if (st != PO_OK) {
-        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
-        r->d_rows.release();
-        r->d_rank.release();
-        r->d_nrank.release();
-        delete r;
-        return st;
-    }
-    ++h->live_results;
-    *kept_out = r;
-    return PO_OK;
+    return stage2_call(h, edges, "po_layout_tips", params->reserved == 0,
+                       "an edge result (po_layout_edges, po_layout_reduce, po_layout_tips)", CANNOT_CLEAN_AGAIN, kept_out,
+                       [&](po_result* r) { return run_tips(h, edges, *params, edge_flags_out, r); });
 }
 
 po_status po_layout_diamonds(po_handle* h, po_result* edges, const po_diamond_params* params, uint8_t* edge_flags_out,
                              po_result** kept_out) {
     if (!h || !edges || !kept_out) return PO_ERR_INVALID;
     *kept_out = nullptr;
-    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: the edges belong to another handle");
-    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: bad parameters");
-    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
-    const po_status dev = init_device(h);
-    if (dev != PO_OK) return dev;
-    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
-        return fail(h, PO_ERR_INVALID,
-                    "po_layout_diamonds needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds)");
-    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_diamonds: a merged graph (po_layout_merge) cannot be cleaned again");
-    po_result* r = new (std::nothrow) po_result();
-    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
-    r->h = h;
-    po_status st;
-    try {
-        st = run_diamonds(h, edges, edge_flags_out, r);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_diamonds");
-    }
-    if (st != PO_OK) {
-        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
-        r->d_rows.release();
-        r->d_rank.release();
-        r->d_nrank.release();
-        delete r;
-        return st;
-    }
-    ++h->live_results;
-    *kept_out = r;
-    return PO_OK;
-}
-
-po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    *out = h->dstats;
-    return PO_OK;
+    return stage2_call(h, edges, "po_layout_diamonds", !params || params->reserved == 0,
+                       "an edge result (po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds)", CANNOT_CLEAN_AGAIN,
+                       kept_out, [&](po_result* r) { return run_diamonds(h, edges, edge_flags_out, r); });
 }
 
 po_status po_layout_merge(po_handle* h, po_result* edges, const po_merge_params* params, uint8_t* edge_flags_out,
                           po_result** merged_out) {
     if (!h || !edges || !merged_out) return PO_ERR_INVALID;
     *merged_out = nullptr;
-    if (edges->h != h) return fail(h, PO_ERR_INVALID, "po_layout_merge: the edges belong to another handle");
-    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_merge: bad parameters");
-    // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
-    const po_status dev = init_device(h);
-    if (dev != PO_OK) return dev;
-    if (edges->elem != sizeof(po_edge) || !edges->kind_edges)
-        return fail(h, PO_ERR_INVALID,
-                    "po_layout_merge needs an edge result (po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds)");
-    if (edges->merged) return fail(h, PO_ERR_INVALID, "po_layout_merge: the graph is merged already");
-    po_result* r = new (std::nothrow) po_result();
-    if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
-    r->h = h;
-    po_status st;
-    try {
-        st = run_merge(h, edges, edge_flags_out, r);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_merge");
-    }
-    if (st != PO_OK) {
-        if (h->dev_ready) (void)hipStreamSynchronize(h->stream);
-        for (DevBuf* b : {&r->d_rows, &r->d_rank, &r->d_nrank, &r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen}) b->release();
-        delete r;
-        return st;
-    }
-    ++h->live_results;
-    *merged_out = r;
-    return PO_OK;
-}
-
-po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    *out = h->mstats;
-    return PO_OK;
+    return stage2_call(h, edges, "po_layout_merge", !params || params->reserved == 0,
+                       "an edge result (po_layout_edges, po_layout_reduce, po_layout_tips, po_layout_diamonds)",
+                       "the graph is merged already", merged_out, [&](po_result* r) { return run_merge(h, edges, edge_flags_out, r); });
 }
 
 po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, const po_coverage_params* params,
@@ -5887,11 +5766,13 @@ po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, co
     return st;
 }
 
-po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    *out = h->cstats;
-    return PO_OK;
-}
+po_status po_get_layout_stats(const po_handle* h, po_layout_stats* out) { return get_stats(h, &po_handle::lstats, out); }
+po_status po_get_node_order_stats(const po_handle* h, po_node_order_stats* out) { return get_stats(h, &po_handle::nostats, out); }
+po_status po_get_reduce_stats(const po_handle* h, po_reduce_stats* out) { return get_stats(h, &po_handle::rstats, out); }
+po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out) { return get_stats(h, &po_handle::tstats, out); }
+po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out) { return get_stats(h, &po_handle::dstats, out); }
+po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out) { return get_stats(h, &po_handle::mstats, out); }
+po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out) { return get_stats(h, &po_handle::cstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {
@@ -5921,18 +5802,6 @@ po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_me
     return PO_OK;
 }
 
-po_status po_get_node_order_stats(const po_handle* h, po_node_order_stats* out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    *out = h->nostats;
-    return PO_OK;
-}
-
-po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    *out = h->tstats;
-    return PO_OK;
-}
-
 po_status po_result_node_order(po_result* r, uint32_t* nodes_out, uint64_t cap, uint64_t* n_out) {
     if (!r || !n_out || (!nodes_out && cap)) return PO_ERR_INVALID;
     *n_out = 0;
@@ -5954,18 +5823,6 @@ po_status po_result_node_order(po_result* r, uint32_t* nodes_out, uint64_t cap, 
     } catch (const std::bad_alloc&) {
         return fail(h, PO_ERR_NOMEM, "out of host memory in po_result_node_order");
     }
-    return PO_OK;
-}
-
-po_status po_get_reduce_stats(const po_handle* h, po_reduce_stats* out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    *out = h->rstats;
-    return PO_OK;
-}
-
-po_status po_get_layout_stats(const po_handle* h, po_layout_stats* out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    *out = h->lstats;
     return PO_OK;
 }
 

@@ -417,10 +417,23 @@ class ExactOverlapper:
             removed.ctypes.data_as(ctypes.c_void_p) if removed is not None and len(removed) else None, ctypes.byref(r)))
         return OverlapResult(self, r, EDGE_DTYPE), removed
 
-    def layout_stats(self) -> dict:
-        s = PoLayoutStats()
-        _check(self._h, self._lib.po_get_layout_stats(self._h, ctypes.byref(s)))
+    def _edge_stage(self, fn, edges: OverlapResult, prm, want_flags: bool):
+        """The tail of the stage-2 calls: ``fn(handle, edges, params, flags, &result)``; the kept edges (EDGE_DTYPE
+        result), or with ``want_flags`` the pair (kept edges, one byte per input edge)."""
+        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
+        r = ctypes.c_void_p()
+        _check(self._h, fn(self._h, edges._ptr, ctypes.byref(prm),
+                           flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
+        kept = OverlapResult(self, r, EDGE_DTYPE)
+        return (kept, flags) if want_flags else kept
+
+    def _stats(self, fn, struct) -> dict:
+        s = struct()
+        _check(self._h, fn(self._h, ctypes.byref(s)))
         return s.as_dict()
+
+    def layout_stats(self) -> dict:
+        return self._stats(self._lib.po_get_layout_stats, PoLayoutStats)
 
     def layout_reduce(self, edges: OverlapResult, length_fuzz: int = 1000, want_flags: bool = False):
         """``po_layout_reduce``: transitive reduction (``remove_transitive_edges``) and ``make_symmetric`` on a
@@ -429,18 +442,10 @@ class ExactOverlapper:
         if not -2**31 <= int(length_fuzz) < 2**31:
             raise ValueError("length_fuzz does not fit 32 bits")
         prm = PoReduceParams(int(length_fuzz), 0)
-        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
-        r = ctypes.c_void_p()
-        _check(self._h, self._lib.po_layout_reduce(
-            self._h, edges._ptr, ctypes.byref(prm),
-            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
-        kept = OverlapResult(self, r, EDGE_DTYPE)
-        return (kept, flags) if want_flags else kept
+        return self._edge_stage(self._lib.po_layout_reduce, edges, prm, want_flags)
 
     def reduce_stats(self) -> dict:
-        s = PoReduceStats()
-        _check(self._h, self._lib.po_get_reduce_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
+        return self._stats(self._lib.po_get_reduce_stats, PoReduceStats)
 
     def layout_tips(self, edges: OverlapResult, max_tip_len: int = 4, max_tip_len_bases: int = 5000, want_flags: bool = False):
         """``po_layout_tips``: ``remove_tips`` + ``make_symmetric`` + ``clean_graph`` on an edge result (of
@@ -452,13 +457,7 @@ class ExactOverlapper:
         if not -2**31 <= int(max_tip_len_bases) < 2**31:
             raise ValueError("max_tip_len_bases does not fit 32 bits")
         prm = PoTipsParams(int(max_tip_len), int(max_tip_len_bases), 0)
-        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
-        r = ctypes.c_void_p()
-        _check(self._h, self._lib.po_layout_tips(
-            self._h, edges._ptr, ctypes.byref(prm),
-            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
-        kept = OverlapResult(self, r, EDGE_DTYPE)
-        return (kept, flags) if want_flags else kept
+        return self._edge_stage(self._lib.po_layout_tips, edges, prm, want_flags)
 
     def layout_diamonds(self, edges: OverlapResult, want_flags: bool = False):
         """``po_layout_diamonds``: ``remove_diamond_tips`` on an edge result (of ``layout_edges``, ``layout_reduce``,
@@ -466,18 +465,10 @@ class ExactOverlapper:
         ``want_flags`` the pair (kept edges, one byte per input edge: 0 kept, 1 in-edge of a removed end node, 2 the
         in-edge of a removed pred1).  Nodes left without an edge stay in the result's node order."""
         prm = PoDiamondParams(0)
-        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
-        r = ctypes.c_void_p()
-        _check(self._h, self._lib.po_layout_diamonds(
-            self._h, edges._ptr, ctypes.byref(prm),
-            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
-        kept = OverlapResult(self, r, EDGE_DTYPE)
-        return (kept, flags) if want_flags else kept
+        return self._edge_stage(self._lib.po_layout_diamonds, edges, prm, want_flags)
 
     def diamond_stats(self) -> dict:
-        s = PoDiamondStats()
-        _check(self._h, self._lib.po_get_diamond_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
+        return self._stats(self._lib.po_get_diamond_stats, PoDiamondStats)
 
     def layout_merge(self, edges: OverlapResult, want_flags: bool = False):
         """``po_layout_merge``: ``merge_unambiguous_paths`` on an edge result (of ``layout_edges``, ``layout_reduce``,
@@ -486,18 +477,10 @@ class ExactOverlapper:
         describe its nodes), or with ``want_flags`` the pair (merged graph, one byte per input edge: 0 kept as it is,
         1 link of a path, 2 kept with a renamed end or a raised weight)."""
         prm = PoMergeParams(0)
-        flags = np.zeros(len(edges), dtype=np.uint8) if want_flags else None
-        r = ctypes.c_void_p()
-        _check(self._h, self._lib.po_layout_merge(
-            self._h, edges._ptr, ctypes.byref(prm),
-            flags.ctypes.data_as(ctypes.c_void_p) if flags is not None and len(flags) else None, ctypes.byref(r)))
-        merged = OverlapResult(self, r, EDGE_DTYPE)
-        return (merged, flags) if want_flags else merged
+        return self._edge_stage(self._lib.po_layout_merge, edges, prm, want_flags)
 
     def merge_stats(self) -> dict:
-        s = PoMergeStats()
-        _check(self._h, self._lib.po_get_merge_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
+        return self._stats(self._lib.po_get_merge_stats, PoMergeStats)
 
     def layout_coverage(self, graph: OverlapResult, rows: OverlapResult) -> np.ndarray:
         """``po_layout_coverage``: the operands of the reference's ``average_coverage_path(g, read_alignments, [u, v])`` for
@@ -511,20 +494,14 @@ class ExactOverlapper:
         return out
 
     def coverage_stats(self) -> dict:
-        s = PoCoverageStats()
-        _check(self._h, self._lib.po_get_coverage_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
+        return self._stats(self._lib.po_get_coverage_stats, PoCoverageStats)
 
     def node_order_stats(self) -> dict:
         """Times of the two node-order passes of the last ``layout_edges`` call (not part of ``layout_stats``)."""
-        s = PoNodeOrderStats()
-        _check(self._h, self._lib.po_get_node_order_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
+        return self._stats(self._lib.po_get_node_order_stats, PoNodeOrderStats)
 
     def tips_stats(self) -> dict:
-        s = PoTipsStats()
-        _check(self._h, self._lib.po_get_tips_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
+        return self._stats(self._lib.po_get_tips_stats, PoTipsStats)
 
     def __len__(self) -> int:
         return int(self._lib.po_num_sequences(self._h))
