@@ -563,6 +563,62 @@ po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, co
                              po_edge_coverage* coverage_out /* host, po_result_count(graph) entries */);
 po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * The first step of `phasm chain` (phasm/cli/assembler.py:289-304): the weakly connected components of the graph,
+ * numbered as networkx.weakly_connected_components yields them.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_components_params;
+
+typedef struct {
+    uint32_t first_node;         /* the component's lowest-ranked node                                           */
+    uint32_t n_nodes;
+    uint64_t n_edges;            /* "Connected component %d with %d nodes and %d edges."                         */
+} po_component;                  /* 16 bytes                                                                     */
+
+typedef struct {
+    uint64_t n_nodes;            /* nodes of the graph (those in its node order)                                 */
+    uint64_t n_edges;
+    uint64_t n_components;
+    uint64_t n_singletons;       /* components of one node                                                       */
+    uint64_t max_component_nodes, max_component_edges;
+    uint64_t n_invalid;          /* edges with an end that is not in the node order (the call fails then)        */
+    uint32_t n_rounds;           /* hook + jump rounds run, the one that changed nothing included                */
+    uint32_t n_batches;          /* readbacks of the round loop                                                  */
+    float ms_rounds, ms_label, ms_total;
+} po_components_stats;
+
+/* `graph` is a graph result of this handle: an edge result (po_layout_edges, po_layout_reduce, po_layout_tips,
+ * po_layout_diamonds), a merged graph (po_layout_merge) or a po_graph_from_edges result; it stays valid and unchanged.
+ * With the node order of po_result_node_order (n_order nodes; the rank of a node is its place in it): two nodes are in
+ * one component iff a chain of edges joins them, direction ignored; a node without an edge is a component of its own; a
+ * self-loop joins nothing.  Component i is the i-th in the order of each component's lowest-ranked node -- what
+ * `for v in G: if v not in seen: yield bfs(v)` yields.  node_component_out: the component of every node, parallel to the
+ * node order.  edge_component_out: the component of u of every edge, in the graph's edge order.  components_out: one
+ * entry per component (room for n_order entries).  Any of the three may be NULL; *n_components_out is always written.
+ * Only integers are involved: every output is the same on every run.  An edge with an end that is not in the node order
+ * is counted in n_invalid; the call then fails with PO_ERR_INVALID and writes nothing.  Device memory beyond the inputs
+ * is linear: at most 57 bytes per node (12 of them per slot of the sort, padded to a power of two) and 12 per edge.
+ * params may be NULL.  An empty graph with an empty order: PO_OK, 0 components.  The rounds are bounded by n_order + 2
+ * on the host; reaching the bound is PO_ERR_HIP with a message, never a partition.  There is no CPU fallback: without a
+ * GPU the call returns PO_ERR_HIP.  A row result, a result of another handle, reserved != 0, n_components_out NULL:
+ * PO_ERR_INVALID. */
+po_status po_layout_components(po_handle* h, po_result* graph, const po_components_params* params,
+                               uint32_t* node_component_out, uint32_t* edge_component_out, po_component* components_out,
+                               uint64_t* n_components_out);
+po_status po_get_components_stats(const po_handle* h, po_components_stats* out);
+
+/* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
+ * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the
+ * device, each violation PO_ERR_INVALID with a message: u, v < po_num_sequences; node_order entries in range and
+ * distinct; every edge end present in node_order; the (u, v) pairs distinct.  The result works with po_result_count,
+ * po_result_rows, po_result_node_order, po_result_free and po_layout_components; po_layout_reduce, _tips, _diamonds,
+ * _merge and _coverage refuse it with PO_ERR_INVALID.  Without a GPU a valid call returns PO_ERR_HIP. */
+po_status po_graph_from_edges(po_handle* h, const po_edge* edges, uint64_t n_edges, const uint32_t* node_order,
+                              uint64_t n_order, po_result** out);
+
 /* The nodes of an edge result's graph in the reference's order (`for n in g`: the order in which add_edge first saw
  * each node, phasm/assembly_graph.py:136-179, without the nodes of contained reads), computed by po_layout_edges from
  * the rows: a row reaches build_assembly_graph iff it passes the filters and no earlier row has marked one of its

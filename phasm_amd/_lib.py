@@ -26,6 +26,8 @@ CAND_DTYPE = np.dtype([("a_idx", "<u4"), ("p", "<u4"), ("b_idx", "<u4"), ("type"
 EDGE_DTYPE = np.dtype([("u", "<u4"), ("v", "<u4"), ("weight", "<i4"), ("overlap_len", "<i4")])
 # po_edge_coverage
 COVERAGE_DTYPE = np.dtype([("read_length_sum", "<u8"), ("path_length", "<i8")])
+# po_component
+COMPONENT_DTYPE = np.dtype([("first_node", "<u4"), ("n_nodes", "<u4"), ("n_edges", "<u8")])
 
 
 class PoLayoutParams(ctypes.Structure):
@@ -115,6 +117,20 @@ class PoCoverageStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("n_edges", ctypes.c_uint64), ("n_nodes", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64),
                 ("max_set", ctypes.c_uint64), ("n_zero_path", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64),
                 ("ms_sets", ctypes.c_float), ("ms_edges", ctypes.c_float), ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PoComponentsParams(ctypes.Structure):
+    _fields_ = [("reserved", ctypes.c_uint32)]
+
+
+class PoComponentsStats(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("n_edges", ctypes.c_uint64), ("n_components", ctypes.c_uint64),
+                ("n_singletons", ctypes.c_uint64), ("max_component_nodes", ctypes.c_uint64), ("max_component_edges", ctypes.c_uint64),
+                ("n_invalid", ctypes.c_uint64), ("n_rounds", ctypes.c_uint32), ("n_batches", ctypes.c_uint32),
+                ("ms_rounds", ctypes.c_float), ("ms_label", ctypes.c_float), ("ms_total", ctypes.c_float)]
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -218,6 +234,10 @@ SYMBOLS = [
                                               ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     ("po_layout_coverage", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(PoCoverageParams), ctypes.c_void_p]),
     ("po_get_coverage_stats", ctypes.c_int, [_P, ctypes.POINTER(PoCoverageStats)]),
+    ("po_layout_components", ctypes.c_int, [_P, _P, ctypes.POINTER(PoComponentsParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_components_stats", ctypes.c_int, [_P, ctypes.POINTER(PoComponentsStats)]),
+    ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),
     ("po_get_stats", ctypes.c_int, [_P, ctypes.POINTER(PoStats)]),

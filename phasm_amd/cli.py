@@ -276,6 +276,27 @@ def layout_edges(args) -> int:
         ov.close()
 
 
+def chain_components(args) -> int:
+    """The start of `phasm chain` (assembler.py:231-310): the graph file's weakly connected components, one file each."""
+    from . import layout
+    allowed, formats = {"gfa1", "gfa2", "graphml"}, []
+    for file_format in args.format.split(","):
+        file_format = file_format.strip()
+        if file_format in allowed:
+            formats.append(file_format)
+        else:
+            logger.warning("File format '%s' not recognised, ignoring.", file_format)
+    if not formats:
+        logger.critical("No valid file formats specified.")
+        sys.exit(1)
+    logger.info("Reconstructing assembly graph...")
+    g = layout.chain_components(args.graph_gfa, device=args.device)
+    logger.info("Enumerate weakly connected components in the graph...")
+    n = layout.write_component_graphs(args.output_dir, g, formats)
+    logger.info("Wrote %d weakly connected components.", n)
+    return 0
+
+
 def main(argv=None) -> int:
     parser = argparse.ArgumentParser(prog="phasm-amd", description="MI355X-native PHASM overlap step")
     parser.add_argument("-v", "--verbose", action="count", default=0)
@@ -346,6 +367,14 @@ def main(argv=None) -> int:
     c.add_argument("db_input", help="DBdump text")
     c.add_argument("las_input", nargs="?", default=None, help="LAdump text (default: stdin)")
     c.set_defaults(func=daligner2gfa)
+    # option names of `phasm chain`, assembler.py
+    k = sub.add_parser("chain-components", help="The first step of `phasm chain`: the weakly connected components of a graph "
+                                                "file written by `layout-edges --merge`, one file per component.")
+    k.add_argument("-f", "--format", default="gfa2", help="comma separated: gfa1, gfa2, graphml (default: gfa2)")
+    k.add_argument("-o", "--output-dir", required=True)
+    k.add_argument("--device", type=int, default=None)
+    k.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
+    k.set_defaults(func=chain_components)
     args = parser.parse_args(argv)
     if not getattr(args, "func", None):
         parser.print_help()

@@ -41,6 +41,7 @@
 #include "diamond.hip.h"
 #include "merge.hip.h"
 #include "coverage.hip.h"
+#include "components.hip.h"
 
 namespace {
 
@@ -57,10 +58,12 @@ enum { MB_CNT, MB_RCNT, MB_OUTDEG, MB_INDEG, MB_OUTE, MB_INE, MB_LINK, MB_BACK, 
 // workspaces of po_layout_coverage (coverage.hip.h)
 enum { VB_CNT, VB_USED, VB_NODEOF, VB_LEN, VB_TABLE, VB_SUM, VB_SETCNT, VB_OFF, VB_CUR, VB_LIST, VB_OUT, VB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 30;
+// workspaces of po_layout_components (components.hip.h)
+enum { KB_CNT, KB_RCNT, KB_KEY, KB_VAL, KB_RANKOF, KB_P, KB_ENDS, KB_ROOT, KB_INDEX, KB_COMP, KB_ECOMP, KB_TABLE, KB_N };
+constexpr int EV_LAY_N = 34;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
-enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27 };
-static_assert(EV_COVERAGE + 3 == EV_LAY_N, "the three events of po_layout_coverage are the last of the layout events");
+enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30 };
+static_assert(EV_COMPONENTS + 4 == EV_LAY_N, "the four events of po_layout_components are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -414,6 +417,10 @@ struct po_handle {
     // average coverage per edge (po_layout_coverage, coverage.hip.h)
     DevBuf d_cov[VB_N];
     po_coverage_stats cstats = {};
+
+    // weakly connected components (po_layout_components, components.hip.h)
+    DevBuf d_cc[KB_N];
+    po_components_stats ccstats = {};
 };
 
 struct po_result {
@@ -437,6 +444,9 @@ struct po_result {
     // po_layout_merge: a merged graph -- node ids >= the handle's reads name merged nodes (d_nrank holds their ranks too);
     // the tables of po_result_merged_paths
     bool merged = false;
+    // po_graph_from_edges: edges and node order came from the caller, not from the rows (po_layout_components takes it;
+    // the stages that clean, merge or cover a graph do not)
+    bool host_graph = false;
     uint64_t n_merged = 0, n_members = 0;
     DevBuf d_moff, d_member, d_prefix, d_mlen;
     // po_candidates_shard_into: the caller's buffer the candidates go to when they fit
@@ -3544,6 +3554,131 @@ po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_
     return PO_OK;
 }
 
+// ---- weakly connected components (po_layout_components): graph result -> component per node and per edge, the table ----
+
+po_status run_components(po_handle* h, po_result* graph, uint32_t* node_out, uint32_t* edge_out, po_component* table_out,
+                         uint64_t* n_components_out) {
+    hipStream_t st = h->stream;
+    po_components_stats& S = h->ccstats;
+    S = po_components_stats();
+    if (graph->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_components: too many edges for one call");
+    const uint32_t n = (uint32_t)graph->count;
+    const uint64_t K = graph->merged ? graph->n_merged : 0;
+    if (h->len.size() + K >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_components: too many nodes for one call");
+    const uint32_t n_total = (uint32_t)(h->len.size() + K);
+    S.n_edges = n;
+    if (n_total == 0 || !graph->d_nrank.p) {
+        if (n) return fail(h, PO_ERR_INVALID, "po_layout_components: the graph carries no node order");
+        return PO_OK;
+    }
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_COMPONENTS;
+    PO_TRY(rows_to_device(h, graph));
+    const uint32_t pad = po::merge_sort_pad(n_total);
+    const size_t nn = (size_t)n_total + 2, ne = (size_t)n + 1;
+    DevBuf* B = h->d_cc;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[KB_CNT], 128));
+    PO_TRY(ensure(h, B[KB_RCNT], po::CC_BATCH * 8));
+    PO_TRY(ensure(h, B[KB_KEY], (size_t)pad * 8));
+    PO_TRY(ensure(h, B[KB_VAL], (size_t)pad * 4));
+    for (int k : {KB_RANKOF, KB_P, KB_INDEX, KB_COMP}) PO_TRY(ensure(h, B[k], nn * 4));
+    PO_TRY(ensure(h, B[KB_ROOT], nn));
+    PO_TRY(ensure(h, B[KB_TABLE], nn * sizeof(po::Component)));
+    PO_TRY(ensure(h, B[KB_ENDS], ne * sizeof(po::EdgeRanks)));
+    PO_TRY(ensure(h, B[KB_ECOMP], ne * 4));
+    unsigned long long *cnt = B[KB_CNT].as<unsigned long long>(), *rcnt = B[KB_RCNT].as<unsigned long long>(),
+                       *key = B[KB_KEY].as<unsigned long long>();
+    uint32_t *val = B[KB_VAL].as<uint32_t>(), *rank_of = B[KB_RANKOF].as<uint32_t>(), *p = B[KB_P].as<uint32_t>(),
+             *index = B[KB_INDEX].as<uint32_t>(), *comp = B[KB_COMP].as<uint32_t>(), *ecomp = B[KB_ECOMP].as<uint32_t>();
+    uint8_t* root = B[KB_ROOT].as<uint8_t>();
+    po::Component* table = B[KB_TABLE].as<po::Component>();
+    po::EdgeRanks* ends = B[KB_ENDS].as<po::EdgeRanks>();
+    const po::Edge* d_edges = graph->d_rows.as<po::Edge>();
+    const uint32_t edge_grid = stride_grid(h, n);
+    // rank of every node: the rank words sorted (bitonic, padded with all ones to a power of two), place r = rank r
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    HIP_TRY(h, hipMemsetAsync(rank_of, 0xFF, nn * 4, st));
+    hipLaunchKernelGGL(po::k_cc_keys, dim3(cdiv(pad, 256)), dim3(256), 0, st, graph->d_nrank.as<unsigned long long>(), n_total, pad, key, val);
+    po::merge_sort_steps(n_total, [&](uint32_t j, uint32_t k) {
+        hipLaunchKernelGGL(po::k_merge_bitonic, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, j, k);
+    });
+    hipLaunchKernelGGL(po::k_cc_init, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, n_total, p, rank_of, cnt);
+    if (n) hipLaunchKernelGGL(po::k_cc_ends, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_total, rank_of, ends, cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::KC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    S.n_invalid = h->pinned[16 + po::KC_INVALID];
+    S.n_nodes = h->pinned[16 + po::KC_ORDER];
+    if (S.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_components: an edge has an end that is not in the node order");
+    if (S.n_nodes > n_total) return fail(h, PO_ERR_HIP, "internal: po_layout_components counted more ranks than nodes");
+    const uint32_t n_order = (uint32_t)S.n_nodes;
+    const uint32_t rank_grid = stride_grid(h, n_order);
+    // Rounds of hook + jump in batches, one change word per round and one readback per batch; the first round that
+    // lowered no word ends them (the later rounds of its batch lower nothing either).  The bound is the host's.
+    const uint64_t cap = po::cc_round_cap(n_order);
+    uint64_t launched = 0;
+    uint32_t rounds = 0, batches = 0;
+    bool done = n_order == 0;
+    while (!done && launched < cap) {
+        const uint32_t batch = (uint32_t)std::min<uint64_t>(po::CC_BATCH, cap - launched);
+        HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
+        for (uint32_t j = 0; j < batch; ++j, ++launched) {
+            if (n) hipLaunchKernelGGL(po::k_cc_hook, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, p, rcnt + j);
+            hipLaunchKernelGGL(po::k_cc_jump, dim3(rank_grid), dim3(256), 0, st, n_order, p, rcnt + j);
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        ++batches;
+        done = po::cc_rounds_done(h->pinned + 32, batch, rounds);
+    }
+    S.n_rounds = rounds;
+    S.n_batches = batches;
+    if (!done) return fail(h, PO_ERR_HIP, "internal: po_layout_components reached its bound of n_order + 2 rounds");
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    if (n_order) {
+        hipLaunchKernelGGL(po::k_cc_roots, dim3(rank_grid), dim3(256), 0, st, p, n_order, root);
+        HIP_TRY(h, hipGetLastError());
+    }
+    PO_TRY(prefix_sum<uint8_t>(h, root, n_order, index, &h->pinned[2]));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_comp64 = h->pinned[2];
+    if (n_comp64 > n_order || (n_order && !n_comp64)) return fail(h, PO_ERR_HIP, "internal: the roots of po_layout_components do not add up");
+    const uint32_t n_comp = (uint32_t)n_comp64;
+    S.n_components = n_comp;
+    if (n_comp) {
+        HIP_TRY(h, hipMemsetAsync(table, 0, (size_t)n_comp * sizeof(po::Component), st));
+        hipLaunchKernelGGL(po::k_cc_label_nodes, dim3(rank_grid), dim3(256), 0, st, p, index, val, n_order, n_comp, comp, table);
+        if (n) hipLaunchKernelGGL(po::k_cc_label_edges, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, n_comp, comp, ecomp, table);
+        hipLaunchKernelGGL(po::k_cc_max, dim3(stride_grid(h, n_comp)), dim3(256), 0, st, table, n_comp, cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    static_assert(sizeof(po_component) == sizeof(po::Component), "po_component is the device's table entry");
+    const size_t tb = (size_t)n_comp * sizeof(po_component), nb = (size_t)n_order * 4, eb = (size_t)n * 4;
+    PO_TRY(ensure_host(h, h->scratch_host, tb + nb + eb + 16));
+    char* land = static_cast<char*>(h->scratch_host.p);
+    if (tb && table_out) HIP_TRY(h, hipMemcpyAsync(land, table, tb, hipMemcpyDeviceToHost, st));
+    if (nb && node_out) HIP_TRY(h, hipMemcpyAsync(land + tb, comp, nb, hipMemcpyDeviceToHost, st));
+    if (eb && edge_out) HIP_TRY(h, hipMemcpyAsync(land + tb + nb, ecomp, eb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::KC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    S.n_singletons = h->pinned[16 + po::KC_SINGLE];
+    S.max_component_nodes = h->pinned[16 + po::KC_MAXN];
+    S.max_component_edges = h->pinned[16 + po::KC_MAXE];
+    if (tb && table_out) std::memcpy(table_out, land, tb);
+    if (nb && node_out) std::memcpy(node_out, land + tb, nb);
+    if (eb && edge_out) std::memcpy(edge_out, land + tb + nb, eb);
+    *n_components_out = n_comp;
+    (void)hipEventElapsedTime(&S.ms_rounds, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&S.ms_label, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
+    return PO_OK;
+}
+
 // ---- what the po_layout_* entry points share ------------------------------------------------------------------------
 
 // Everything an edge-producing entry point does behind its checks: `run(result)` fills a new result of handle h, which
@@ -3579,7 +3714,8 @@ po_status stage2_call(po_handle* h, po_result* edges, const char* name, bool par
     if (!params_ok) return fail(h, PO_ERR_INVALID, std::string(name) + ": bad parameters");
     // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
     PO_TRY(init_device(h));
-    if (edges->elem != sizeof(po_edge) || !edges->kind_edges) return fail(h, PO_ERR_INVALID, std::string(name) + " needs " + needs);
+    if (edges->elem != sizeof(po_edge) || !edges->kind_edges || edges->host_graph)
+        return fail(h, PO_ERR_INVALID, std::string(name) + " needs " + needs);
     if (edges->merged) return fail(h, PO_ERR_INVALID, std::string(name) + ": " + merged_msg);
     return new_edge_result(h, name, out, run);
 }
@@ -3981,6 +4117,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_tip) b.release();
         for (DevBuf& b : h->d_mrg) b.release();
         for (DevBuf& b : h->d_cov) b.release();
+        for (DevBuf& b : h->d_cc) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -5752,7 +5889,7 @@ po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, co
     // (no CPU fallback: without a usable GPU nothing below can be true of a result either)
     const po_status dev = init_device(h);
     if (dev != PO_OK) return dev;
-    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
+    if (graph->elem != sizeof(po_edge) || !graph->kind_edges || graph->host_graph)
         return fail(h, PO_ERR_INVALID, "po_layout_coverage needs an edge result or a merged graph in the first position");
     if (rows->elem != sizeof(po_row) || rows->kind_edges) return fail(h, PO_ERR_INVALID, "po_layout_coverage needs a row result in the second position");
     if (graph->count && !coverage_out) return fail(h, PO_ERR_INVALID, "po_layout_coverage: no room for the coverage of the edges");
@@ -5766,6 +5903,83 @@ po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, co
     return st;
 }
 
+po_status po_layout_components(po_handle* h, po_result* graph, const po_components_params* params, uint32_t* node_component_out,
+                               uint32_t* edge_component_out, po_component* components_out, uint64_t* n_components_out) {
+    if (!h || !graph) return PO_ERR_INVALID;
+    if (!n_components_out) return fail(h, PO_ERR_INVALID, "po_layout_components: no room for the number of components");
+    *n_components_out = 0;
+    if (graph->h != h) return fail(h, PO_ERR_INVALID, "po_layout_components: the graph belongs to another handle");
+    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_components: bad parameters");
+    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
+        return fail(h, PO_ERR_INVALID, "po_layout_components needs an edge result, a merged graph or a po_graph_from_edges result");
+    // (no CPU fallback)
+    const po_status dev = init_device(h);
+    if (dev != PO_OK) return dev;
+    po_status st;
+    try {
+        st = run_components(h, graph, node_component_out, edge_component_out, components_out, n_components_out);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_components");
+    }
+    if (st != PO_OK && h->dev_ready) (void)hipStreamSynchronize(h->stream);
+    return st;
+}
+
+po_status po_graph_from_edges(po_handle* h, const po_edge* edges, uint64_t n_edges, const uint32_t* node_order, uint64_t n_order,
+                              po_result** out) {
+    if (!h || !out || (!edges && n_edges) || (!node_order && n_order)) return PO_ERR_INVALID;
+    *out = nullptr;
+    if (n_edges >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_graph_from_edges: too many edges for one call");
+    const size_t n_ids = h->len.size();
+    try {
+        std::vector<uint8_t> in_order(n_ids, 0);
+        for (uint64_t i = 0; i < n_order; ++i) {
+            const uint32_t x = node_order[i];
+            if (x >= n_ids) return fail(h, PO_ERR_INVALID, "po_graph_from_edges: the node order names a read the handle does not hold");
+            if (in_order[x]) return fail(h, PO_ERR_INVALID, "po_graph_from_edges: a node appears twice in the node order");
+            in_order[x] = 1;
+        }
+        std::vector<uint64_t> pairs(n_edges);
+        for (uint64_t e = 0; e < n_edges; ++e) {
+            const uint32_t u = edges[e].u, v = edges[e].v;
+            if (u >= n_ids || v >= n_ids) return fail(h, PO_ERR_INVALID, "po_graph_from_edges: an edge names a read the handle does not hold");
+            if (!in_order[u] || !in_order[v])
+                return fail(h, PO_ERR_INVALID, "po_graph_from_edges: an edge has an end that is not in the node order");
+            pairs[e] = ((uint64_t)u << 32) | v;
+        }
+        std::sort(pairs.begin(), pairs.end());
+        if (std::adjacent_find(pairs.begin(), pairs.end()) != pairs.end())
+            return fail(h, PO_ERR_INVALID, "po_graph_from_edges: an edge appears twice");
+    } catch (const std::bad_alloc&) {
+        return fail(h, PO_ERR_NOMEM, "out of host memory in po_graph_from_edges");
+    }
+    // (no CPU fallback: the node order of a graph result lives on the device)
+    PO_TRY(init_device(h));
+    return new_edge_result(h, "po_graph_from_edges", out, [&](po_result* r) {
+        r->elem = sizeof(po_edge);
+        r->kind_edges = true;
+        r->host_graph = true;
+        // rank words: the place in the node order, all ones for every other read (and behind the reads)
+        const size_t nrank_bytes = std::max<size_t>(n_ids * 8, 256);
+        PO_TRY(ensure_nrank(h, r, nrank_bytes));
+        PO_TRY(ensure_host(h, h->scratch_host, nrank_bytes));
+        std::memset(h->scratch_host.p, 0xFF, nrank_bytes);
+        uint64_t* words = static_cast<uint64_t*>(h->scratch_host.p);
+        for (uint64_t i = 0; i < n_order; ++i) words[node_order[i]] = i;
+        HIP_TRY(h, hipMemcpyAsync(r->d_nrank.p, words, nrank_bytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (n_edges) {
+            void* copy = std::malloc(n_edges * sizeof(po_edge));
+            if (!copy) return fail(h, PO_ERR_NOMEM, "out of host memory for the edge array");
+            std::memcpy(copy, edges, n_edges * sizeof(po_edge));
+            r->host = copy;
+            r->host_malloced = true;
+        }
+        r->count = n_edges;
+        return PO_OK;
+    });
+}
+
 po_status po_get_layout_stats(const po_handle* h, po_layout_stats* out) { return get_stats(h, &po_handle::lstats, out); }
 po_status po_get_node_order_stats(const po_handle* h, po_node_order_stats* out) { return get_stats(h, &po_handle::nostats, out); }
 po_status po_get_reduce_stats(const po_handle* h, po_reduce_stats* out) { return get_stats(h, &po_handle::rstats, out); }
@@ -5773,6 +5987,7 @@ po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out) { return get
 po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out) { return get_stats(h, &po_handle::dstats, out); }
 po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out) { return get_stats(h, &po_handle::mstats, out); }
 po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out) { return get_stats(h, &po_handle::cstats, out); }
+po_status po_get_components_stats(const po_handle* h, po_components_stats* out) { return get_stats(h, &po_handle::ccstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

@@ -97,3 +97,79 @@ def read_gfa2_rows(lines):
             rows.append((nodes[0], nodes[1], ar[0], ar[1], br[0], br[1]))
     names = list(order)
     return names, np.asarray(length, dtype=np.int64), np.asarray(rows, dtype=np.int64).reshape(-1, 6)
+
+
+# ---- reading side: what `phasm chain` takes from the graph file `phasm layout` wrote --------------
+
+class GraphFile:
+    """A graph file as `phasm chain` rebuilds it (gfa2_parse_segments_with_fragments and gfa2_reconstruct_assembly_graph,
+    phasm/io/gfa.py:112-227 of the reference).  Segment i of ``names`` / ``lengths`` (file order) has the nodes 2i (``+``)
+    and 2i+1 (``-``); a segment with ``F`` lines is a merged node, which exists as ``+`` only: ``fragments[i]`` holds its
+    reads (as written, strand sign included) and its prefix lengths.  ``edges`` is an int64 array (u, v, weight,
+    overlap_len) in the order the graph first saw each edge, ``node_order`` the nodes in the graph's order."""
+
+    def __init__(self, names, lengths, fragments, edges, node_order):
+        self.names, self.lengths, self.fragments, self.edges, self.node_order = names, lengths, fragments, edges, node_order
+
+    def node_name(self, n: int) -> str:
+        n = int(n)
+        return self.names[n >> 1] + "+-"[n & 1]
+
+    def node_length(self, n: int) -> int:
+        return int(self.lengths[int(n) >> 1])
+
+
+def read_graph_gfa(lines) -> GraphFile:
+    """``S``, ``F`` and ``E`` lines of a graph file -> GraphFile.  Segments keep their file order (the last ``S`` line of a
+    name wins and keeps the first one's place); the fragments of a merged segment are sorted by segment start, its prefix
+    lengths are the fragment lengths with the last dropped.  An edge has weight ``astart - bstart`` and overlap_len
+    ``max(aend - astart, bend - bstart)``; positions may carry a trailing ``$``; a second ``E`` line for the same (u, v)
+    overwrites the attributes and keeps the position.  Node order: first appearance in the ``E`` lines, u before v; then,
+    in ``S``-line order, the ``+`` node of every segment of which neither orientation got an edge.  An ``E`` line that
+    names an unknown node (the ``-`` of a merged segment included) raises KeyError, as the reference's lookup does."""
+    lines = list(lines)
+    index, seg_line, frags = {}, [], {}
+    for ln in lines:
+        if not ln.startswith("S") and not ln.startswith("F"):
+            continue
+        parts = ln.strip().split("\t")
+        kind, name = parts[0].strip(), parts[1].strip()
+        if kind == "S":
+            if name in index:
+                seg_line[index[name]] = ln
+            else:
+                index[name] = len(seg_line)
+                seg_line.append(ln)
+        if kind == "F":
+            seg_range = tuple(map(_gfa_pos_to_int, parts[3:5]))
+            frag_range = tuple(map(_gfa_pos_to_int, parts[5:7]))
+            frags.setdefault(name, []).append((seg_range[0], parts[2].strip(), frag_range[1] - frag_range[0]))
+    names = list(index)
+    lengths = np.asarray([gfa2_parse_segment(ln)[1] for ln in seg_line], dtype=np.int64)
+    fragments, nodes = {}, {}
+    for name, i in index.items():
+        nodes[name + "+"] = 2 * i
+        if name in frags:
+            ordered = sorted(frags[name], key=lambda f: f[0])          # (stable, like the reference's sorted)
+            fragments[i] = ([f[1] for f in ordered], [f[2] for f in ordered][:-1])
+        else:
+            nodes[name + "-"] = 2 * i + 1
+    place, edges, order, seen = {}, [], [], set()
+    for ln in lines:
+        if ln.startswith("E"):
+            s1, s2, ar, br = gfa2_parse_edge(ln)
+            u, v = nodes[s1], nodes[s2]
+            attrs = [u, v, ar[0] - br[0], max(ar[1] - ar[0], br[1] - br[0])]
+            for n in (u, v):
+                if n not in seen:
+                    seen.add(n)
+                    order.append(n)
+            if (u, v) in place:
+                edges[place[(u, v)]] = attrs
+            else:
+                place[(u, v)] = len(edges)
+                edges.append(attrs)
+    for i in range(len(names)):
+        if 2 * i not in seen and 2 * i + 1 not in seen:
+            order.append(2 * i)
+    return GraphFile(names, lengths, fragments, np.asarray(edges, dtype=np.int64).reshape(-1, 4), order)

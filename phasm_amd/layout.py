@@ -23,17 +23,24 @@ node, and the result describes the GFA2 file the command writes (``S``, ``F`` an
 ``average_coverage`` / ``coverage=True`` computes what the command computes next, the average coverage of every edge
 (``average_coverage_path``, assembly_graph.py:544-591; assembler.py:190-193), by ``po_layout_coverage`` from all the rows
 still in HBM, and ``write_graphml`` writes the graph with that attribute (the counterpart of assembler.py:208-209).
-What follows that point (bubbles, GFA1 output, `phasm chain`, phasing) is out of scope.
+``weakly_connected_components`` is the first step of the command that reads that file, `phasm chain`
+(assembler.py:231-310): the components of a graph result by ``po_layout_components``, numbered as networkx yields them;
+``chain_components`` runs it on a graph file and ``write_component_graphs`` writes ``component{i}.gfa`` / ``.graphml``.
+What follows that point (bubble chains, contigs, phasing) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
 
+import logging
+import os
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .overlapper import ExactOverlapper, OverlapResult
+
+logger = logging.getLogger("phasm_amd")
 
 # `phasm layout` defaults, assembler.py:469-489
 DEFAULTS = dict(min_read_length=0, min_overlap_length=0, max_overhang_abs=1000, max_overhang_rel=0.8)
@@ -424,3 +431,149 @@ def layout_from_overlaps(ov: ExactOverlapper, min_length: int, reduce: bool = Fa
                                         max_tip_len_bases=max_tip_len_bases, clean=clean, merge=merge, coverage=coverage, **{**DEFAULTS, **params})
     finally:
         rows.free()
+
+
+# ---- the first step of `phasm chain`: weakly connected components (assembler.py:231-310) --------------------------------
+
+@dataclass
+class Components:
+    """The weakly connected components of a graph result.  ``node_order``: the graph's nodes in the reference's order;
+    ``component_of_node``: parallel to it; ``component_of_edge``: the component of u of every edge, in the graph's edge
+    order; ``table``: structured (``first_node``, ``n_nodes``, ``n_edges``), one entry per component -- component i is the
+    i-th in the order of each component's lowest-ranked node, what ``networkx.weakly_connected_components`` yields;
+    ``stats``: ``po_get_components_stats``."""
+    node_order: np.ndarray
+    component_of_node: np.ndarray
+    component_of_edge: np.ndarray
+    table: np.ndarray
+    stats: dict
+
+    def __len__(self) -> int:
+        return len(self.table)
+
+    def _group(self, of, counts):
+        # (grouping is done here, not on the device: it needs a stable sort, and the writers touch every edge anyway)
+        return np.argsort(of, kind="stable"), np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+
+    def edges_of(self, i: int) -> np.ndarray:
+        """The indices of the edges of component ``i``, in the graph's edge order."""
+        if not hasattr(self, "_edge_group"):
+            self._edge_group = self._group(self.component_of_edge, self.table["n_edges"])
+        by, off = self._edge_group
+        return by[off[i]:off[i + 1]]
+
+    def nodes_of(self, i: int) -> np.ndarray:
+        """The nodes of component ``i``, in node order."""
+        if not hasattr(self, "_node_group"):
+            self._node_group = self._group(self.component_of_node, self.table["n_nodes"])
+        by, off = self._node_group
+        return self.node_order[by[off[i]:off[i + 1]]]
+
+
+def weakly_connected_components(ov: ExactOverlapper, graph_res: OverlapResult) -> Components:
+    """``networkx.weakly_connected_components`` on a graph result of ``ov`` (an edge result, a merged graph or a
+    ``graph_from_edges`` result), which stays valid and in HBM; the numbering follows the result's own node order."""
+    order = graph_res.node_order()
+    nodes, edges, table = ov.layout_components(graph_res, len(order))
+    return Components(order, nodes, edges, table, ov.components_stats())
+
+
+@dataclass
+class ChainGraph:
+    """What ``chain_components`` hands to the writers: the graph file as read (``phasm_amd.io.gfa.GraphFile``) and its
+    components."""
+    graph: object
+    components: Components
+
+
+def chain_components(path: str, device: Optional[int] = None) -> ChainGraph:
+    """The start of `phasm chain` on a graph file: ``read_graph_gfa``, one segment per ``S`` line on a fresh handle, the
+    graph on the device (``graph_from_edges``) and its weakly connected components."""
+    from .io import gfa
+    with open(path) as f:
+        graph = gfa.read_graph_gfa(f)
+    ov = ExactOverlapper(device=device)
+    try:
+        for name, n in zip(graph.names, graph.lengths.tolist()):
+            ov.add_segment(name, n)
+        res = ov.graph_from_edges(graph.edges, graph.node_order)
+        try:
+            return ChainGraph(graph, weakly_connected_components(ov, res))
+        finally:
+            res.free()
+    finally:
+        ov.close()
+
+
+def component_gfa2_lines(graph, nodes: Sequence[int], edges: np.ndarray) -> List[str]:
+    """What ``gfa2_write_graph`` (phasm/io/gfa.py:281-326) writes for the subgraph of ``nodes`` (in node order) with
+    ``edges`` (rows of ``graph.edges``, input order)."""
+    from .io import gfa
+    out, segments = [gfa.gfa_header()], set()
+    for n in nodes:
+        seg = int(n) >> 1
+        name, length = graph.names[seg], graph.node_length(n)
+        if name in segments:
+            continue
+        segments.add(name)
+        out.append(gfa.gfa_line("S", name, length, "*"))
+        if seg in graph.fragments:
+            reads, prefix = graph.fragments[seg]
+            total, cur = sum(prefix), 0
+            for k, read in enumerate(reads):
+                p = prefix[k] if k < len(prefix) else None
+                out.append(gfa.gfa_line("F", name, read, cur, cur + p if p else length, 0, p if p else length - total, "*"))
+                if p:
+                    cur += p
+    for u, v, w, o in np.asarray(edges).reshape(-1, 4).tolist():
+        out.append("E\t*\t%s\t%s\t%d\t%d\t0\t%d\t*\n" % (graph.node_name(u), graph.node_name(v), w, graph.node_length(u), o))
+    return out
+
+
+def component_gfa1_lines(graph, nodes: Sequence[int], edges: np.ndarray) -> List[str]:
+    """What ``gfa1_write_graph`` (phasm/io/gfa.py:250-278) writes for the same subgraph."""
+    from .io import gfa
+    out, segments = [gfa.gfa_header("1.0")], set()
+    for n in nodes:
+        name = graph.names[int(n) >> 1]
+        if name in segments:
+            continue
+        segments.add(name)
+        out.append(gfa.gfa_line("S", name, "*", "LN:i:{}".format(graph.node_length(n))))
+    for u, v, _, o in np.asarray(edges).reshape(-1, 4).tolist():
+        a, b = graph.node_name(u), graph.node_name(v)
+        out.append(gfa.gfa_line("L", a[:-1], a[-1:], b[:-1], b[-1:], str(o) + "M"))
+    return out
+
+
+class _ComponentView:
+    """One component with the surface ``write_graphml`` reads."""
+
+    def __init__(self, graph, nodes, edges):
+        self.node_order, self.avg_coverage = np.asarray(nodes), None
+        self.node_name = graph.node_name
+        self._edges = [(graph.node_name(u), graph.node_name(v), w, o) for u, v, w, o in np.asarray(edges).reshape(-1, 4).tolist()]
+
+    def edge_tuples(self):
+        return self._edges
+
+
+def write_component_graphs(out_dir: str, g: ChainGraph, formats: Sequence[str] = ("gfa2",)) -> int:
+    """``component{i}.gfa`` and / or ``component{i}.graphml`` for every component, as ``_write_graphs`` writes them
+    (assembler.py:215-228, :303-304): ``gfa1`` and ``gfa2`` go to the same name, so with both the later one wins.
+    Returns the number of components."""
+    os.makedirs(out_dir, exist_ok=True)
+    comps = g.components
+    for i in range(len(comps)):
+        nodes, idx = comps.nodes_of(i).tolist(), comps.edges_of(i)
+        edges = g.graph.edges[idx]
+        logger.info("Connected component %d with %d nodes and %d edges.", i, len(nodes), len(edges))
+        for file_format in formats:
+            if file_format.startswith("gfa"):
+                lines = (component_gfa1_lines if int(file_format[-1]) == 1 else component_gfa2_lines)(g.graph, nodes, edges)
+                with open(os.path.join(out_dir, "component%d.gfa" % i), "w") as f:
+                    f.write("".join(lines))
+            else:
+                with open(os.path.join(out_dir, "component%d.graphml" % i), "w") as f:
+                    write_graphml(f, _ComponentView(g.graph, nodes, edges))
+    return len(comps)

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -495,6 +495,47 @@ class ExactOverlapper:
 
     def coverage_stats(self) -> dict:
         return self._stats(self._lib.po_get_coverage_stats, PoCoverageStats)
+
+    def layout_components(self, graph: OverlapResult, n_order: Optional[int] = None):
+        """``po_layout_components``: the weakly connected components of a graph result (an edge result, a merged graph or a
+        ``graph_from_edges`` result), which stays valid.  Returns ``(node_component, edge_component, table)``: the
+        component of every node, parallel to ``graph.node_order()`` (``n_order``: its length, if the caller has it); the
+        component of every edge in the graph's edge order; one entry (``first_node``, ``n_nodes``, ``n_edges``) per
+        component.  Component i is the i-th in the order of each component's lowest-ranked node."""
+        if n_order is None:
+            n_order = len(graph.node_order())
+        prm = PoComponentsParams(0)
+        nodes = np.zeros(int(n_order), dtype=np.uint32)
+        edges = np.zeros(len(graph), dtype=np.uint32)
+        table = np.zeros(int(n_order), dtype=COMPONENT_DTYPE)
+        n = ctypes.c_uint64()
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
+        _check(self._h, self._lib.po_layout_components(self._h, graph._ptr, ctypes.byref(prm), ptr(nodes), ptr(edges), ptr(table),
+                                                       ctypes.byref(n)))
+        return nodes, edges, table[:int(n.value)].copy()
+
+    def components_stats(self) -> dict:
+        return self._stats(self._lib.po_get_components_stats, PoComponentsStats)
+
+    def graph_from_edges(self, edges, node_order) -> OverlapResult:
+        """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:
+        u, v, weight, overlap_len over this handle's oriented reads) and the order of its nodes."""
+        edges = np.asarray(edges)
+        if edges.dtype != EDGE_DTYPE:
+            arr = edges.reshape(-1, 4)
+            out = np.empty(len(arr), dtype=EDGE_DTYPE)
+            for k, name in enumerate(EDGE_DTYPE.names):
+                out[name] = arr[:, k]
+            edges = out
+        edges = np.ascontiguousarray(edges)
+        order = np.ascontiguousarray(np.asarray(node_order, dtype=np.int64).reshape(-1))
+        if len(order) and (order.min() < 0 or order.max() >= 2**32):
+            raise ValueError("a node of the node order does not fit 32 bits")
+        order = order.astype(np.uint32)
+        r = ctypes.c_void_p()
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
+        _check(self._h, self._lib.po_graph_from_edges(self._h, ptr(edges), len(edges), ptr(order), len(order), ctypes.byref(r)))
+        return OverlapResult(self, r, EDGE_DTYPE)
 
     def node_order_stats(self) -> dict:
         """Times of the two node-order passes of the last ``layout_edges`` call (not part of ``layout_stats``)."""
