@@ -422,8 +422,10 @@ typedef struct {
  * 2 outgoing-tip edge, 3 removed by the symmetry pass.  kept_out holds the kept edges in input order.
  * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
  * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds, the merging
- * of unambiguous paths with po_layout_merge, the average coverage per edge with po_layout_coverage; bubbles and what follows
- * them (`phasm chain`, phasing) are not part of this library. */
+ * of unambiguous paths with po_layout_merge, the average coverage per edge with po_layout_coverage; of `phasm chain`
+ * this library has the weakly connected components (po_layout_components) and the partition that superbubble detection
+ * starts with (po_layout_partition).  graph_to_dag, the superbubble finder, bubble chains, contigs and phasing are not
+ * part of it. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -609,6 +611,68 @@ po_status po_layout_components(po_handle* h, po_result* graph, const po_componen
                                uint32_t* node_component_out, uint32_t* edge_component_out, po_component* components_out,
                                uint64_t* n_components_out);
 po_status po_get_components_stats(const po_handle* h, po_components_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The first step of superbubble detection inside `phasm chain` (partition_graph, phasm/bubbles.py:32-84): the strongly
+ * connected components of the graph and what the reference's partitions are made of.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_partition_params;
+
+typedef struct {
+    uint32_t first_node;         /* the SCC's lowest-ranked node                                                 */
+    uint32_t n_nodes;
+    uint64_t n_edges;            /* edges with both ends in the SCC, self-loops included                         */
+    uint32_t n_r_in;             /* members with PO_PART_R_IN                                                    */
+    uint32_t n_re_out;           /* members with PO_PART_RE_OUT                                                  */
+} po_scc;                        /* 24 bytes                                                                     */
+
+/* node_flags_out, one byte per node of the order */
+#define PO_PART_R_IN 1u          /* an in-edge from outside the node's partition: the reference adds ('r_', v)   */
+#define PO_PART_RE_OUT 2u        /* an out-edge to outside the node's partition: the reference adds (u, 're_')   */
+#define PO_PART_START 4u         /* a singleton with in-degree 0 in the graph (a self-loop is an in-edge)        */
+#define PO_PART_SINK 8u          /* a singleton with out-degree 0 in the graph                                   */
+
+typedef struct {
+    uint64_t n_nodes;            /* nodes of the graph (those in its node order)                                 */
+    uint64_t n_edges;
+    uint64_t n_sccs, n_nonsingleton_sccs, n_singletons;
+    uint64_t n_self_loops;       /* edges (u, u)                                                                 */
+    uint64_t max_scc_nodes, max_scc_edges;
+    uint64_t n_trimmed;          /* nodes retired by the trim rounds                                             */
+    uint64_t n_class[5];         /* edges per class byte                                                         */
+    uint64_t n_invalid;          /* edges with an end that is not in the node order (the call fails then)        */
+    uint32_t n_outer;            /* trim + colour iterations                                                     */
+    uint32_t n_trim_rounds, n_forward_rounds, n_backward_rounds;   /* each phase's closing round included          */
+    uint32_t n_batches;          /* readbacks of the round loops                                                 */
+    float ms_ranks, ms_rounds, ms_label, ms_total;
+} po_partition_stats;
+
+/* `graph` is a graph result of this handle, of the kinds po_layout_components takes; it stays valid and unchanged.  With
+ * the node order of po_result_node_order (n_order nodes; the rank of a node is its place in it): two nodes are in one SCC
+ * iff each reaches the other along directed edges; a node without edges is an SCC of its own; a node is a SINGLETON iff
+ * its SCC has one node, self-loop or not.  SCC i is the i-th in the order of each SCC's lowest-ranked node (networkx
+ * yields SCCs in a DFS order, which is not reproduced).  The reference's partitions are: every non-singleton SCC, and
+ * per weakly connected component all its singletons together (the acyclic partition).
+ *   node_scc_out    the SCC of every node, parallel to the node order
+ *   node_flags_out  PO_PART_* bits of every node, parallel to the node order
+ *   edge_class_out  per edge, in the graph's edge order: 0 both ends in one non-singleton SCC; 1 both ends singletons (a
+ *                   self-loop on a singleton included): an edge of the acyclic partition; 2 singleton -> member of a
+ *                   non-singleton SCC; 3 member of a non-singleton SCC -> singleton; 4 between two non-singleton SCCs
+ *   sccs_out        one entry per SCC (room for n_order entries)
+ * Any of the four may be NULL; *n_sccs_out is always written.  Only integers are involved: every output is the same on
+ * every run (the round counts of the stats are statistics).  An edge with an end that is not in the node order is
+ * counted in n_invalid; the call then fails with PO_ERR_INVALID and writes nothing.  Device memory beyond the inputs is
+ * linear: at most 78 bytes per node (12 of them per slot of the sort, padded to a power of two) and 9 per edge.  params
+ * may be NULL.  An empty graph with an empty order: PO_OK, 0 SCCs.  Every round loop is bounded on the host (a phase by
+ * its live nodes + 2, the iterations by n_order); reaching a bound is PO_ERR_HIP with a message, never a partition.
+ * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A row result, a result of another handle,
+ * reserved != 0, n_sccs_out NULL: PO_ERR_INVALID. */
+po_status po_layout_partition(po_handle* h, po_result* graph, const po_partition_params* params, uint32_t* node_scc_out,
+                              uint8_t* node_flags_out, uint8_t* edge_class_out, po_scc* sccs_out, uint64_t* n_sccs_out);
+po_status po_get_partition_stats(const po_handle* h, po_partition_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

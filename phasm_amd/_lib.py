@@ -28,6 +28,10 @@ EDGE_DTYPE = np.dtype([("u", "<u4"), ("v", "<u4"), ("weight", "<i4"), ("overlap_
 COVERAGE_DTYPE = np.dtype([("read_length_sum", "<u8"), ("path_length", "<i8")])
 # po_component
 COMPONENT_DTYPE = np.dtype([("first_node", "<u4"), ("n_nodes", "<u4"), ("n_edges", "<u8")])
+# po_scc
+SCC_DTYPE = np.dtype([("first_node", "<u4"), ("n_nodes", "<u4"), ("n_edges", "<u8"), ("n_r_in", "<u4"), ("n_re_out", "<u4")])
+# PO_PART_*: the bits of po_layout_partition's flag byte per node
+PART_R_IN, PART_RE_OUT, PART_START, PART_SINK = 1, 2, 4, 8
 
 
 class PoLayoutParams(ctypes.Structure):
@@ -136,6 +140,25 @@ class PoComponentsStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoPartitionParams(ctypes.Structure):
+    _fields_ = [("reserved", ctypes.c_uint32)]
+
+
+class PoPartitionStats(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("n_edges", ctypes.c_uint64), ("n_sccs", ctypes.c_uint64),
+                ("n_nonsingleton_sccs", ctypes.c_uint64), ("n_singletons", ctypes.c_uint64), ("n_self_loops", ctypes.c_uint64),
+                ("max_scc_nodes", ctypes.c_uint64), ("max_scc_edges", ctypes.c_uint64), ("n_trimmed", ctypes.c_uint64),
+                ("n_class", ctypes.c_uint64 * 5), ("n_invalid", ctypes.c_uint64), ("n_outer", ctypes.c_uint32),
+                ("n_trim_rounds", ctypes.c_uint32), ("n_forward_rounds", ctypes.c_uint32), ("n_backward_rounds", ctypes.c_uint32),
+                ("n_batches", ctypes.c_uint32),
+                ("ms_ranks", ctypes.c_float), ("ms_rounds", ctypes.c_float), ("ms_label", ctypes.c_float), ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["n_class"] = list(self.n_class)
+        return d
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -237,6 +260,9 @@ SYMBOLS = [
     ("po_layout_components", ctypes.c_int, [_P, _P, ctypes.POINTER(PoComponentsParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_components_stats", ctypes.c_int, [_P, ctypes.POINTER(PoComponentsStats)]),
+    ("po_layout_partition", ctypes.c_int, [_P, _P, ctypes.POINTER(PoPartitionParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_partition_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPartitionStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

@@ -290,9 +290,13 @@ def chain_components(args) -> int:
         logger.critical("No valid file formats specified.")
         sys.exit(1)
     logger.info("Reconstructing assembly graph...")
-    g = layout.chain_components(args.graph_gfa, device=args.device)
+    g = layout.chain_components(args.graph_gfa, device=args.device, partitions=args.partitions)
     logger.info("Enumerate weakly connected components in the graph...")
     n = layout.write_component_graphs(args.output_dir, g, formats)
+    for parts in g.partitions or ():
+        for part in parts:   # (find_superbubbles, phasm/bubbles.py:402-409, logs this line per partition)
+            logger.info("Partition with %d nodes with in-degree 0, %d nodes with out-degree 0, acyclic: %s", part.num_sources,
+                        part.num_sinks, part.acyclic)
     logger.info("Wrote %d weakly connected components.", n)
     return 0
 
@@ -373,6 +377,8 @@ def main(argv=None) -> int:
     k.add_argument("-f", "--format", default="gfa2", help="comma separated: gfa1, gfa2, graphml (default: gfa2)")
     k.add_argument("-o", "--output-dir", required=True)
     k.add_argument("--device", type=int, default=None)
+    k.add_argument("--partitions", action="store_true",
+                   help="also log, per component, the partitions superbubble detection starts with (strongly connected components)")
     k.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
     k.set_defaults(func=chain_components)
     args = parser.parse_args(argv)

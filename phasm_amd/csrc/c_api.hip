@@ -42,6 +42,7 @@
 #include "merge.hip.h"
 #include "coverage.hip.h"
 #include "components.hip.h"
+#include "partition.hip.h"
 
 namespace {
 
@@ -60,10 +61,14 @@ enum { VB_CNT, VB_USED, VB_NODEOF, VB_LEN, VB_TABLE, VB_SUM, VB_SETCNT, VB_OFF, 
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
 // workspaces of po_layout_components (components.hip.h)
 enum { KB_CNT, KB_RCNT, KB_KEY, KB_VAL, KB_RANKOF, KB_P, KB_ENDS, KB_ROOT, KB_INDEX, KB_COMP, KB_ECOMP, KB_TABLE, KB_N };
-constexpr int EV_LAY_N = 34;
+// workspaces of po_layout_partition (partition.hip.h)
+enum { PB_CNT, PB_RCNT, PB_KEY, PB_VAL, PB_RANKOF, PB_ENDS, PB_LIVE, PB_SCC, PB_COLOUR, PB_MARK, PB_HASIN, PB_HASOUT, PB_ROOT, PB_INDEX,
+       PB_NODESCC, PB_FLAGW, PB_FLAGS, PB_ECLASS, PB_TABLE, PB_N };
+constexpr int EV_LAY_N = 38;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
-enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30 };
-static_assert(EV_COMPONENTS + 4 == EV_LAY_N, "the four events of po_layout_components are the last of the layout events");
+enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
+       EV_PARTITION = 34 };
+static_assert(EV_PARTITION + 4 == EV_LAY_N, "the four events of po_layout_partition are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -421,6 +426,9 @@ struct po_handle {
     // weakly connected components (po_layout_components, components.hip.h)
     DevBuf d_cc[KB_N];
     po_components_stats ccstats = {};
+    // strongly connected components and the superbubble partition (po_layout_partition, partition.hip.h)
+    DevBuf d_scc[PB_N];
+    po_partition_stats pstats = {};
 };
 
 struct po_result {
@@ -3679,6 +3687,179 @@ po_status run_components(po_handle* h, po_result* graph, uint32_t* node_out, uin
     return PO_OK;
 }
 
+// ---- strongly connected components and the superbubble partition (po_layout_partition) -----------------------------------
+
+// what scc_drive (partition.hip.h) launches and reads back, on the handle's stream
+struct SccOps {
+    po_handle* h;
+    hipStream_t st;
+    uint32_t n, n_order, edge_grid, rank_grid;
+    const po::EdgeRanks* ends;
+    uint8_t *live, *mark, *has_in, *has_out;
+    uint32_t *scc, *colour;
+    unsigned long long* rcnt;
+    hipError_t err = hipSuccess;
+
+    bool ok(hipError_t e) {
+        if (e != hipSuccess && err == hipSuccess) err = e;
+        return e == hipSuccess;
+    }
+    bool begin(uint32_t batch) { return ok(hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st)); }
+    bool end(uint32_t batch, const volatile uint64_t*& words) {
+        words = h->pinned + 32;
+        return ok(hipGetLastError()) && ok(hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st)) &&
+               ok(hipStreamSynchronize(st));
+    }
+    void trim_round(uint32_t j) {
+        if (n) hipLaunchKernelGGL(po::k_scc_trim_edges, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, live, has_in, has_out);
+        hipLaunchKernelGGL(po::k_scc_trim_ranks, dim3(rank_grid), dim3(256), 0, st, n_order, live, scc, has_in, has_out, rcnt + j);
+    }
+    void colour_init() { hipLaunchKernelGGL(po::k_scc_colour_init, dim3(rank_grid), dim3(256), 0, st, n_order, live, colour, mark); }
+    void forward_round(uint32_t j) {
+        if (n) hipLaunchKernelGGL(po::k_scc_forward, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, live, colour, rcnt + j);
+    }
+    void back_init() { hipLaunchKernelGGL(po::k_scc_back_init, dim3(rank_grid), dim3(256), 0, st, n_order, live, colour, mark); }
+    void backward_round(uint32_t j) {
+        if (n) hipLaunchKernelGGL(po::k_scc_backward, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, live, colour, mark, rcnt + j);
+    }
+    bool retire(uint64_t& retired) {
+        if (!ok(hipMemsetAsync(rcnt, 0, 8, st))) return false;
+        hipLaunchKernelGGL(po::k_scc_retire, dim3(rank_grid), dim3(256), 0, st, n_order, live, colour, mark, scc, rcnt);
+        if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(h->pinned + 40, rcnt, 8, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
+            return false;
+        retired = h->pinned[40];
+        return true;
+    }
+};
+
+po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint8_t* flags_out, uint8_t* class_out, po_scc* table_out,
+                        uint64_t* n_sccs_out) {
+    hipStream_t st = h->stream;
+    po_partition_stats& S = h->pstats;
+    S = po_partition_stats();
+    if (graph->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_partition: too many edges for one call");
+    const uint32_t n = (uint32_t)graph->count;
+    const uint64_t K = graph->merged ? graph->n_merged : 0;
+    if (h->len.size() + K >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_partition: too many nodes for one call");
+    const uint32_t n_total = (uint32_t)(h->len.size() + K);
+    S.n_edges = n;
+    if (n_total == 0 || !graph->d_nrank.p) {
+        if (n) return fail(h, PO_ERR_INVALID, "po_layout_partition: the graph carries no node order");
+        return PO_OK;
+    }
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_PARTITION;
+    PO_TRY(rows_to_device(h, graph));
+    const uint32_t pad = po::merge_sort_pad(n_total);
+    const size_t nn = (size_t)n_total + 2, ne = (size_t)n + 1;
+    DevBuf* B = h->d_scc;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[PB_CNT], 128));
+    PO_TRY(ensure(h, B[PB_RCNT], po::CC_BATCH * 8));
+    PO_TRY(ensure(h, B[PB_KEY], (size_t)pad * 8));
+    PO_TRY(ensure(h, B[PB_VAL], (size_t)pad * 4));
+    for (int k : {PB_RANKOF, PB_SCC, PB_COLOUR, PB_INDEX, PB_NODESCC, PB_FLAGW}) PO_TRY(ensure(h, B[k], nn * 4));
+    for (int k : {PB_LIVE, PB_MARK, PB_HASIN, PB_HASOUT, PB_ROOT, PB_FLAGS}) PO_TRY(ensure(h, B[k], nn));
+    PO_TRY(ensure(h, B[PB_TABLE], nn * sizeof(po::Scc)));
+    PO_TRY(ensure(h, B[PB_ENDS], ne * sizeof(po::EdgeRanks)));
+    PO_TRY(ensure(h, B[PB_ECLASS], ne));
+    unsigned long long *cnt = B[PB_CNT].as<unsigned long long>(), *rcnt = B[PB_RCNT].as<unsigned long long>(),
+                       *key = B[PB_KEY].as<unsigned long long>();
+    uint32_t *val = B[PB_VAL].as<uint32_t>(), *rank_of = B[PB_RANKOF].as<uint32_t>(), *scc = B[PB_SCC].as<uint32_t>(),
+             *colour = B[PB_COLOUR].as<uint32_t>(), *index = B[PB_INDEX].as<uint32_t>(), *node_scc = B[PB_NODESCC].as<uint32_t>(),
+             *flagw = B[PB_FLAGW].as<uint32_t>();
+    uint8_t *live = B[PB_LIVE].as<uint8_t>(), *mark = B[PB_MARK].as<uint8_t>(), *has_in = B[PB_HASIN].as<uint8_t>(),
+            *has_out = B[PB_HASOUT].as<uint8_t>(), *root = B[PB_ROOT].as<uint8_t>(), *flags = B[PB_FLAGS].as<uint8_t>(),
+            *eclass = B[PB_ECLASS].as<uint8_t>();
+    po::Scc* table = B[PB_TABLE].as<po::Scc>();
+    po::EdgeRanks* ends = B[PB_ENDS].as<po::EdgeRanks>();
+    const po::Edge* d_edges = graph->d_rows.as<po::Edge>();
+    const uint32_t edge_grid = stride_grid(h, n);
+    // rank of every node and the two ranks of every edge: the kernels of po_layout_components, as they are
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    HIP_TRY(h, hipMemsetAsync(rank_of, 0xFF, nn * 4, st));
+    hipLaunchKernelGGL(po::k_cc_keys, dim3(cdiv(pad, 256)), dim3(256), 0, st, graph->d_nrank.as<unsigned long long>(), n_total, pad, key, val);
+    po::merge_sort_steps(n_total, [&](uint32_t j, uint32_t k) {
+        hipLaunchKernelGGL(po::k_merge_bitonic, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, j, k);
+    });
+    hipLaunchKernelGGL(po::k_cc_init, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, n_total, colour, rank_of, cnt);
+    if (n) hipLaunchKernelGGL(po::k_cc_ends, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_total, rank_of, ends, cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::PC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    S.n_invalid = h->pinned[16 + po::PC_INVALID];
+    S.n_nodes = h->pinned[16 + po::PC_ORDER];
+    if (S.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_partition: an edge has an end that is not in the node order");
+    if (S.n_nodes > n_total) return fail(h, PO_ERR_HIP, "internal: po_layout_partition counted more ranks than nodes");
+    const uint32_t n_order = (uint32_t)S.n_nodes;
+    const uint32_t rank_grid = stride_grid(h, n_order);
+    // trim rounds, forward colouring, backward marking, again while live ranks remain: every bound is scc_drive's
+    po::SccWork W;
+    if (n_order) {
+        hipLaunchKernelGGL(po::k_scc_init, dim3(rank_grid), dim3(256), 0, st, n_order, live, scc, has_in, has_out);
+        SccOps ops{h, st, n, n_order, edge_grid, rank_grid, ends, live, mark, has_in, has_out, scc, colour, rcnt};
+        const int how = po::scc_drive(ops, n_order, W);
+        S.n_trimmed = W.n_trimmed;
+        S.n_outer = W.outer;
+        S.n_trim_rounds = W.trim_rounds;
+        S.n_forward_rounds = W.forward_rounds;
+        S.n_backward_rounds = W.backward_rounds;
+        S.n_batches = W.batches;
+        if (how == po::SCC_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how == po::SCC_ROUND_CAP) return fail(h, PO_ERR_HIP, "internal: a phase of po_layout_partition reached its bound of live + 2 rounds");
+        if (how == po::SCC_OUTER_CAP) return fail(h, PO_ERR_HIP, "internal: po_layout_partition reached its bound of n_order iterations");
+        if (how != po::SCC_DONE) return fail(h, PO_ERR_HIP, "internal: the live nodes of po_layout_partition do not add up");
+    }
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    if (n_order) {
+        hipLaunchKernelGGL(po::k_scc_roots, dim3(rank_grid), dim3(256), 0, st, scc, n_order, root, flagw);
+        HIP_TRY(h, hipGetLastError());
+    }
+    PO_TRY(prefix_sum<uint8_t>(h, root, n_order, index, &h->pinned[2]));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_scc64 = h->pinned[2];
+    if (n_scc64 > n_order || (n_order && !n_scc64)) return fail(h, PO_ERR_HIP, "internal: the roots of po_layout_partition do not add up");
+    const uint32_t n_scc = (uint32_t)n_scc64;
+    S.n_sccs = n_scc;
+    if (n_scc) {
+        HIP_TRY(h, hipMemsetAsync(table, 0, (size_t)n_scc * sizeof(po::Scc), st));
+        hipLaunchKernelGGL(po::k_scc_label_nodes, dim3(rank_grid), dim3(256), 0, st, scc, index, val, n_order, n_scc, node_scc, table);
+        if (n) hipLaunchKernelGGL(po::k_scc_edges, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, n_scc, node_scc, table, eclass, flagw, cnt);
+        hipLaunchKernelGGL(po::k_scc_flags, dim3(rank_grid), dim3(256), 0, st, n_order, n_scc, node_scc, flagw, table, flags);
+        hipLaunchKernelGGL(po::k_scc_max, dim3(stride_grid(h, n_scc)), dim3(256), 0, st, table, n_scc, cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    static_assert(sizeof(po_scc) == sizeof(po::Scc) && sizeof(po_scc) == 24, "po_scc is the device's table entry");
+    const size_t tb = (size_t)n_scc * sizeof(po_scc), nb = (size_t)n_order * 4, fb = n_order, eb = n;
+    PO_TRY(ensure_host(h, h->scratch_host, tb + nb + fb + eb + 16));
+    char* land = static_cast<char*>(h->scratch_host.p);
+    if (tb && table_out) HIP_TRY(h, hipMemcpyAsync(land, table, tb, hipMemcpyDeviceToHost, st));
+    if (nb && node_out) HIP_TRY(h, hipMemcpyAsync(land + tb, node_scc, nb, hipMemcpyDeviceToHost, st));
+    if (fb && flags_out) HIP_TRY(h, hipMemcpyAsync(land + tb + nb, flags, fb, hipMemcpyDeviceToHost, st));
+    if (eb && class_out) HIP_TRY(h, hipMemcpyAsync(land + tb + nb + fb, eclass, eb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::PC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    S.n_singletons = h->pinned[16 + po::PC_SINGLE];
+    S.n_nonsingleton_sccs = S.n_sccs - S.n_singletons;
+    S.max_scc_nodes = h->pinned[16 + po::PC_MAXN];
+    S.max_scc_edges = h->pinned[16 + po::PC_MAXE];
+    S.n_self_loops = h->pinned[16 + po::PC_SELF];
+    for (int k = 0; k < 5; ++k) S.n_class[k] = h->pinned[16 + po::PC_CLASS + k];
+    if (tb && table_out) std::memcpy(table_out, land, tb);
+    if (nb && node_out) std::memcpy(node_out, land + tb, nb);
+    if (fb && flags_out) std::memcpy(flags_out, land + tb + nb, fb);
+    if (eb && class_out) std::memcpy(class_out, land + tb + nb + fb, eb);
+    *n_sccs_out = n_scc;
+    (void)hipEventElapsedTime(&S.ms_ranks, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&S.ms_rounds, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&S.ms_label, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
+    return PO_OK;
+}
+
 // ---- what the po_layout_* entry points share ------------------------------------------------------------------------
 
 // Everything an edge-producing entry point does behind its checks: `run(result)` fills a new result of handle h, which
@@ -4118,6 +4299,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_mrg) b.release();
         for (DevBuf& b : h->d_cov) b.release();
         for (DevBuf& b : h->d_cc) b.release();
+        for (DevBuf& b : h->d_scc) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -5925,6 +6107,28 @@ po_status po_layout_components(po_handle* h, po_result* graph, const po_componen
     return st;
 }
 
+po_status po_layout_partition(po_handle* h, po_result* graph, const po_partition_params* params, uint32_t* node_scc_out,
+                              uint8_t* node_flags_out, uint8_t* edge_class_out, po_scc* sccs_out, uint64_t* n_sccs_out) {
+    if (!h || !graph) return PO_ERR_INVALID;
+    if (!n_sccs_out) return fail(h, PO_ERR_INVALID, "po_layout_partition: no room for the number of strongly connected components");
+    *n_sccs_out = 0;
+    if (graph->h != h) return fail(h, PO_ERR_INVALID, "po_layout_partition: the graph belongs to another handle");
+    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_partition: bad parameters");
+    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
+        return fail(h, PO_ERR_INVALID, "po_layout_partition needs an edge result, a merged graph or a po_graph_from_edges result");
+    // (no CPU fallback)
+    const po_status dev = init_device(h);
+    if (dev != PO_OK) return dev;
+    po_status st;
+    try {
+        st = run_partition(h, graph, node_scc_out, node_flags_out, edge_class_out, sccs_out, n_sccs_out);
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_partition");
+    }
+    if (st != PO_OK && h->dev_ready) (void)hipStreamSynchronize(h->stream);
+    return st;
+}
+
 po_status po_graph_from_edges(po_handle* h, const po_edge* edges, uint64_t n_edges, const uint32_t* node_order, uint64_t n_order,
                               po_result** out) {
     if (!h || !out || (!edges && n_edges) || (!node_order && n_order)) return PO_ERR_INVALID;
@@ -5988,6 +6192,7 @@ po_status po_get_diamond_stats(const po_handle* h, po_diamond_stats* out) { retu
 po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out) { return get_stats(h, &po_handle::mstats, out); }
 po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out) { return get_stats(h, &po_handle::cstats, out); }
 po_status po_get_components_stats(const po_handle* h, po_components_stats* out) { return get_stats(h, &po_handle::ccstats, out); }
+po_status po_get_partition_stats(const po_handle* h, po_partition_stats* out) { return get_stats(h, &po_handle::pstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

@@ -26,6 +26,8 @@ still in HBM, and ``write_graphml`` writes the graph with that attribute (the co
 ``weakly_connected_components`` is the first step of the command that reads that file, `phasm chain`
 (assembler.py:231-310): the components of a graph result by ``po_layout_components``, numbered as networkx yields them;
 ``chain_components`` runs it on a graph file and ``write_component_graphs`` writes ``component{i}.gfa`` / ``.graphml``.
+``strongly_connected_components`` (``po_layout_partition``) and ``superbubble_partitions`` are what superbubble detection
+starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).
 What follows that point (bubble chains, contigs, phasing) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
@@ -478,17 +480,120 @@ def weakly_connected_components(ov: ExactOverlapper, graph_res: OverlapResult) -
     return Components(order, nodes, edges, table, ov.components_stats())
 
 
+# ---- the partition superbubble detection starts with (partition_graph, phasm/bubbles.py:32-84) ---------------------------
+
+@dataclass
+class StrongComponents:
+    """The strongly connected components of a graph result and what ``partition_graph`` makes of them
+    (``po_layout_partition``).  ``node_order``: the graph's nodes in the reference's order; ``scc_of_node`` and
+    ``node_flags`` (``_lib.PART_*`` bits): parallel to it; ``edge_class``: the class byte of every edge and ``scc_of_edge``
+    the SCC of its u, in the graph's edge order; ``table``: structured (``first_node``, ``n_nodes``, ``n_edges``,
+    ``n_r_in``, ``n_re_out``), one entry per SCC -- SCC i is the i-th in the order of each SCC's lowest-ranked node (not
+    the DFS order in which networkx yields them); ``stats``: ``po_get_partition_stats``."""
+    node_order: np.ndarray
+    scc_of_node: np.ndarray
+    node_flags: np.ndarray
+    edge_class: np.ndarray
+    scc_of_edge: np.ndarray
+    table: np.ndarray
+    stats: dict
+
+    def __len__(self) -> int:
+        return len(self.table)
+
+
+def strongly_connected_components(ov: ExactOverlapper, graph_res: OverlapResult) -> StrongComponents:
+    """``po_layout_partition`` on a graph result of ``ov`` (an edge result, a merged graph or a ``graph_from_edges``
+    result), which stays valid and in HBM; the numbering follows the result's own node order."""
+    order = graph_res.node_order()
+    nodes, flags, classes, table = ov.layout_partition(graph_res, len(order))
+    stats = ov.partition_stats()
+    if len(graph_res):
+        u = graph_res.rows()["u"].astype(np.int64)
+        rank = np.zeros(int(max(order.max(), u.max())) + 1, dtype=np.int64)
+        rank[order] = np.arange(len(order))
+        scc_of_edge = nodes[rank[u]]
+    else:
+        scc_of_edge = np.zeros(0, dtype=np.uint32)
+    return StrongComponents(order, nodes, flags, classes, scc_of_edge, table, stats)
+
+
+@dataclass
+class Partition:
+    """One subgraph ``partition_graph(component)`` yields.  ``nodes``: its members, in node order; ``edges``: the indices
+    of its real edges, in the graph's edge order; ``r_targets`` / ``re_sources``: the nodes v / u of the artificial edges
+    ``('r_', v)`` / ``(u, 're_')``, in node order; ``scc``: the SCC of a cyclic partition, None for the acyclic one;
+    ``number_of_nodes`` / ``number_of_edges``: of the reference's subgraph, artificial nodes and edges included;
+    ``num_sources`` / ``num_sinks``: what ``find_superbubbles`` counts and logs (phasm/bubbles.py:403-406)."""
+    component: int
+    scc: Optional[int]
+    acyclic: bool
+    nodes: np.ndarray
+    edges: np.ndarray
+    r_targets: np.ndarray
+    re_sources: np.ndarray
+    number_of_nodes: int
+    number_of_edges: int
+    num_sources: int
+    num_sinks: int
+
+
+def _groups(of: np.ndarray, n_groups: int, among: np.ndarray):
+    """(indices of ``among`` sorted by their group, stably; the start of every group in them)."""
+    key = of[among].astype(np.int64)
+    by = among[np.argsort(key, kind="stable")]
+    return by, np.concatenate([[0], np.cumsum(np.bincount(key, minlength=n_groups))]).astype(np.int64)
+
+
+def superbubble_partitions(sccs: StrongComponents, components: Components) -> List[List[Partition]]:
+    """Per weakly connected component, the partitions ``partition_graph`` yields on it: its non-singleton SCCs in SCC
+    order (``acyclic`` False), then exactly one acyclic partition of its singletons, even when that is empty.  The
+    grouping is done with numpy on the host, like ``Components.edges_of``."""
+    from ._lib import PART_R_IN, PART_RE_OUT, PART_START, PART_SINK
+    order, n_comp, n_scc = sccs.node_order, len(components), len(sccs)
+    flags = sccs.node_flags
+    single_scc = sccs.table["n_nodes"] == 1
+    single_node = single_scc[sccs.scc_of_node] if len(order) else np.zeros(0, dtype=bool)
+    comp_of_scc = np.zeros(n_scc, dtype=np.int64)
+    comp_of_scc[sccs.scc_of_node] = components.component_of_node
+    ranks, eids = np.arange(len(order)), np.arange(len(sccs.edge_class))
+    cyc_nodes, cyc_noff = _groups(sccs.scc_of_node, n_scc, ranks[~single_node])
+    cyc_edges, cyc_eoff = _groups(sccs.scc_of_edge, n_scc, eids[sccs.edge_class == 0])
+    acy_nodes, acy_noff = _groups(components.component_of_node, n_comp, ranks[single_node])
+    acy_edges, acy_eoff = _groups(components.component_of_edge, n_comp, eids[sccs.edge_class == 1])
+    sccs_by_comp, scc_off = _groups(comp_of_scc, n_comp, np.flatnonzero(~single_scc))
+
+    def make(comp, scc, r, e, in_bits, out_bits):
+        r_t, re_s = order[r[(flags[r] & in_bits) != 0]], order[r[(flags[r] & out_bits) != 0]]
+        return Partition(comp, scc, scc is None, order[r], e, r_t, re_s, len(r) + (len(r_t) > 0) + (len(re_s) > 0),
+                         len(e) + len(r_t) + len(re_s), int(len(r_t) > 0), int(len(re_s) > 0))
+
+    out = []
+    for c in range(n_comp):
+        parts = []
+        for k in sccs_by_comp[scc_off[c]:scc_off[c + 1]].tolist():
+            parts.append(make(c, k, cyc_nodes[cyc_noff[k]:cyc_noff[k + 1]], cyc_edges[cyc_eoff[k]:cyc_eoff[k + 1]], PART_R_IN, PART_RE_OUT))
+        parts.append(make(c, None, acy_nodes[acy_noff[c]:acy_noff[c + 1]], acy_edges[acy_eoff[c]:acy_eoff[c + 1]],
+                          PART_R_IN | PART_START, PART_RE_OUT | PART_SINK))
+        out.append(parts)
+    return out
+
+
 @dataclass
 class ChainGraph:
     """What ``chain_components`` hands to the writers: the graph file as read (``phasm_amd.io.gfa.GraphFile``) and its
-    components."""
+    components; with ``partitions=True`` also the strongly connected components and, per component, the partitions that
+    superbubble detection starts with."""
     graph: object
     components: Components
+    sccs: Optional[StrongComponents] = None
+    partitions: Optional[List[List[Partition]]] = None
 
 
-def chain_components(path: str, device: Optional[int] = None) -> ChainGraph:
+def chain_components(path: str, device: Optional[int] = None, partitions: bool = False) -> ChainGraph:
     """The start of `phasm chain` on a graph file: ``read_graph_gfa``, one segment per ``S`` line on a fresh handle, the
-    graph on the device (``graph_from_edges``) and its weakly connected components."""
+    graph on the device (``graph_from_edges``) and its weakly connected components; with ``partitions`` also
+    ``strongly_connected_components`` and ``superbubble_partitions``."""
     from .io import gfa
     with open(path) as f:
         graph = gfa.read_graph_gfa(f)
@@ -498,7 +603,11 @@ def chain_components(path: str, device: Optional[int] = None) -> ChainGraph:
             ov.add_segment(name, n)
         res = ov.graph_from_edges(graph.edges, graph.node_order)
         try:
-            return ChainGraph(graph, weakly_connected_components(ov, res))
+            comps = weakly_connected_components(ov, res)
+            if not partitions:
+                return ChainGraph(graph, comps)
+            sccs = strongly_connected_components(ov, res)
+            return ChainGraph(graph, comps, sccs, superbubble_partitions(sccs, comps))
         finally:
             res.free()
     finally:

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -516,6 +516,29 @@ class ExactOverlapper:
 
     def components_stats(self) -> dict:
         return self._stats(self._lib.po_get_components_stats, PoComponentsStats)
+
+    def layout_partition(self, graph: OverlapResult, n_order: Optional[int] = None):
+        """``po_layout_partition``: the strongly connected components of a graph result (of the kinds ``layout_components``
+        takes), which stays valid, and what the reference's ``partition_graph`` (phasm/bubbles.py:32-84) makes of them.
+        Returns ``(node_scc, node_flags, edge_class, table)``: the SCC and the ``PART_*`` flag byte of every node, parallel
+        to ``graph.node_order()`` (``n_order``: its length, if the caller has it); the class byte of every edge in the
+        graph's edge order; one entry (``first_node``, ``n_nodes``, ``n_edges``, ``n_r_in``, ``n_re_out``) per SCC.  SCC i
+        is the i-th in the order of each SCC's lowest-ranked node."""
+        if n_order is None:
+            n_order = len(graph.node_order())
+        prm = PoPartitionParams(0)
+        nodes = np.zeros(int(n_order), dtype=np.uint32)
+        flags = np.zeros(int(n_order), dtype=np.uint8)
+        classes = np.zeros(len(graph), dtype=np.uint8)
+        table = np.zeros(int(n_order), dtype=SCC_DTYPE)
+        n = ctypes.c_uint64()
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
+        _check(self._h, self._lib.po_layout_partition(self._h, graph._ptr, ctypes.byref(prm), ptr(nodes), ptr(flags), ptr(classes),
+                                                      ptr(table), ctypes.byref(n)))
+        return nodes, flags, classes, table[:int(n.value)].copy()
+
+    def partition_stats(self) -> dict:
+        return self._stats(self._lib.po_get_partition_stats, PoPartitionStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:
