@@ -58,12 +58,14 @@ enum { MB_CNT, MB_RCNT, MB_OUTDEG, MB_INDEG, MB_OUTE, MB_INE, MB_LINK, MB_BACK, 
        MB_N };
 // workspaces of po_layout_coverage (coverage.hip.h)
 enum { VB_CNT, VB_USED, VB_NODEOF, VB_LEN, VB_TABLE, VB_SUM, VB_SETCNT, VB_OFF, VB_CUR, VB_LIST, VB_OUT, VB_N };
+// what every analysis stage on a graph result works in (po_handle::d_rank, ranked_open): counters, change words, the sort,
+// node -> rank, the two ranks of every edge, the root bytes and their prefix sum
+enum { RK_CNT, RK_RCNT, RK_KEY, RK_VAL, RK_RANKOF, RK_ENDS, RK_ROOT, RK_INDEX, RK_N };
+// workspaces of po_layout_components (components.hip.h) beyond those
+enum { KB_P, KB_COMP, KB_ECOMP, KB_TABLE, KB_N };
+// workspaces of po_layout_partition (partition.hip.h) beyond those
+enum { PB_LIVE, PB_SCC, PB_COLOUR, PB_MARK, PB_HASIN, PB_HASOUT, PB_NODESCC, PB_FLAGW, PB_FLAGS, PB_ECLASS, PB_TABLE, PB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-// workspaces of po_layout_components (components.hip.h)
-enum { KB_CNT, KB_RCNT, KB_KEY, KB_VAL, KB_RANKOF, KB_P, KB_ENDS, KB_ROOT, KB_INDEX, KB_COMP, KB_ECOMP, KB_TABLE, KB_N };
-// workspaces of po_layout_partition (partition.hip.h)
-enum { PB_CNT, PB_RCNT, PB_KEY, PB_VAL, PB_RANKOF, PB_ENDS, PB_LIVE, PB_SCC, PB_COLOUR, PB_MARK, PB_HASIN, PB_HASOUT, PB_ROOT, PB_INDEX,
-       PB_NODESCC, PB_FLAGW, PB_FLAGS, PB_ECLASS, PB_TABLE, PB_N };
 constexpr int EV_LAY_N = 38;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
@@ -423,6 +425,8 @@ struct po_handle {
     DevBuf d_cov[VB_N];
     po_coverage_stats cstats = {};
 
+    // the ranks of a graph result, recomputed by every call of the two stages below (ranked_open)
+    DevBuf d_rank[RK_N];
     // weakly connected components (po_layout_components, components.hip.h)
     DevBuf d_cc[KB_N];
     po_components_stats ccstats = {};
@@ -3469,6 +3473,36 @@ po_status run_merge(po_handle* h, po_result* edges, uint8_t* flags_out, po_resul
     return PO_OK;
 }
 
+// one output of po_layout_coverage, _components or _partition on its way to the caller (`dst` null: not wanted)
+struct Landing {
+    const void* src;
+    size_t bytes;
+    void* dst;
+};
+
+// The outputs through the handle's pinned landing buffer, in list order, then the first `n_counters` counters to words
+// 16.. of the landing zone; one synchronise, then the copies into the caller's memory.
+po_status land_outputs(po_handle* h, std::initializer_list<Landing> outs, const unsigned long long* cnt, int n_counters) {
+    hipStream_t st = h->stream;
+    size_t total = 16;
+    for (const Landing& o : outs) total += o.bytes;
+    PO_TRY(ensure_host(h, h->scratch_host, total));
+    char* land = static_cast<char*>(h->scratch_host.p);
+    size_t at = 0;
+    for (const Landing& o : outs) {
+        if (o.bytes && o.dst) HIP_TRY(h, hipMemcpyAsync(land + at, o.src, o.bytes, hipMemcpyDeviceToHost, st));
+        at += o.bytes;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, (size_t)n_counters * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    at = 0;
+    for (const Landing& o : outs) {
+        if (o.bytes && o.dst) std::memcpy(o.dst, land + at, o.bytes);
+        at += o.bytes;
+    }
+    return PO_OK;
+}
+
 // ---- average_coverage_path per edge (po_layout_coverage): edges + all rows -> (read_length_sum, path_length) per edge ----
 
 po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_coverage* out) {
@@ -3550,153 +3584,107 @@ po_status run_coverage(po_handle* h, po_result* graph, po_result* rows, po_edge_
                        sum, setcnt, off, list, n_pairs, d_out, cnt);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[2], st));
-    PO_TRY(ensure_host(h, h->scratch_host, (size_t)n * sizeof(po_edge_coverage)));
-    HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, d_out, (size_t)n * sizeof(po_edge_coverage), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::CC_N * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    PO_TRY(land_outputs(h, {{d_out, (size_t)n * sizeof(po_edge_coverage), out}}, cnt, po::CC_N));
     C.n_zero_path = h->pinned[16 + po::CC_ZERO];
-    std::memcpy(out, h->scratch_host.p, (size_t)n * sizeof(po_edge_coverage));
     (void)hipEventElapsedTime(&C.ms_sets, ev[0], ev[1]);
     (void)hipEventElapsedTime(&C.ms_edges, ev[1], ev[2]);
     (void)hipEventElapsedTime(&C.ms_total, ev[0], ev[2]);
     return PO_OK;
 }
 
-// ---- weakly connected components (po_layout_components): graph result -> component per node and per edge, the table ----
+// ---- what the analysis stages on a graph result (po_layout_components, po_layout_partition) share --------------------
+// A driver resets its stats, opens with ranked_open, runs its rounds on the ranks, launches its k_*_roots, and closes with
+// ranked_roots, its label kernels and land_outputs (above); it reads its own counters from words 16.. of the landing zone.
 
-po_status run_components(po_handle* h, po_result* graph, uint32_t* node_out, uint32_t* edge_out, po_component* table_out,
-                         uint64_t* n_components_out) {
+// a graph result by rank (the place of a node in the node order), as ranked_open leaves it on the device
+struct RankedGraph {
+    uint32_t n = 0, n_total = 0, n_order = 0, pad = 0, edge_grid = 0, rank_grid = 0;
+    uint32_t *val = nullptr, *rank_of = nullptr, *index = nullptr;   // node at rank; rank of node; root number (ranked_roots)
+    po::EdgeRanks* ends = nullptr;
+    uint8_t* root = nullptr;
+    unsigned long long *cnt = nullptr, *rcnt = nullptr;
+    hipEvent_t* ev = nullptr;   // the stage's four events; null: an empty graph, nothing was launched and nothing is to do
+};
+
+// The open: the bounds, the early return of the empty graph, events, edges on the device, the shared workspaces and the
+// stage's own (`own(nn, ne)` ensures them for nn node and ne edge places, `ident` among them), then the rank of every
+// node -- the rank words sorted (bitonic, padded with all ones to a power of two), place r = rank r, `ident`[r] = r --
+// and the two ranks of every edge, the first `n_counters` counters on the host (words 16.. of the landing zone), one
+// synchronise.  Fills the n_edges, n_invalid and n_nodes of the stage's stats.
+template <class Stats, class Own>
+po_status ranked_open(po_handle* h, po_result* graph, const std::string& stage, int ev_first, int n_counters, Stats& S, DevBuf& ident,
+                      Own&& own, RankedGraph& R) {
     hipStream_t st = h->stream;
-    po_components_stats& S = h->ccstats;
-    S = po_components_stats();
-    if (graph->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_components: too many edges for one call");
+    if (graph->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, stage + ": too many edges for one call");
     const uint32_t n = (uint32_t)graph->count;
     const uint64_t K = graph->merged ? graph->n_merged : 0;
-    if (h->len.size() + K >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_components: too many nodes for one call");
+    if (h->len.size() + K >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, stage + ": too many nodes for one call");
     const uint32_t n_total = (uint32_t)(h->len.size() + K);
     S.n_edges = n;
     if (n_total == 0 || !graph->d_nrank.p) {
-        if (n) return fail(h, PO_ERR_INVALID, "po_layout_components: the graph carries no node order");
+        if (n) return fail(h, PO_ERR_INVALID, stage + ": the graph carries no node order");
         return PO_OK;
     }
     PO_TRY(lay_events(h));
-    hipEvent_t* ev = h->ev_lay + EV_COMPONENTS;
+    hipEvent_t* ev = h->ev_lay + ev_first;
     PO_TRY(rows_to_device(h, graph));
     const uint32_t pad = po::merge_sort_pad(n_total);
     const size_t nn = (size_t)n_total + 2, ne = (size_t)n + 1;
-    DevBuf* B = h->d_cc;
+    DevBuf* B = h->d_rank;
     PO_TRY(ensure(h, h->d_scalars, 128));
-    PO_TRY(ensure(h, B[KB_CNT], 128));
-    PO_TRY(ensure(h, B[KB_RCNT], po::CC_BATCH * 8));
-    PO_TRY(ensure(h, B[KB_KEY], (size_t)pad * 8));
-    PO_TRY(ensure(h, B[KB_VAL], (size_t)pad * 4));
-    for (int k : {KB_RANKOF, KB_P, KB_INDEX, KB_COMP}) PO_TRY(ensure(h, B[k], nn * 4));
-    PO_TRY(ensure(h, B[KB_ROOT], nn));
-    PO_TRY(ensure(h, B[KB_TABLE], nn * sizeof(po::Component)));
-    PO_TRY(ensure(h, B[KB_ENDS], ne * sizeof(po::EdgeRanks)));
-    PO_TRY(ensure(h, B[KB_ECOMP], ne * 4));
-    unsigned long long *cnt = B[KB_CNT].as<unsigned long long>(), *rcnt = B[KB_RCNT].as<unsigned long long>(),
-                       *key = B[KB_KEY].as<unsigned long long>();
-    uint32_t *val = B[KB_VAL].as<uint32_t>(), *rank_of = B[KB_RANKOF].as<uint32_t>(), *p = B[KB_P].as<uint32_t>(),
-             *index = B[KB_INDEX].as<uint32_t>(), *comp = B[KB_COMP].as<uint32_t>(), *ecomp = B[KB_ECOMP].as<uint32_t>();
-    uint8_t* root = B[KB_ROOT].as<uint8_t>();
-    po::Component* table = B[KB_TABLE].as<po::Component>();
-    po::EdgeRanks* ends = B[KB_ENDS].as<po::EdgeRanks>();
-    const po::Edge* d_edges = graph->d_rows.as<po::Edge>();
-    const uint32_t edge_grid = stride_grid(h, n);
-    // rank of every node: the rank words sorted (bitonic, padded with all ones to a power of two), place r = rank r
+    PO_TRY(ensure(h, B[RK_CNT], 128));
+    PO_TRY(ensure(h, B[RK_RCNT], po::CC_BATCH * 8));
+    PO_TRY(ensure(h, B[RK_KEY], (size_t)pad * 8));
+    PO_TRY(ensure(h, B[RK_VAL], (size_t)pad * 4));
+    for (int k : {RK_RANKOF, RK_INDEX}) PO_TRY(ensure(h, B[k], nn * 4));
+    PO_TRY(ensure(h, B[RK_ROOT], nn));
+    PO_TRY(ensure(h, B[RK_ENDS], ne * sizeof(po::EdgeRanks)));
+    PO_TRY(own(nn, ne));
+    R = RankedGraph{n, n_total, 0, pad, stride_grid(h, n), 0, B[RK_VAL].as<uint32_t>(), B[RK_RANKOF].as<uint32_t>(),
+                    B[RK_INDEX].as<uint32_t>(), B[RK_ENDS].as<po::EdgeRanks>(), B[RK_ROOT].as<uint8_t>(),
+                    B[RK_CNT].as<unsigned long long>(), B[RK_RCNT].as<unsigned long long>(), nullptr};
+    unsigned long long* key = B[RK_KEY].as<unsigned long long>();
     HIP_TRY(h, hipEventRecord(ev[0], st));
-    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
-    HIP_TRY(h, hipMemsetAsync(rank_of, 0xFF, nn * 4, st));
-    hipLaunchKernelGGL(po::k_cc_keys, dim3(cdiv(pad, 256)), dim3(256), 0, st, graph->d_nrank.as<unsigned long long>(), n_total, pad, key, val);
+    HIP_TRY(h, hipMemsetAsync(R.cnt, 0, 128, st));
+    HIP_TRY(h, hipMemsetAsync(R.rank_of, 0xFF, nn * 4, st));
+    hipLaunchKernelGGL(po::k_cc_keys, dim3(cdiv(pad, 256)), dim3(256), 0, st, graph->d_nrank.as<unsigned long long>(), n_total, pad, key,
+                       R.val);
     po::merge_sort_steps(n_total, [&](uint32_t j, uint32_t k) {
-        hipLaunchKernelGGL(po::k_merge_bitonic, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, j, k);
+        hipLaunchKernelGGL(po::k_merge_bitonic, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, R.val, pad, j, k);
     });
-    hipLaunchKernelGGL(po::k_cc_init, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, n_total, p, rank_of, cnt);
-    if (n) hipLaunchKernelGGL(po::k_cc_ends, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_total, rank_of, ends, cnt);
+    hipLaunchKernelGGL(po::k_cc_init, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, R.val, pad, n_total, ident.as<uint32_t>(), R.rank_of,
+                       R.cnt);
+    if (n)
+        hipLaunchKernelGGL(po::k_cc_ends, dim3(R.edge_grid), dim3(256), 0, st, graph->d_rows.as<po::Edge>(), n, n_total, R.rank_of, R.ends,
+                           R.cnt);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::KC_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, R.cnt, (size_t)n_counters * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipEventRecord(ev[1], st));
     HIP_TRY(h, hipStreamSynchronize(st));
     S.n_invalid = h->pinned[16 + po::KC_INVALID];
     S.n_nodes = h->pinned[16 + po::KC_ORDER];
-    if (S.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_components: an edge has an end that is not in the node order");
-    if (S.n_nodes > n_total) return fail(h, PO_ERR_HIP, "internal: po_layout_components counted more ranks than nodes");
-    const uint32_t n_order = (uint32_t)S.n_nodes;
-    const uint32_t rank_grid = stride_grid(h, n_order);
-    // Rounds of hook + jump in batches, one change word per round and one readback per batch; the first round that
-    // lowered no word ends them (the later rounds of its batch lower nothing either).  The bound is the host's.
-    const uint64_t cap = po::cc_round_cap(n_order);
-    uint64_t launched = 0;
-    uint32_t rounds = 0, batches = 0;
-    bool done = n_order == 0;
-    while (!done && launched < cap) {
-        const uint32_t batch = (uint32_t)std::min<uint64_t>(po::CC_BATCH, cap - launched);
-        HIP_TRY(h, hipMemsetAsync(rcnt, 0, (size_t)batch * 8, st));
-        for (uint32_t j = 0; j < batch; ++j, ++launched) {
-            if (n) hipLaunchKernelGGL(po::k_cc_hook, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, p, rcnt + j);
-            hipLaunchKernelGGL(po::k_cc_jump, dim3(rank_grid), dim3(256), 0, st, n_order, p, rcnt + j);
-        }
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        ++batches;
-        done = po::cc_rounds_done(h->pinned + 32, batch, rounds);
-    }
-    S.n_rounds = rounds;
-    S.n_batches = batches;
-    if (!done) return fail(h, PO_ERR_HIP, "internal: po_layout_components reached its bound of n_order + 2 rounds");
-    HIP_TRY(h, hipEventRecord(ev[2], st));
-    if (n_order) {
-        hipLaunchKernelGGL(po::k_cc_roots, dim3(rank_grid), dim3(256), 0, st, p, n_order, root);
-        HIP_TRY(h, hipGetLastError());
-    }
-    PO_TRY(prefix_sum<uint8_t>(h, root, n_order, index, &h->pinned[2]));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    const uint64_t n_comp64 = h->pinned[2];
-    if (n_comp64 > n_order || (n_order && !n_comp64)) return fail(h, PO_ERR_HIP, "internal: the roots of po_layout_components do not add up");
-    const uint32_t n_comp = (uint32_t)n_comp64;
-    S.n_components = n_comp;
-    if (n_comp) {
-        HIP_TRY(h, hipMemsetAsync(table, 0, (size_t)n_comp * sizeof(po::Component), st));
-        hipLaunchKernelGGL(po::k_cc_label_nodes, dim3(rank_grid), dim3(256), 0, st, p, index, val, n_order, n_comp, comp, table);
-        if (n) hipLaunchKernelGGL(po::k_cc_label_edges, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, n_comp, comp, ecomp, table);
-        hipLaunchKernelGGL(po::k_cc_max, dim3(stride_grid(h, n_comp)), dim3(256), 0, st, table, n_comp, cnt);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipEventRecord(ev[3], st));
-    static_assert(sizeof(po_component) == sizeof(po::Component), "po_component is the device's table entry");
-    const size_t tb = (size_t)n_comp * sizeof(po_component), nb = (size_t)n_order * 4, eb = (size_t)n * 4;
-    PO_TRY(ensure_host(h, h->scratch_host, tb + nb + eb + 16));
-    char* land = static_cast<char*>(h->scratch_host.p);
-    if (tb && table_out) HIP_TRY(h, hipMemcpyAsync(land, table, tb, hipMemcpyDeviceToHost, st));
-    if (nb && node_out) HIP_TRY(h, hipMemcpyAsync(land + tb, comp, nb, hipMemcpyDeviceToHost, st));
-    if (eb && edge_out) HIP_TRY(h, hipMemcpyAsync(land + tb + nb, ecomp, eb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::KC_N * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    S.n_singletons = h->pinned[16 + po::KC_SINGLE];
-    S.max_component_nodes = h->pinned[16 + po::KC_MAXN];
-    S.max_component_edges = h->pinned[16 + po::KC_MAXE];
-    if (tb && table_out) std::memcpy(table_out, land, tb);
-    if (nb && node_out) std::memcpy(node_out, land + tb, nb);
-    if (eb && edge_out) std::memcpy(edge_out, land + tb + nb, eb);
-    *n_components_out = n_comp;
-    (void)hipEventElapsedTime(&S.ms_rounds, ev[1], ev[2]);
-    (void)hipEventElapsedTime(&S.ms_label, ev[2], ev[3]);
-    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
+    if (S.n_invalid) return fail(h, PO_ERR_INVALID, stage + ": an edge has an end that is not in the node order");
+    if (S.n_nodes > n_total) return fail(h, PO_ERR_HIP, "internal: " + stage + " counted more ranks than nodes");
+    R.n_order = (uint32_t)S.n_nodes;
+    R.rank_grid = stride_grid(h, R.n_order);
+    R.ev = ev;
     return PO_OK;
 }
 
-// ---- strongly connected components and the superbubble partition (po_layout_partition) -----------------------------------
+// After the stage's k_*_roots: the roots numbered by rank (R.index), their number on the host.  One synchronise.
+po_status ranked_roots(po_handle* h, const RankedGraph& R, const char* name, uint32_t& n_roots) {
+    PO_TRY(prefix_sum<uint8_t>(h, R.root, R.n_order, R.index, &h->pinned[2]));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const uint64_t n64 = h->pinned[2];
+    if (n64 > R.n_order || (R.n_order && !n64)) return fail(h, PO_ERR_HIP, std::string("internal: the roots of ") + name + " do not add up");
+    n_roots = (uint32_t)n64;
+    return PO_OK;
+}
 
-// what scc_drive (partition.hip.h) launches and reads back, on the handle's stream
-struct SccOps {
+// what round_phase (components.hip.h) clears and reads back, on the handle's stream; the first HIP error sticks
+struct RoundOps {
     po_handle* h;
     hipStream_t st;
-    uint32_t n, n_order, edge_grid, rank_grid;
-    const po::EdgeRanks* ends;
-    uint8_t *live, *mark, *has_in, *has_out;
-    uint32_t *scc, *colour;
     unsigned long long* rcnt;
     hipError_t err = hipSuccess;
 
@@ -3710,21 +3698,91 @@ struct SccOps {
         return ok(hipGetLastError()) && ok(hipMemcpyAsync(h->pinned + 32, rcnt, (size_t)batch * 8, hipMemcpyDeviceToHost, st)) &&
                ok(hipStreamSynchronize(st));
     }
+};
+
+// ---- weakly connected components (po_layout_components): graph result -> component per node and per edge, the table ----
+
+po_status run_components(po_handle* h, po_result* graph, uint32_t* node_out, uint32_t* edge_out, po_component* table_out,
+                         uint64_t* n_components_out) {
+    hipStream_t st = h->stream;
+    po_components_stats& S = h->ccstats;
+    S = po_components_stats();
+    DevBuf* B = h->d_cc;
+    RankedGraph R;
+    PO_TRY(ranked_open(h, graph, "po_layout_components", EV_COMPONENTS, po::KC_N, S, B[KB_P], [&](size_t nn, size_t ne) {
+        for (int k : {KB_P, KB_COMP}) PO_TRY(ensure(h, B[k], nn * 4));
+        PO_TRY(ensure(h, B[KB_TABLE], nn * sizeof(po::Component)));
+        return ensure(h, B[KB_ECOMP], ne * 4);
+    }, R));
+    if (!R.ev) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order;
+    uint32_t *p = B[KB_P].as<uint32_t>(), *comp = B[KB_COMP].as<uint32_t>(), *ecomp = B[KB_ECOMP].as<uint32_t>();
+    po::Component* table = B[KB_TABLE].as<po::Component>();
+    // Rounds of hook + jump in batches, one change word per round and one readback per batch; the first round that
+    // lowered no word ends them (the later rounds of its batch lower nothing either).  The bound is the host's.
+    if (n_order) {
+        RoundOps ops{h, st, R.rcnt};
+        uint64_t lowered = 0;
+        const int how = po::round_phase(ops, n_order, [&](uint32_t j) {
+            if (n) hipLaunchKernelGGL(po::k_cc_hook, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, p, R.rcnt + j);
+            hipLaunchKernelGGL(po::k_cc_jump, dim3(R.rank_grid), dim3(256), 0, st, n_order, p, R.rcnt + j);
+        }, S.n_rounds, S.n_batches, lowered);
+        if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, "internal: po_layout_components reached its bound of n_order + 2 rounds");
+    }
+    HIP_TRY(h, hipEventRecord(R.ev[2], st));
+    if (n_order) {
+        hipLaunchKernelGGL(po::k_cc_roots, dim3(R.rank_grid), dim3(256), 0, st, p, n_order, R.root);
+        HIP_TRY(h, hipGetLastError());
+    }
+    uint32_t n_comp = 0;
+    PO_TRY(ranked_roots(h, R, "po_layout_components", n_comp));
+    S.n_components = n_comp;
+    if (n_comp) {
+        HIP_TRY(h, hipMemsetAsync(table, 0, (size_t)n_comp * sizeof(po::Component), st));
+        hipLaunchKernelGGL(po::k_cc_label_nodes, dim3(R.rank_grid), dim3(256), 0, st, p, R.index, R.val, n_order, n_comp, comp, table);
+        if (n) hipLaunchKernelGGL(po::k_cc_label_edges, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, n_comp, comp, ecomp, table);
+        hipLaunchKernelGGL(po::k_cc_max, dim3(stride_grid(h, n_comp)), dim3(256), 0, st, table, n_comp, R.cnt);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(R.ev[3], st));
+    static_assert(sizeof(po_component) == sizeof(po::Component), "po_component is the device's table entry");
+    PO_TRY(land_outputs(h, {{table, (size_t)n_comp * sizeof(po_component), table_out}, {comp, (size_t)n_order * 4, node_out},
+                            {ecomp, (size_t)n * 4, edge_out}}, R.cnt, po::KC_N));
+    S.n_singletons = h->pinned[16 + po::KC_SINGLE];
+    S.max_component_nodes = h->pinned[16 + po::KC_MAXN];
+    S.max_component_edges = h->pinned[16 + po::KC_MAXE];
+    *n_components_out = n_comp;
+    (void)hipEventElapsedTime(&S.ms_rounds, R.ev[1], R.ev[2]);
+    (void)hipEventElapsedTime(&S.ms_label, R.ev[2], R.ev[3]);
+    (void)hipEventElapsedTime(&S.ms_total, R.ev[0], R.ev[3]);
+    return PO_OK;
+}
+
+// ---- strongly connected components and the superbubble partition (po_layout_partition) -----------------------------------
+
+// what scc_drive (partition.hip.h) launches and reads back, on the handle's stream
+struct SccOps : RoundOps {
+    const RankedGraph& R;
+    uint8_t *live, *mark, *has_in, *has_out;
+    uint32_t *scc, *colour;
+
     void trim_round(uint32_t j) {
-        if (n) hipLaunchKernelGGL(po::k_scc_trim_edges, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, live, has_in, has_out);
-        hipLaunchKernelGGL(po::k_scc_trim_ranks, dim3(rank_grid), dim3(256), 0, st, n_order, live, scc, has_in, has_out, rcnt + j);
+        if (R.n) hipLaunchKernelGGL(po::k_scc_trim_edges, dim3(R.edge_grid), dim3(256), 0, st, R.ends, R.n, R.n_order, live, has_in, has_out);
+        hipLaunchKernelGGL(po::k_scc_trim_ranks, dim3(R.rank_grid), dim3(256), 0, st, R.n_order, live, scc, has_in, has_out, rcnt + j);
     }
-    void colour_init() { hipLaunchKernelGGL(po::k_scc_colour_init, dim3(rank_grid), dim3(256), 0, st, n_order, live, colour, mark); }
+    void colour_init() { hipLaunchKernelGGL(po::k_scc_colour_init, dim3(R.rank_grid), dim3(256), 0, st, R.n_order, live, colour, mark); }
     void forward_round(uint32_t j) {
-        if (n) hipLaunchKernelGGL(po::k_scc_forward, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, live, colour, rcnt + j);
+        if (R.n) hipLaunchKernelGGL(po::k_scc_forward, dim3(R.edge_grid), dim3(256), 0, st, R.ends, R.n, R.n_order, live, colour, rcnt + j);
     }
-    void back_init() { hipLaunchKernelGGL(po::k_scc_back_init, dim3(rank_grid), dim3(256), 0, st, n_order, live, colour, mark); }
+    void back_init() { hipLaunchKernelGGL(po::k_scc_back_init, dim3(R.rank_grid), dim3(256), 0, st, R.n_order, live, colour, mark); }
     void backward_round(uint32_t j) {
-        if (n) hipLaunchKernelGGL(po::k_scc_backward, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, live, colour, mark, rcnt + j);
+        if (R.n)
+            hipLaunchKernelGGL(po::k_scc_backward, dim3(R.edge_grid), dim3(256), 0, st, R.ends, R.n, R.n_order, live, colour, mark, rcnt + j);
     }
     bool retire(uint64_t& retired) {
         if (!ok(hipMemsetAsync(rcnt, 0, 8, st))) return false;
-        hipLaunchKernelGGL(po::k_scc_retire, dim3(rank_grid), dim3(256), 0, st, n_order, live, colour, mark, scc, rcnt);
+        hipLaunchKernelGGL(po::k_scc_retire, dim3(R.rank_grid), dim3(256), 0, st, R.n_order, live, colour, mark, scc, rcnt);
         if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(h->pinned + 40, rcnt, 8, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
             return false;
         retired = h->pinned[40];
@@ -3737,69 +3795,27 @@ po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint
     hipStream_t st = h->stream;
     po_partition_stats& S = h->pstats;
     S = po_partition_stats();
-    if (graph->count >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_partition: too many edges for one call");
-    const uint32_t n = (uint32_t)graph->count;
-    const uint64_t K = graph->merged ? graph->n_merged : 0;
-    if (h->len.size() + K >= 0x7FFFFF00ull) return fail(h, PO_ERR_CAPACITY, "po_layout_partition: too many nodes for one call");
-    const uint32_t n_total = (uint32_t)(h->len.size() + K);
-    S.n_edges = n;
-    if (n_total == 0 || !graph->d_nrank.p) {
-        if (n) return fail(h, PO_ERR_INVALID, "po_layout_partition: the graph carries no node order");
-        return PO_OK;
-    }
-    PO_TRY(lay_events(h));
-    hipEvent_t* ev = h->ev_lay + EV_PARTITION;
-    PO_TRY(rows_to_device(h, graph));
-    const uint32_t pad = po::merge_sort_pad(n_total);
-    const size_t nn = (size_t)n_total + 2, ne = (size_t)n + 1;
     DevBuf* B = h->d_scc;
-    PO_TRY(ensure(h, h->d_scalars, 128));
-    PO_TRY(ensure(h, B[PB_CNT], 128));
-    PO_TRY(ensure(h, B[PB_RCNT], po::CC_BATCH * 8));
-    PO_TRY(ensure(h, B[PB_KEY], (size_t)pad * 8));
-    PO_TRY(ensure(h, B[PB_VAL], (size_t)pad * 4));
-    for (int k : {PB_RANKOF, PB_SCC, PB_COLOUR, PB_INDEX, PB_NODESCC, PB_FLAGW}) PO_TRY(ensure(h, B[k], nn * 4));
-    for (int k : {PB_LIVE, PB_MARK, PB_HASIN, PB_HASOUT, PB_ROOT, PB_FLAGS}) PO_TRY(ensure(h, B[k], nn));
-    PO_TRY(ensure(h, B[PB_TABLE], nn * sizeof(po::Scc)));
-    PO_TRY(ensure(h, B[PB_ENDS], ne * sizeof(po::EdgeRanks)));
-    PO_TRY(ensure(h, B[PB_ECLASS], ne));
-    unsigned long long *cnt = B[PB_CNT].as<unsigned long long>(), *rcnt = B[PB_RCNT].as<unsigned long long>(),
-                       *key = B[PB_KEY].as<unsigned long long>();
-    uint32_t *val = B[PB_VAL].as<uint32_t>(), *rank_of = B[PB_RANKOF].as<uint32_t>(), *scc = B[PB_SCC].as<uint32_t>(),
-             *colour = B[PB_COLOUR].as<uint32_t>(), *index = B[PB_INDEX].as<uint32_t>(), *node_scc = B[PB_NODESCC].as<uint32_t>(),
+    RankedGraph R;
+    // (the identity words land in `colour`: colour[r] = r is where the first forward phase starts anyway)
+    PO_TRY(ranked_open(h, graph, "po_layout_partition", EV_PARTITION, po::PC_N, S, B[PB_COLOUR], [&](size_t nn, size_t ne) {
+        for (int k : {PB_SCC, PB_COLOUR, PB_NODESCC, PB_FLAGW}) PO_TRY(ensure(h, B[k], nn * 4));
+        for (int k : {PB_LIVE, PB_MARK, PB_HASIN, PB_HASOUT, PB_FLAGS}) PO_TRY(ensure(h, B[k], nn));
+        PO_TRY(ensure(h, B[PB_TABLE], nn * sizeof(po::Scc)));
+        return ensure(h, B[PB_ECLASS], ne);
+    }, R));
+    if (!R.ev) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order;
+    uint32_t *scc = B[PB_SCC].as<uint32_t>(), *colour = B[PB_COLOUR].as<uint32_t>(), *node_scc = B[PB_NODESCC].as<uint32_t>(),
              *flagw = B[PB_FLAGW].as<uint32_t>();
     uint8_t *live = B[PB_LIVE].as<uint8_t>(), *mark = B[PB_MARK].as<uint8_t>(), *has_in = B[PB_HASIN].as<uint8_t>(),
-            *has_out = B[PB_HASOUT].as<uint8_t>(), *root = B[PB_ROOT].as<uint8_t>(), *flags = B[PB_FLAGS].as<uint8_t>(),
-            *eclass = B[PB_ECLASS].as<uint8_t>();
+            *has_out = B[PB_HASOUT].as<uint8_t>(), *flags = B[PB_FLAGS].as<uint8_t>(), *eclass = B[PB_ECLASS].as<uint8_t>();
     po::Scc* table = B[PB_TABLE].as<po::Scc>();
-    po::EdgeRanks* ends = B[PB_ENDS].as<po::EdgeRanks>();
-    const po::Edge* d_edges = graph->d_rows.as<po::Edge>();
-    const uint32_t edge_grid = stride_grid(h, n);
-    // rank of every node and the two ranks of every edge: the kernels of po_layout_components, as they are
-    HIP_TRY(h, hipEventRecord(ev[0], st));
-    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
-    HIP_TRY(h, hipMemsetAsync(rank_of, 0xFF, nn * 4, st));
-    hipLaunchKernelGGL(po::k_cc_keys, dim3(cdiv(pad, 256)), dim3(256), 0, st, graph->d_nrank.as<unsigned long long>(), n_total, pad, key, val);
-    po::merge_sort_steps(n_total, [&](uint32_t j, uint32_t k) {
-        hipLaunchKernelGGL(po::k_merge_bitonic, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, j, k);
-    });
-    hipLaunchKernelGGL(po::k_cc_init, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, n_total, colour, rank_of, cnt);
-    if (n) hipLaunchKernelGGL(po::k_cc_ends, dim3(edge_grid), dim3(256), 0, st, d_edges, n, n_total, rank_of, ends, cnt);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::PC_N * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipEventRecord(ev[1], st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    S.n_invalid = h->pinned[16 + po::PC_INVALID];
-    S.n_nodes = h->pinned[16 + po::PC_ORDER];
-    if (S.n_invalid) return fail(h, PO_ERR_INVALID, "po_layout_partition: an edge has an end that is not in the node order");
-    if (S.n_nodes > n_total) return fail(h, PO_ERR_HIP, "internal: po_layout_partition counted more ranks than nodes");
-    const uint32_t n_order = (uint32_t)S.n_nodes;
-    const uint32_t rank_grid = stride_grid(h, n_order);
     // trim rounds, forward colouring, backward marking, again while live ranks remain: every bound is scc_drive's
     po::SccWork W;
     if (n_order) {
-        hipLaunchKernelGGL(po::k_scc_init, dim3(rank_grid), dim3(256), 0, st, n_order, live, scc, has_in, has_out);
-        SccOps ops{h, st, n, n_order, edge_grid, rank_grid, ends, live, mark, has_in, has_out, scc, colour, rcnt};
+        hipLaunchKernelGGL(po::k_scc_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, live, scc, has_in, has_out);
+        SccOps ops{{h, st, R.rcnt}, R, live, mark, has_in, has_out, scc, colour};
         const int how = po::scc_drive(ops, n_order, W);
         S.n_trimmed = W.n_trimmed;
         S.n_outer = W.outer;
@@ -3812,51 +3828,39 @@ po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint
         if (how == po::SCC_OUTER_CAP) return fail(h, PO_ERR_HIP, "internal: po_layout_partition reached its bound of n_order iterations");
         if (how != po::SCC_DONE) return fail(h, PO_ERR_HIP, "internal: the live nodes of po_layout_partition do not add up");
     }
-    HIP_TRY(h, hipEventRecord(ev[2], st));
+    HIP_TRY(h, hipEventRecord(R.ev[2], st));
     if (n_order) {
-        hipLaunchKernelGGL(po::k_scc_roots, dim3(rank_grid), dim3(256), 0, st, scc, n_order, root, flagw);
+        hipLaunchKernelGGL(po::k_scc_roots, dim3(R.rank_grid), dim3(256), 0, st, scc, n_order, R.root, flagw);
         HIP_TRY(h, hipGetLastError());
     }
-    PO_TRY(prefix_sum<uint8_t>(h, root, n_order, index, &h->pinned[2]));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    const uint64_t n_scc64 = h->pinned[2];
-    if (n_scc64 > n_order || (n_order && !n_scc64)) return fail(h, PO_ERR_HIP, "internal: the roots of po_layout_partition do not add up");
-    const uint32_t n_scc = (uint32_t)n_scc64;
+    uint32_t n_scc = 0;
+    PO_TRY(ranked_roots(h, R, "po_layout_partition", n_scc));
     S.n_sccs = n_scc;
     if (n_scc) {
         HIP_TRY(h, hipMemsetAsync(table, 0, (size_t)n_scc * sizeof(po::Scc), st));
-        hipLaunchKernelGGL(po::k_scc_label_nodes, dim3(rank_grid), dim3(256), 0, st, scc, index, val, n_order, n_scc, node_scc, table);
-        if (n) hipLaunchKernelGGL(po::k_scc_edges, dim3(edge_grid), dim3(256), 0, st, ends, n, n_order, n_scc, node_scc, table, eclass, flagw, cnt);
-        hipLaunchKernelGGL(po::k_scc_flags, dim3(rank_grid), dim3(256), 0, st, n_order, n_scc, node_scc, flagw, table, flags);
-        hipLaunchKernelGGL(po::k_scc_max, dim3(stride_grid(h, n_scc)), dim3(256), 0, st, table, n_scc, cnt);
+        hipLaunchKernelGGL(po::k_scc_label_nodes, dim3(R.rank_grid), dim3(256), 0, st, scc, R.index, R.val, n_order, n_scc, node_scc, table);
+        if (n)
+            hipLaunchKernelGGL(po::k_scc_edges, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, n_scc, node_scc, table, eclass, flagw,
+                               R.cnt);
+        hipLaunchKernelGGL(po::k_scc_flags, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_scc, node_scc, flagw, table, flags);
+        hipLaunchKernelGGL(po::k_scc_max, dim3(stride_grid(h, n_scc)), dim3(256), 0, st, table, n_scc, R.cnt);
         HIP_TRY(h, hipGetLastError());
     }
-    HIP_TRY(h, hipEventRecord(ev[3], st));
+    HIP_TRY(h, hipEventRecord(R.ev[3], st));
     static_assert(sizeof(po_scc) == sizeof(po::Scc) && sizeof(po_scc) == 24, "po_scc is the device's table entry");
-    const size_t tb = (size_t)n_scc * sizeof(po_scc), nb = (size_t)n_order * 4, fb = n_order, eb = n;
-    PO_TRY(ensure_host(h, h->scratch_host, tb + nb + fb + eb + 16));
-    char* land = static_cast<char*>(h->scratch_host.p);
-    if (tb && table_out) HIP_TRY(h, hipMemcpyAsync(land, table, tb, hipMemcpyDeviceToHost, st));
-    if (nb && node_out) HIP_TRY(h, hipMemcpyAsync(land + tb, node_scc, nb, hipMemcpyDeviceToHost, st));
-    if (fb && flags_out) HIP_TRY(h, hipMemcpyAsync(land + tb + nb, flags, fb, hipMemcpyDeviceToHost, st));
-    if (eb && class_out) HIP_TRY(h, hipMemcpyAsync(land + tb + nb + fb, eclass, eb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::PC_N * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    PO_TRY(land_outputs(h, {{table, (size_t)n_scc * sizeof(po_scc), table_out}, {node_scc, (size_t)n_order * 4, node_out},
+                            {flags, n_order, flags_out}, {eclass, n, class_out}}, R.cnt, po::PC_N));
     S.n_singletons = h->pinned[16 + po::PC_SINGLE];
     S.n_nonsingleton_sccs = S.n_sccs - S.n_singletons;
     S.max_scc_nodes = h->pinned[16 + po::PC_MAXN];
     S.max_scc_edges = h->pinned[16 + po::PC_MAXE];
     S.n_self_loops = h->pinned[16 + po::PC_SELF];
     for (int k = 0; k < 5; ++k) S.n_class[k] = h->pinned[16 + po::PC_CLASS + k];
-    if (tb && table_out) std::memcpy(table_out, land, tb);
-    if (nb && node_out) std::memcpy(node_out, land + tb, nb);
-    if (fb && flags_out) std::memcpy(flags_out, land + tb + nb, fb);
-    if (eb && class_out) std::memcpy(class_out, land + tb + nb + fb, eb);
     *n_sccs_out = n_scc;
-    (void)hipEventElapsedTime(&S.ms_ranks, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&S.ms_rounds, ev[1], ev[2]);
-    (void)hipEventElapsedTime(&S.ms_label, ev[2], ev[3]);
-    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_ranks, R.ev[0], R.ev[1]);
+    (void)hipEventElapsedTime(&S.ms_rounds, R.ev[1], R.ev[2]);
+    (void)hipEventElapsedTime(&S.ms_label, R.ev[2], R.ev[3]);
+    (void)hipEventElapsedTime(&S.ms_total, R.ev[0], R.ev[3]);
     return PO_OK;
 }
 
@@ -3902,6 +3906,37 @@ po_status stage2_call(po_handle* h, po_result* edges, const char* name, bool par
 }
 
 constexpr const char* CANNOT_CLEAN_AGAIN = "a merged graph (po_layout_merge) cannot be cleaned again";
+
+// What an entry point that fills the caller's arrays does behind its checks: the driver under the `bad_alloc` guard; a
+// failed call leaves nothing in flight on the stream.
+template <class Run>
+po_status guarded_run(po_handle* h, const char* name, Run&& run) {
+    po_status st;
+    try {
+        st = run();
+    } catch (const std::bad_alloc&) {
+        st = fail(h, PO_ERR_NOMEM, std::string("out of host memory in ") + name);
+    }
+    if (st != PO_OK && h->dev_ready) (void)hipStreamSynchronize(h->stream);
+    return st;
+}
+
+// An analysis entry point on a graph result (po_layout_components, po_layout_partition): the checks both make, in the
+// order the messages promise, then the call.  `counted` ends the sentence about the count the caller must take.
+template <class Run>
+po_status graph_call(po_handle* h, po_result* graph, const char* name, bool params_ok, const char* counted, uint64_t* count_out,
+                     Run&& run) {
+    if (!h || !graph) return PO_ERR_INVALID;
+    if (!count_out) return fail(h, PO_ERR_INVALID, std::string(name) + ": no room for the number of " + counted);
+    *count_out = 0;
+    if (graph->h != h) return fail(h, PO_ERR_INVALID, std::string(name) + ": the graph belongs to another handle");
+    if (!params_ok) return fail(h, PO_ERR_INVALID, std::string(name) + ": bad parameters");
+    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
+        return fail(h, PO_ERR_INVALID, std::string(name) + " needs an edge result, a merged graph or a po_graph_from_edges result");
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return guarded_run(h, name, run);
+}
 
 template <class S>
 po_status get_stats(const po_handle* h, S po_handle::*member, S* out) {
@@ -4298,6 +4333,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_tip) b.release();
         for (DevBuf& b : h->d_mrg) b.release();
         for (DevBuf& b : h->d_cov) b.release();
+        for (DevBuf& b : h->d_rank) b.release();
         for (DevBuf& b : h->d_cc) b.release();
         for (DevBuf& b : h->d_scc) b.release();
         const bool pooled = kit_give(h);
@@ -6075,58 +6111,21 @@ po_status po_layout_coverage(po_handle* h, po_result* graph, po_result* rows, co
         return fail(h, PO_ERR_INVALID, "po_layout_coverage needs an edge result or a merged graph in the first position");
     if (rows->elem != sizeof(po_row) || rows->kind_edges) return fail(h, PO_ERR_INVALID, "po_layout_coverage needs a row result in the second position");
     if (graph->count && !coverage_out) return fail(h, PO_ERR_INVALID, "po_layout_coverage: no room for the coverage of the edges");
-    po_status st;
-    try {
-        st = run_coverage(h, graph, rows, coverage_out);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_coverage");
-    }
-    if (st != PO_OK && h->dev_ready) (void)hipStreamSynchronize(h->stream);
-    return st;
+    return guarded_run(h, "po_layout_coverage", [&] { return run_coverage(h, graph, rows, coverage_out); });
 }
 
 po_status po_layout_components(po_handle* h, po_result* graph, const po_components_params* params, uint32_t* node_component_out,
                                uint32_t* edge_component_out, po_component* components_out, uint64_t* n_components_out) {
-    if (!h || !graph) return PO_ERR_INVALID;
-    if (!n_components_out) return fail(h, PO_ERR_INVALID, "po_layout_components: no room for the number of components");
-    *n_components_out = 0;
-    if (graph->h != h) return fail(h, PO_ERR_INVALID, "po_layout_components: the graph belongs to another handle");
-    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_components: bad parameters");
-    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
-        return fail(h, PO_ERR_INVALID, "po_layout_components needs an edge result, a merged graph or a po_graph_from_edges result");
-    // (no CPU fallback)
-    const po_status dev = init_device(h);
-    if (dev != PO_OK) return dev;
-    po_status st;
-    try {
-        st = run_components(h, graph, node_component_out, edge_component_out, components_out, n_components_out);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_components");
-    }
-    if (st != PO_OK && h->dev_ready) (void)hipStreamSynchronize(h->stream);
-    return st;
+    return graph_call(h, graph, "po_layout_components", !params || params->reserved == 0, "components", n_components_out, [&] {
+        return run_components(h, graph, node_component_out, edge_component_out, components_out, n_components_out);
+    });
 }
 
 po_status po_layout_partition(po_handle* h, po_result* graph, const po_partition_params* params, uint32_t* node_scc_out,
                               uint8_t* node_flags_out, uint8_t* edge_class_out, po_scc* sccs_out, uint64_t* n_sccs_out) {
-    if (!h || !graph) return PO_ERR_INVALID;
-    if (!n_sccs_out) return fail(h, PO_ERR_INVALID, "po_layout_partition: no room for the number of strongly connected components");
-    *n_sccs_out = 0;
-    if (graph->h != h) return fail(h, PO_ERR_INVALID, "po_layout_partition: the graph belongs to another handle");
-    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, "po_layout_partition: bad parameters");
-    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
-        return fail(h, PO_ERR_INVALID, "po_layout_partition needs an edge result, a merged graph or a po_graph_from_edges result");
-    // (no CPU fallback)
-    const po_status dev = init_device(h);
-    if (dev != PO_OK) return dev;
-    po_status st;
-    try {
-        st = run_partition(h, graph, node_scc_out, node_flags_out, edge_class_out, sccs_out, n_sccs_out);
-    } catch (const std::bad_alloc&) {
-        st = fail(h, PO_ERR_NOMEM, "out of host memory in po_layout_partition");
-    }
-    if (st != PO_OK && h->dev_ready) (void)hipStreamSynchronize(h->stream);
-    return st;
+    return graph_call(h, graph, "po_layout_partition", !params || params->reserved == 0, "strongly connected components", n_sccs_out, [&] {
+        return run_partition(h, graph, node_scc_out, node_flags_out, edge_class_out, sccs_out, n_sccs_out);
+    });
 }
 
 po_status po_graph_from_edges(po_handle* h, const po_edge* edges, uint64_t n_edges, const uint32_t* node_order, uint64_t n_order,

@@ -37,8 +37,9 @@ struct EdgeRanks {
     uint32_t ru, rv;
 };
 
-// n_order + 2: the words are final after at most diameter < n_order rounds, the round after that counts nothing
-inline uint64_t cc_round_cap(uint64_t n_order) { return n_order + 2; }
+// live + 2, `live` = the ranks a loop of rounds works on (all n_order of them here, the live ones of a phase of
+// partition.hip.h): the words are final after at most `live` rounds, the round after that counts nothing
+inline uint64_t cc_round_cap(uint64_t live) { return live + 2; }
 
 // The words of one batch: word j = parent words lowered in round j.  Counts the rounds up to and including the first
 // that lowered none; true when that round was met.
@@ -48,6 +49,31 @@ inline bool cc_rounds_done(const volatile uint64_t* words, uint32_t batch, uint3
         if (words[j] == 0) return true;
     }
     return false;
+}
+
+enum { ROUNDS_DONE = 0, ROUNDS_CAP = 1, ROUNDS_FAILED = 3 };   // (the values scc_drive of partition.hip.h hands on)
+
+// One loop of rounds: in batches of CC_BATCH, one change word per round and one readback per batch, up to and including
+// the first round whose word is 0 (the later rounds of its batch change nothing either), at most cc_round_cap(live) of
+// them.  ops.begin(batch) clears the words, round(j) launches the round that counts into word j, ops.end(batch, words)
+// brings the words to the host; `total` sums them.  The loop of po_layout_components, every phase of po_layout_partition,
+// and what the host emulations of both launch by.
+template <class Ops, class Round>
+inline int round_phase(Ops& ops, uint64_t live, Round&& round, uint32_t& rounds, uint32_t& batches, uint64_t& total) {
+    const uint64_t cap = cc_round_cap(live);
+    uint64_t launched = 0;
+    bool done = false;
+    while (!done && launched < cap) {
+        const uint32_t batch = (uint32_t)(cap - launched < CC_BATCH ? cap - launched : CC_BATCH);
+        if (!ops.begin(batch)) return ROUNDS_FAILED;
+        for (uint32_t j = 0; j < batch; ++j, ++launched) round(j);
+        const volatile uint64_t* words = nullptr;
+        if (!ops.end(batch, words)) return ROUNDS_FAILED;
+        ++batches;
+        for (uint32_t j = 0; j < batch; ++j) total += words[j];
+        done = cc_rounds_done(words, batch, rounds);
+    }
+    return done ? ROUNDS_DONE : ROUNDS_CAP;
 }
 
 // the sort's input: the rank word of every node (reads, then merged nodes), all ones behind them

@@ -41,41 +41,18 @@ struct Scc {
     uint32_t n_r_in, n_re_out;
 };
 
-// live + 2: a phase's words are final after at most `live` rounds (every round but the last removes, lowers along one more
-// edge of a shortest path, or marks at least one rank), the round after that counts nothing
-inline uint64_t scc_round_cap(uint64_t live) { return live + 2; }
-
 struct SccWork {
     uint64_t n_trimmed = 0;
     uint32_t outer = 0, trim_rounds = 0, forward_rounds = 0, backward_rounds = 0, batches = 0;
 };
 
-enum { SCC_DONE = 0, SCC_ROUND_CAP = 1, SCC_OUTER_CAP = 2, SCC_FAILED = 3, SCC_STUCK = 4 };
-
-// One phase: rounds in batches of CC_BATCH, one change word per round and one readback per batch, up to and including the
-// first round whose word is 0 (the later rounds of its batch change nothing either).  ops.begin(batch) clears the words,
-// ops.end(batch, words) brings them to the host; `total` sums them.
-template <class Ops, class Round>
-inline int scc_phase(Ops& ops, uint64_t live, Round&& round, uint32_t& rounds, uint32_t& batches, uint64_t& total) {
-    const uint64_t cap = scc_round_cap(live);
-    uint64_t launched = 0;
-    bool done = false;
-    while (!done && launched < cap) {
-        const uint32_t batch = (uint32_t)(cap - launched < CC_BATCH ? cap - launched : CC_BATCH);
-        if (!ops.begin(batch)) return SCC_FAILED;
-        for (uint32_t j = 0; j < batch; ++j, ++launched) round(j);
-        const volatile uint64_t* words = nullptr;
-        if (!ops.end(batch, words)) return SCC_FAILED;
-        ++batches;
-        for (uint32_t j = 0; j < batch; ++j) total += words[j];
-        done = cc_rounds_done(words, batch, rounds);
-    }
-    return done ? SCC_DONE : SCC_ROUND_CAP;
-}
+enum { SCC_DONE = ROUNDS_DONE, SCC_ROUND_CAP = ROUNDS_CAP, SCC_OUTER_CAP = 2, SCC_FAILED = ROUNDS_FAILED, SCC_STUCK = 4 };
 
 // The whole loop.  Ops launches (trim_round, colour_init, forward_round, back_init, backward_round take the index of the
 // round's change word) and reads back (begin / end, retire).  Every outer iteration retires at least its lowest live rank,
-// so there are at most n_order of them.
+// so there are at most n_order of them.  A phase is one round_phase (components.hip.h) on the ranks live at its start: its
+// words are final after at most `live` rounds (every round but the last removes, lowers along one more edge of a shortest
+// path, or marks at least one rank), the round after that counts nothing.
 template <class Ops>
 inline int scc_drive(Ops& ops, uint64_t n_order, SccWork& w) {
     uint64_t live = n_order;
@@ -83,17 +60,17 @@ inline int scc_drive(Ops& ops, uint64_t n_order, SccWork& w) {
         if (w.outer >= n_order) return SCC_OUTER_CAP;
         ++w.outer;
         uint64_t trimmed = 0, ignored = 0, retired = 0;
-        int s = scc_phase(ops, live, [&](uint32_t j) { ops.trim_round(j); }, w.trim_rounds, w.batches, trimmed);
+        int s = round_phase(ops, live, [&](uint32_t j) { ops.trim_round(j); }, w.trim_rounds, w.batches, trimmed);
         if (s != SCC_DONE) return s;
         if (trimmed > live) return SCC_STUCK;
         w.n_trimmed += trimmed;
         live -= trimmed;
         if (!live) break;
         ops.colour_init();
-        s = scc_phase(ops, live, [&](uint32_t j) { ops.forward_round(j); }, w.forward_rounds, w.batches, ignored);
+        s = round_phase(ops, live, [&](uint32_t j) { ops.forward_round(j); }, w.forward_rounds, w.batches, ignored);
         if (s != SCC_DONE) return s;
         ops.back_init();
-        s = scc_phase(ops, live, [&](uint32_t j) { ops.backward_round(j); }, w.backward_rounds, w.batches, ignored);
+        s = round_phase(ops, live, [&](uint32_t j) { ops.backward_round(j); }, w.backward_rounds, w.batches, ignored);
         if (s != SCC_DONE) return s;
         if (!ops.retire(retired)) return SCC_FAILED;
         if (retired == 0 || retired > live) return SCC_STUCK;

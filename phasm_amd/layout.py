@@ -453,21 +453,18 @@ class Components:
     def __len__(self) -> int:
         return len(self.table)
 
-    def _group(self, of, counts):
-        # (grouping is done here, not on the device: it needs a stable sort, and the writers touch every edge anyway)
-        return np.argsort(of, kind="stable"), np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
-
     def edges_of(self, i: int) -> np.ndarray:
         """The indices of the edges of component ``i``, in the graph's edge order."""
+        # (grouping is done here, not on the device: it needs a stable sort, and the writers touch every edge anyway)
         if not hasattr(self, "_edge_group"):
-            self._edge_group = self._group(self.component_of_edge, self.table["n_edges"])
+            self._edge_group = _groups(self.component_of_edge, len(self), np.arange(len(self.component_of_edge)))
         by, off = self._edge_group
         return by[off[i]:off[i + 1]]
 
     def nodes_of(self, i: int) -> np.ndarray:
         """The nodes of component ``i``, in node order."""
         if not hasattr(self, "_node_group"):
-            self._node_group = self._group(self.component_of_node, self.table["n_nodes"])
+            self._node_group = _groups(self.component_of_node, len(self), np.arange(len(self.component_of_node)))
         by, off = self._node_group
         return self.node_order[by[off[i]:off[i + 1]]]
 

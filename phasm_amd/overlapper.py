@@ -70,6 +70,11 @@ def _check(handle, status: int):
     raise RuntimeError(msg)
 
 
+def _ptr(a: np.ndarray):
+    """The address of an array's data for a C call; NULL for an empty array."""
+    return a.ctypes.data_as(ctypes.c_void_p) if len(a) else None
+
+
 class OverlapResult:
     """Owns one ``po_result``: rows stay on the device until asked for."""
 
@@ -151,9 +156,8 @@ class OverlapResult:
         lengths = np.zeros(int(k.value), dtype=np.int64)
         members = np.zeros(int(m.value), dtype=np.uint32)
         prefix = np.zeros(int(m.value), dtype=np.int32)
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
-        _check(self._owner._h, self._lib.po_result_merged_paths(self._ptr, ctypes.byref(k), ctypes.byref(m), ptr(offsets), len(lengths),
-                                                                 ptr(members), ptr(prefix), len(members), ptr(lengths)))
+        _check(self._owner._h, self._lib.po_result_merged_paths(self._ptr, ctypes.byref(k), ctypes.byref(m), _ptr(offsets), len(lengths),
+                                                                 _ptr(members), _ptr(prefix), len(members), _ptr(lengths)))
         return offsets, members, prefix, lengths
 
     def copy_to_device(self, dst_ptr: int, count: Optional[int] = None) -> None:
@@ -496,23 +500,25 @@ class ExactOverlapper:
     def coverage_stats(self) -> dict:
         return self._stats(self._lib.po_get_coverage_stats, PoCoverageStats)
 
+    def _graph_stage(self, fn, graph: OverlapResult, prm, n_order: Optional[int], outputs):
+        """The analysis calls on a graph result: ``fn(handle, graph, params, *outputs, &count)``.  ``outputs`` lists
+        (dtype, "node" | "edge") per array -- one entry per node of the order or per edge --, the last one the table, which
+        is cut to the ``count`` entries the call filled."""
+        if n_order is None:
+            n_order = len(graph.node_order())
+        arrays = [np.zeros(int(n_order) if per == "node" else len(graph), dtype=dt) for dt, per in outputs]
+        n = ctypes.c_uint64()
+        _check(self._h, fn(self._h, graph._ptr, ctypes.byref(prm), *[_ptr(a) for a in arrays], ctypes.byref(n)))
+        return (*arrays[:-1], arrays[-1][:int(n.value)].copy())
+
     def layout_components(self, graph: OverlapResult, n_order: Optional[int] = None):
         """``po_layout_components``: the weakly connected components of a graph result (an edge result, a merged graph or a
         ``graph_from_edges`` result), which stays valid.  Returns ``(node_component, edge_component, table)``: the
         component of every node, parallel to ``graph.node_order()`` (``n_order``: its length, if the caller has it); the
         component of every edge in the graph's edge order; one entry (``first_node``, ``n_nodes``, ``n_edges``) per
         component.  Component i is the i-th in the order of each component's lowest-ranked node."""
-        if n_order is None:
-            n_order = len(graph.node_order())
-        prm = PoComponentsParams(0)
-        nodes = np.zeros(int(n_order), dtype=np.uint32)
-        edges = np.zeros(len(graph), dtype=np.uint32)
-        table = np.zeros(int(n_order), dtype=COMPONENT_DTYPE)
-        n = ctypes.c_uint64()
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
-        _check(self._h, self._lib.po_layout_components(self._h, graph._ptr, ctypes.byref(prm), ptr(nodes), ptr(edges), ptr(table),
-                                                       ctypes.byref(n)))
-        return nodes, edges, table[:int(n.value)].copy()
+        return self._graph_stage(self._lib.po_layout_components, graph, PoComponentsParams(0), n_order,
+                                 [(np.uint32, "node"), (np.uint32, "edge"), (COMPONENT_DTYPE, "node")])
 
     def components_stats(self) -> dict:
         return self._stats(self._lib.po_get_components_stats, PoComponentsStats)
@@ -524,18 +530,8 @@ class ExactOverlapper:
         to ``graph.node_order()`` (``n_order``: its length, if the caller has it); the class byte of every edge in the
         graph's edge order; one entry (``first_node``, ``n_nodes``, ``n_edges``, ``n_r_in``, ``n_re_out``) per SCC.  SCC i
         is the i-th in the order of each SCC's lowest-ranked node."""
-        if n_order is None:
-            n_order = len(graph.node_order())
-        prm = PoPartitionParams(0)
-        nodes = np.zeros(int(n_order), dtype=np.uint32)
-        flags = np.zeros(int(n_order), dtype=np.uint8)
-        classes = np.zeros(len(graph), dtype=np.uint8)
-        table = np.zeros(int(n_order), dtype=SCC_DTYPE)
-        n = ctypes.c_uint64()
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
-        _check(self._h, self._lib.po_layout_partition(self._h, graph._ptr, ctypes.byref(prm), ptr(nodes), ptr(flags), ptr(classes),
-                                                      ptr(table), ctypes.byref(n)))
-        return nodes, flags, classes, table[:int(n.value)].copy()
+        return self._graph_stage(self._lib.po_layout_partition, graph, PoPartitionParams(0), n_order,
+                                 [(np.uint32, "node"), (np.uint8, "node"), (np.uint8, "edge"), (SCC_DTYPE, "node")])
 
     def partition_stats(self) -> dict:
         return self._stats(self._lib.po_get_partition_stats, PoPartitionStats)
@@ -556,8 +552,7 @@ class ExactOverlapper:
             raise ValueError("a node of the node order does not fit 32 bits")
         order = order.astype(np.uint32)
         r = ctypes.c_void_p()
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
-        _check(self._h, self._lib.po_graph_from_edges(self._h, ptr(edges), len(edges), ptr(order), len(order), ctypes.byref(r)))
+        _check(self._h, self._lib.po_graph_from_edges(self._h, _ptr(edges), len(edges), _ptr(order), len(order), ctypes.byref(r)))
         return OverlapResult(self, r, EDGE_DTYPE)
 
     def node_order_stats(self) -> dict:

@@ -123,6 +123,53 @@ def test_three_calls_and_a_fresh_handle_give_identical_bytes(tmp_path):
     assert all(s == seen[0] for s in seen)
 
 
+TURN_NAMES = ("direct_three_cycle_with_tails", "direct_ring_1025_scrambled", "direct_random_200_300_seed1")   # small, large, small
+
+
+def test_components_and_partition_take_turns_in_the_rank_workspaces_of_one_handle():
+    """Both calls rank the graph in the same buffers of the handle: on one handle they alternate, twice each, on a few
+    nodes, then 1 025, then 200, so every call finds what a call of the other stage -- and, behind the large graph, of a
+    larger graph -- left there.  Every call's arrays are the restatements', and its bytes those of the same call on a
+    handle that has run nothing else."""
+    inputs = [stage_inputs(next(c for c in DIRECT if c["name"] == name))["a"] for name in TURN_NAMES]
+    n_ids = max(i[2] for i in inputs)
+    assert [len(i[1]) for i in inputs] == [5, 1025, 200]
+
+    def graph(ov, uv, order):
+        return ov.graph_from_edges(np.concatenate([uv, np.full((len(uv), 1), 100), np.full((len(uv), 1), 17)], axis=1).astype(np.int64), order)
+
+    def components(ov, g):
+        nodes, edges, table = ov.layout_components(g)
+        return {"node_component": nodes, "edge_component": edges, **{k: table[k] for k in table.dtype.names}}
+
+    def partition(ov, g):
+        nodes, flags, classes, table = ov.layout_partition(g)
+        return {"node_scc": nodes, "node_flags": flags, "edge_class": classes, **{k: table[k] for k in table.dtype.names}}
+
+    def fresh(call, uv, order):
+        ov = segments(n_ids)
+        g = graph(ov, uv, order)
+        out = call(ov, g)
+        g.free()
+        ov.close()
+        return out
+
+    ov = segments(n_ids)
+    for uv, order, _ in inputs:
+        g = graph(ov, uv, order)
+        e = edge_array(g.rows())
+        want = {components: cu.weak_components(e[:, :2], list(order)), partition: pu.partition(e, list(order))}
+        alone = {call: fresh(call, uv, order) for call in (components, partition)}
+        for call in (components, partition, components, partition):
+            got = call(ov, g)
+            assert set(got) == set(alone[call]) and len(got) >= 5
+            for k, a in got.items():
+                assert a.tolist() == np.asarray(want[call][k]).tolist(), (call.__name__, k)
+                assert a.dtype == alone[call][k].dtype and a.tobytes() == alone[call][k].tobytes(), (call.__name__, k)
+        g.free()
+    ov.close()
+
+
 def expected_lines(parts):
     return ["Partition with %d nodes with in-degree 0, %d nodes with out-degree 0, acyclic: %s" % (p["num_sources"], p["num_sinks"], p["acyclic"])
             for p in parts]

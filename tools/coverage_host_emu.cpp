@@ -6,33 +6,13 @@
 //   stdin:  n_ids n_paths n_members n_edges n_rows; n_ids lengths; n_paths offsets; n_paths merged lengths; the members;
 //           one "u v weight" line per edge; one "a b" line per row
 //   stdout: "invalid N" alone, or the counters nodes, pairs, largest set, zero paths; then one "sum path" line per edge
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-#define __global__
-#define __device__
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(x)
-struct D3 { uint32_t x; };
-static D3 threadIdx, blockIdx, blockDim, gridDim;
-static inline void __syncthreads() {}
-template <class T, class V> T atomicAdd(T* p, V v) { T o = *p; *p = (T)(*p + (T)v); return o; }
-template <class T> T atomicMax(T* p, T v) { T o = *p; if (v > o) *p = v; return o; }
-template <class T> T atomicCAS(T* p, T cmp, T v) { T o = *p; if (o == cmp) *p = v; return o; }
+#include "host_emu.h"
 namespace po {
-constexpr int WAVE = 1;
 struct Edge { uint32_t u, v; int32_t weight, overlap_len; };
 struct Row { uint32_t a_idx, b_idx; int32_t astart, aend, bstart, bend; };
-static inline uint32_t lane_id() { return 0; }
-static inline uint64_t wave_sum64(uint64_t v) { return v; }
-template <int N> void block_add(const uint64_t (&v)[N], unsigned long long* c) { for (int k = 0; k < N; ++k) c[k] += v[k]; }
 }
 #include "../phasm_amd/csrc/coverage.hip.h"
 using namespace po;
-#define LAUNCH(grid, block, ...) do { gridDim.x = (grid); blockDim.x = (block); for (uint32_t b_ = 0; b_ < (grid); ++b_) for (uint32_t t_ = 0; t_ < (block); ++t_) { blockIdx.x = b_; threadIdx.x = t_; __VA_ARGS__; } } while (0)
 int main() {
     uint32_t n_ids, K, n_members, n, n_rows;
     if (scanf("%u %u %u %u %u", &n_ids, &K, &n_members, &n, &n_rows) != 5) return 1;

@@ -8,40 +8,18 @@
 //   stdin:  n_nodes n_edges n_order, then one "u v" line per edge, then the nodes in node order
 //   stdout: the flag digits; the counters invalid, candidates, diamonds, nodes, removed, kept and the rounds; the nodes
 //           left, in order
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-#define __global__
-#define __device__
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(x)
-struct D3 { uint32_t x; };
-static D3 threadIdx, blockIdx, blockDim, gridDim;
-static inline void __syncthreads() {}
-template <class T, class V> T atomicAdd(T* p, V v) { T o = *p; *p = (T)(*p + (T)v); return o; }
-template <class T, class V> T atomicSub(T* p, V v) { T o = *p; *p = (T)(*p - (T)v); return o; }
-template <class T> T atomicMin(T* p, T v) { T o = *p; if (v < o) *p = v; return o; }
-template <class T> T atomicMax(T* p, T v) { T o = *p; if (v > o) *p = v; return o; }
-template <class T> T atomicCAS(T* p, T c, T v) { T o = *p; if (o == c) *p = v; return o; }
+#include "host_emu.h"
 namespace po {
-constexpr int WAVE = 1;
 struct Edge { uint32_t u, v; int32_t weight, overlap_len; };
 constexpr unsigned long long EDGE_EMPTY = ~0ull;
 static inline uint32_t edge_slot(uint32_t u, uint32_t v, uint32_t n_slots) {
     const unsigned long long k = (((unsigned long long)u << 32) | v) * 0x9E3779B97F4A7C15ull;
     return (uint32_t)(((k >> 32) * (unsigned long long)n_slots) >> 32);
 }
-static inline uint32_t lane_id() { return 0; }
-static inline uint64_t wave_sum64(uint64_t v) { return v; }
-template <int N> void block_add(const uint64_t (&v)[N], unsigned long long* c) { for (int k = 0; k < N; ++k) c[k] += v[k]; }
 }
 #include "../phasm_amd/csrc/tips.hip.h"
 #include "../phasm_amd/csrc/diamond.hip.h"
 using namespace po;
-#define LAUNCH(grid, block, ...) do { gridDim.x = (grid); blockDim.x = (block); for (uint32_t b_ = 0; b_ < (grid); ++b_) for (uint32_t t_ = 0; t_ < (block); ++t_) { blockIdx.x = b_; threadIdx.x = t_; __VA_ARGS__; } } while (0)
 int main() {
     uint32_t n_nodes, n, n_order;
     if (scanf("%u %u %u", &n_nodes, &n, &n_order) != 3) return 1;

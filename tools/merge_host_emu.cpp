@@ -10,34 +10,13 @@
 //   stdout: the flag digits (or "invalid" / "overflow N" alone); the counters invalid, nodes, heads, merged, cycle,
 //           longest, self-loops, overflow, kept and the rounds; the nodes of the result in order; offsets; members;
 //           prefixes; lengths; the kept edges as "u v w o;"
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-#define __global__
-#define __device__
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(x)
-struct D3 { uint32_t x; };
-static D3 threadIdx, blockIdx, blockDim, gridDim;
-static inline void __syncthreads() {}
-template <class T, class V> T atomicAdd(T* p, V v) { T o = *p; *p = (T)(*p + (T)v); return o; }
-template <class T> T atomicMin(T* p, T v) { T o = *p; if (v < o) *p = v; return o; }
-template <class T> T atomicMax(T* p, T v) { T o = *p; if (v > o) *p = v; return o; }
-template <class T> T __shfl_xor(T v, int, int) { return v; }
+#include "host_emu.h"
 namespace po {
-constexpr int WAVE = 1;
 struct Edge { uint32_t u, v; int32_t weight, overlap_len; };
 constexpr unsigned long long NODE_NO_RANK = ~0ull;
-static inline uint32_t lane_id() { return 0; }
-static inline uint64_t wave_sum64(uint64_t v) { return v; }
-template <int N> void block_add(const uint64_t (&v)[N], unsigned long long* c) { for (int k = 0; k < N; ++k) c[k] += v[k]; }
 }
 #include "../phasm_amd/csrc/merge.hip.h"
 using namespace po;
-#define LAUNCH(grid, block, ...) do { gridDim.x = (grid); blockDim.x = (block); for (uint32_t b_ = 0; b_ < (grid); ++b_) for (uint32_t t_ = 0; t_ < (block); ++t_) { blockIdx.x = b_; threadIdx.x = t_; __VA_ARGS__; } } while (0)
 int main() {
     uint32_t n_nodes, n, n_order;
     if (scanf("%u %u %u", &n_nodes, &n, &n_order) != 3) return 1;

@@ -3,46 +3,26 @@
 // -- the ranks (the kernels of components.hip.h, as po_layout_partition launches them), the trim rounds, the forward
 // colouring, the backward marking, the retiring, the numbering of the roots, the table, the edge classes and the node flags
 // -- against the goldens, under the host sanitizers.  The launches follow run_partition (c_api.hip): the same memsets, and
-// every bound, the batches and the stop at the first round that changes nothing come from scc_drive / scc_phase of
-// partition.hip.h, which run_partition itself launches by.  The workspaces start as a call before could have left them.
-// Every loop here and in the kernels is bounded by a count.
+// every bound, the batches and the stop at the first round that changes nothing come from scc_drive of partition.hip.h
+// and round_phase of components.hip.h, which run_partition itself launches by.  The workspaces start as a call before
+// could have left them.  Every loop here and in the kernels is bounded by a count.
 //   stdin:  n_total n_edges n_order, one "u v" line per edge, the nodes in node order (node ids < n_total; ids at or
 //           above the reads are merged nodes: the kernels do not tell them apart)
 //   stdout: "invalid N" alone, "bound K" alone, or: order, SCCs, singletons, max nodes, max edges, self-loops, the five class
 //           counts; trimmed, iterations, trim / forward / backward rounds, batches, the largest batch, the largest number of
 //           rounds one phase was given beyond its live nodes; the SCC of every rank; the flags of every rank; the class of
 //           every edge; per SCC "first_node n_nodes n_edges n_r_in n_re_out;"
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-#define __global__
-#define __device__
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(x)
-struct D3 { uint32_t x; };
-static D3 threadIdx, blockIdx, blockDim, gridDim;
-static inline void __syncthreads() {}
-template <class T, class V> T atomicAdd(T* p, V v) { T o = *p; *p = (T)(*p + (T)v); return o; }
-template <class T> T atomicMin(T* p, T v) { T o = *p; if (v < o) *p = v; return o; }
-template <class T> T atomicMax(T* p, T v) { T o = *p; if (v > o) *p = v; return o; }
-template <class T> T atomicOr(T* p, T v) { T o = *p; *p = o | v; return o; }
-template <class T> T __shfl_xor(T v, int, int) { return v; }
+#include "host_emu.h"
 namespace po {
-constexpr int WAVE = 1;
 struct Edge { uint32_t u, v; int32_t weight, overlap_len; };
 constexpr unsigned long long NODE_NO_RANK = ~0ull;
-static inline uint32_t lane_id() { return 0; }
-static inline uint64_t wave_sum64(uint64_t v) { return v; }
-template <int N> void block_add(const uint64_t (&v)[N], unsigned long long* c) { for (int k = 0; k < N; ++k) c[k] += v[k]; }
 }
 #include "../phasm_amd/csrc/merge.hip.h"
 #include "../phasm_amd/csrc/components.hip.h"
 #include "../phasm_amd/csrc/partition.hip.h"
 using namespace po;
-#define LAUNCH(grid, block, ...) do { gridDim.x = (grid); blockDim.x = (block); for (uint32_t b_ = 0; b_ < (grid); ++b_) for (uint32_t t_ = 0; t_ < (block); ++t_) { blockIdx.x = b_; threadIdx.x = t_; __VA_ARGS__; } } while (0)
+
+#include "rank_host_emu.h"
 
 struct EmuOps {
     uint32_t n, n_order;
@@ -118,28 +98,16 @@ struct EmuOps {
 };
 
 int main() {
-    uint32_t n_total, n, n_order_in;
-    if (scanf("%u %u %u", &n_total, &n, &n_order_in) != 3) return 1;
-    std::vector<Edge> e(n + 1);
-    for (uint32_t i = 0; i < n; ++i) { if (scanf("%u %u", &e[i].u, &e[i].v) != 2) return 1; e[i].weight = 100; e[i].overlap_len = 17; }
-    std::vector<unsigned long long> nrank(n_total + 1, NODE_NO_RANK);
-    for (uint32_t i = 0; i < n_order_in; ++i) { uint32_t x; if (scanf("%u", &x) != 1 || x >= n_total) return 1; nrank[x] = ((unsigned long long)(3u * i + 5) << 2) | (i & 3); }
-    const uint32_t pad = merge_sort_pad(n_total);
-    const uint32_t nn = n_total + 2;
-    std::vector<unsigned long long> key(pad, 7);
-    std::vector<uint32_t> val(pad, 0xDEADu), rank_of(nn, 0xFFFFFFFFu), scc(nn, 0xDEADu), colour(nn, 0xDEADu), index(nn, 0xDEADu), node_scc(nn, 0xDEADu),
-        flagw(nn, 0xDEADu);
-    std::vector<uint8_t> live(nn, 9), mark(nn, 9), has_in(nn, 9), has_out(nn, 9), root(nn, 9), flags(nn, 9), eclass(n + 1, 9);
-    std::vector<EdgeRanks> ends(n + 1, EdgeRanks{0xDEADu, 0xDEADu});
+    RankedInput g;
+    std::vector<uint32_t> colour;
+    const int status = ranked_input(g, colour);
+    if (status >= 0) return status;
+    const uint32_t n = g.n, n_order = g.n_order, nn = g.nn;
+    const std::vector<EdgeRanks>& ends = g.ends;
+    std::vector<uint32_t> scc(nn, 0xDEADu), node_scc(nn, 0xDEADu), flagw(nn, 0xDEADu);
+    std::vector<uint8_t> live(nn, 9), mark(nn, 9), has_in(nn, 9), has_out(nn, 9), flags(nn, 9), eclass(n + 1, 9);
     std::vector<Scc> table(nn, Scc{0xDEADu, 0xDEADu, 0xDEADull, 0xDEADu, 0xDEADu});
-    unsigned long long cnt[16] = {};
-    LAUNCH((pad + 3) / 4, 4, k_cc_keys(nrank.data(), n_total, pad, key.data(), val.data()));
-    merge_sort_steps(n_total, [&](uint32_t j, uint32_t k) { LAUNCH((pad + 3) / 4, 4, k_merge_bitonic(key.data(), val.data(), pad, j, k)); });
-    LAUNCH((pad + 3) / 4, 4, k_cc_init(key.data(), val.data(), pad, n_total, colour.data(), rank_of.data(), cnt));
-    if (n) LAUNCH(3, 4, k_cc_ends(e.data(), n, n_total, rank_of.data(), ends.data(), cnt));
-    if (cnt[PC_INVALID]) { printf("invalid %llu\n", cnt[PC_INVALID]); return 0; }
-    if (cnt[PC_ORDER] != n_order_in) { printf("order\n"); return 0; }
-    const uint32_t n_order = (uint32_t)cnt[PC_ORDER];
+    unsigned long long* cnt = g.cnt;
     SccWork W;
     EmuOps ops{n, n_order, ends.data(), live.data(), mark.data(), has_in.data(), has_out.data(), scc.data(), colour.data(), {}, {}};
     if (n_order) {
@@ -148,13 +116,12 @@ int main() {
         if (how != SCC_DONE) { printf("bound %d\n", how); return 0; }
         ops.phase_end();
         for (uint32_t r = 0; r < n_order; ++r) if (live[r] || scc[r] > r) { printf("live\n"); return 0; }
-        LAUNCH(3, 4, k_scc_roots(scc.data(), n_order, root.data(), flagw.data()));
+        LAUNCH(3, 4, k_scc_roots(scc.data(), n_order, g.root.data(), flagw.data()));
     }
-    uint32_t n_scc = 0;
-    for (uint32_t r = 0; r < n_order; ++r) { index[r] = n_scc; n_scc += root[r]; }   // (prefix_sum of the library)
+    const uint32_t n_scc = number_roots(g);
     if (n_scc) {
         std::memset(table.data(), 0, (size_t)n_scc * sizeof(Scc));
-        LAUNCH(3, 4, k_scc_label_nodes(scc.data(), index.data(), val.data(), n_order, n_scc, node_scc.data(), table.data()));
+        LAUNCH(3, 4, k_scc_label_nodes(scc.data(), g.index.data(), g.val.data(), n_order, n_scc, node_scc.data(), table.data()));
         if (n) LAUNCH(3, 4, k_scc_edges(ends.data(), n, n_order, n_scc, node_scc.data(), table.data(), eclass.data(), flagw.data(), cnt));
         LAUNCH(3, 4, k_scc_flags(n_order, n_scc, node_scc.data(), flagw.data(), table.data(), flags.data()));
         LAUNCH(3, 4, k_scc_max(table.data(), n_scc, cnt));

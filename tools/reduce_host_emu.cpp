@@ -3,33 +3,12 @@
 // their indexing and logic -- CSR order, both state placements of k_reduce_mark, the symmetry look-up -- against the
 // goldens, under the host sanitizers.  What it cannot see: anything that needs lanes to run side by side.
 //   stdin:  n_nodes fuzz n_edges, then one "u v weight rank" line per edge;  stdout: the flag digits, then the counters
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-#define __global__
-#define __device__
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(x)
-struct D3 { uint32_t x; };
-static D3 threadIdx, blockIdx, blockDim, gridDim;
-static inline void __syncthreads() {}
-template <class T> T atomicAdd(T* p, T v) { T o = *p; *p += v; return o; }
-template <class T> T atomicMax(T* p, T v) { T o = *p; if (v > o) *p = v; return o; }
-static inline int __shfl_xor(int v, int) { return v; }
-using std::max;
+#include "host_emu.h"
 namespace po {
-constexpr int WAVE = 1;
 struct Edge { uint32_t u, v; int32_t weight, overlap_len; };
-static inline uint32_t lane_id() { return 0; }
-static inline uint64_t wave_sum64(uint64_t v) { return v; }
-template <int N> void block_add(const uint64_t (&v)[N], unsigned long long* c) { for (int k = 0; k < N; ++k) c[k] += v[k]; }
 }
 #include "../phasm_amd/csrc/reduce.hip.h"
 using namespace po;
-#define LAUNCH(grid, block, ...) do { gridDim.x = (grid); blockDim.x = (block); for (uint32_t b_ = 0; b_ < (grid); ++b_) for (uint32_t t_ = 0; t_ < (block); ++t_) { blockIdx.x = b_; threadIdx.x = t_; __VA_ARGS__; } } while (0)
 int main(int argc, char** argv) {
     // input: n_nodes fuzz n ; then n lines u v w rank ; output flags
     uint32_t n_nodes, n; int fuzz;
