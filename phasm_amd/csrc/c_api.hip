@@ -281,9 +281,6 @@ struct po_handle {
     HostBuf scratch_host;  // pinned landing zone for small device->host copies into caller memory
     // pinned result pool sized while the reads are added (result_pool_grow): bytes of total_bases it was sized for
     uint64_t pool_bases = 0;
-    // streamed step: per-piece workspaces are sized for the LARGEST piece when the first one asks (ws_scale > 1), so
-    // that no later piece has to free and re-allocate (hipFree synchronises the device)
-    double ws_scale = 1.0;
     // small device workspaces (<= 8 MB each, some forty of them) are carved out of 64 MB chunks instead of being
     // allocated one by one: on a process whose allocator has handed memory back, every small hipMalloc is a trip to
     // the kernel driver (0.2 ms each, 4 ms per first call of a handle)
@@ -291,7 +288,6 @@ struct po_handle {
     char* arena_cur = nullptr;
     size_t arena_left = 0;
     int poison = -1;       // PHASM_POISON=<byte>: per-call workspaces are filled with it before every call
-    // po_overlaps_ex: the verify step is the banded DP of extend.hip.h (set around the call by po_overlaps_ex)
     // po_overlaps_to_host: a second stream copies chunk k's rows to the host while chunk k + 1 is computed
     hipStream_t copy_stream = nullptr;
     DevBuf chunk_rows[PO_MAX_PIECES + 1];
@@ -363,14 +359,10 @@ struct po_handle {
     uint64_t st_pred_cand[PO_MAX_PIECES] = {};
     std::vector<uint32_t> st_pred_sig;
     bool st_pred_valid = false;
-    bool phase_events = true;   // this call records the stage-boundary events (phase_events_env)
-    bool pair_events = true;    // ... at least the pairs around the two big kernels and the call's start / end
     bool st_selfclean = false;     // the previous piece of this streamed step left the per-call counters zero (no reset launch needed)
     bool st_early_index = false;   // this streamed step builds its index before piece 0 has landed
     bool st_tail_gave_up = false;  // the last streamed step was abandoned because of tandem-repeat reads (statistics / tests)
-    bool idx_only = false;         // run_overlaps stops behind the index build (the streamed step builds it ahead of piece 0)
-    bool st_on = false;            // run_overlaps works on piece [st_r_begin, st_r_end) of a streamed step
-    uint32_t st_r_begin = 0, st_r_end = 0, st_defer_cap = 0;
+    uint32_t st_defer_cap = 0;
     uint64_t last_host_rows = 0;   // rows of the previous po_overlaps_to_host call (sizes the pinned buffer up front)
     // the anchor index of the last call, reusable while the device copy of the reads and the parameters it was built
     // for are unchanged (the chunks of po_overlaps_to_host, the shards of a multi-GPU step, repeated calls)
@@ -379,20 +371,15 @@ struct po_handle {
     uint64_t idx_gen = 0;
     uint32_t idx_m = 0, idx_tbits = 0, idx_bits = 0, idx_ww = 0;
     bool idx_wide = false;
-    // sliced wide index (multi-GPU, phasm_amd/dist.py IndexExchange): sl_build_n > 1 makes run_overlaps stop after it has
-    // built sub-table sl_build_slice; ext_index makes it probe a gathered sliced index instead of building one
-    uint32_t sl_build_slice = 0, sl_build_n = 0;
+    // sliced wide index (multi-GPU, phasm_amd/dist.py IndexExchange): what the last slice build (OverlapArgs::build_n > 1)
+    // left in the workspaces for po_index_slice_export
     bool sl_is_wide = false;
     uint32_t sl_tbits = 0;
     uint64_t sl_entries = 0;
-    const void* ext_index = nullptr;
-    uint32_t ext_slices = 0, ext_tbits = 0, ext_chunk_slots = 0, ext_chain_off = 0;
     // sharded upload (multi-GPU): store 0 arrives as nshards pieces that other ranks uploaded and xGMI carried here
     const uint64_t* asm_pieces = nullptr;
     uint64_t asm_slot_words = 0;
     uint32_t asm_n = 0, asm_parts = 1;
-    bool ex_on = false;
-    uint32_t ex_E = 0, ex_W = 0;
     DevBuf d_end_a, d_end_b, d_dpcnt;
     int live_results = 0;
 
@@ -501,14 +488,35 @@ struct AllocTrace {
     }
 };
 
-po_status ensure(po_handle* h, DevBuf& b, size_t bytes, double scale = 1.0, bool arena_ok = true) {
+// What a caller wants from run_overlaps.  Every call mode travels here and nowhere else: run_overlaps can see what it was
+// called with, and nothing a call was asked for is left on the handle for the next one.
+struct OverlapArgs {
+    uint32_t min_length = 0, shard = 0, nshards = 1;
+    bool want_cands = false;   // the multi-GPU form: verified candidates (one per strand-mirror pair) instead of rows
+    // a piece of a streamed step: reads [r_begin, r_end), `shard` is the piece's number.  idx_only: stop behind the index
+    // build (the step builds it ahead of piece 0).  ws_scale > 1: per-piece workspaces are sized for the step's LARGEST
+    // piece when the first one asks, so that no later piece has to free and re-allocate (hipFree synchronises the device)
+    bool streamed = false, idx_only = false;
+    uint32_t r_begin = 0, r_end = 0;
+    double ws_scale = 1.0;
+    // sliced wide index (multi-GPU, phasm_amd/dist.py IndexExchange): build_n > 1 builds sub-table build_slice and stops;
+    // ext_index probes a gathered sliced index (its geometry in the four words behind it) instead of building one
+    uint32_t build_slice = 0, build_n = 0;
+    const void* ext_index = nullptr;
+    uint32_t ext_slices = 0, ext_tbits = 0, ext_chunk_slots = 0, ext_chain_off = 0;
+    // po_overlaps_ex: the verify step is the banded DP of extend.hip.h, at most dp_E differences in a band of dp_W
+    bool dp = false;
+    uint32_t dp_E = 0, dp_W = 0;
+};
+
+po_status ensure(po_handle* h, DevBuf& b, size_t bytes, double scale = 1.0, bool arena_ok = true, bool streamed = false) {
     if (bytes <= b.cap) return PO_OK;
     AllocTrace tr("hipMalloc", bytes);
     const bool first = b.p == nullptr;
     b.release();
     size_t want = bytes + bytes / 8 + 256;
     if (scale > 1.0) want = (size_t)((double)bytes * scale) + 256;   // (a streamed piece: room for the largest piece)
-    if (h && h->st_on) want += 8192;   // (... and for the next call's predicted count plus its slack, small inputs included)
+    if (streamed) want += 8192;   // (... and for the next call's predicted count plus its slack, small inputs included)
     constexpr size_t ARENA_CHUNK = 64u << 20, ARENA_MAX = 8u << 20;
     // (arena_ok = false: buffers that leave the handle with a result -- rows, candidates, edges -- are freed or kept as
     // spares one by one; carved out of a chunk they would stay behind until the handle dies)
@@ -549,7 +557,7 @@ po_status ensure(po_handle* h, DevBuf& b, size_t bytes, double scale = 1.0, bool
 }
 
 // a workspace whose size follows the candidate count of the a-side range at hand
-po_status ensure_piece(po_handle* h, DevBuf& b, size_t bytes) { return ensure(h, b, bytes, h->ws_scale); }
+po_status ensure_piece(po_handle* h, DevBuf& b, size_t bytes, const OverlapArgs& a) { return ensure(h, b, bytes, a.ws_scale, true, a.streamed); }
 
 po_status ensure_host(po_handle* h, HostBuf& b, size_t bytes) {
     if (bytes <= b.cap) return PO_OK;
@@ -1624,10 +1632,10 @@ void shard_range(const po_handle* h, uint32_t shard, uint32_t nshards, uint32_t*
 // exclusive scan of n items (u8 or u32) -> u32 offsets; *total_host gets the grand total
 // (a pinned slot: valid after the next hipStreamSynchronize)
 // the state of the single-pass scans (kernels.hip.h, ChainState): zero when allocated, left zero by every launch
-po_status chain_state(po_handle* h, uint32_t n_tiles, po::ChainState** out, hipStream_t on) {
+po_status chain_state(po_handle* h, uint32_t n_tiles, po::ChainState** out, hipStream_t on, bool streamed = false) {
     const size_t need = po::chain_state_bytes(n_tiles);
     if (need > h->d_chain_state.cap) {
-        PO_TRY(ensure(h, h->d_chain_state, std::max<size_t>(need * 2, 1u << 16)));
+        PO_TRY(ensure(h, h->d_chain_state, std::max<size_t>(need * 2, 1u << 16), 1.0, true, streamed));
         HIP_TRY(h, hipMemsetAsync(h->d_chain_state.p, 0, h->d_chain_state.cap, on));
     }
     *out = h->d_chain_state.as<po::ChainState>();
@@ -1637,7 +1645,7 @@ po_status chain_state(po_handle* h, uint32_t n_tiles, po::ChainState** out, hipS
 template <typename T>
 po_status prefix_sum(po_handle* h, const T* in, uint64_t n, uint32_t* out, volatile uint64_t* total_host,
                      const uint64_t* also_src = nullptr, volatile uint64_t* also_host = nullptr, const uint32_t* extra = nullptr,
-                     hipStream_t on = nullptr, uint64_t* total_dev_at = nullptr) {
+                     hipStream_t on = nullptr, uint64_t* total_dev_at = nullptr, const OverlapArgs& a = OverlapArgs()) {
     *total_host = 0;
     if (n == 0) return PO_OK;
     const hipStream_t ps = on ? on : h->stream;
@@ -1651,7 +1659,7 @@ po_status prefix_sum(po_handle* h, const T* in, uint64_t n, uint32_t* out, volat
         // XCDs are slower than three launches
 
         po::ChainState* cs = nullptr;
-        PO_TRY(chain_state(h, nblocks, &cs, ps));
+        PO_TRY(chain_state(h, nblocks, &cs, ps, a.streamed));
         hipLaunchKernelGGL(po::k_ps_chain<T>, dim3(nblocks), dim3(po::PS_BLOCK), 0, ps, const_cast<T*>(in), extra, n, out, cs,
                            nblocks, total_dev, total_mapped, also_src, also_mapped);
         HIP_TRY(h, hipGetLastError());
@@ -1661,7 +1669,7 @@ po_status prefix_sum(po_handle* h, const T* in, uint64_t n, uint32_t* out, volat
         hipLaunchKernelGGL(po::k_add_extra, dim3(cdiv(n, 256)), dim3(256), 0, ps, const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(in)),
                            extra, 0u, (uint32_t)n);
     }
-    PO_TRY(ensure_piece(h, h->d_ps_blocks, (size_t)nblocks * 8));
+    PO_TRY(ensure_piece(h, h->d_ps_blocks, (size_t)nblocks * 8, a));
     uint64_t* blocks = h->d_ps_blocks.as<uint64_t>();
     hipLaunchKernelGGL(po::k_ps_reduce<T>, dim3(nblocks), dim3(po::PS_BLOCK), 0, ps, in, n, blocks);
     hipLaunchKernelGGL(po::k_ps_spine, dim3(1), dim3(1024), 0, ps, blocks, nblocks, total_dev, total_mapped, also_src, also_mapped);
@@ -1712,665 +1720,783 @@ void stage_times(po_stats& S, hipEvent_t* ev, bool ver_timed, bool full, bool pa
     if (ver_timed) (void)hipEventElapsedTime(&S.ms_verify_kernel, ev[EV_VER0], ev[EV_VER1]);
 }
 
+// The closing numbers of a call, or of a pending piece of a streamed step, once the stream behind them has been
+// synchronised: the row count (pinned[rows_at]; rows_at < 0: there were no candidates, nothing was written there) and the
+// four emit counters (pinned[cnt_at ..]), then the stage times.  Returns the row count.
+uint64_t close_stats(po_handle* h, po_stats& S, int rows_at, int cnt_at, hipEvent_t* ev, bool ver_timed, bool full, bool pairs) {
+    const uint64_t n_rows = rows_at < 0 ? 0 : h->pinned[rows_at];
+    S.n_rows = n_rows;
+    S.n_verified = h->pinned[cnt_at];
+    S.sum_overlap_bases = h->pinned[cnt_at + 1];
+    S.verify_bytes_algo = h->pinned[cnt_at + 2];
+    S.verify_bytes_exec = h->pinned[cnt_at + 3];
+    stage_times(S, ev, ver_timed, full, pairs);
+    return n_rows;
+}
+
 // the closing part of run_overlaps for a pending piece of a streamed step; the handle's stream has been synchronised
 // since the piece was queued.  Returns the piece's row count.
 // *needs_classic: k_tail found reads handed to the global (a, b) table and wrote nothing (the piece's workspaces have
 // been reused by now: the streamed step gives up and the call takes the chunked form).
 uint64_t finish_piece(po_handle* h, bool* needs_classic) {
     po_handle::Pending& P = h->st_pend;
-    const int o = P.tail ? P.zone : 2, c = P.tail ? P.zone + 1 : 4;
     *needs_classic = P.tail && h->pinned[P.zone + 7] != 0;
     if (P.cap_c) {   // the count that was predicted: more than the buffers held -> nothing was computed
         P.S.n_candidates = h->pinned[P.zone + 8];
         if (P.S.n_candidates > P.cap_c) *needs_classic = true;
     }
-    const uint64_t n_rows = h->pinned[o];
-    P.S.n_rows = n_rows;
-    P.S.n_verified = h->pinned[c];
-    P.S.sum_overlap_bases = h->pinned[c + 1];
-    P.S.verify_bytes_algo = h->pinned[c + 2];
-    P.S.verify_bytes_exec = h->pinned[c + 3];
-    stage_times(P.S, P.ev, P.ver_timed, P.full_events, P.pair_events);
     P.valid = false;
-    return n_rows;
+    return close_stats(h, P.S, P.tail ? P.zone : 2, P.tail ? P.zone + 1 : 4, P.ev, P.ver_timed, P.full_events, P.pair_events);
 }
 
-template <int BITS>
-po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32_t nshards, bool want_cands,
-                       po_result* res) {
-    constexpr uint32_t W = 64 / BITS;
-    const uint32_t n = (uint32_t)h->len.size();
-    const uint32_t m = min_length ? min_length : 1;  // a suffix array has no empty suffix
-    const uint32_t K = m < W ? m : W;
-    const uint64_t kmask = K * BITS >= 64 ? ~0ull : ((1ull << (K * BITS)) - 1ull);
-    hipStream_t st = h->stream;
-    po_stats& S = h->stats;
-    const float keep_upload = S.ms_upload;
-    S = po_stats();
-    S.ms_upload = keep_upload;
-    S.upload_bytes = h->upload_bytes;
-    S.bits_per_base = BITS;
-    S.kmer = K;
-    S.n_reads = n;
-    S.total_bases = h->total_bases;
-    // strand-mirror mode + the read order that picks the canonical member of a mirror pair (keep_bits):
-    // 1 = index order (whole-set calls), 2 = scrambled block order (sharded calls, balances verify work)
-    const bool dp = h->ex_on;
-    const uint32_t dpE = dp ? h->ex_E : 0u, dpW = dp && h->ex_E ? h->ex_W : 0u;
-    // (inexact extension: every candidate is extended itself, no strand-mirror shortcut)
-    // 3 = reversed index order, a piece of a streamed step (kernels.hip.h, mirror_rank): the scan keeps containment
-    // candidates of any b, the verify kernel only those whose b has arrived (b < st_r_end)
-    const bool streamed = h->st_on;
-    const uint32_t paired = (BITS == 2 && h->paired && dpE == 0) ? (streamed ? po::PAIRED_STREAM_ALL : nshards > 1 ? 2u : 1u) : 0u;
-    const uint32_t paired_ver = streamed ? po::paired_stream(h->st_r_end) : paired;
-    if (streamed && (!paired || want_cands)) return fail(h, PO_ERR_INVALID, "streamed step without strand pairs");
-    S.paired = paired ? 1u : 0u;
-    S.max_diff = dpE;
-    S.band = dpW;
-    if (dp && dpE && want_cands) return fail(h, PO_ERR_INVALID, "the candidate (multi-GPU) form has no inexact mode");
-    if (dp && dpE && BITS == 2 && !h->exc_pos.empty())
-        return fail(h, PO_ERR_INVALID, "po_overlaps_ex with max_diff > 0 needs pure upper-case ACGT reads (or the 8-bit representation)");
+// The PHASM_* switches of run_overlaps, read once per call: plan() and index_flavour() decide from them before anything is
+// launched, the stages see what was decided.
+struct OverlapSwitches {
+    const char* index = getenv("PHASM_INDEX");                  // wide | narrow
+    const char* wide_window = getenv("PHASM_WIDE_WINDOW");      // 1 | 4 | 16: a smaller window than min_length allows (tests, A/B)
+    const char* table_mult = getenv("PHASM_TABLE_MULT");
+    const char* scan_waves = getenv("PHASM_SCAN_WAVES");
+    const char* pred_scale = getenv("PHASM_PRED_SCALE");        // (tests: a prediction that is too small)
+    const char* verify_order = getenv("PHASM_VERIFY_ORDER");
+    const char* verify_staged = getenv("PHASM_VERIFY_STAGED");  // 0: candidate records not staged in LDS
+    const char* dp_kernel = getenv("PHASM_DP_KERNEL");          // bits | lanes | wave
+    const char* dp_kernel_soft = getenv("PHASM_DP_KERNEL_SOFT");  // (tests: "lanes" where a lane mapping applies at all, no error elsewhere)
+    const char* dp_sort = getenv("PHASM_DP_SORT");              // (tests force it on small inputs)
+    const bool no_index_reuse = getenv("PHASM_NO_INDEX_REUSE") != nullptr;
+    const bool debug_left = getenv("PHASM_DEBUG_LEFT") != nullptr;   // how many positions did the scan waves defer to k_scan_fixup?
+    const bool piece_reset = getenv("PHASM_PIECE_RESET") != nullptr;
+    const bool sync_count = getenv("PHASM_SYNC_COUNT") != nullptr;
+    const bool tail_classic = getenv("PHASM_TAIL_CLASSIC") != nullptr;
+    const bool select_kernel = getenv("PHASM_SELECT_KERNEL") != nullptr;   // the separate k_select_local launch (tests compare)
+    const bool compact_sync = getenv("PHASM_COMPACT_SYNC") != nullptr;
+    const int phase_events = phase_events_env();
+};
 
-    uint32_t r_begin = 0, r_end = n;
-    S.shard_bases = h->total_bases;
-    if (streamed) {
-        r_begin = h->st_r_begin;
-        r_end = h->st_r_end;
-        S.shard_bases = 0;
-        for (uint32_t r = r_begin; r < r_end; ++r) S.shard_bases += h->len[r];
-    } else if (nshards > 1) {
-        shard_range(h, shard, nshards, &r_begin, &r_end, &S.shard_bases);
+// ---- index flavour.  narrow: prefix K-mer per read + LDS filter + every position probed (best up
+// to ~150 k reads: the filter needs ~10 bits per read in 128 KB of LDS).  wide: W K-mers per read,
+// only word-aligned K-mers of a probed, no filter (linear in the input; needs min_length >= 2W-1).
+// ww: window of the wide index's minimiser scheme (kernels.hip.h WideEnc) -- the largest of 16 / 4 / 1 words with
+// W ww + W - 1 <= min_length.  A streamed step's index is built from the `lead` words of every read that travel ahead of
+// the pieces: two, or five (LEAD_WORDS, windows of 4).  overlaps_streamed asks with lead = LEAD_WORDS to learn whether five
+// are worth sending, run_overlaps with what was sent.
+struct IndexFlavour {
+    bool wide;
+    uint32_t ww;
+};
+IndexFlavour index_flavour(po_handle* h, uint32_t m, bool streamed, uint32_t lead, const OverlapSwitches& sw) {
+    const uint32_t W = 64 / h->bits;
+    bool wide = count_eligible(h, m) > 160000 && m >= 2 * W - 1;
+    if (sw.index) {
+        if (!strcmp(sw.index, "wide")) wide = m >= 2 * W - 1;
+        if (!strcmp(sw.index, "narrow")) wide = false;
     }
-    const uint32_t tile_begin = h->h_read_tile0[r_begin], tile_end = h->h_read_tile0[r_end];
-    const uint32_t ntiles = tile_end - tile_begin;
-    S.n_tiles = ntiles;
-
-    const uint64_t n_elig = count_eligible(h, m);
-    S.n_eligible = n_elig;
-    res->count = 0;
-    if (n == 0 || n_elig == 0 || ntiles == 0) return PO_OK;
-
-    // ---- index flavour.  narrow: prefix K-mer per read + LDS filter + every position probed (best up
-    // to ~150 k reads: the filter needs ~10 bits per read in 128 KB of LDS).  wide: W K-mers per read,
-    // only word-aligned K-mers of a probed, no filter (linear in the input; needs min_length >= 2W-1).
-    bool wide = n_elig > 160000 && m >= 2 * W - 1;
-    if (const char* e = getenv("PHASM_INDEX")) {
-        if (!strcmp(e, "wide")) wide = m >= 2 * W - 1;
-        if (!strcmp(e, "narrow")) wide = false;
-    }
-    S.wide_index = wide ? 1u : 0u;
-    // wide index: window of the minimiser scheme (kernels.hip.h WideEnc) -- the largest of 16 / 4 / 1 words with
-    // W ww + W - 1 <= min_length.  The streamed step keeps 1: its index is built from the first two words of every read,
-    // which travel ahead of the pieces.  PHASM_WIDE_WINDOW=1|4|16 forces a smaller one (tests, A/B).
     uint32_t ww = 1;
-    if (wide && BITS == 2) {
+    if (wide && h->bits == 2) {
         ww = m >= W * 16 + W - 1 ? 16u : m >= W * 4 + W - 1 ? 4u : 1u;
-        // (a streamed step's index is built from the words that travel ahead of the pieces: two per read, or five)
-        if (streamed) ww = (ww >= 4 && h->st_lead >= LEAD_WORDS) ? 4u : 1u;
-        if (const char* e = getenv("PHASM_WIDE_WINDOW")) {
-            const uint32_t v = (uint32_t)atoi(e);
+        if (streamed) ww = (ww >= 4 && lead >= LEAD_WORDS) ? 4u : 1u;
+        if (sw.wide_window) {
+            const uint32_t v = (uint32_t)atoi(sw.wide_window);
             if ((v == 1 || v == 4 || v == 16) && v <= ww) ww = v;
         }
     }
-    bool WA_ext = false;
-    const bool slice_build = h->sl_build_n > 1;     // build one sub-table of the sliced wide index, then stop
-    const bool ext_idx = h->ext_index != nullptr;   // probe a gathered sliced index
-    if (slice_build) {
-        h->sl_is_wide = wide;
-        if (!wide) return PO_OK;                    // (the narrow index is 0.06 ms: every rank builds its own)
+    return {wide, ww};
+}
+
+// the row buffer of a result: the one kept from an earlier call where it is large enough (rows_late: it holds worst_rows,
+// the rows are written before their number has reached the host), else a new one for n_rows -- with room for the worst
+// case up to 2 GiB, so that the next call of this size need not ask
+po_status take_row_buffer(po_handle* h, po_result* res, bool rows_late, uint64_t n_rows, uint64_t worst_rows, bool streamed = false) {
+    if (rows_late || (h->spare_rows.cap >= n_rows * sizeof(po_row) && h->spare_rows.p)) {
+        res->d_rows = h->spare_rows;
+        h->spare_rows = DevBuf();
+    } else {
+        h->spare_rows.release();
     }
-    if (ext_idx && !wide) return fail(h, PO_ERR_INVALID, "a sliced index was supplied, but this call uses the narrow index");
-    bool rows_late = false;  // rows emitted into a kept buffer before their number reached the host
+    if (rows_late) return PO_OK;
+    const size_t exact = n_rows * sizeof(po_row);
+    size_t roomy = worst_rows * sizeof(po_row) <= (2ull << 30) ? (size_t)(worst_rows * sizeof(po_row)) : 0;
+    if (roomy && streamed) roomy += 4096 * sizeof(po_row);   // (room for the next call's predicted count and its slack)
+    return ensure(h, res->d_rows, std::max<size_t>(std::max(exact, roomy), 256), 1.0, false, streamed);
+}
+
+// One run_overlaps call: what plan() decided, the workspaces, and what each stage leaves for the stages behind it.
+// A stage may read the arguments, the plan and what earlier stages wrote here; it reads no environment.  On the handle
+// it uses the device buffers, the landing zone and the streams, and it writes only what outlives the call: the idx_* cache,
+// sl_*, st_pend / st_selfclean, the kept buffers and the statistics.
+template <int BITS>
+struct OverlapCall {
+    static constexpr uint32_t W = 64 / BITS;
+    po_handle* const h;
+    const OverlapArgs& a;
+    po_result* const res;
+    const OverlapSwitches sw;
+    const hipStream_t st;
+    po_stats& S;
+
+    // ---- plan(): decided before anything is launched
+    uint32_t n = 0, m = 1, K = 1;
+    uint64_t kmask = 0;
+    // strand-mirror mode + the read order that picks the canonical member of a mirror pair (keep_bits):
+    // 1 = index order (whole-set calls), 2 = scrambled block order (sharded calls, balances verify work)
+    // (inexact extension: every candidate is extended itself, no strand-mirror shortcut)
+    // 3 = reversed index order, a piece of a streamed step (kernels.hip.h, mirror_rank): the scan keeps containment
+    // candidates of any b, the verify kernel only those whose b has arrived (b < a.r_end)
+    uint32_t paired = 0, paired_ver = 0, dpE = 0, dpW = 0;
+    uint32_t r_begin = 0, r_end = 0, tile_begin = 0, tile_end = 0, ntiles = 0;
+    uint64_t n_elig = 0;
+    bool wide = false;
+    uint32_t ww = 1;
+    bool slice_build = false;   // build one sub-table of the sliced wide index, then stop
+    bool ext_idx = false;       // probe a gathered sliced index
+    bool own_lists = false;     // duplicates are settled inside each read's own candidate list (k_select_local), see build_index
+    uint32_t tbits = 10, nslots = 0, bloom_log2 = 13;
+    size_t bloom_bytes = 0, n_entries = 0, chain_elem = 4;
+    bool phase_events = true;   // this call records the stage-boundary events (phase_events_env)
+    bool pair_events = true;    // ... at least the pairs around the two big kernels and the call's start / end
+    bool reuse_index = false, fold_clear = false;
+    uint32_t scan_waves = 0, scan_grid = 0;
+    bool self_clean = false;    // a piece of a streamed step that leaves the per-call counters zero for the next piece
+    bool sel_in_verify = false, staged = false, dp_lanes = false, dp_bitvec = false;
+    int zone = 64;              // this piece's slots of the pinned landing area
+
+    // ---- workspaces()
+    const uint64_t* words = nullptr;
+    const uint64_t* woff = nullptr;
+    const uint32_t* len = nullptr;
+    po::Slot* table = nullptr;
+    uint32_t *slot_cnt = nullptr, *slot_cur = nullptr, *slot_start = nullptr, *read_slot = nullptr, *chain = nullptr;
+    uint32_t *bloom = nullptr, *selfrep = nullptr, *tile_off_p = nullptr, *n_long = nullptr;
+    unsigned long long* scalars = nullptr;   // [0] scan total, [1] n_long, [3] rows, [4..7] emit counters
+    uint32_t* n_deferred = nullptr;          // reads k_select_local hands to the global table
+
+    // ---- the stages' results
+    po::ScanArgs A = {};
+    po::WideArgs WA = {};
+    uint32_t cap_c = 0;
+    bool async_count = false, pred_order = true;
+    po::CandGuard G = {nullptr, 0u};
+    uint64_t n_cand64 = 0, worst_rows = 0;
+    uint32_t n_cand = 0, n_selfrep_reads = 0;
+    bool use_order = false, defer_needed = false;
+    bool ver_timed = false;     // the verify kernel ran (there were candidates): its own events are valid
+    bool compact_tail = false, can_tail = false;
+    bool rows_late = false;     // rows emitted into a kept buffer before their number reached the host
     bool cands_late = false, cands_ext = false;  // the same for compacted candidates (want_cands): destination chosen before the number was known
     uint64_t cands_cap = 0;
-    bool self_clean = false;  // a piece of a streamed step that leaves the per-call counters zero for the next piece
-    bool used_tail = false;  // the call's tail ran as k_tail (counts in pinned[tail_zone..], fallback flag in pinned[tail_zone + 7])
+    bool used_tail = false;     // the call's tail ran as k_tail (counts in pinned[tail_zone..], fallback flag in pinned[tail_zone + 7])
     int tail_zone = 48;
-    std::function<po_status()> tail_fallback;
-    bool ver_timed = false;  // the verify kernel ran (there were candidates): its own events are valid
-    uint64_t n_keys = wide ? n_elig * W : n_elig;
-    if (slice_build) n_keys = n_keys / h->sl_build_n + n_keys / (16ull * h->sl_build_n) + 4096;  // (a slice's share + slack)
-    // ---- sizes
-    uint32_t tbits = 10;
-    // narrow: 5-10 slots per key, probed in aligned groups of four (kernels.hip.h PROBE_GROUP).  A probe for an
-    // absent key needs more than its group when all four slots are taken: 0.75 % of the groups at 5.2 slots per
-    // key (7 % at 2.6), and those positions go to the leftover list; 8 MB at config 2
-    double table_mult = wide ? 2.0 : 5.0;
-    if (const char* e = getenv("PHASM_TABLE_MULT")) table_mult = std::max(wide ? 2.0 : 1.5, atof(e));
-    if (slice_build) table_mult = 1.5;   // (a sub-table travels over xGMI: the smallest power of two that keeps the load <= 2/3)
-    while ((double)(1ull << tbits) < table_mult * (double)n_keys) ++tbits;
-    if (ext_idx) tbits = h->ext_tbits;
-    if (tbits > 30) return fail(h, PO_ERR_CAPACITY, "too many reads for the anchor table");
-    // (+1: the slot of the all-ones key; narrow: three more so that a group fetch of that slot stays in bounds)
-    const uint32_t nslots = (1u << tbits) + (wide ? 1u : po::PROBE_GROUP);
-    uint32_t bloom_log2 = 13;
-    while (bloom_log2 < 20 && (1ull << bloom_log2) < 16 * n_elig) ++bloom_log2;
-    const size_t bloom_bytes = (size_t)1 << (bloom_log2 - 3);
 
-    PO_TRY(ensure(h, h->d_scalars, 128));
-    const size_t n_entries = wide ? (size_t)n * W : (size_t)n;     // index entries (slots of read_slot / chain)
-    const size_t chain_elem = wide ? 8 : 4;
-    if (!ext_idx) {   // (a supplied index needs none of the build's workspaces)
-        PO_TRY(ensure(h, h->d_table, (size_t)nslots * sizeof(po::Slot)));
-        PO_TRY(ensure(h, h->d_slot_cnt, (size_t)nslots * 4));
-        PO_TRY(ensure(h, h->d_slot_cur, (size_t)nslots * 4));
-        PO_TRY(ensure(h, h->d_slot_start, ((size_t)nslots + 1) * 4));
-        PO_TRY(ensure(h, h->d_read_slot, n_entries * 4));
-        // a slice's chain holds its share of the entries (+ slack; the exact number comes back from the prefix sum)
-        const size_t chain_entries = slice_build ? n_entries / h->sl_build_n + n_entries / (4ull * h->sl_build_n) + 65536 : n_entries;
-        PO_TRY(ensure(h, h->d_chain, std::min(chain_entries, n_entries) * chain_elem));
-        PO_TRY(ensure(h, h->d_chain_tmp, std::min(chain_entries, n_entries) * chain_elem));
-        PO_TRY(ensure(h, h->d_long_list, (size_t)nslots * 4));
-        if (wide) PO_TRY(ensure(h, h->d_entry_off, n_entries * 2));
-    }
-    PO_TRY(ensure(h, h->d_bloom, bloom_bytes));
-    PO_TRY(ensure(h, h->d_selfrep, (size_t)n * 4));
-    PO_TRY(ensure(h, h->d_tile_count, ((size_t)h->n_tiles + 1) * 4));
-    PO_TRY(ensure(h, h->d_tile_off, ((size_t)h->n_tiles + 2) * 4 * 2));   // (twice: the pieces of a streamed step alternate)
-    PO_TRY(ensure(h, h->d_truemask, ((size_t)h->n_tiles + 1) * po::WAVE * 4));
+    OverlapCall(po_handle* h_, const OverlapArgs& a_, po_result* res_) : h(h_), a(a_), res(res_), st(h_->stream), S(h_->stats) {}
 
-    const uint64_t* words = h->d_words.as<uint64_t>();
-    const uint64_t* woff = h->d_woff.as<uint64_t>();
-    const uint32_t* len = h->d_len.as<uint32_t>();
-    po::Slot* table = h->d_table.as<po::Slot>();
-    uint32_t* slot_cnt = h->d_slot_cnt.as<uint32_t>();
-    uint32_t* slot_cur = h->d_slot_cur.as<uint32_t>();
-    uint32_t* slot_start = h->d_slot_start.as<uint32_t>();
-    uint32_t* read_slot = h->d_read_slot.as<uint32_t>();
-    uint32_t* chain = h->d_chain.as<uint32_t>();
-    uint32_t* bloom = h->d_bloom.as<uint32_t>();
-    uint32_t* selfrep = h->d_selfrep.as<uint32_t>();
-    // the small per-piece state (candidate count, emit counters, tile offsets) exists twice, by the piece's parity, like the
-    // piece's slots of the landing zone (`zone`, below)
-    const uint32_t parity = streamed ? (shard & 1u) : 0u;
-    unsigned long long* scalars = h->d_scalars.as<unsigned long long>() + 8 * parity;  // [0] scan total, [1] n_long, [3] rows, [4..7] emit counters
-    uint32_t* const tile_off_p = h->d_tile_off.as<uint32_t>() + (size_t)parity * ((size_t)h->n_tiles + 2);
-    uint32_t* n_long = reinterpret_cast<uint32_t*>(scalars + 1);
+    // a workspace of this call; ws_piece: one whose size follows the candidate count of the a-side range at hand
+    po_status ws(DevBuf& b, size_t bytes, bool arena_ok = true) { return ensure(h, b, bytes, 1.0, arena_ok, a.streamed); }
+    po_status ws_piece(DevBuf& b, size_t bytes) { return ensure_piece(h, b, bytes, a); }
+    template <typename T>
+    po_status prefix(const T* in, uint64_t count, uint32_t* out, volatile uint64_t* total_host) {
+        return prefix_sum<T>(h, in, count, out, total_host, nullptr, nullptr, nullptr, nullptr, nullptr, a);
+    }
 
-    if (h->poison >= 0) {
-        // PHASM_POISON: whatever earlier calls left in the per-call workspaces is replaced by the caller's byte
-        DevBuf* ws[] = {&h->d_table, &h->d_slot_cnt, &h->d_slot_cur, &h->d_slot_start, &h->d_read_slot, &h->d_chain,
-                        &h->d_chain_tmp, &h->d_long_list, &h->d_bloom, &h->d_selfrep, &h->d_tile_count, &h->d_tile_off,
-                        &h->d_truemask, &h->d_ps_blocks, &h->d_left, &h->d_left_cnt, &h->d_tile_extra, &h->d_cand_a,
-                        &h->d_cand_p, &h->d_cand_b, &h->d_type, &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key,
-                        &h->d_vlabel, &h->d_vrank, &h->d_vperm, &h->spare_rows, &h->spare_cands};
-        for (DevBuf* b : ws)
-            if (b->p) HIP_TRY(h, hipMemsetAsync(b->p, h->poison, b->cap, st));
-    }
-    // ---- index: anchor table, chains, Bloom filter.  Built per call like the reference builds its suffix array per
-    // call (overlapper.cpp:33-36) -- unless THIS handle built exactly this index for exactly this device copy of the
-    // reads already (same upload, min_length, flavour, size): the chunks of po_overlaps_to_host and the shards of a
-    // multi-GPU step then share one build instead of repeating it (the replicated part of a sharded step).
-    {
-        const int pe = phase_events_env();
-        h->phase_events = pe >= 0 ? pe == 1 : !streamed;
-        h->pair_events = h->phase_events || pe == 2 || (pe < 0 && !streamed);
-    }
-    if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_START], st));
-    const bool reuse_index = !slice_build && !ext_idx && h->idx_valid && h->idx_gen == h->upload_gen && h->idx_m == m &&
-                             h->idx_wide == wide && h->idx_tbits == tbits && h->idx_bits == (uint32_t)BITS && h->idx_ww == ww && h->poison < 0 &&
-                             !getenv("PHASM_NO_INDEX_REUSE");
-    S.index_reused = reuse_index ? 1u : 0u;
-    h->idx_valid = false;
-    // (narrow scan on a reused index: the reset kernel also clears the scan's two small per-call arrays, below)
-    const bool fold_clear = reuse_index && !wide;
-    if (fold_clear) {
-    } else if (reuse_index || ext_idx) {
-        hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(n, 16u), 256)), dim3(256), 0, st, selfrep, n, scalars, 8u,
-                           (uint32_t*)nullptr, 0u, (uint32_t*)nullptr, 0u);
-    } else {
-        const uint32_t bloom_words = (uint32_t)(bloom_bytes / 4);
-        const uint32_t init_n = std::max(std::max(nslots, n), std::max(bloom_words, 8u));
-        hipLaunchKernelGGL(po::k_call_init, dim3(cdiv(init_n, 256)), dim3(256), 0, st, table, nslots, slot_cnt, slot_cur, selfrep, n,
-                           bloom, bloom_words, h->d_scalars.as<unsigned long long>());
-    }
-    if (reuse_index || ext_idx) {
-        // (nothing to build)
-    } else if (!wide) {
-        hipLaunchKernelGGL(po::k_table_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, words, woff, len, n, m, kmask, table,
-                           tbits, slot_cnt, read_slot, bloom, bloom_log2, (uint32_t)BITS);
-        PO_TRY(prefix_sum<uint32_t>(h, slot_cnt, nslots, slot_start, &h->pinned[0]));
-        hipLaunchKernelGGL(po::k_chain_fill, dim3(cdiv(n, 256)), dim3(256), 0, st, read_slot, n, slot_start, slot_cur, chain);
-        hipLaunchKernelGGL(po::k_chain_sort_short<uint32_t>, dim3(cdiv(nslots, 256)), dim3(256), 0, st, slot_cnt, slot_start,
-                           nslots, chain, h->d_long_list.as<uint32_t>(), n_long);
-        hipLaunchKernelGGL(po::k_chain_sort_long<uint32_t>, dim3(64), dim3(256), 0, st, slot_cnt, slot_start,
-                           h->d_long_list.as<uint32_t>(), n_long, chain, h->d_chain_tmp.as<uint32_t>());
-        hipLaunchKernelGGL(po::k_table_finalize, dim3(cdiv(nslots, 256)), dim3(256), 0, st, table, nslots, slot_cnt,
-                           slot_start, chain, len);
-    } else {
-        uint16_t* entry_off = h->d_entry_off.as<uint16_t>();
-        auto k_ins = ww == 16 ? po::k_wide_insert<BITS, 16> : ww == 4 ? po::k_wide_insert<BITS, 4> : po::k_wide_insert<BITS, 1>;
-        auto k_cfill = ww == 16 ? po::k_wide_chain_fill<BITS, 16> : ww == 4 ? po::k_wide_chain_fill<BITS, 4> : po::k_wide_chain_fill<BITS, 1>;
-        auto k_fin = ww == 16 ? po::k_wide_finalize<BITS, 16> : ww == 4 ? po::k_wide_finalize<BITS, 4> : po::k_wide_finalize<BITS, 1>;
-        hipLaunchKernelGGL(k_ins, dim3(cdiv(n_entries, 256)), dim3(256), 0, st, words, woff, len, n, m,
-                           table, tbits, slot_cnt, read_slot, entry_off, slice_build ? h->sl_build_n : 1u, h->sl_build_slice);
-        PO_TRY(prefix_sum<uint32_t>(h, slot_cnt, nslots, slot_start, &h->pinned[0]));
-        if (slice_build) {
-            // a sub-table's chain segment was sized for its expected share: learn the real number before anything is
-            // written (repetitive reads put all their entries into one sub-table)
-            HIP_TRY(h, hipStreamSynchronize(st));
-            PO_TRY(ensure(h, h->d_chain, (size_t)h->pinned[0] * chain_elem));
-            PO_TRY(ensure(h, h->d_chain_tmp, (size_t)h->pinned[0] * chain_elem));
+    // *done: the call has nothing (more) to do
+    po_status plan(bool* done) {
+        *done = true;
+        n = (uint32_t)h->len.size();
+        m = a.min_length ? a.min_length : 1;  // a suffix array has no empty suffix
+        K = m < W ? m : W;
+        kmask = K * BITS >= 64 ? ~0ull : ((1ull << (K * BITS)) - 1ull);
+        const float keep_upload = S.ms_upload;
+        S = po_stats();
+        S.ms_upload = keep_upload;
+        S.upload_bytes = h->upload_bytes;
+        S.bits_per_base = BITS;
+        S.kmer = K;
+        S.n_reads = n;
+        S.total_bases = h->total_bases;
+        dpE = a.dp ? a.dp_E : 0u;
+        dpW = a.dp && a.dp_E ? a.dp_W : 0u;
+        paired = (BITS == 2 && h->paired && dpE == 0) ? (a.streamed ? po::PAIRED_STREAM_ALL : a.nshards > 1 ? 2u : 1u) : 0u;
+        paired_ver = a.streamed ? po::paired_stream(a.r_end) : paired;
+        if (a.streamed && (!paired || a.want_cands)) return fail(h, PO_ERR_INVALID, "streamed step without strand pairs");
+        S.paired = paired ? 1u : 0u;
+        S.max_diff = dpE;
+        S.band = dpW;
+        if (a.dp && dpE && a.want_cands) return fail(h, PO_ERR_INVALID, "the candidate (multi-GPU) form has no inexact mode");
+        if (a.dp && dpE && BITS == 2 && !h->exc_pos.empty())
+            return fail(h, PO_ERR_INVALID, "po_overlaps_ex with max_diff > 0 needs pure upper-case ACGT reads (or the 8-bit representation)");
+
+        r_end = n;
+        S.shard_bases = h->total_bases;
+        if (a.streamed) {
+            r_begin = a.r_begin;
+            r_end = a.r_end;
+            S.shard_bases = 0;
+            for (uint32_t r = r_begin; r < r_end; ++r) S.shard_bases += h->len[r];
+        } else if (a.nshards > 1) {
+            shard_range(h, a.shard, a.nshards, &r_begin, &r_end, &S.shard_bases);
         }
-        uint64_t* chain64 = h->d_chain.as<uint64_t>();
-        hipLaunchKernelGGL(k_cfill, dim3(cdiv(n_entries, 256)), dim3(256), 0, st, read_slot, entry_off,
-                           (uint64_t)n_entries, slot_start, slot_cur, chain64, len);
-        hipLaunchKernelGGL(po::k_chain_sort_short<uint64_t>, dim3(cdiv(nslots, 256)), dim3(256), 0, st, slot_cnt, slot_start,
-                           nslots, chain64, h->d_long_list.as<uint32_t>(), n_long);
-        hipLaunchKernelGGL(po::k_chain_sort_long<uint64_t>, dim3(64), dim3(256), 0, st, slot_cnt, slot_start,
-                           h->d_long_list.as<uint32_t>(), n_long, chain64, h->d_chain_tmp.as<uint64_t>());
-        hipLaunchKernelGGL(k_fin, dim3(cdiv(nslots, 256)), dim3(256), 0, st, table, nslots, slot_cnt,
-                           slot_start, chain64, len);
-    }
-    // Which reads repeat their own prefix K-mer (selfrep: only their A candidates can be non-longest duplicates)?
-    // The narrow whole-set scan finds that as a side effect.  The other cases do not scan every read for it -- a
-    // pass over all positions cost 2.2 ms at config 3 with the wide index, and more than the shard's own scan at 8
-    // shards -- and settle duplicates inside each read's own candidate list instead (k_select_local, below).
-    HIP_TRY(h, hipGetLastError());
-    if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_INDEX], st));
-    if (slice_build) {
-        // the sub-table and its chain segment are complete in the workspaces: po_index_slice_export copies them out
-        HIP_TRY(h, hipStreamSynchronize(st));
-        h->sl_tbits = tbits;
-        h->sl_entries = h->pinned[0];   // (the prefix sum's total = chain entries of this sub-table)
-        if (h->phase_events) (void)hipEventElapsedTime(&S.ms_index, h->ev[EV_START], h->ev[EV_INDEX]);
+        tile_begin = h->h_read_tile0[r_begin];
+        tile_end = h->h_read_tile0[r_end];
+        ntiles = tile_end - tile_begin;
+        S.n_tiles = ntiles;
+
+        n_elig = count_eligible(h, m);
+        S.n_eligible = n_elig;
+        res->count = 0;
+        if (n == 0 || n_elig == 0 || ntiles == 0) return PO_OK;
+
+        const IndexFlavour f = index_flavour(h, m, a.streamed, h->st_lead, sw);
+        wide = f.wide;
+        ww = f.ww;
+        S.wide_index = wide ? 1u : 0u;
+        slice_build = a.build_n > 1;
+        ext_idx = a.ext_index != nullptr;
+        if (slice_build) {
+            h->sl_is_wide = wide;
+            if (!wide) return PO_OK;                    // (the narrow index is 0.06 ms: every rank builds its own)
+        }
+        if (ext_idx && !wide) return fail(h, PO_ERR_INVALID, "a sliced index was supplied, but this call uses the narrow index");
+        own_lists = a.nshards > 1 || a.streamed || wide;
+        uint64_t n_keys = wide ? n_elig * W : n_elig;
+        if (slice_build) n_keys = n_keys / a.build_n + n_keys / (16ull * a.build_n) + 4096;  // (a slice's share + slack)
+        // ---- sizes
+        // narrow: 5-10 slots per key, probed in aligned groups of four (kernels.hip.h PROBE_GROUP).  A probe for an
+        // absent key needs more than its group when all four slots are taken: 0.75 % of the groups at 5.2 slots per
+        // key (7 % at 2.6), and those positions go to the leftover list; 8 MB at config 2
+        double table_mult = wide ? 2.0 : 5.0;
+        if (sw.table_mult) table_mult = std::max(wide ? 2.0 : 1.5, atof(sw.table_mult));
+        if (slice_build) table_mult = 1.5;   // (a sub-table travels over xGMI: the smallest power of two that keeps the load <= 2/3)
+        while ((double)(1ull << tbits) < table_mult * (double)n_keys) ++tbits;
+        if (ext_idx) tbits = a.ext_tbits;
+        if (tbits > 30) return fail(h, PO_ERR_CAPACITY, "too many reads for the anchor table");
+        // (+1: the slot of the all-ones key; narrow: three more so that a group fetch of that slot stays in bounds)
+        nslots = (1u << tbits) + (wide ? 1u : po::PROBE_GROUP);
+        while (bloom_log2 < 20 && (1ull << bloom_log2) < 16 * n_elig) ++bloom_log2;
+        bloom_bytes = (size_t)1 << (bloom_log2 - 3);
+        n_entries = wide ? (size_t)n * W : (size_t)n;     // index entries (slots of read_slot / chain)
+        chain_elem = wide ? 8 : 4;
+
+        phase_events = sw.phase_events >= 0 ? sw.phase_events == 1 : !a.streamed;
+        pair_events = phase_events || sw.phase_events == 2 || (sw.phase_events < 0 && !a.streamed);
+        // the index THIS handle built for exactly this device copy of the reads (same upload, min_length, flavour, size)
+        reuse_index = !slice_build && !ext_idx && h->idx_valid && h->idx_gen == h->upload_gen && h->idx_m == m &&
+                      h->idx_wide == wide && h->idx_tbits == tbits && h->idx_bits == (uint32_t)BITS && h->idx_ww == ww && h->poison < 0 &&
+                      !sw.no_index_reuse;
+        // (narrow scan on a reused index: the reset kernel also clears the scan's two small per-call arrays, scan_count)
+        fold_clear = reuse_index && !wide;
+        scan_waves = po::SCAN_BLOCK / 64;
+        if (sw.scan_waves) scan_waves = std::max(1, std::min(16, atoi(sw.scan_waves)));
+        scan_grid = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)h->n_cu, cdiv(ntiles, scan_waves)));
+        // (the pieces of a streamed step clean up after themselves -- k_scan_fixup zeroes its list counters, the fused tail its
+        // counters, the first piece's reset clears tile_extra for every tile of the read set --: no reset launch per piece)
+        self_clean = !wide && a.streamed && !sw.debug_left && !sw.piece_reset;
+        zone = 64 + 16 * (int)(a.shard & 1u);
+        // the longest-only selection inside each read's list runs in the verify kernel's epilogue where the exact verify runs
+        // (not the DP kernels, which have no per-read workgroup); PHASM_SELECT_KERNEL=1 keeps the separate launch
+        sel_in_verify = own_lists && !a.dp && !sw.select_kernel;
+        // candidate records staged in LDS (word offsets must fit 32 bits); PHASM_VERIFY_STAGED=0 switches back
+        staged = h->dev_words < 0xFFFFFFF0ull;
+        if (sw.verify_staged) staged = staged && atoi(sw.verify_staged) != 0;
+        if (a.dp) {
+            // three mappings of the same DP (extend.hip.h), same rows bit for bit: a LANE per candidate with the band row as a
+            // BIT VECTOR (k_extend_bits: 2-bit reads, band <= 15 -- the default where it applies), a lane per candidate with
+            // the band row in registers (k_extend_lanes), a WAVE per candidate with a lane per diagonal (k_extend_dp: any
+            // encoding, band <= 30).  PHASM_DP_KERNEL=bits|lanes|wave forces one (the tests run all three)
+            dp_lanes = dp_bitvec = BITS == 2 && dpW <= 15;
+            if (sw.dp_kernel) {
+                if (!strcmp(sw.dp_kernel, "wave")) dp_lanes = dp_bitvec = false;
+                if (!strcmp(sw.dp_kernel, "lanes")) dp_bitvec = false;
+                if ((!strcmp(sw.dp_kernel, "lanes") || !strcmp(sw.dp_kernel, "bits")) && !(BITS == 2 && dpW <= 15))
+                    return fail(h, PO_ERR_INVALID, "PHASM_DP_KERNEL=lanes|bits needs 2-bit reads and band <= 15");
+            }
+            if (sw.dp_kernel_soft && !strcmp(sw.dp_kernel_soft, "lanes")) dp_bitvec = false;
+        }
+        *done = false;
         return PO_OK;
     }
-    if (ext_idx) {
-        WA_ext = true;
+
+    po_status workspaces() {
+        PO_TRY(ws(h->d_scalars, 128));
+        if (!ext_idx) {   // (a supplied index needs none of the build's workspaces)
+            PO_TRY(ws(h->d_table, (size_t)nslots * sizeof(po::Slot)));
+            PO_TRY(ws(h->d_slot_cnt, (size_t)nslots * 4));
+            PO_TRY(ws(h->d_slot_cur, (size_t)nslots * 4));
+            PO_TRY(ws(h->d_slot_start, ((size_t)nslots + 1) * 4));
+            PO_TRY(ws(h->d_read_slot, n_entries * 4));
+            // a slice's chain holds its share of the entries (+ slack; the exact number comes back from the prefix sum)
+            const size_t chain_entries = slice_build ? n_entries / a.build_n + n_entries / (4ull * a.build_n) + 65536 : n_entries;
+            PO_TRY(ws(h->d_chain, std::min(chain_entries, n_entries) * chain_elem));
+            PO_TRY(ws(h->d_chain_tmp, std::min(chain_entries, n_entries) * chain_elem));
+            PO_TRY(ws(h->d_long_list, (size_t)nslots * 4));
+            if (wide) PO_TRY(ws(h->d_entry_off, n_entries * 2));
+        }
+        PO_TRY(ws(h->d_bloom, bloom_bytes));
+        PO_TRY(ws(h->d_selfrep, (size_t)n * 4));
+        PO_TRY(ws(h->d_tile_count, ((size_t)h->n_tiles + 1) * 4));
+        PO_TRY(ws(h->d_tile_off, ((size_t)h->n_tiles + 2) * 4 * 2));   // (twice: the pieces of a streamed step alternate)
+        PO_TRY(ws(h->d_truemask, ((size_t)h->n_tiles + 1) * po::WAVE * 4));
+
+        words = h->d_words.as<uint64_t>();
+        woff = h->d_woff.as<uint64_t>();
+        len = h->d_len.as<uint32_t>();
+        table = h->d_table.as<po::Slot>();
+        slot_cnt = h->d_slot_cnt.as<uint32_t>();
+        slot_cur = h->d_slot_cur.as<uint32_t>();
+        slot_start = h->d_slot_start.as<uint32_t>();
+        read_slot = h->d_read_slot.as<uint32_t>();
+        chain = h->d_chain.as<uint32_t>();
+        bloom = h->d_bloom.as<uint32_t>();
+        selfrep = h->d_selfrep.as<uint32_t>();
+        // the small per-piece state (candidate count, emit counters, tile offsets) exists twice, by the piece's parity, like the
+        // piece's slots of the landing zone (`zone`)
+        const uint32_t parity = a.streamed ? (a.shard & 1u) : 0u;
+        scalars = h->d_scalars.as<unsigned long long>() + 8 * parity;
+        tile_off_p = h->d_tile_off.as<uint32_t>() + (size_t)parity * ((size_t)h->n_tiles + 2);
+        n_long = reinterpret_cast<uint32_t*>(scalars + 1);
+        n_deferred = reinterpret_cast<uint32_t*>(scalars + 1) + 1;
+
+        if (h->poison >= 0) {
+            // PHASM_POISON: whatever earlier calls left in the per-call workspaces is replaced by the caller's byte
+            DevBuf* all[] = {&h->d_table, &h->d_slot_cnt, &h->d_slot_cur, &h->d_slot_start, &h->d_read_slot, &h->d_chain,
+                             &h->d_chain_tmp, &h->d_long_list, &h->d_bloom, &h->d_selfrep, &h->d_tile_count, &h->d_tile_off,
+                             &h->d_truemask, &h->d_ps_blocks, &h->d_left, &h->d_left_cnt, &h->d_tile_extra, &h->d_cand_a,
+                             &h->d_cand_p, &h->d_cand_b, &h->d_type, &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key,
+                             &h->d_vlabel, &h->d_vrank, &h->d_vperm, &h->spare_rows, &h->spare_cands};
+            for (DevBuf* b : all)
+                if (b->p) HIP_TRY(h, hipMemsetAsync(b->p, h->poison, b->cap, st));
+        }
+        return PO_OK;
     }
-    if (h->idx_only) {
-        // (streamed step: the index is built from the first words of every read while piece 0 is still on the wire; the
-        // pieces find it valid -- same upload, min_length, flavour -- and reuse it)
-        h->idx_valid = true;
+
+    // every chain sorted by the order the scan walks it in: short ones in place, the long ones listed for k_chain_sort_long
+    template <typename T>
+    void sort_chains() {
+        hipLaunchKernelGGL(po::k_chain_sort_short<T>, dim3(cdiv(nslots, 256)), dim3(256), 0, st, slot_cnt, slot_start,
+                           nslots, h->d_chain.as<T>(), h->d_long_list.as<uint32_t>(), n_long);
+        hipLaunchKernelGGL(po::k_chain_sort_long<T>, dim3(64), dim3(256), 0, st, slot_cnt, slot_start,
+                           h->d_long_list.as<uint32_t>(), n_long, h->d_chain.as<T>(), h->d_chain_tmp.as<T>());
+    }
+
+    // ---- index: anchor table, chains, Bloom filter.  Built per call like the reference builds its suffix array per
+    // call (overlapper.cpp:33-36) -- unless THIS handle built exactly this index for exactly this device copy of the
+    // reads already (reuse_index): the chunks of po_overlaps_to_host and the shards of a multi-GPU step then share one
+    // build instead of repeating it (the replicated part of a sharded step).
+    // *done: a slice build or the index-only pass of a streamed step, which end here
+    po_status build_index(bool* done) {
+        *done = true;
+        if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_START], st));
+        S.index_reused = reuse_index ? 1u : 0u;
+        h->idx_valid = false;
+        if (fold_clear) {
+        } else if (reuse_index || ext_idx) {
+            hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(n, 16u), 256)), dim3(256), 0, st, selfrep, n, scalars, 8u,
+                               (uint32_t*)nullptr, 0u, (uint32_t*)nullptr, 0u);
+        } else {
+            const uint32_t bloom_words = (uint32_t)(bloom_bytes / 4);
+            const uint32_t init_n = std::max(std::max(nslots, n), std::max(bloom_words, 8u));
+            hipLaunchKernelGGL(po::k_call_init, dim3(cdiv(init_n, 256)), dim3(256), 0, st, table, nslots, slot_cnt, slot_cur, selfrep, n,
+                               bloom, bloom_words, h->d_scalars.as<unsigned long long>());
+        }
+        if (reuse_index || ext_idx) {
+            // (nothing to build)
+        } else if (!wide) {
+            hipLaunchKernelGGL(po::k_table_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, words, woff, len, n, m, kmask, table,
+                               tbits, slot_cnt, read_slot, bloom, bloom_log2, (uint32_t)BITS);
+            PO_TRY(prefix<uint32_t>(slot_cnt, nslots, slot_start, &h->pinned[0]));
+            hipLaunchKernelGGL(po::k_chain_fill, dim3(cdiv(n, 256)), dim3(256), 0, st, read_slot, n, slot_start, slot_cur, chain);
+            sort_chains<uint32_t>();
+            hipLaunchKernelGGL(po::k_table_finalize, dim3(cdiv(nslots, 256)), dim3(256), 0, st, table, nslots, slot_cnt,
+                               slot_start, chain, len);
+        } else {
+            uint16_t* entry_off = h->d_entry_off.as<uint16_t>();
+            auto k_ins = ww == 16 ? po::k_wide_insert<BITS, 16> : ww == 4 ? po::k_wide_insert<BITS, 4> : po::k_wide_insert<BITS, 1>;
+            auto k_cfill = ww == 16 ? po::k_wide_chain_fill<BITS, 16> : ww == 4 ? po::k_wide_chain_fill<BITS, 4> : po::k_wide_chain_fill<BITS, 1>;
+            auto k_fin = ww == 16 ? po::k_wide_finalize<BITS, 16> : ww == 4 ? po::k_wide_finalize<BITS, 4> : po::k_wide_finalize<BITS, 1>;
+            hipLaunchKernelGGL(k_ins, dim3(cdiv(n_entries, 256)), dim3(256), 0, st, words, woff, len, n, m,
+                               table, tbits, slot_cnt, read_slot, entry_off, slice_build ? a.build_n : 1u, a.build_slice);
+            PO_TRY(prefix<uint32_t>(slot_cnt, nslots, slot_start, &h->pinned[0]));
+            if (slice_build) {
+                // a sub-table's chain segment was sized for its expected share: learn the real number before anything is
+                // written (repetitive reads put all their entries into one sub-table)
+                HIP_TRY(h, hipStreamSynchronize(st));
+                PO_TRY(ws(h->d_chain, (size_t)h->pinned[0] * chain_elem));
+                PO_TRY(ws(h->d_chain_tmp, (size_t)h->pinned[0] * chain_elem));
+            }
+            uint64_t* chain64 = h->d_chain.as<uint64_t>();
+            hipLaunchKernelGGL(k_cfill, dim3(cdiv(n_entries, 256)), dim3(256), 0, st, read_slot, entry_off,
+                               (uint64_t)n_entries, slot_start, slot_cur, chain64, len);
+            sort_chains<uint64_t>();
+            hipLaunchKernelGGL(k_fin, dim3(cdiv(nslots, 256)), dim3(256), 0, st, table, nslots, slot_cnt,
+                               slot_start, chain64, len);
+        }
+        // Which reads repeat their own prefix K-mer (selfrep: only their A candidates can be non-longest duplicates)?
+        // The narrow whole-set scan finds that as a side effect.  The other cases (own_lists) do not scan every read for it
+        // -- a pass over all positions cost 2.2 ms at config 3 with the wide index, and more than the shard's own scan at 8
+        // shards -- and settle duplicates inside each read's own candidate list instead (k_select_local).
+        HIP_TRY(h, hipGetLastError());
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_INDEX], st));
+        if (slice_build) {
+            // the sub-table and its chain segment are complete in the workspaces: po_index_slice_export copies them out
+            HIP_TRY(h, hipStreamSynchronize(st));
+            h->sl_tbits = tbits;
+            h->sl_entries = h->pinned[0];   // (the prefix sum's total = chain entries of this sub-table)
+            if (phase_events) (void)hipEventElapsedTime(&S.ms_index, h->ev[EV_START], h->ev[EV_INDEX]);
+            return PO_OK;
+        }
+        // (a.idx_only, streamed step: the index is built from the first words of every read while piece 0 is still on the
+        // wire; the pieces find it valid -- same upload, min_length, flavour -- and reuse it)
+        h->idx_valid = a.idx_only || !ext_idx;
         h->idx_gen = h->upload_gen;
         h->idx_m = m;
         h->idx_wide = wide;
         h->idx_tbits = tbits;
         h->idx_bits = (uint32_t)BITS;
         h->idx_ww = ww;
+        *done = a.idx_only;
         return PO_OK;
     }
-    h->idx_valid = !ext_idx;
-    h->idx_gen = h->upload_gen;
-    h->idx_m = m;
-    h->idx_wide = wide;
-    h->idx_tbits = tbits;
-    h->idx_bits = (uint32_t)BITS;
-    h->idx_ww = ww;
 
     // ---- scan, counting pass
-    po::ScanArgs A = {};
-    A.words = words;
-    A.tiles = h->d_tiles.as<po::TileRec>();
-    A.tile_begin = tile_begin;
-    A.tile_end = tile_end;
-    A.m = m;
-    A.kmask = kmask;
-    A.bloom = bloom;
-    A.bloom_log2 = bloom_log2;
-    A.table = table;
-    A.tbits = tbits;
-    A.chain = chain;
-    A.len = len;
-    A.paired = paired;
-    A.selfrep = selfrep;
-    A.n_selfrep = reinterpret_cast<uint32_t*>(scalars + 2);  // scalars[2] lo: reads with a self-repeating prefix
-    A.tile_count = h->d_tile_count.as<uint32_t>();
-    A.tile_off = tile_off_p;
-    A.truemask = h->d_truemask.as<uint32_t>();
+    po_status scan_count() {
+        A.words = words;
+        A.tiles = h->d_tiles.as<po::TileRec>();
+        A.tile_begin = tile_begin;
+        A.tile_end = tile_end;
+        A.m = m;
+        A.kmask = kmask;
+        A.bloom = bloom;
+        A.bloom_log2 = bloom_log2;
+        A.table = table;
+        A.tbits = tbits;
+        A.chain = chain;
+        A.len = len;
+        A.paired = paired;
+        A.selfrep = selfrep;
+        A.n_selfrep = reinterpret_cast<uint32_t*>(scalars + 2);  // scalars[2] lo: reads with a self-repeating prefix
+        A.tile_count = h->d_tile_count.as<uint32_t>();
+        A.tile_off = tile_off_p;
+        A.truemask = h->d_truemask.as<uint32_t>();
 #ifdef PO_STAMPS
-    PO_TRY(ensure(h, h->d_flag, (size_t)4096 * 64));
-    HIP_TRY(h, hipMemsetAsync(h->d_flag.p, 0, (size_t)4096 * 64, st));
-    A.dbg = h->d_flag.as<unsigned long long>();
+        PO_TRY(ws(h->d_flag, (size_t)4096 * 64));
+        HIP_TRY(h, hipMemsetAsync(h->d_flag.p, 0, (size_t)4096 * 64, st));
+        A.dbg = h->d_flag.as<unsigned long long>();
 #endif
-    uint32_t scan_waves = po::SCAN_BLOCK / 64;
-    if (const char* e = getenv("PHASM_SCAN_WAVES")) scan_waves = std::max(1, std::min(16, atoi(e)));
-    const uint32_t scan_grid = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)h->n_cu, cdiv(ntiles, scan_waves)));
-    po::WideArgs WA = {};
-    WA.words = words;
-    WA.tiles = A.tiles;
-    WA.tile_begin = tile_begin;
-    WA.tile_end = tile_end;
-    WA.m = m;
-    WA.table = table;
-    WA.tbits = tbits;
-    WA.chain = h->d_chain.as<uint64_t>();
-    WA.n_slices = 1;
-    if (WA_ext) {   // the gathered sliced index: N chunks of [sub-table | chain segment]
-        WA.table = static_cast<const po::Slot*>(h->ext_index);
-        WA.chain = nullptr;
-        WA.n_slices = h->ext_slices;
-        WA.chunk_slots = h->ext_chunk_slots;
-        WA.chain_off_slots = h->ext_chain_off;
-    }
-    WA.len = len;
-    WA.paired = paired;
-    WA.tile_count = A.tile_count;
-    WA.lane_slot = A.truemask;
-    WA.tile_off = A.tile_off;
-    if (wide) {
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], st));
-        auto wscan = streamed ? (ww == 4 ? po::k_wide_scan<BITS, false, BITS == 2, 4> : po::k_wide_scan<BITS, false, BITS == 2, 1>)
-                     : ww == 16 ? po::k_wide_scan<BITS, false, false, 16> : ww == 4 ? po::k_wide_scan<BITS, false, false, 4> : po::k_wide_scan<BITS, false, false, 1>;
-        hipLaunchKernelGGL(wscan, dim3(cdiv(ntiles, 4)), dim3(256), 0, st, WA, po::CandGuard{nullptr, 0u});
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], st));
-    } else {
-        const size_t scan_lds = (size_t)scan_waves * po::SCAN_LDS_PER_WAVE + bloom_bytes;
-        if (scan_lds > h->lds_max) return fail(h, PO_ERR_HIP, "device LDS too small for the scan kernel");
-        // (a streamed step -- 2-bit reads only -- has its own instantiations: the reversed pair order is a compile-time choice)
-        constexpr bool CAN_STREAM = BITS == 2;
-        auto probe_full = streamed ? po::k_scan_probe<BITS, true, CAN_STREAM> : po::k_scan_probe<BITS, true, false>;
-        auto probe_part = streamed ? po::k_scan_probe<BITS, false, CAN_STREAM> : po::k_scan_probe<BITS, false, false>;
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(probe_full), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_lds));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(probe_part), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_lds));
-        const uint32_t n_scan_waves = scan_grid * scan_waves;
-        PO_TRY(ensure(h, h->d_left, (size_t)n_scan_waves * po::LEFT_CAP * sizeof(uint2)));
-        PO_TRY(ensure(h, h->d_left_cnt, (size_t)n_scan_waves * 4));
-        PO_TRY(ensure(h, h->d_tile_extra, ((size_t)h->n_tiles + 1) * 4));
-        // (the pieces of a streamed step clean up after themselves -- k_scan_fixup zeroes its list counters, the fused tail its
-        // counters, the first piece's reset clears tile_extra for every tile of the read set --: no reset launch per piece)
-        self_clean = streamed && !getenv("PHASM_DEBUG_LEFT") && !getenv("PHASM_PIECE_RESET");
-        if (fold_clear && self_clean && h->st_selfclean) {
-            // nothing to launch
-        } else if (fold_clear) {
-            const uint32_t te0 = self_clean ? 0u : tile_begin, ten = self_clean ? h->n_tiles : ntiles;
-            // (a self-cleaning step's first piece zeroes both parities' scalars; any other reset only its own block)
-            hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(std::max(n, 16u), std::max(n_scan_waves, ten)), 256)), dim3(256), 0, st,
-                               selfrep, n, self_clean ? h->d_scalars.as<unsigned long long>() : scalars, self_clean ? 16u : 8u,
-                               h->d_left_cnt.as<uint32_t>(), n_scan_waves, h->d_tile_extra.as<uint32_t>() + te0, ten);
+        WA.words = words;
+        WA.tiles = A.tiles;
+        WA.tile_begin = tile_begin;
+        WA.tile_end = tile_end;
+        WA.m = m;
+        WA.table = table;
+        WA.tbits = tbits;
+        WA.chain = h->d_chain.as<uint64_t>();
+        WA.n_slices = 1;
+        if (ext_idx) {   // the gathered sliced index: N chunks of [sub-table | chain segment]
+            WA.table = static_cast<const po::Slot*>(a.ext_index);
+            WA.chain = nullptr;
+            WA.n_slices = a.ext_slices;
+            WA.chunk_slots = a.ext_chunk_slots;
+            WA.chain_off_slots = a.ext_chain_off;
+        }
+        WA.len = len;
+        WA.paired = paired;
+        WA.tile_count = A.tile_count;
+        WA.lane_slot = A.truemask;
+        WA.tile_off = A.tile_off;
+        if (wide) {
+            if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], st));
+            auto wscan = a.streamed ? (ww == 4 ? po::k_wide_scan<BITS, false, BITS == 2, 4> : po::k_wide_scan<BITS, false, BITS == 2, 1>)
+                         : ww == 16 ? po::k_wide_scan<BITS, false, false, 16> : ww == 4 ? po::k_wide_scan<BITS, false, false, 4> : po::k_wide_scan<BITS, false, false, 1>;
+            hipLaunchKernelGGL(wscan, dim3(cdiv(ntiles, 4)), dim3(256), 0, st, WA, po::CandGuard{nullptr, 0u});
+            if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], st));
         } else {
-            HIP_TRY(h, hipMemsetAsync(h->d_left_cnt.p, 0, (size_t)n_scan_waves * 4, st));
-            HIP_TRY(h, hipMemsetAsync(h->d_tile_extra.as<uint32_t>() + tile_begin, 0, (size_t)ntiles * 4, st));
+            const size_t scan_lds = (size_t)scan_waves * po::SCAN_LDS_PER_WAVE + bloom_bytes;
+            if (scan_lds > h->lds_max) return fail(h, PO_ERR_HIP, "device LDS too small for the scan kernel");
+            // (a streamed step -- 2-bit reads only -- has its own instantiations: the reversed pair order is a compile-time choice)
+            constexpr bool CAN_STREAM = BITS == 2;
+            auto probe_full = a.streamed ? po::k_scan_probe<BITS, true, CAN_STREAM> : po::k_scan_probe<BITS, true, false>;
+            auto probe_part = a.streamed ? po::k_scan_probe<BITS, false, CAN_STREAM> : po::k_scan_probe<BITS, false, false>;
+            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(probe_full), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_lds));
+            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(probe_part), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_lds));
+            const uint32_t n_scan_waves = scan_grid * scan_waves;
+            PO_TRY(ws(h->d_left, (size_t)n_scan_waves * po::LEFT_CAP * sizeof(uint2)));
+            PO_TRY(ws(h->d_left_cnt, (size_t)n_scan_waves * 4));
+            PO_TRY(ws(h->d_tile_extra, ((size_t)h->n_tiles + 1) * 4));
+            if (fold_clear && self_clean && h->st_selfclean) {
+                // nothing to launch
+            } else if (fold_clear) {
+                const uint32_t te0 = self_clean ? 0u : tile_begin, ten = self_clean ? h->n_tiles : ntiles;
+                // (a self-cleaning step's first piece zeroes both parities' scalars; any other reset only its own block)
+                hipLaunchKernelGGL(po::k_call_reset, dim3(cdiv(std::max(std::max(n, 16u), std::max(n_scan_waves, ten)), 256)), dim3(256), 0, st,
+                                   selfrep, n, self_clean ? h->d_scalars.as<unsigned long long>() : scalars, self_clean ? 16u : 8u,
+                                   h->d_left_cnt.as<uint32_t>(), n_scan_waves, h->d_tile_extra.as<uint32_t>() + te0, ten);
+            } else {
+                HIP_TRY(h, hipMemsetAsync(h->d_left_cnt.p, 0, (size_t)n_scan_waves * 4, st));
+                HIP_TRY(h, hipMemsetAsync(h->d_tile_extra.as<uint32_t>() + tile_begin, 0, (size_t)ntiles * 4, st));
+            }
+            A.left = h->d_left.as<uint2>();
+            A.left_cnt = h->d_left_cnt.as<uint32_t>();
+            A.tile_extra = h->d_tile_extra.as<uint32_t>();
+            if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], st));
+            hipLaunchKernelGGL(K == W ? probe_full : probe_part, dim3(scan_grid), dim3(scan_waves * 64), scan_lds, st, A);
+            if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], st));
+            auto fixup = a.streamed ? po::k_scan_fixup<BITS, CAN_STREAM> : po::k_scan_fixup<BITS, false>;
+            hipLaunchKernelGGL(fixup, dim3(n_scan_waves), dim3(256), 0, st, A, n_scan_waves, self_clean ? 1u : 0u);
+            // (the leftover counts, tile_extra, are added to the tile counts by the prefix sum of candidate_count)
+            if (sw.debug_left) {
+                PO_TRY(ensure_host(h, h->scratch_host, (size_t)n_scan_waves * 4));
+                HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_left_cnt.p, (size_t)n_scan_waves * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(h, hipStreamSynchronize(st));
+                const uint32_t* lc = static_cast<const uint32_t*>(h->scratch_host.p);
+                uint64_t sum = 0;
+                uint32_t mx = 0;
+                for (uint32_t k = 0; k < n_scan_waves; ++k) sum += lc[k], mx = std::max(mx, lc[k]);
+                std::fprintf(stderr, "[left] %u scan waves deferred %llu positions (max %u per wave, cap %d)\n", n_scan_waves,
+                             (unsigned long long)sum, mx, (int)po::LEFT_CAP);
+            }
         }
-        A.left = h->d_left.as<uint2>();
-        A.left_cnt = h->d_left_cnt.as<uint32_t>();
-        A.tile_extra = h->d_tile_extra.as<uint32_t>();
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE0], st));
-        hipLaunchKernelGGL(K == W ? probe_full : probe_part, dim3(scan_grid), dim3(scan_waves * 64), scan_lds, st, A);
-        if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_PROBE1], st));
-        auto fixup = streamed ? po::k_scan_fixup<BITS, CAN_STREAM> : po::k_scan_fixup<BITS, false>;
-        hipLaunchKernelGGL(fixup, dim3(n_scan_waves), dim3(256), 0, st, A, n_scan_waves, self_clean ? 1u : 0u);
-        // (the leftover counts, tile_extra, are added to the tile counts by the prefix sum below)
-        if (getenv("PHASM_DEBUG_LEFT")) {  // how many positions did the scan waves defer to k_scan_fixup?
-            PO_TRY(ensure_host(h, h->scratch_host, (size_t)n_scan_waves * 4));
-            HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, h->d_left_cnt.p, (size_t)n_scan_waves * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(h, hipStreamSynchronize(st));
-            const uint32_t* lc = static_cast<const uint32_t*>(h->scratch_host.p);
-            uint64_t sum = 0;
-            uint32_t mx = 0;
-            for (uint32_t k = 0; k < n_scan_waves; ++k) sum += lc[k], mx = std::max(mx, lc[k]);
-            std::fprintf(stderr, "[left] %u scan waves deferred %llu positions (max %u per wave, cap %d)\n", n_scan_waves,
-                         (unsigned long long)sum, mx, (int)po::LEFT_CAP);
-        }
-    }
-    HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipGetLastError());
 #ifdef PO_STAMPS
-    if (!wide) {
-        std::vector<unsigned long long> dbg(4096 * 8);
-        HIP_TRY(h, hipMemcpyAsync(dbg.data(), h->d_flag.p, dbg.size() * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        double sum[6] = {0, 0, 0, 0, 0, 0};
-        for (size_t w = 0; w < 4096; ++w) for (int k = 0; k < 6; ++k) sum[k] += (double)dbg[w * 8 + k];
-        if (sum[5] > 0)
-            std::fprintf(stderr, "[stamps] per pass (cycles): wait_rw %.0f  filter %.0f  wait_probe %.0f  consume %.0f  issue %.0f  (passes %.0f)\n",
-                         sum[0] / sum[5], sum[1] / sum[5], sum[2] / sum[5], sum[3] / sum[5], sum[4] / sum[5], sum[5]);
-    }
+        if (!wide) {
+            std::vector<unsigned long long> dbg(4096 * 8);
+            HIP_TRY(h, hipMemcpyAsync(dbg.data(), h->d_flag.p, dbg.size() * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            double sum[6] = {0, 0, 0, 0, 0, 0};
+            for (size_t w = 0; w < 4096; ++w) for (int k = 0; k < 6; ++k) sum[k] += (double)dbg[w * 8 + k];
+            if (sum[5] > 0)
+                std::fprintf(stderr, "[stamps] per pass (cycles): wait_rw %.0f  filter %.0f  wait_probe %.0f  consume %.0f  issue %.0f  (passes %.0f)\n",
+                             sum[0] / sum[5], sum[1] / sum[5], sum[2] / sum[5], sum[3] / sum[5], sum[4] / sum[5], sum[5]);
+        }
 #endif
-    // ---- a piece of a streamed step whose candidate count is PREDICTED (the same piece of the previous call): nothing
+        return PO_OK;
+    }
+
+    // ---- the candidate count: tile offsets by prefix sum, then the number itself -- waited for, or PREDICTED.
+    // A piece of a streamed step whose candidate count is predicted (the same piece of the previous call): nothing
     // waits for the counting pass -- the kernels behind it are launched at once, sized for `cap_c` candidates, and read
     // the real count on the device (CandGuard); the host learns it with the piece's other numbers when it collects the
     // piece.  Needs every per-piece buffer to hold cap_c already (a re-allocation would synchronise the device).
-    const int zone = 64 + 16 * (int)(shard & 1u);   // this piece's slots of the pinned landing area
-    uint32_t cap_c = 0;
-    bool async_count = false, pred_order = true;
-    if (streamed && h->st_harvest && h->st_pred_valid && !dp && !want_cands && !getenv("PHASM_SYNC_COUNT") && !getenv("PHASM_TAIL_CLASSIC")) {
-        uint64_t pred = h->st_pred_cand[shard];
-        uint64_t cap = pred + pred / 50 + 256;
-        if (const char* e = getenv("PHASM_PRED_SCALE")) cap = pred = (uint64_t)((double)pred * atof(e));   // (tests: a prediction that is too small)
-        const uint64_t worst = cap * 4u;
-        bool order = pred >= 400000 && (r_end - r_begin) >= 4096;
-        if (const char* e = getenv("PHASM_VERIFY_ORDER")) order = atoi(e) != 0;
-        pred_order = order;
-        auto fits = [](const DevBuf& b, uint64_t bytes) { return b.p && b.cap >= bytes; };
-        async_count = pred > 0 && cap < (16u << 20) && cdiv(cap, po::TAIL_TILE) <= po::TAIL_MAX_TILES &&
-                      fits(h->d_cand_a, cap * 4) && fits(h->d_cand_p, cap * 4) && fits(h->d_cand_b, cap * 4) && fits(h->d_type, cap) &&
-                      fits(h->d_rowcnt, cap) && fits(h->d_row_off, (cap + 1) * 4) &&
-                      fits(h->spare_rows, h->home_on ? cap * sizeof(po::Cand) : worst * sizeof(po_row)) &&
-                      (!order || (fits(h->d_vlabel, (uint64_t)(r_end - r_begin) * 4) && fits(h->d_vperm, (uint64_t)(r_end - r_begin) * 4) &&
-                                  fits(h->d_vrank, (uint64_t)(r_end - r_begin) * 4))) && h->dev_words < 0xFFFFFFF0ull;
-        cap_c = (uint32_t)cap;
-    }
-    volatile uint64_t* count_slot = async_count ? &h->pinned[zone + 8] : &h->pinned[1];
-    volatile uint64_t* also_slot = async_count ? &h->pinned[zone + 9] : &h->pinned[8];
-    if (ntiles <= po::PS_SMALL_MAX) {
-        PO_TRY(prefix_sum_small(h, A.tile_count + tile_begin, wide ? nullptr : A.tile_extra + tile_begin, ntiles,
-                                tile_off_p + tile_begin, count_slot,
-                                reinterpret_cast<const uint64_t*>(scalars + 2), also_slot, st, reinterpret_cast<uint64_t*>(scalars)));
-    } else {
-        PO_TRY(prefix_sum<uint32_t>(h, A.tile_count + tile_begin, ntiles, tile_off_p + tile_begin, count_slot,
-                                    reinterpret_cast<const uint64_t*>(scalars + 2), also_slot,
-                                    wide ? nullptr : A.tile_extra + tile_begin, st, reinterpret_cast<uint64_t*>(scalars)));
-    }
-    if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_COUNT], st));
-    po::CandGuard G = {nullptr, 0u};
-    uint64_t n_cand64;
-    uint32_t n_selfrep_reads;
-    if (async_count) {
-        // (sizes and grids below are for cap_c candidates; the kernels read the real number from scalars[0])
-        n_cand64 = cap_c;
-        n_selfrep_reads = 0;
-        S.n_predicted = 1;
-        G.n_dev = scalars;
-        G.cap = cap_c;
-    } else {
-        if (h->st_pend.valid && h->st_harvest) {
-            // the previous piece of a streamed step returned with its kernels queued; this piece's counting pass is queued
-            // behind them now.  Wait for the previous piece alone, send its rows home, THEN wait for this piece's count:
-            // the device is never idle while the host does that, and the rows leave the moment they exist
-            HIP_TRY(h, hipEventSynchronize(h->st_pend.ev[EV_DONE]));
-            PO_TRY(h->st_harvest());
+    po_status candidate_count() {
+        if (a.streamed && h->st_harvest && h->st_pred_valid && !a.dp && !a.want_cands && !sw.sync_count && !sw.tail_classic) {
+            uint64_t pred = h->st_pred_cand[a.shard];
+            uint64_t cap = pred + pred / 50 + 256;
+            if (sw.pred_scale) cap = pred = (uint64_t)((double)pred * atof(sw.pred_scale));
+            const uint64_t worst = cap * 4u;
+            bool order = pred >= 400000 && (r_end - r_begin) >= 4096;
+            if (sw.verify_order) order = atoi(sw.verify_order) != 0;
+            pred_order = order;
+            auto fits = [](const DevBuf& b, uint64_t bytes) { return b.p && b.cap >= bytes; };
+            async_count = pred > 0 && cap < (16u << 20) && cdiv(cap, po::TAIL_TILE) <= po::TAIL_MAX_TILES &&
+                          fits(h->d_cand_a, cap * 4) && fits(h->d_cand_p, cap * 4) && fits(h->d_cand_b, cap * 4) && fits(h->d_type, cap) &&
+                          fits(h->d_rowcnt, cap) && fits(h->d_row_off, (cap + 1) * 4) &&
+                          fits(h->spare_rows, h->home_on ? cap * sizeof(po::Cand) : worst * sizeof(po_row)) &&
+                          (!order || (fits(h->d_vlabel, (uint64_t)(r_end - r_begin) * 4) && fits(h->d_vperm, (uint64_t)(r_end - r_begin) * 4) &&
+                                      fits(h->d_vrank, (uint64_t)(r_end - r_begin) * 4))) && h->dev_words < 0xFFFFFFF0ull;
+            cap_c = (uint32_t)cap;
         }
-        HIP_TRY(h, hipStreamSynchronize(st));
-        n_cand64 = h->pinned[1];
-        n_selfrep_reads = (uint32_t)h->pinned[8];
+        volatile uint64_t* count_slot = async_count ? &h->pinned[zone + 8] : &h->pinned[1];
+        volatile uint64_t* also_slot = async_count ? &h->pinned[zone + 9] : &h->pinned[8];
+        if (ntiles <= po::PS_SMALL_MAX) {
+            PO_TRY(prefix_sum_small(h, A.tile_count + tile_begin, wide ? nullptr : A.tile_extra + tile_begin, ntiles,
+                                    tile_off_p + tile_begin, count_slot,
+                                    reinterpret_cast<const uint64_t*>(scalars + 2), also_slot, st, reinterpret_cast<uint64_t*>(scalars)));
+        } else {
+            PO_TRY(prefix_sum<uint32_t>(h, A.tile_count + tile_begin, ntiles, tile_off_p + tile_begin, count_slot,
+                                        reinterpret_cast<const uint64_t*>(scalars + 2), also_slot,
+                                        wide ? nullptr : A.tile_extra + tile_begin, st, reinterpret_cast<uint64_t*>(scalars), a));
+        }
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_COUNT], st));
+        if (async_count) {
+            // (sizes and grids below are for cap_c candidates; the kernels read the real number from scalars[0])
+            n_cand64 = cap_c;
+            n_selfrep_reads = 0;
+            S.n_predicted = 1;
+            G.n_dev = scalars;
+            G.cap = cap_c;
+        } else {
+            if (h->st_pend.valid && h->st_harvest) {
+                // the previous piece of a streamed step returned with its kernels queued; this piece's counting pass is queued
+                // behind them now.  Wait for the previous piece alone, send its rows home, THEN wait for this piece's count:
+                // the device is never idle while the host does that, and the rows leave the moment they exist
+                HIP_TRY(h, hipEventSynchronize(h->st_pend.ev[EV_DONE]));
+                PO_TRY(h->st_harvest());
+            }
+            HIP_TRY(h, hipStreamSynchronize(st));
+            n_cand64 = h->pinned[1];
+            n_selfrep_reads = (uint32_t)h->pinned[8];
+        }
+        if (own_lists || dpE) n_selfrep_reads |= 1u;  // k_select_local may hand repetitive reads to the global selection
+        S.n_candidates = n_cand64;
+        if (n_cand64 >= 0xFFFFFF00ull)
+            return fail(h, PO_ERR_CAPACITY, "candidate count " + std::to_string(n_cand64) + " exceeds one call's capacity (2^32)");
+        n_cand = (uint32_t)n_cand64;
+        worst_rows = (uint64_t)n_cand * (paired ? 4u : 2u);
+        return PO_OK;
     }
-    if (nshards > 1 || streamed || wide || dpE) n_selfrep_reads |= 1u;  // k_select_local may hand repetitive reads to the global selection
-    S.n_candidates = n_cand64;
-    if (n_cand64 >= 0xFFFFFF00ull)
-        return fail(h, PO_ERR_CAPACITY, "candidate count " + std::to_string(n_cand64) + " exceeds one call's capacity (2^32)");
-    const uint32_t n_cand = (uint32_t)n_cand64;
 
-    uint64_t n_rows64 = 0;
-    // (the tail's variables live at function scope: classic_tail may run after the block below, as k_tail's fallback)
-    po::PairSlot* ptab = nullptr;
-    uint32_t pbits = 0;
-    uint32_t* n_deferred = reinterpret_cast<uint32_t*>(scalars + 1) + 1;  // reads k_select_local hands to the global table
-    const uint32_t* gate = nullptr;
-    const uint64_t worst_rows = (uint64_t)n_cand * (paired ? 4u : 2u);
-    std::function<po_status()> classic_tail;
-    // the longest-only selection inside each read's list runs in the verify kernel's epilogue where the exact verify runs
-    // (not the DP kernels, which have no per-read workgroup); PHASM_SELECT_KERNEL=1 keeps the separate launch (tests compare)
-    const bool sel_in_verify = (nshards > 1 || streamed || wide) && !dp && !getenv("PHASM_SELECT_KERNEL");
-    if (n_cand) {
-        PO_TRY(ensure_piece(h, h->d_cand_a, (size_t)n_cand * 4));
-        PO_TRY(ensure_piece(h, h->d_cand_p, (size_t)n_cand * 4));
-        PO_TRY(ensure_piece(h, h->d_cand_b, (size_t)n_cand * 4));
-        PO_TRY(ensure_piece(h, h->d_type, (size_t)n_cand));
-        PO_TRY(ensure_piece(h, h->d_rowcnt, (size_t)n_cand));
-        PO_TRY(ensure_piece(h, h->d_row_off, ((size_t)n_cand + 1) * 4));
+    // ---- scan, fill pass; containment candidates whose b has not arrived go onto the deferred list
+    po_status scan_fill() {
+        PO_TRY(ws_piece(h->d_cand_a, (size_t)n_cand * 4));
+        PO_TRY(ws_piece(h->d_cand_p, (size_t)n_cand * 4));
+        PO_TRY(ws_piece(h->d_cand_b, (size_t)n_cand * 4));
+        PO_TRY(ws_piece(h->d_type, (size_t)n_cand));
+        PO_TRY(ws_piece(h->d_rowcnt, (size_t)n_cand));
+        PO_TRY(ws_piece(h->d_row_off, ((size_t)n_cand + 1) * 4));
         A.cand_a = h->d_cand_a.as<uint32_t>();
         A.cand_p = h->d_cand_p.as<uint32_t>();
         A.cand_b = h->d_cand_b.as<uint32_t>();
-        // ---- scan, fill pass
         if (wide) {
             WA.cand_a = A.cand_a;
             WA.cand_p = A.cand_p;
             WA.cand_b = A.cand_b;
-            auto wfill = streamed ? (ww == 4 ? po::k_wide_scan<BITS, true, BITS == 2, 4> : po::k_wide_scan<BITS, true, BITS == 2, 1>)
+            auto wfill = a.streamed ? (ww == 4 ? po::k_wide_scan<BITS, true, BITS == 2, 4> : po::k_wide_scan<BITS, true, BITS == 2, 1>)
                          : ww == 16 ? po::k_wide_scan<BITS, true, false, 16> : ww == 4 ? po::k_wide_scan<BITS, true, false, 4> : po::k_wide_scan<BITS, true, false, 1>;
             hipLaunchKernelGGL(wfill, dim3(cdiv(ntiles, 4)), dim3(256), 0, st, WA, G);
         } else {
-            auto fill = streamed ? po::k_scan_fill<BITS, BITS == 2> : po::k_scan_fill<BITS, false>;
+            auto fill = a.streamed ? po::k_scan_fill<BITS, BITS == 2> : po::k_scan_fill<BITS, false>;
             hipLaunchKernelGGL(fill, dim3(cdiv(ntiles, 4 * po::FILL_TILES)), dim3(256), 0, st, A, G);
         }
         // locality order of the a-side reads (k_read_label): worth its ~50 us only when the verify is long
-        const bool use_order_early = [&]() {
-            bool u = n_cand >= 400000 && (r_end - r_begin) >= 4096;
-            if (const char* e = getenv("PHASM_VERIFY_ORDER")) u = atoi(e) != 0;
-            if (async_count) u = pred_order;   // (decided from the predicted count, before anything was launched)
-            return u && !dp;
-        }();
-        const bool defer_needed = streamed && r_end < n;
-        if (defer_needed && !use_order_early) {
+        use_order = n_cand >= 400000 && (r_end - r_begin) >= 4096;
+        if (sw.verify_order) use_order = atoi(sw.verify_order) != 0;
+        if (async_count) use_order = pred_order;   // (decided from the predicted count, before anything was launched)
+        use_order = use_order && !a.dp;
+        defer_needed = a.streamed && r_end < n;
+        if (defer_needed && !use_order) {
             // containment candidates whose b has not arrived: onto the deferred list (the verify kernel skips them);
             // when the locality order is computed, k_read_label's walk over the candidates does this on the way
             hipLaunchKernelGGL(po::k_defer_split, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b, n_cand,
                                r_end, h->d_defer.as<po::Cand>(), h->st_defer_cap, h->d_defer.as<uint32_t>() + (size_t)h->st_defer_cap * 4, G);
         }
         HIP_TRY(h, hipGetLastError());
-        if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_FILL], st));
-        // ---- verify
-        if (dp) {
-            // banded seed-extension DP, one wave per candidate (extend.hip.h); max_diff = 0 gives the packed compare's answer
-            if (2ull * h->max_len + 64ull >= (1ull << 30))   // (the kernel's "infinity" plus the longest sweep must fit 32 bits)
-                return fail(h, PO_ERR_CAPACITY, "po_overlaps_ex: reads of 2^29 bases or more are beyond the DP kernel");
-            PO_TRY(ensure(h, h->d_end_a, (size_t)n_cand * 4));
-            PO_TRY(ensure(h, h->d_end_b, (size_t)n_cand * 4));
-            PO_TRY(ensure(h, h->d_dpcnt, 64));
-            HIP_TRY(h, hipMemsetAsync(h->d_dpcnt.p, 0, 64, st));
-            po::ExtArgs X = {};
-            X.words = words;
-            X.woff = woff;
-            X.len = len;
-            X.cand_a = A.cand_a;
-            X.cand_p = A.cand_p;
-            X.cand_b = A.cand_b;
-            X.n_cand = n_cand;
-            X.max_diff = dpE;
-            X.band = dpW;
-            X.paired = paired;
-            X.exc_off = h->n_exc_uploaded ? h->d_exc_off.as<uint32_t>() : nullptr;
-            X.exc_pos = h->d_exc_pos.as<uint32_t>();
-            X.exc_byte = h->d_exc_byte.as<uint8_t>();
-            X.type = h->d_type.as<uint8_t>();
-            X.end_a = h->d_end_a.as<uint32_t>();
-            X.end_b = h->d_end_b.as<uint32_t>();
-            X.counters = h->d_dpcnt.as<unsigned long long>();
-            // two mappings of the same DP (extend.hip.h): a LANE per candidate (2-bit reads, band <= 15: the one an
-            // overlap job wants -- millions of candidates, narrow bands), or a WAVE per candidate with a lane per
-            // diagonal (any encoding, band <= 30); PHASM_DP_KERNEL=wave|lanes forces one (tests run both)
-            // three mappings of the same DP (extend.hip.h), same rows bit for bit: a LANE per candidate with the band row as a
-            // BIT VECTOR (k_extend_bits: 2-bit reads, band <= 15 -- the default where it applies), a lane per candidate with
-            // the band row in registers (k_extend_lanes), a WAVE per candidate with a lane per diagonal (k_extend_dp: any
-            // encoding, band <= 30).  PHASM_DP_KERNEL=bits|lanes|wave forces one (the tests run all three)
-            bool lanes = BITS == 2 && dpW <= 15;
-            bool bitvec = lanes;
-            if (const char* e = getenv("PHASM_DP_KERNEL")) {
-                if (!strcmp(e, "wave")) lanes = bitvec = false;
-                if (!strcmp(e, "lanes")) bitvec = false;
-                if ((!strcmp(e, "lanes") || !strcmp(e, "bits")) && !(BITS == 2 && dpW <= 15))
-                    return fail(h, PO_ERR_INVALID, "PHASM_DP_KERNEL=lanes|bits needs 2-bit reads and band <= 15");
-            }
-            if (const char* e = getenv("PHASM_DP_KERNEL_SOFT"))   // (tests: "lanes" where a lane mapping applies at all, no error elsewhere)
-                if (!strcmp(e, "lanes")) bitvec = false;
-            S.dp_lanes = bitvec ? 2u : lanes ? 1u : 0u;
-            if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER0], st));
-            if (lanes) {
-                // candidates ordered by the rows they need, so that the 64 lanes of a wave finish together
-                const uint32_t* perm = nullptr;
-                bool sorted = n_cand >= 4096;
-                if (const char* e = getenv("PHASM_DP_SORT")) sorted = atoi(e) != 0;   // (tests force it on small inputs)
-                if (sorted) {
-                    const uint32_t max_bins = (uint32_t)((std::min<size_t>(h->lds_max, 160 * 1024) - 1024) / 4);
-                    const uint32_t max_rows = h->max_len + dpW;
-                    uint32_t shift = 0;
-                    while ((max_rows >> shift) + 1 > max_bins) ++shift;
-                    const uint32_t n_bins = (max_rows >> shift) + 1;
-                    const size_t sort_lds = ((size_t)n_bins + po::SORT_BLOCK / 64) * 4;
-                    PO_TRY(ensure(h, h->d_vlabel, (size_t)n_cand * 4));
-                    PO_TRY(ensure(h, h->d_vrank, (size_t)n_cand * 4));
-                    PO_TRY(ensure(h, h->d_vperm, (size_t)n_cand * 4));
-                    hipLaunchKernelGGL(po::k_dp_rows, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b, len, n_cand,
-                                       dpW, h->d_vlabel.as<uint32_t>());
-                    if (sort_lds > 48 * 1024)
-                        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(po::k_read_sort),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
-                    hipLaunchKernelGGL(po::k_read_sort, dim3(1), dim3(po::SORT_BLOCK), sort_lds, st, h->d_vlabel.as<uint32_t>(), n_cand,
-                                       shift, n_bins, h->d_vrank.as<uint32_t>());
-                    hipLaunchKernelGGL(po::k_read_invert, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, h->d_vrank.as<uint32_t>(), n_cand, 0u,
-                                       h->d_vperm.as<uint32_t>());
-                    perm = h->d_vperm.as<uint32_t>();
-                }
-                auto kern = bitvec ? po::k_extend_bits : dpW <= 4 ? po::k_extend_lanes<4> : dpW <= 8 ? po::k_extend_lanes<8> : po::k_extend_lanes<15>;
-                hipLaunchKernelGGL(kern, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, X, perm);
-            } else {
-                hipLaunchKernelGGL((po::k_extend_dp<BITS>), dim3(cdiv(n_cand, 256 / po::WAVE)), dim3(256), 0, st, X);
-            }
-            if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER1], st));
-            HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, h->d_dpcnt.p, 16, hipMemcpyDeviceToHost, st));
-            ver_timed = true;
-        } else {
-            // a's words live in LDS (read length + 3 guard words); reads too long for 64 KB use the global path
-            const uint64_t need_words = ((uint64_t)h->max_len + W - 1) / W + 3;
-            const uint32_t lds_words_raw = (uint32_t)std::min<uint64_t>(need_words, 8192 - 1100);  // (room for the records in 64 KB)
-            const uint32_t n_a = r_end - r_begin;
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_FILL], st));
+        return PO_OK;
+    }
+
+    // ---- verify, po_overlaps_ex: banded seed-extension DP, one wave per candidate (extend.hip.h); max_diff = 0 gives the
+    // packed compare's answer
+    po_status verify_dp() {
+        if (2ull * h->max_len + 64ull >= (1ull << 30))   // (the kernel's "infinity" plus the longest sweep must fit 32 bits)
+            return fail(h, PO_ERR_CAPACITY, "po_overlaps_ex: reads of 2^29 bases or more are beyond the DP kernel");
+        PO_TRY(ws(h->d_end_a, (size_t)n_cand * 4));
+        PO_TRY(ws(h->d_end_b, (size_t)n_cand * 4));
+        PO_TRY(ws(h->d_dpcnt, 64));
+        HIP_TRY(h, hipMemsetAsync(h->d_dpcnt.p, 0, 64, st));
+        po::ExtArgs X = {};
+        X.words = words;
+        X.woff = woff;
+        X.len = len;
+        X.cand_a = A.cand_a;
+        X.cand_p = A.cand_p;
+        X.cand_b = A.cand_b;
+        X.n_cand = n_cand;
+        X.max_diff = dpE;
+        X.band = dpW;
+        X.paired = paired;
+        X.exc_off = h->n_exc_uploaded ? h->d_exc_off.as<uint32_t>() : nullptr;
+        X.exc_pos = h->d_exc_pos.as<uint32_t>();
+        X.exc_byte = h->d_exc_byte.as<uint8_t>();
+        X.type = h->d_type.as<uint8_t>();
+        X.end_a = h->d_end_a.as<uint32_t>();
+        X.end_b = h->d_end_b.as<uint32_t>();
+        X.counters = h->d_dpcnt.as<unsigned long long>();
+        S.dp_lanes = dp_bitvec ? 2u : dp_lanes ? 1u : 0u;   // (which of the three mappings: plan())
+        if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER0], st));
+        if (dp_lanes) {
+            // candidates ordered by the rows they need, so that the 64 lanes of a wave finish together
             const uint32_t* perm = nullptr;
-            // (sharded calls too: 0.65 -> 0.51 ms at 2 shards, 0.19 -> 0.17 at 8 -- once the label of a read ranked by
-            // the scrambled order was turned back into a read index, see k_read_label)
-            const bool use_order = use_order_early;
-            if (use_order) {
-                // bins of label >> shift, as many as fit into one workgroup's LDS.  Labels are read indices
-                // (whole-set calls) or 32-bit scrambled ranks (sharded calls)
+            bool sorted = n_cand >= 4096;
+            if (sw.dp_sort) sorted = atoi(sw.dp_sort) != 0;
+            if (sorted) {
                 const uint32_t max_bins = (uint32_t)((std::min<size_t>(h->lds_max, 160 * 1024) - 1024) / 4);
-                uint32_t shift = 0, n_bins;
-                while ((n >> shift) + 1 > max_bins) ++shift;   // labels are read indices in both pairing modes
-                n_bins = (n >> shift) + 1;
+                const uint32_t max_rows = h->max_len + dpW;
+                uint32_t shift = 0;
+                while ((max_rows >> shift) + 1 > max_bins) ++shift;
+                const uint32_t n_bins = (max_rows >> shift) + 1;
                 const size_t sort_lds = ((size_t)n_bins + po::SORT_BLOCK / 64) * 4;
-                PO_TRY(ensure(h, h->d_vlabel, (size_t)n_a * 4));
-                PO_TRY(ensure(h, h->d_vperm, (size_t)n_a * 4));
-                po::DeferOut dfo = {};
-                if (defer_needed) {
-                    dfo.cand_p = A.cand_p;
-                    dfo.b_limit = r_end;
-                    dfo.list = h->d_defer.as<uint4>();
-                    dfo.cap = h->st_defer_cap;
-                    dfo.counter = h->d_defer.as<uint32_t>() + (size_t)h->st_defer_cap * 4;
-                }
-                hipLaunchKernelGGL(po::k_read_label, dim3(cdiv((uint64_t)n_a * 16, 256)), dim3(256), 0, st,
-                                   h->d_read_tile0.as<uint32_t>(), tile_off_p, A.cand_b, r_begin, n_a, paired,
-                                   h->d_vlabel.as<uint32_t>(), dfo, G);
+                PO_TRY(ws(h->d_vlabel, (size_t)n_cand * 4));
+                PO_TRY(ws(h->d_vrank, (size_t)n_cand * 4));
+                PO_TRY(ws(h->d_vperm, (size_t)n_cand * 4));
+                hipLaunchKernelGGL(po::k_dp_rows, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b, len, n_cand,
+                                   dpW, h->d_vlabel.as<uint32_t>());
                 if (sort_lds > 48 * 1024)
                     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(po::k_read_sort),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
-                PO_TRY(ensure(h, h->d_vrank, (size_t)n_a * 4));
-                hipLaunchKernelGGL(po::k_read_sort, dim3(1), dim3(po::SORT_BLOCK), sort_lds, st, h->d_vlabel.as<uint32_t>(), n_a,
+                hipLaunchKernelGGL(po::k_read_sort, dim3(1), dim3(po::SORT_BLOCK), sort_lds, st, h->d_vlabel.as<uint32_t>(), n_cand,
                                    shift, n_bins, h->d_vrank.as<uint32_t>());
-                hipLaunchKernelGGL(po::k_read_invert, dim3(cdiv(n_a, 256)), dim3(256), 0, st, h->d_vrank.as<uint32_t>(), n_a, r_begin,
+                hipLaunchKernelGGL(po::k_read_invert, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, h->d_vrank.as<uint32_t>(), n_cand, 0u,
                                    h->d_vperm.as<uint32_t>());
                 perm = h->d_vperm.as<uint32_t>();
             }
-            const uint32_t ver_grid = perm ? 8 * ((n_a + 7) / 8) : n_a;
-            // candidate records staged in LDS (word offsets must fit 32 bits); PHASM_VERIFY_STAGED=0 switches back
-            bool staged = h->dev_words < 0xFFFFFFF0ull;
-            if (const char* e = getenv("PHASM_VERIFY_STAGED")) staged = staged && atoi(e) != 0;
-            auto verify = paired == 2u ? (staged ? po::k_verify_a<BITS, true, true> : po::k_verify_a<BITS, true, false>)
-                                       : (staged ? po::k_verify_a<BITS, false, true> : po::k_verify_a<BITS, false, false>);
-            if (streamed) verify = staged ? po::k_verify_a<BITS, false, true, BITS == 2> : po::k_verify_a<BITS, false, false, BITS == 2>;
-            const uint32_t lds_words = (lds_words_raw + 1u) & ~1u;  // even: the records behind a sit on a 16-byte boundary
-            const size_t ver_lds = (size_t)lds_words * 8 + (size_t)po::VREC_CAP * sizeof(po::VRec) + 16;
-            if (ver_lds > 48 * 1024)
-                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(verify), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ver_lds));
-            if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER0], st));
-            hipLaunchKernelGGL(verify, dim3(ver_grid), dim3(po::VER_BLOCK), ver_lds, st,
-                               words, woff, len, h->d_read_tile0.as<uint32_t>(), tile_off_p, A.cand_p,
-                               A.cand_b, r_begin, lds_words, paired_ver,
-                               h->n_exc_uploaded ? h->d_exc_off.as<uint32_t>() : nullptr, h->d_exc_pos.as<uint32_t>(),
-                               h->d_exc_byte.as<uint8_t>(), h->d_type.as<uint8_t>(), perm, n_a, G,
-                               sel_in_verify ? selfrep : nullptr, sel_in_verify ? n_deferred : nullptr);
-            if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER1], st));
-            ver_timed = true;
+            auto kern = dp_bitvec ? po::k_extend_bits : dpW <= 4 ? po::k_extend_lanes<4> : dpW <= 8 ? po::k_extend_lanes<8> : po::k_extend_lanes<15>;
+            hipLaunchKernelGGL(kern, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, X, perm);
+        } else {
+            hipLaunchKernelGGL((po::k_extend_dp<BITS>), dim3(cdiv(n_cand, 256 / po::WAVE)), dim3(256), 0, st, X);
         }
+        if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER1], st));
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 32, h->d_dpcnt.p, 16, hipMemcpyDeviceToHost, st));
+        return PO_OK;
+    }
+
+    // ---- verify, exact: one workgroup per a-side read
+    po_status verify_exact() {
+        // a's words live in LDS (read length + 3 guard words); reads too long for 64 KB use the global path
+        const uint64_t need_words = ((uint64_t)h->max_len + W - 1) / W + 3;
+        const uint32_t lds_words_raw = (uint32_t)std::min<uint64_t>(need_words, 8192 - 1100);  // (room for the records in 64 KB)
+        const uint32_t n_a = r_end - r_begin;
+        const uint32_t* perm = nullptr;
+        // (sharded calls too: 0.65 -> 0.51 ms at 2 shards, 0.19 -> 0.17 at 8 -- once the label of a read ranked by
+        // the scrambled order was turned back into a read index, see k_read_label)
+        if (use_order) {
+            // bins of label >> shift, as many as fit into one workgroup's LDS.  Labels are read indices
+            // (whole-set calls) or 32-bit scrambled ranks (sharded calls)
+            const uint32_t max_bins = (uint32_t)((std::min<size_t>(h->lds_max, 160 * 1024) - 1024) / 4);
+            uint32_t shift = 0, n_bins;
+            while ((n >> shift) + 1 > max_bins) ++shift;   // labels are read indices in both pairing modes
+            n_bins = (n >> shift) + 1;
+            const size_t sort_lds = ((size_t)n_bins + po::SORT_BLOCK / 64) * 4;
+            PO_TRY(ws(h->d_vlabel, (size_t)n_a * 4));
+            PO_TRY(ws(h->d_vperm, (size_t)n_a * 4));
+            po::DeferOut dfo = {};
+            if (defer_needed) {
+                dfo.cand_p = A.cand_p;
+                dfo.b_limit = r_end;
+                dfo.list = h->d_defer.as<uint4>();
+                dfo.cap = h->st_defer_cap;
+                dfo.counter = h->d_defer.as<uint32_t>() + (size_t)h->st_defer_cap * 4;
+            }
+            hipLaunchKernelGGL(po::k_read_label, dim3(cdiv((uint64_t)n_a * 16, 256)), dim3(256), 0, st,
+                               h->d_read_tile0.as<uint32_t>(), tile_off_p, A.cand_b, r_begin, n_a, paired,
+                               h->d_vlabel.as<uint32_t>(), dfo, G);
+            if (sort_lds > 48 * 1024)
+                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(po::k_read_sort),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
+            PO_TRY(ws(h->d_vrank, (size_t)n_a * 4));
+            hipLaunchKernelGGL(po::k_read_sort, dim3(1), dim3(po::SORT_BLOCK), sort_lds, st, h->d_vlabel.as<uint32_t>(), n_a,
+                               shift, n_bins, h->d_vrank.as<uint32_t>());
+            hipLaunchKernelGGL(po::k_read_invert, dim3(cdiv(n_a, 256)), dim3(256), 0, st, h->d_vrank.as<uint32_t>(), n_a, r_begin,
+                               h->d_vperm.as<uint32_t>());
+            perm = h->d_vperm.as<uint32_t>();
+        }
+        const uint32_t ver_grid = perm ? 8 * ((n_a + 7) / 8) : n_a;
+        auto verify = paired == 2u ? (staged ? po::k_verify_a<BITS, true, true> : po::k_verify_a<BITS, true, false>)
+                                   : (staged ? po::k_verify_a<BITS, false, true> : po::k_verify_a<BITS, false, false>);
+        if (a.streamed) verify = staged ? po::k_verify_a<BITS, false, true, BITS == 2> : po::k_verify_a<BITS, false, false, BITS == 2>;
+        const uint32_t lds_words = (lds_words_raw + 1u) & ~1u;  // even: the records behind a sit on a 16-byte boundary
+        const size_t ver_lds = (size_t)lds_words * 8 + (size_t)po::VREC_CAP * sizeof(po::VRec) + 16;
+        if (ver_lds > 48 * 1024)
+            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(verify), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ver_lds));
+        if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER0], st));
+        hipLaunchKernelGGL(verify, dim3(ver_grid), dim3(po::VER_BLOCK), ver_lds, st,
+                           words, woff, len, h->d_read_tile0.as<uint32_t>(), tile_off_p, A.cand_p,
+                           A.cand_b, r_begin, lds_words, paired_ver,
+                           h->n_exc_uploaded ? h->d_exc_off.as<uint32_t>() : nullptr, h->d_exc_pos.as<uint32_t>(),
+                           h->d_exc_byte.as<uint8_t>(), h->d_type.as<uint8_t>(), perm, n_a, G,
+                           sel_in_verify ? selfrep : nullptr, sel_in_verify ? n_deferred : nullptr);
+        if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VER1], st));
+        return PO_OK;
+    }
+
+    // ---- select inside each read's own list (where the verify kernel has not done it), then which tail
+    po_status select_local() {
+        ver_timed = true;
         HIP_TRY(h, hipGetLastError());
 #ifdef PO_VSTAMPS
         {
@@ -2385,9 +2511,8 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
                              sum[0] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6], sum[4] / sum[6], sum[5] / sum[6], sum[7] / sum[5], sum[6]);
         }
 #endif
-        if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VERIFY], st));
-        // ---- select + row offsets
-        if ((nshards > 1 || streamed || wide || dpE) && !sel_in_verify) {
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VERIFY], st));
+        if ((own_lists || dpE) && !sel_in_verify) {
             static_assert(po::SEL_CAP == 512, "k_select_local hashes to 9 bits");
             hipLaunchKernelGGL(po::k_select_local, dim3(cdiv(r_end - r_begin, 256 / po::WAVE)), dim3(256), 0, st,
                                h->d_read_tile0.as<uint32_t>(), tile_off_p, A.cand_p, A.cand_b, h->d_type.as<uint8_t>(),
@@ -2397,29 +2522,71 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
         // call holds that many, the rows are written without asking the host for their number first.
         // ---- the tail in ONE launch (k_tail: rows per candidate, their prefix sum, the rows, the counters) when the kept
         // row buffer holds the worst case and no global (a, b) table is needed -- or only a gated one: if k_select_local
-        // hands a read over after all, k_tail writes nothing but a flag and the classic tail below runs instead
+        // hands a read over after all, k_tail writes nothing but a flag and the classic tail runs instead
         // (rows home in compact form -- h->home_on, po_overlaps_to_host -- : the tail writes one 16-byte record per verified
         // candidate, so its buffer needs n_cand records, not the worst case of rows; a call whose kept buffer is too small
         // makes one here -- never a piece with a predicted count, whose buffers were checked before anything was launched)
-        const bool home_tail_ok = h->home_on && !want_cands && !dpE && !getenv("PHASM_TAIL_CLASSIC") &&
-                                  (!n_selfrep_reads || ((nshards > 1 || streamed || wide) && n_cand < (16u << 20))) &&
+        const bool gated_ok = !n_selfrep_reads || (own_lists && n_cand < (16u << 20));
+        const bool home_tail_ok = h->home_on && !a.want_cands && !dpE && !sw.tail_classic && gated_ok &&
                                   cdiv(n_cand, po::TAIL_TILE) <= po::TAIL_MAX_TILES;
         if (home_tail_ok && !async_count && h->spare_rows.cap < (size_t)n_cand * sizeof(po::Cand))
-            PO_TRY(ensure(h, h->spare_rows, (size_t)n_cand * sizeof(po::Cand) + (streamed ? 65536 : 0), 1.0, false));
-        const bool compact_tail = home_tail_ok && h->spare_rows.p && h->spare_rows.cap >= (size_t)n_cand * sizeof(po::Cand);
-        const bool can_tail = compact_tail ||
-                              (!want_cands && !dpE && h->spare_rows.p && h->spare_rows.cap >= worst_rows * sizeof(po_row) &&
-                               (!n_selfrep_reads || ((nshards > 1 || streamed || wide) && n_cand < (16u << 20))) &&
-                               // (rows left in HBM, whole set: 6.5 M candidates are 0.02 ms faster through the classic kernels)
-                               cdiv(n_cand, po::TAIL_TILE) <= (streamed || h->home_on ? po::TAIL_MAX_TILES : 4096u) && !getenv("PHASM_TAIL_CLASSIC"));
+            PO_TRY(ws(h->spare_rows, (size_t)n_cand * sizeof(po::Cand) + (a.streamed ? 65536 : 0), false));
+        compact_tail = home_tail_ok && h->spare_rows.p && h->spare_rows.cap >= (size_t)n_cand * sizeof(po::Cand);
+        can_tail = compact_tail ||
+                   (!a.want_cands && !dpE && h->spare_rows.p && h->spare_rows.cap >= worst_rows * sizeof(po_row) && gated_ok &&
+                    // (rows left in HBM, whole set: 6.5 M candidates are 0.02 ms faster through the classic kernels)
+                    cdiv(n_cand, po::TAIL_TILE) <= (a.streamed || h->home_on ? po::TAIL_MAX_TILES : 4096u) && !sw.tail_classic);
         // (a piece with a predicted count has nothing but the fused tail: the classic kernels take the real count from the host)
         if (async_count && !can_tail) return fail(h, PO_ERR_HIP, "internal: a piece with a predicted candidate count needs the fused tail");
-        classic_tail = [&]() -> po_status {
+        return PO_OK;
+    }
+
+    // ---- the tail in one launch behind k_tile_rows
+    po_status fused_tail() {
+        const uint32_t n_tt = cdiv(n_cand, po::TAIL_TILE);
+        // [tile row sums x n_tt | done counter]; the counter is zero between launches (allocated zero, reset by k_tail)
+        if (((size_t)po::TAIL_MAX_TILES + 4) * 4 > h->d_tail_state.cap) {
+            PO_TRY(ws(h->d_tail_state, ((size_t)po::TAIL_MAX_TILES + 4) * 4));
+            HIP_TRY(h, hipMemsetAsync(h->d_tail_state.p, 0, h->d_tail_state.cap, st));
+        }
+        uint32_t* tile_rows = h->d_tail_state.as<uint32_t>();
+        uint32_t* tail_done = tile_rows + po::TAIL_MAX_TILES;
+        const uint32_t* tgate = n_selfrep_reads ? n_deferred : nullptr;
+        hipLaunchKernelGGL(compact_tail ? po::k_tile_rows<true> : po::k_tile_rows<false>, dim3(n_tt), dim3(po::TAIL_BLOCK), 0, st, A.cand_a,
+                           A.cand_b, h->d_type.as<uint8_t>(), n_cand, paired, tgate, tile_rows, G);
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
+        rows_late = true;
+        used_tail = true;
+        S.fused_tail = 1;
+        res->d_rows = h->spare_rows;
+        h->spare_rows = DevBuf();
+        tail_zone = async_count ? zone : 48;
+        h->pinned[tail_zone] = 0;
+        h->pinned[tail_zone + 7] = 0;
+        if (compact_tail) {
+            res->compact = true;
+            hipLaunchKernelGGL(po::k_tail_cands, dim3(n_tt), dim3(po::TAIL_BLOCK), 0, st, A.cand_a, A.cand_p, A.cand_b, h->d_type.as<uint8_t>(),
+                               n_cand, res->d_rows.as<po::Cand>(), paired, tgate, tile_rows, n_tt, tail_done,
+                               scalars + 3, h->pinned_dev + tail_zone, G, h->home_sh_b, h->home_sh_p);
+        } else
+        hipLaunchKernelGGL(po::k_tail, dim3(n_tt), dim3(po::TAIL_BLOCK), 0, st, A.cand_a, A.cand_p, A.cand_b, h->d_type.as<uint8_t>(),
+                           n_cand, len, res->d_rows.as<po::Row>(), (uint32_t)BITS, paired, tgate, tile_rows, n_tt, tail_done,
+                           scalars + 4, h->pinned_dev + tail_zone, G);
+        HIP_TRY(h, hipGetLastError());
+        return PO_OK;
+    }
+
+    // ---- the tail as separate kernels: global selection, row offsets, emit (or the compaction of the multi-GPU form)
+    po_status classic_tail() {
+        po::PairSlot* ptab = nullptr;
+        uint32_t pbits = 0;
+        const uint32_t* gate = nullptr;
+        uint64_t n_rows64 = 0;
         if (n_selfrep_reads) {
             // some read's prefix recurs inside it (or a read was too repetitive for k_select_local): A candidates
             // of such b may be non-longest duplicates
             uint32_t n_sus;
-            if ((nshards > 1 || streamed || wide) && n_cand < (4u << 20)) {
+            if (own_lists && n_cand < (4u << 20)) {
                 n_sus = n_cand;  // upper bound: no counting pass, no host round trip (a big call sizes its table exactly)
                 gate = n_deferred;  // ... and nothing of it is touched unless k_select_local handed a read over
             } else {
@@ -2433,7 +2600,7 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
             if (n_sus) {
                 pbits = 4;
                 while ((1ull << pbits) < 2ull * n_sus) ++pbits;
-                PO_TRY(ensure_piece(h, h->d_pair_key, ((size_t)1 << pbits) * sizeof(po::PairSlot)));
+                PO_TRY(ws_piece(h->d_pair_key, ((size_t)1 << pbits) * sizeof(po::PairSlot)));
                 hipLaunchKernelGGL(po::k_fill_gated, dim3((uint32_t)h->n_cu * 8), dim3(256), 0, st, h->d_pair_key.as<uint4>(),
                                    (uint64_t)((size_t)1 << pbits) * sizeof(po::PairSlot) / 16, 0xFFFFFFFFu, gate);
                 ptab = h->d_pair_key.as<po::PairSlot>();
@@ -2441,84 +2608,25 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
                                    h->d_type.as<uint8_t>(), n_cand, selfrep, ptab, pbits, gate);
             }
         }
-        if (want_cands) PO_TRY(ensure(h, h->d_flag, (size_t)n_cand));
+        if (a.want_cands) PO_TRY(ws(h->d_flag, (size_t)n_cand));
         hipLaunchKernelGGL(po::k_select, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b,
                            h->d_type.as<uint8_t>(), n_cand, selfrep, ptab, pbits, paired, h->d_rowcnt.as<uint8_t>(),
-                           want_cands ? h->d_flag.as<uint8_t>() : nullptr, gate);
+                           a.want_cands ? h->d_flag.as<uint8_t>() : nullptr, gate);
         HIP_TRY(h, hipGetLastError());
         // A candidate gives at most 2 rows (4 with their mirrors).  When the row buffer kept from an earlier call
         // holds that many, the rows are emitted without asking the host for their number first (one host round
         // trip less per step); the number arrives with the counters at the end.
-        if (!want_cands) {
-            PO_TRY(prefix_sum<uint8_t>(h, h->d_rowcnt.as<uint8_t>(), n_cand, h->d_row_off.as<uint32_t>(), &h->pinned[2]));
-            if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
+        if (!a.want_cands) {
+            PO_TRY(prefix<uint8_t>(h->d_rowcnt.as<uint8_t>(), n_cand, h->d_row_off.as<uint32_t>(), &h->pinned[2]));
+            if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
             rows_late = h->spare_rows.p && h->spare_rows.cap >= worst_rows * sizeof(po_row);
             if (!rows_late) {
                 HIP_TRY(h, hipStreamSynchronize(st));
                 n_rows64 = h->pinned[2];
                 if (n_rows64 >= 0xFFFFFF00ull) return fail(h, PO_ERR_CAPACITY, "row count exceeds one call's capacity (2^32)");
             }
-        }
-        if (want_cands) {
-            // ---- multi-GPU form: hand out the verified candidates (one per strand-mirror pair), compacted.  Where the
-            // destination is known to be large enough for what the call is expected to keep -- the caller's exchange slot,
-            // or a buffer kept from an earlier call that holds even the worst case -- the compaction is queued without
-            // asking the host for the number first (one host round trip less per shard call: ~40 us of ~0.5 ms at 8
-            // shards); the number arrives with the closing synchronisation, and a slot that turns out too small is
-            // handled there (cands_late below)
-            PO_TRY(prefix_sum<uint8_t>(h, h->d_flag.as<uint8_t>(), n_cand, h->d_row_off.as<uint32_t>(), &h->pinned[3]));
-            if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
-            po::Cand* dst;
-            uint64_t dst_cap;
-            if (res->ext_dst && res->ext_cap && !getenv("PHASM_COMPACT_SYNC")) {
-                dst = static_cast<po::Cand*>(res->ext_dst);  // straight into the caller's exchange buffer
-                dst_cap = res->ext_cap;
-                cands_late = true;
-                cands_ext = true;
-            } else if (h->spare_cands.p && h->spare_cands.cap >= (size_t)n_cand * sizeof(po::Cand) && !getenv("PHASM_COMPACT_SYNC")) {
-                res->d_rows = h->spare_cands;
-                h->spare_cands = DevBuf();
-                dst = res->d_rows.as<po::Cand>();
-                dst_cap = n_cand;
-                cands_late = true;
-            } else {
-                HIP_TRY(h, hipStreamSynchronize(st));
-                const uint64_t n_ver = h->pinned[3];
-                if (res->ext_dst && n_ver <= res->ext_cap) {
-                    dst = static_cast<po::Cand*>(res->ext_dst);
-                    res->wrote_ext = true;
-                } else {
-                    if (h->spare_cands.p && h->spare_cands.cap >= n_ver * sizeof(po::Cand)) {
-                        res->d_rows = h->spare_cands;
-                        h->spare_cands = DevBuf();
-                    }
-                    PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_ver * sizeof(po::Cand), 256), 1.0, false));
-                    dst = res->d_rows.as<po::Cand>();
-                }
-                dst_cap = n_ver;
-                n_rows64 = n_ver;
-            }
-            cands_cap = dst_cap;
-            hipLaunchKernelGGL(po::k_compact, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b,
-                               h->d_type.as<uint8_t>(), h->d_flag.as<uint8_t>(), h->d_row_off.as<uint32_t>(), n_cand, dst,
-                               (uint32_t)std::min<uint64_t>(dst_cap, 0xFFFFFFFFull));
-            HIP_TRY(h, hipGetLastError());
-            res->elem = sizeof(po::Cand);
-        } else {
             // ---- emit
-            if (rows_late || (h->spare_rows.cap >= n_rows64 * sizeof(po_row) && h->spare_rows.p)) {
-                res->d_rows = h->spare_rows;
-                h->spare_rows = DevBuf();
-            } else {
-                h->spare_rows.release();
-            }
-            if (!rows_late) {
-                // (room for the worst case up to 2 GiB, so that the next call of this size need not ask)
-                const size_t exact = n_rows64 * sizeof(po_row);
-                size_t roomy = worst_rows * sizeof(po_row) <= (2ull << 30) ? (size_t)(worst_rows * sizeof(po_row)) : 0;
-                if (roomy && streamed) roomy += 4096 * sizeof(po_row);   // (room for the next call's predicted count and its slack)
-                PO_TRY(ensure(h, res->d_rows, std::max<size_t>(std::max(exact, roomy), 256), 1.0, false));
-            }
+            PO_TRY(take_row_buffer(h, res, rows_late, n_rows64, worst_rows, a.streamed));
             if (dpE)
                 hipLaunchKernelGGL(po::k_emit_ex, dim3(std::min<uint32_t>(cdiv(n_cand, 256), (uint32_t)h->n_cu * 16)), dim3(256), 0,
                                    st, A.cand_a, A.cand_p, A.cand_b, h->d_type.as<uint8_t>(), h->d_end_a.as<uint32_t>(),
@@ -2529,131 +2637,164 @@ po_status run_overlaps(po_handle* h, uint32_t min_length, uint32_t shard, uint32
                                st, A.cand_a, A.cand_p, A.cand_b, h->d_type.as<uint8_t>(), h->d_row_off.as<uint32_t>(),
                                n_cand, len, res->d_rows.as<po::Row>(), (uint32_t)BITS, paired, scalars + 4);
             HIP_TRY(h, hipGetLastError());
-        }
-        return PO_OK;
-        };
-        if (can_tail) {
-            const uint32_t n_tt = cdiv(n_cand, po::TAIL_TILE);
-            // [tile row sums x n_tt | done counter]; the counter is zero between launches (allocated zero, reset by k_tail)
-            if (((size_t)po::TAIL_MAX_TILES + 4) * 4 > h->d_tail_state.cap) {
-                PO_TRY(ensure(h, h->d_tail_state, ((size_t)po::TAIL_MAX_TILES + 4) * 4));
-                HIP_TRY(h, hipMemsetAsync(h->d_tail_state.p, 0, h->d_tail_state.cap, st));
-            }
-            uint32_t* tile_rows = h->d_tail_state.as<uint32_t>();
-            uint32_t* tail_done = tile_rows + po::TAIL_MAX_TILES;
-            const uint32_t* tgate = n_selfrep_reads ? n_deferred : nullptr;
-            hipLaunchKernelGGL(compact_tail ? po::k_tile_rows<true> : po::k_tile_rows<false>, dim3(n_tt), dim3(po::TAIL_BLOCK), 0, st, A.cand_a,
-                               A.cand_b, h->d_type.as<uint8_t>(), n_cand, paired, tgate, tile_rows, G);
-            if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
-            rows_late = true;
-            used_tail = true;
-            S.fused_tail = 1;
-            res->d_rows = h->spare_rows;
-            h->spare_rows = DevBuf();
-            tail_zone = async_count ? zone : 48;
-            h->pinned[tail_zone] = 0;
-            h->pinned[tail_zone + 7] = 0;
-            if (compact_tail) {
-                res->compact = true;
-                hipLaunchKernelGGL(po::k_tail_cands, dim3(n_tt), dim3(po::TAIL_BLOCK), 0, st, A.cand_a, A.cand_p, A.cand_b, h->d_type.as<uint8_t>(),
-                                   n_cand, res->d_rows.as<po::Cand>(), paired, tgate, tile_rows, n_tt, tail_done,
-                                   scalars + 3, h->pinned_dev + tail_zone, G, h->home_sh_b, h->home_sh_p);
-            } else
-            hipLaunchKernelGGL(po::k_tail, dim3(n_tt), dim3(po::TAIL_BLOCK), 0, st, A.cand_a, A.cand_p, A.cand_b, h->d_type.as<uint8_t>(),
-                               n_cand, len, res->d_rows.as<po::Row>(), (uint32_t)BITS, paired, tgate, tile_rows, n_tt, tail_done,
-                               scalars + 4, h->pinned_dev + tail_zone, G);
-            HIP_TRY(h, hipGetLastError());
-        } else {
-            PO_TRY(classic_tail());
-        }
-        tail_fallback = [&]() -> po_status {
-            // k_tail found reads handed to the global table: nothing was written -- the classic tail, now
-            h->spare_rows = res->d_rows;
-            res->d_rows = DevBuf();
-            res->compact = false;
-            rows_late = false;
-            used_tail = false;
-            S.fused_tail = 0;
-            S.tail_fallback = 1;
-            PO_TRY(classic_tail());
             return PO_OK;
-        };
-    } else {
-        if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_FILL], st));
-        if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VERIFY], st));
-        if (h->phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
-    }
-    if (h->pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_EMIT], st));
-    uint64_t* counters = h->pinned + 4;
-    if (!used_tail) HIP_TRY(h, hipMemcpyAsync(counters, scalars + 4, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    res->unique_twins = !want_cands && paired != 0 && !dpE;
-    HIP_TRY(h, hipEventRecord(h->ev[EV_DONE], st));
-    h->st_selfclean = streamed && self_clean && used_tail && !wide;   // (the next piece of this step may skip its reset)
-    if (async_count && h->st_pend.valid) {
-        // everything of this piece is queued; now collect the piece before it (its numbers sit in the other zone)
-        HIP_TRY(h, hipEventSynchronize(h->st_pend.ev[EV_DONE]));
-        PO_TRY(h->st_harvest());
-    }
-    if (streamed && rows_late && h->st_harvest && !h->st_pend.valid) {
-        h->st_pend.tail = used_tail;
-        h->st_pend.compact = res->compact;
-        h->st_pend.zone = tail_zone;
-        h->st_pend.cap_c = async_count ? cap_c : 0u;
-        // a piece of a streamed step with its rows in a buffer known to be large enough: nothing here needs the host
-        // to wait -- the counts are read when the next piece waits for ITS candidate count (finish_piece)
-        h->st_pend.valid = true;
-        h->st_pend.k = shard;
-        h->st_pend.S = S;
-        h->st_pend.ver_timed = ver_timed;
-        h->st_pend.full_events = h->phase_events;
-        h->st_pend.pair_events = h->pair_events;
-        h->st_pend.ev = h->ev;
-        res->count = 0;
+        }
+        // ---- multi-GPU form: hand out the verified candidates (one per strand-mirror pair), compacted.  Where the
+        // destination is known to be large enough for what the call is expected to keep -- the caller's exchange slot,
+        // or a buffer kept from an earlier call that holds even the worst case -- the compaction is queued without
+        // asking the host for the number first (one host round trip less per shard call: ~40 us of ~0.5 ms at 8
+        // shards); the number arrives with the closing synchronisation, and a slot that turns out too small is
+        // handled there (cands_late, finish)
+        PO_TRY(prefix<uint8_t>(h->d_flag.as<uint8_t>(), n_cand, h->d_row_off.as<uint32_t>(), &h->pinned[3]));
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
+        po::Cand* dst;
+        uint64_t dst_cap;
+        if (res->ext_dst && res->ext_cap && !sw.compact_sync) {
+            dst = static_cast<po::Cand*>(res->ext_dst);  // straight into the caller's exchange buffer
+            dst_cap = res->ext_cap;
+            cands_late = true;
+            cands_ext = true;
+        } else if (h->spare_cands.p && h->spare_cands.cap >= (size_t)n_cand * sizeof(po::Cand) && !sw.compact_sync) {
+            res->d_rows = h->spare_cands;
+            h->spare_cands = DevBuf();
+            dst = res->d_rows.as<po::Cand>();
+            dst_cap = n_cand;
+            cands_late = true;
+        } else {
+            HIP_TRY(h, hipStreamSynchronize(st));
+            const uint64_t n_ver = h->pinned[3];
+            if (res->ext_dst && n_ver <= res->ext_cap) {
+                dst = static_cast<po::Cand*>(res->ext_dst);
+                res->wrote_ext = true;
+            } else {
+                if (h->spare_cands.p && h->spare_cands.cap >= n_ver * sizeof(po::Cand)) {
+                    res->d_rows = h->spare_cands;
+                    h->spare_cands = DevBuf();
+                }
+                PO_TRY(ws(res->d_rows, std::max<size_t>(n_ver * sizeof(po::Cand), 256), false));
+                dst = res->d_rows.as<po::Cand>();
+            }
+            dst_cap = n_ver;
+        }
+        cands_cap = dst_cap;
+        hipLaunchKernelGGL(po::k_compact, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b,
+                           h->d_type.as<uint8_t>(), h->d_flag.as<uint8_t>(), h->d_row_off.as<uint32_t>(), n_cand, dst,
+                           (uint32_t)std::min<uint64_t>(dst_cap, 0xFFFFFFFFull));
+        HIP_TRY(h, hipGetLastError());
+        res->elem = sizeof(po::Cand);
         return PO_OK;
     }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    if (async_count) return fail(h, PO_ERR_HIP, "internal: a piece with a predicted count must stay pending");
-    if (used_tail && h->pinned[tail_zone + 7]) {
-        PO_TRY(tail_fallback());
-        HIP_TRY(h, hipEventRecord(h->ev[EV_EMIT], st));
-        HIP_TRY(h, hipMemcpyAsync(counters, scalars + 4, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+
+    // k_tail found reads handed to the global table: nothing was written -- the classic tail, now
+    po_status tail_fallback() {
+        h->spare_rows = res->d_rows;
+        res->d_rows = DevBuf();
+        res->compact = false;
+        rows_late = false;
+        used_tail = false;
+        S.fused_tail = 0;
+        S.tail_fallback = 1;
+        return classic_tail();
+    }
+
+    // (a call without candidates still marks the boundaries of the stages it skipped)
+    po_status no_candidates() {
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_FILL], st));
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_VERIFY], st));
+        if (phase_events) HIP_TRY(h, hipEventRecord(h->ev[EV_SELECT], st));
+        return PO_OK;
+    }
+
+    // ---- the call's end: a piece of a streamed step with its rows in a kept buffer stays pending, any other call waits
+    // for its numbers here
+    po_status finish() {
+        if (pair_events) HIP_TRY(h, hipEventRecord(h->ev[EV_EMIT], st));
+        if (!used_tail) HIP_TRY(h, hipMemcpyAsync(h->pinned + 4, scalars + 4, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        res->unique_twins = !a.want_cands && paired != 0 && !dpE;
         HIP_TRY(h, hipEventRecord(h->ev[EV_DONE], st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-    }
-    if (cands_late) {
-        const uint64_t n_ver = h->pinned[3];
-        if (n_ver > cands_cap) {
-            // the exchange slot was too small for this shard (the caller sizes it from the previous step): once more, into
-            // a buffer of the library's own -- the candidate arrays, flags and offsets are all still in place
-            PO_TRY(ensure(h, res->d_rows, std::max<size_t>(n_ver * sizeof(po::Cand), 256), 1.0, false));
-            hipLaunchKernelGGL(po::k_compact, dim3(cdiv((uint32_t)S.n_candidates, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b,
-                               h->d_type.as<uint8_t>(), h->d_flag.as<uint8_t>(), h->d_row_off.as<uint32_t>(), (uint32_t)S.n_candidates,
-                               res->d_rows.as<po::Cand>(), (uint32_t)n_ver);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipStreamSynchronize(st));
-        } else if (cands_ext) {
-            res->wrote_ext = true;
+        h->st_selfclean = self_clean && used_tail;   // (the next piece of this step may skip its reset)
+        if (async_count && h->st_pend.valid) {
+            // everything of this piece is queued; now collect the piece before it (its numbers sit in the other zone)
+            HIP_TRY(h, hipEventSynchronize(h->st_pend.ev[EV_DONE]));
+            PO_TRY(h->st_harvest());
         }
-        n_rows64 = n_ver;
+        if (a.streamed && rows_late && h->st_harvest && !h->st_pend.valid) {
+            // a piece of a streamed step with its rows in a buffer known to be large enough: nothing here needs the host
+            // to wait -- the counts are read when the next piece waits for ITS candidate count (finish_piece)
+            po_handle::Pending& P = h->st_pend;
+            P.tail = used_tail;
+            P.compact = res->compact;
+            P.zone = tail_zone;
+            P.cap_c = async_count ? cap_c : 0u;
+            P.valid = true;
+            P.k = a.shard;
+            P.S = S;
+            P.ver_timed = ver_timed;
+            P.full_events = phase_events;
+            P.pair_events = pair_events;
+            P.ev = h->ev;
+            res->count = 0;
+            return PO_OK;
+        }
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if (async_count) return fail(h, PO_ERR_HIP, "internal: a piece with a predicted count must stay pending");
+        if (used_tail && h->pinned[tail_zone + 7]) {
+            PO_TRY(tail_fallback());
+            HIP_TRY(h, hipEventRecord(h->ev[EV_EMIT], st));
+            HIP_TRY(h, hipMemcpyAsync(h->pinned + 4, scalars + 4, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipEventRecord(h->ev[EV_DONE], st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+        }
+        if (cands_late) {
+            const uint64_t n_ver = h->pinned[3];
+            if (n_ver > cands_cap) {
+                // the exchange slot was too small for this shard (the caller sizes it from the previous step): once more, into
+                // a buffer of the library's own -- the candidate arrays, flags and offsets are all still in place
+                PO_TRY(ws(res->d_rows, std::max<size_t>(n_ver * sizeof(po::Cand), 256), false));
+                hipLaunchKernelGGL(po::k_compact, dim3(cdiv(n_cand, 256)), dim3(256), 0, st, A.cand_a, A.cand_p, A.cand_b,
+                                   h->d_type.as<uint8_t>(), h->d_flag.as<uint8_t>(), h->d_row_off.as<uint32_t>(), n_cand,
+                                   res->d_rows.as<po::Cand>(), (uint32_t)n_ver);
+                HIP_TRY(h, hipGetLastError());
+                HIP_TRY(h, hipStreamSynchronize(st));
+            } else if (cands_ext) {
+                res->wrote_ext = true;
+            }
+        }
+        // (the fused tail's numbers sit in its zone; the classic kernels' in slots 2 -- rows --, 3 -- candidates kept -- and 4..7)
+        const int rows_at = !n_cand ? -1 : used_tail ? tail_zone : a.want_cands ? 3 : 2;
+        res->count = close_stats(h, S, rows_at, used_tail ? tail_zone + 1 : 4, h->ev, ver_timed, phase_events, pair_events);
+        if (a.want_cands) {
+            S.n_verified = res->count;
+            S.n_rows = 0;
+        }
+        if (a.dp && n_cand64) {
+            S.dp_steps = h->pinned[32];
+            S.dp_stopped = h->pinned[33];
+        }
+        return PO_OK;
     }
-    if (used_tail) {
-        n_rows64 = h->pinned[tail_zone];
-        for (int k = 0; k < 4; ++k) counters[k] = h->pinned[tail_zone + 1 + k];
-    } else if (rows_late) {
-        n_rows64 = h->pinned[2];  // (<= worst_rows < 2^32 by construction of the fast path)
+};
+
+template <int BITS>
+po_status run_overlaps(po_handle* h, const OverlapArgs& a, po_result* res) {
+    OverlapCall<BITS> c(h, a, res);
+    bool done = false;
+    PO_TRY(c.plan(&done));
+    if (done) return PO_OK;
+    PO_TRY(c.workspaces());
+    PO_TRY(c.build_index(&done));
+    if (done) return PO_OK;
+    PO_TRY(c.scan_count());
+    PO_TRY(c.candidate_count());
+    if (c.n_cand) {
+        PO_TRY(c.scan_fill());
+        PO_TRY(a.dp ? c.verify_dp() : c.verify_exact());
+        PO_TRY(c.select_local());
+        PO_TRY(c.can_tail ? c.fused_tail() : c.classic_tail());
+    } else {
+        PO_TRY(c.no_candidates());
     }
-    res->count = n_rows64;
-    S.n_rows = want_cands ? 0 : n_rows64;
-    S.n_verified = want_cands ? n_rows64 : counters[0];
-    S.sum_overlap_bases = counters[1];
-    S.verify_bytes_algo = counters[2];
-    S.verify_bytes_exec = counters[3];
-    if (dp && n_cand64) {
-        S.dp_steps = h->pinned[32];
-        S.dp_stopped = h->pinned[33];
-    }
-    stage_times(S, h->ev, ver_timed, h->phase_events, h->pair_events);
-    return PO_OK;
+    return c.finish();
 }
 
 // rows from a (merged) verified-candidate array that lives on this device
@@ -2688,17 +2829,7 @@ po_status run_expand(po_handle* h, const void* d_cands, uint64_t n, po_result* r
         n_rows = h->pinned[2];
         if (n_rows >= 0xFFFFFF00ull) return fail(h, PO_ERR_CAPACITY, "row count exceeds one call's capacity (2^32)");
     }
-    if (rows_late || (h->spare_rows.cap >= n_rows * sizeof(po_row) && h->spare_rows.p)) {
-        res->d_rows = h->spare_rows;
-        h->spare_rows = DevBuf();
-    } else {
-        h->spare_rows.release();
-    }
-    if (!rows_late) {
-        const size_t exact = n_rows * sizeof(po_row);
-        const size_t roomy = worst_rows * sizeof(po_row) <= (2ull << 30) ? (size_t)(worst_rows * sizeof(po_row)) : 0;
-        PO_TRY(ensure(h, res->d_rows, std::max<size_t>(std::max(exact, roomy), 256), 1.0, false));
-    }
+    PO_TRY(take_row_buffer(h, res, rows_late, n_rows, worst_rows));
     HIP_TRY(h, hipMemsetAsync(h->d_scalars.p, 0, 64, st));
     hipLaunchKernelGGL(po::k_emit_cands, dim3(std::min<uint32_t>(cdiv(nc, 256), (uint32_t)h->n_cu * 16)), dim3(256), 0, st,
                        cands, h->d_rowcnt.as<uint8_t>(), h->d_row_off.as<uint32_t>(), nc, h->d_len.as<uint32_t>(),
@@ -4660,11 +4791,10 @@ po_status po_invalidate(po_handle* h) {
     return PO_OK;
 }
 
-static po_status overlaps_common(po_handle* h, uint32_t min_length, uint32_t shard, uint32_t nshards, bool want_cands,
-                                 po_result** out, void* ext_dst = nullptr, uint64_t ext_cap = 0) {
+static po_status overlaps_common(po_handle* h, const OverlapArgs& a, po_result** out, void* ext_dst = nullptr, uint64_t ext_cap = 0) {
     if (!h || !out) return PO_ERR_INVALID;
     *out = nullptr;
-    if (nshards == 0 || shard >= nshards) return fail(h, PO_ERR_INVALID, "shard must be < nshards");
+    if (a.nshards == 0 || a.shard >= a.nshards) return fail(h, PO_ERR_INVALID, "shard must be < nshards");
     if (h->segments_only) return fail(h, PO_ERR_INVALID, "this handle holds GFA segments without sequences: nothing to overlap");
     po_result* r = new (std::nothrow) po_result();
     if (!r) return fail(h, PO_ERR_NOMEM, "out of host memory");
@@ -4674,8 +4804,7 @@ static po_status overlaps_common(po_handle* h, uint32_t min_length, uint32_t sha
     po_status st;
     try {
         st = upload(h);
-        if (st == PO_OK) st = h->bits == 2 ? run_overlaps<2>(h, min_length, shard, nshards, want_cands, r)
-                                           : run_overlaps<8>(h, min_length, shard, nshards, want_cands, r);
+        if (st == PO_OK) st = h->bits == 2 ? run_overlaps<2>(h, a, r) : run_overlaps<8>(h, a, r);
     } catch (const std::bad_alloc&) {
         st = fail(h, PO_ERR_NOMEM, "out of host memory in po_overlaps");
     }
@@ -4691,18 +4820,18 @@ static po_status overlaps_common(po_handle* h, uint32_t min_length, uint32_t sha
 }
 
 po_status po_overlaps_shard(po_handle* h, uint32_t min_length, uint32_t shard, uint32_t nshards, po_result** out) {
-    return overlaps_common(h, min_length, shard, nshards, false, out);
+    return overlaps_common(h, OverlapArgs{min_length, shard, nshards, false}, out);
 }
 
 po_status po_candidates_shard(po_handle* h, uint32_t min_length, uint32_t shard, uint32_t nshards, po_result** out) {
-    return overlaps_common(h, min_length, shard, nshards, true, out);
+    return overlaps_common(h, OverlapArgs{min_length, shard, nshards, true}, out);
 }
 
 po_status po_candidates_shard_into(po_handle* h, uint32_t min_length, uint32_t shard, uint32_t nshards, void* dst_device,
                                    uint64_t capacity, int* written, po_result** out) {
     if (written) *written = 0;
     if (!dst_device && capacity) return PO_ERR_INVALID;
-    const po_status st = overlaps_common(h, min_length, shard, nshards, true, out, dst_device, capacity);
+    const po_status st = overlaps_common(h, OverlapArgs{min_length, shard, nshards, true}, out, dst_device, capacity);
     if (st == PO_OK && written) *written = (*out)->wrote_ext ? 1 : 0;
     return st;
 }
@@ -4925,7 +5054,8 @@ void add_stats(po_stats& sum, const po_stats& S) {
 }
 
 // chunk k of a call emits into its own device buffer (kept on the handle): it must outlive its copy
-po_status run_chunk(po_handle* h, uint32_t min_length, uint32_t k, uint32_t n_chunks, uint64_t* nk) {
+po_status run_chunk(po_handle* h, const OverlapArgs& a, uint64_t* nk) {
+    const uint32_t k = a.shard;
     po_result part;
     part.h = h;
     if (h->chunk_rows[k].p) {
@@ -4933,8 +5063,7 @@ po_status run_chunk(po_handle* h, uint32_t min_length, uint32_t k, uint32_t n_ch
         h->spare_rows = h->chunk_rows[k];
         h->chunk_rows[k] = DevBuf();
     }
-    const po_status st = h->bits == 2 ? run_overlaps<2>(h, min_length, k, n_chunks, false, &part)
-                                      : run_overlaps<8>(h, min_length, k, n_chunks, false, &part);
+    const po_status st = h->bits == 2 ? run_overlaps<2>(h, a, &part) : run_overlaps<8>(h, a, &part);
     h->chunk_rows[k] = part.d_rows;   // (run_overlaps returned: this chunk's rows are complete on the device)
     h->chunk_compact[k] = part.compact;
     part.d_rows = DevBuf();
@@ -4942,11 +5071,11 @@ po_status run_chunk(po_handle* h, uint32_t min_length, uint32_t k, uint32_t n_ch
     return st;
 }
 
-// May this call take the streamed form?  (the index flavour is decided as run_overlaps decides it)
+// May this call take the streamed form?
 bool stream_eligible(const po_handle* h, uint32_t min_length) {
     const uint32_t n = (uint32_t)h->len.size();
     if (!h->dirty || h->bits != 2 || n < 4 || (n % 2) != 0 || !h->all_pairs_rcx) return false;
-    if (h->asm_pieces || h->ex_on || h->sl_build_n > 1 || h->ext_index) return false;
+    if (h->asm_pieces) return false;
     if (getenv("PHASM_FULL_UPLOAD") || getenv("PHASM_NO_MIRROR")) return false;
     // (worth it from ~16 MB of packed even reads on: below that a piece's fixed cost, ~0.2 ms of small launches, is more
     // than the transfer time it hides)
@@ -5123,27 +5252,23 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
     // 2 M reads) building it inside piece 0 -- after the piece has landed -- kept every later piece 2-3 ms behind its data
     h->st_selfclean = false;
     h->st_early_index = P > 1 && h->poison < 0 && !getenv("PHASM_NO_INDEX_REUSE") && !getenv("PHASM_LATE_INDEX");
-    {
-        // words per read that travel ahead of the pieces: two, or five where the step will take the wide index and min_length
-        // allows windows of 4 (run_overlaps decides the same way: more than 160 k eligible reads, min_length >= 5 W - 1)
-        const uint32_t m = min_length ? min_length : 1;
-        const char* idx = getenv("PHASM_INDEX");
-        const char* win = getenv("PHASM_WIDE_WINDOW");
-        const bool wide = (idx && !strcmp(idx, "wide")) || (!(idx && !strcmp(idx, "narrow")) && count_eligible(h, m) > 160000);
-        h->st_lead = (h->bits == 2 && wide && m >= 32u * 4u + 31u && !(win && atoi(win) < 4) && !getenv("PHASM_STREAM_LEAD2")) ? LEAD_WORDS : 2u;
-    }
+    // words per read that travel ahead of the pieces: five where the pieces' index would use windows of 4 if it had them, else two
+    h->st_lead = index_flavour(h, min_length ? min_length : 1, true, LEAD_WORDS, OverlapSwitches()).ww >= 4 && !getenv("PHASM_STREAM_LEAD2") ? LEAD_WORDS : 2u;
     PO_TRY(stream_begin(h, bounds));
+    auto piece_args = [&](uint32_t k) {
+        OverlapArgs a{min_length, k, P};
+        a.streamed = true;
+        a.r_begin = bounds[k];
+        a.r_end = bounds[k + 1];
+        return a;
+    };
     if (trace) std::fprintf(stderr, "[stream] %u pieces queued at %.3f ms\n", P, since());
     if (h->st_early_index) {
         po_result part;
         part.h = h;
-        h->st_on = true;
-        h->st_r_begin = bounds[0];
-        h->st_r_end = bounds[1];
-        h->idx_only = true;
-        const po_status ist = run_overlaps<2>(h, min_length, 0, P, false, &part);
-        h->idx_only = false;
-        h->st_on = false;
+        OverlapArgs a = piece_args(0);
+        a.idx_only = true;
+        const po_status ist = run_overlaps<2>(h, a, &part);
         part.d_rows.release();
         if (ist != PO_OK) {
             (void)hipStreamSynchronize(h->stream);
@@ -5188,22 +5313,17 @@ po_status overlaps_streamed(po_handle* h, uint32_t min_length, HostRows& R, po_s
     for (uint32_t k = 0; k < P && st == PO_OK; ++k) {
         // piece k has landed and its odd reads (reverse complements) have been written next to it (rc_stream, stream_begin)
         if (hipStreamWaitEvent(h->stream, h->ev_rc[k], 0) != hipSuccess) { st = fail(h, PO_ERR_HIP, "hipStreamWaitEvent"); break; }
-        h->st_on = true;
-        h->st_r_begin = bounds[k];
-        h->st_r_end = bounds[k + 1];
+        OverlapArgs a = piece_args(k);
         // per-piece workspaces: sized for the largest piece when they are first needed.  A piece keeps the candidates
         // whose b lies below its a, so piece j has about (b[j+1]^2 - b[j]^2) / (b[k+1]^2 - b[k]^2) times piece k's
-        h->ws_scale = 1.0;
         {
             const double mine = (double)bounds[k + 1] * bounds[k + 1] - (double)bounds[k] * bounds[k];
             for (uint32_t j = k + 1; j < P; ++j)
-                h->ws_scale = std::max(h->ws_scale, ((double)bounds[j + 1] * bounds[j + 1] - (double)bounds[j] * bounds[j]) / mine * 1.1);
+                a.ws_scale = std::max(a.ws_scale, ((double)bounds[j + 1] * bounds[j + 1] - (double)bounds[j] * bounds[j]) / mine * 1.1);
         }
         h->ev = h->ev_sets[k & 1];
         uint64_t nk = 0;
-        st = run_chunk(h, min_length, k, P, &nk);
-        h->st_on = false;
-        h->ws_scale = 1.0;
+        st = run_chunk(h, a, &nk);
         if (st != PO_OK || tail_gave_up) break;
         if (h->st_pend.valid && h->st_pend.k == k) continue;   // piece k is queued, its counts are read later (an older one was collected inside)
         if (h->st_pend.valid) {
@@ -5356,7 +5476,7 @@ po_status po_overlaps_to_host(po_handle* h, uint32_t min_length, po_result** out
         if (st == PO_OK && !streamed) st = upload(h);
         for (uint32_t k = 0; k < n_chunks && st == PO_OK && !streamed; ++k) {
             uint64_t nk = 0;
-            st = run_chunk(h, min_length, k, n_chunks, &nk);
+            st = run_chunk(h, OverlapArgs{min_length, k, n_chunks}, &nk);
             if (st != PO_OK) break;
             add_stats(sum, h->stats);
             st = h->chunk_compact[k] ? append_home(h, R, h->chunk_rows[k], h->stats.n_verified, nk, k, n_chunks)
@@ -5365,7 +5485,6 @@ po_status po_overlaps_to_host(po_handle* h, uint32_t min_length, po_result** out
     } catch (const std::bad_alloc&) {
         st = fail(h, PO_ERR_NOMEM, "out of host memory in po_overlaps_to_host");
     }
-    h->st_on = false;
     h->st_harvest = nullptr;   // (an exception may have left the streamed step half way: its callback captures dead locals)
     h->st_pend.valid = false;
     h->ev = h->ev_sets[0];
@@ -5438,12 +5557,12 @@ po_status po_index_slice_build(po_handle* h, uint32_t min_length, uint32_t slice
     *is_wide = 0;
     *slice_bits = 0;
     *chain_entries = 0;
-    h->sl_build_slice = slice;
-    h->sl_build_n = n_slices;
+    OverlapArgs a{min_length};
+    a.build_slice = slice;
+    a.build_n = n_slices;
     h->sl_is_wide = false;
     po_result* r = nullptr;
-    const po_status st = overlaps_common(h, min_length, 0, 1, false, &r);
-    h->sl_build_n = 0;
+    const po_status st = overlaps_common(h, a, &r);
     if (r) po_result_free(r);
     if (st != PO_OK) return st;
     *is_wide = h->sl_is_wide ? 1u : 0u;
@@ -5469,6 +5588,20 @@ uint64_t po_index_chunk_bytes(uint32_t slice_bits, uint64_t chain_capacity, uint
     return (off + chain_capacity * 8ull + 255ull) & ~255ull;
 }
 
+// the gathered index of an *_indexed call as run_overlaps wants it described
+static po_status indexed_args(po_handle* h, const void* index_device, uint32_t n_slices, uint32_t slice_bits, uint64_t chain_capacity,
+                              OverlapArgs* a) {
+    uint64_t off = 0;
+    const uint64_t chunk = po_index_chunk_bytes(slice_bits, chain_capacity, &off);
+    if ((chunk / 16) * n_slices >= 0xFFFFFFF0ull) return fail(h, PO_ERR_CAPACITY, "sliced index larger than 64 GB");
+    a->ext_index = index_device;
+    a->ext_slices = n_slices;
+    a->ext_tbits = slice_bits;
+    a->ext_chunk_slots = (uint32_t)(chunk / 16);
+    a->ext_chain_off = (uint32_t)(off / 16);
+    return PO_OK;
+}
+
 po_status po_index_slice_export(po_handle* h, void* dst_device, uint64_t chain_capacity) {
     if (!h || !dst_device) return PO_ERR_INVALID;
     if (!h->sl_is_wide || !h->dev_ready) return fail(h, PO_ERR_INVALID, "po_index_slice_export: no sub-table has been built on this handle");
@@ -5491,16 +5624,9 @@ po_status po_candidates_shard_indexed(po_handle* h, uint32_t min_length, uint32_
     if (!slice_args_ok(n_slices, slice_bits, chain_capacity))
         return fail(h, PO_ERR_INVALID, "sliced index: need 2..4096 slices of 2^1..2^30 slots (slice_bits as po_index_slice_build reported it)");
     if (!dst_device && capacity) return PO_ERR_INVALID;
-    uint64_t off = 0;
-    const uint64_t chunk = po_index_chunk_bytes(slice_bits, chain_capacity, &off);
-    if ((chunk / 16) * n_slices >= 0xFFFFFFF0ull) return fail(h, PO_ERR_CAPACITY, "sliced index larger than 64 GB");
-    h->ext_index = index_device;
-    h->ext_slices = n_slices;
-    h->ext_tbits = slice_bits;
-    h->ext_chunk_slots = (uint32_t)(chunk / 16);
-    h->ext_chain_off = (uint32_t)(off / 16);
-    const po_status st = overlaps_common(h, min_length, shard, nshards, true, out, dst_device, capacity);
-    h->ext_index = nullptr;
+    OverlapArgs a{min_length, shard, nshards, true};
+    PO_TRY(indexed_args(h, index_device, n_slices, slice_bits, chain_capacity, &a));
+    const po_status st = overlaps_common(h, a, out, dst_device, capacity);
     if (st == PO_OK && written) *written = (*out)->wrote_ext ? 1 : 0;
     return st;
 }
@@ -5511,17 +5637,9 @@ po_status po_overlaps_shard_indexed(po_handle* h, uint32_t min_length, uint32_t 
     if (!h || !out || !index_device) return PO_ERR_INVALID;
     if (!slice_args_ok(n_slices, slice_bits, chain_capacity))
         return fail(h, PO_ERR_INVALID, "sliced index: need 2..4096 slices of 2^1..2^30 slots (slice_bits as po_index_slice_build reported it)");
-    uint64_t off = 0;
-    const uint64_t chunk = po_index_chunk_bytes(slice_bits, chain_capacity, &off);
-    if ((chunk / 16) * n_slices >= 0xFFFFFFF0ull) return fail(h, PO_ERR_CAPACITY, "sliced index larger than 64 GB");
-    h->ext_index = index_device;
-    h->ext_slices = n_slices;
-    h->ext_tbits = slice_bits;
-    h->ext_chunk_slots = (uint32_t)(chunk / 16);
-    h->ext_chain_off = (uint32_t)(off / 16);
-    const po_status st = overlaps_common(h, min_length, shard, nshards, false, out);
-    h->ext_index = nullptr;
-    return st;
+    OverlapArgs a{min_length, shard, nshards, false};
+    PO_TRY(indexed_args(h, index_device, n_slices, slice_bits, chain_capacity, &a));
+    return overlaps_common(h, a, out);
 }
 
 po_status po_overlaps_ex(po_handle* h, uint32_t min_length, uint32_t max_diff, uint32_t band, po_result** out) {
@@ -5529,12 +5647,11 @@ po_status po_overlaps_ex(po_handle* h, uint32_t min_length, uint32_t max_diff, u
     *out = nullptr;
     if (band > 30) return fail(h, PO_ERR_INVALID, "po_overlaps_ex: band must be <= 30 (2*band+1 diagonals on lanes 1..61, one lane each; lanes 0 and 63 let the bases in)");
     if (max_diff >= (1u << 16)) return fail(h, PO_ERR_INVALID, "po_overlaps_ex: max_diff must be < 65536");
-    h->ex_on = true;
-    h->ex_E = max_diff;
-    h->ex_W = band;
-    const po_status st = overlaps_common(h, min_length, 0, 1, false, out);
-    h->ex_on = false;
-    return st;
+    OverlapArgs a{min_length};
+    a.dp = true;
+    a.dp_E = max_diff;
+    a.dp_W = band;
+    return overlaps_common(h, a, out);
 }
 
 po_status po_shard_range(const po_handle* h, uint32_t shard, uint32_t nshards, uint32_t* r_begin, uint32_t* r_end) {

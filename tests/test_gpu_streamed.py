@@ -231,7 +231,40 @@ def test_other_entry_points_after_a_streamed_step(monkeypatch):
         parts = np.concatenate([ov.overlaps_shard_array(m, k, 3) for k in range(3)])
         ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(parts)), want, seqs, m, "%s shards after streamed" % name)
         ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(ov.overlaps_ex_array(m, 0, 0))), want, seqs, m, "%s DP after streamed" % name)
+        if name == "ladder_varlen":
+            _modes_after_the_dp_call(ov, seqs, m, want, monkeypatch)
         ov.close()
+
+
+def _modes_after_the_dp_call(ov, seqs, m, want, monkeypatch):
+    """... and the other direction: the sliced-index calls, a call refused on the host and the streamed step again, on the
+    handle that has just been through every other mode -- what one call was asked for must not reach the next."""
+    import torch
+    monkeypatch.setenv("PHASM_INDEX", "wide")
+    built = [ov.index_slice_build(m, k, 2) for k in range(2)]
+    assert all(w for w, _, _ in built) and len({b for _, b, _ in built}) == 1
+    bits, cap = built[0][1], max(e for _, _, e in built)
+    chunk = ov.index_chunk_bytes(bits, cap)
+    buf = torch.empty(2 * chunk, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    for k in range(2):
+        assert ov.index_slice_build(m, k, 2) == built[k]
+        ov.index_slice_export(buf.data_ptr() + k * chunk, cap)
+    parts = [ov.overlaps_shard_indexed_array(m, k, 2, buf.data_ptr(), 2, bits, cap) for k in range(2)]
+    ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(np.concatenate(parts))), want, seqs, m, "sliced index after streamed")
+    monkeypatch.setenv("PHASM_INDEX", "narrow")
+    with pytest.raises(ValueError, match="a sliced index was supplied, but this call uses the narrow index"):
+        ov.overlaps_shard_indexed_array(m, 0, 2, buf.data_ptr(), 2, bits, cap)
+    monkeypatch.delenv("PHASM_INDEX")
+    for call in (2, 3):
+        ov.invalidate()
+        res = ov.overlaps_to_host_result(m)
+        st = ov.stats()
+        print("streamed call %d after the other modes: n_predicted %d" % (call, st["n_predicted"]))
+        assert st["streamed"] == 1
+        ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(res.rows_view())), want, seqs, m, "streamed call %d" % call)
+        res.free()
+    assert st["n_predicted"] > 0   # (the third call's pieces find the second's buffers and counts: measured at the parent)
 
 
 def test_streamed_step_with_empty_and_tiny_reads(monkeypatch):
