@@ -423,9 +423,9 @@ typedef struct {
  * There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A result of another handle, a result that
  * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds, the merging
  * of unambiguous paths with po_layout_merge, the average coverage per edge with po_layout_coverage; of `phasm chain`
- * this library has the weakly connected components (po_layout_components) and the partition that superbubble detection
- * starts with (po_layout_partition).  graph_to_dag, the superbubble finder, bubble chains, contigs and phasing are not
- * part of it. */
+ * this library has the weakly connected components (po_layout_components), the partition that superbubble detection
+ * starts with (po_layout_partition) and the superbubbles of the acyclic partitions (po_layout_superbubbles).  graph_to_dag
+ * and the superbubbles of the cyclic partitions, bubble chains, contigs and phasing are not part of it. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -673,6 +673,77 @@ typedef struct {
 po_status po_layout_partition(po_handle* h, po_result* graph, const po_partition_params* params, uint32_t* node_scc_out,
                               uint8_t* node_flags_out, uint8_t* edge_class_out, po_scc* sccs_out, uint64_t* n_sccs_out);
 po_status po_get_partition_stats(const po_handle* h, po_partition_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The second step of superbubble detection inside `phasm chain`: the superbubbles of the acyclic partitions
+ * (SuperBubbleFinderDAG, phasm/bubbles.py:174-381, as find_superbubbles calls it on every acyclic partition,
+ * bubbles.py:411-414).
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_superbubble_params;
+
+#define PO_NO_NODE 0xFFFFFFFFu   /* "no such node" in node_exit_out / node_inside_out                            */
+
+typedef struct {
+    uint32_t entrance, exit;     /* node ids                                                                     */
+    uint32_t n_inside;           /* nodes strictly inside (neither end), those of nested superbubbles included   */
+    uint32_t nested;             /* 1: another superbubble holds both ends                                       */
+} po_superbubble;                /* 16 bytes                                                                     */
+
+/* node_flags_out, one byte per node of the order */
+#define PO_SB_ENTRANCE 1u        /* the node enters a superbubble (node_exit_out names its exit)                 */
+#define PO_SB_EXIT 2u            /* the node exits a superbubble                                                 */
+#define PO_SB_NESTED 4u          /* on the entrance: the superbubble is nested                                   */
+#define PO_SB_SELF_LOOP 8u       /* a singleton with an edge (u, u): in no superbubble                           */
+
+typedef struct {
+    uint64_t n_nodes;            /* nodes of the graph (those in its node order)                                 */
+    uint64_t n_edges;
+    uint64_t n_p_nodes;          /* nodes of P: the singletons, 'r_' and 're_' where an edge reaches them         */
+    uint64_t n_p_edges;          /* edges of P: class 1, ('r_', v) and (u, 're_')                                */
+    uint64_t n_bubbles, n_nested;
+    uint64_t n_self_loop_nodes;  /* singletons with an edge (u, u)                                               */
+    uint64_t n_discarded;        /* pairs that are superbubbles but for a self-loop in them                      */
+    uint64_t n_invalid;          /* edges with an end that is not in the node order (the call fails then)        */
+    uint32_t n_levels_forward, n_levels_backward;   /* nodes on the longest path of P from a source / to a sink   */
+    uint32_t n_scc_rounds;       /* rounds of the SCC stage (trim + forward + backward)                          */
+    uint32_t n_level_rounds, n_discard_rounds;      /* each loop's closing round included                         */
+    uint32_t n_batches;          /* readbacks of all round loops                                                 */
+    float ms_partition, ms_levels, ms_dominators, ms_label, ms_total;
+} po_superbubble_stats;
+
+/* `graph` is a graph result of this handle, of the kinds po_layout_partition takes; it stays valid and unchanged.  Ranks,
+ * SCCs, singletons, edge classes and the PO_PART_* flags are those of po_layout_partition.  The PARTITION GRAPH P is the
+ * union over all weakly connected components of what partition_graph yields last: the singletons, the class-1 edges, an
+ * edge 'r_' -> v for every singleton with PO_PART_R_IN | PO_PART_START and an edge v -> 're_' for every singleton with
+ * PO_PART_RE_OUT | PO_PART_SINK (one shared 'r_' / 're_' gives the same pairs of real nodes as one per component: 'r_' has
+ * no in-edge and 're_' no out-edge, so neither lies inside a bubble of two real nodes).  A pair (s, t) of real nodes,
+ * s != t, is a SUPERBUBBLE iff t is reachable from s; the set U of nodes reachable from s without passing t equals the set
+ * of nodes that reach t without passing s; P[U] is acyclic (a self-loop on any member of U, s and t included, is a cycle);
+ * and no t' in U without t satisfies the three with s.  It is NESTED iff another superbubble's U holds both its ends.  A node
+ * enters at most one superbubble and exits at most one.
+ *   node_exit_out    the exit of the superbubble the node enters, else PO_NO_NODE; parallel to the node order
+ *   node_inside_out  the entrance of the innermost superbubble whose U holds the node strictly (neither end), else
+ *                    PO_NO_NODE: superbubble_nodes(g, s, t) is {s, t} plus the nodes whose chain of node_inside reaches s
+ *   node_flags_out   PO_SB_* bits of every node
+ *   bubbles_out      one entry per superbubble, in the order of the entrances' ranks (room for n_order entries)
+ * Any of the four may be NULL; *n_bubbles_out is always written.  The cyclic partitions (graph_to_dag) are not covered;
+ * the order in which the reference's finder yields the pairs is not reproduced; where an acyclic partition holds a
+ * self-loop or lacks 'r_' or 're_' the definition above applies, not the finder's behaviour.  Only integers are involved:
+ * every output is the same on every run (the round counts of the stats are statistics).  An edge with an end that is not
+ * in the node order is counted in n_invalid; the call then fails with PO_ERR_INVALID and writes nothing.  Device memory
+ * beyond the inputs is linear: at most 168 bytes per node (78 of them po_layout_partition's, whose workspaces the call
+ * fills first; 90 its own) and 17 per edge (9 + 8).  params may be NULL.  An empty graph with an empty order: PO_OK, 0
+ * superbubbles.  Every round loop is bounded on the host (by its live nodes + 2), the launches per level by the number of
+ * singletons, the one walk along a tree path inside a kernel by twice its level; reaching a bound is PO_ERR_HIP with a
+ * message, never a result.  There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A row result, a result
+ * of another handle, reserved != 0, n_bubbles_out NULL: PO_ERR_INVALID. */
+po_status po_layout_superbubbles(po_handle* h, po_result* graph, const po_superbubble_params* params, uint32_t* node_exit_out,
+                                 uint32_t* node_inside_out, uint8_t* node_flags_out, po_superbubble* bubbles_out,
+                                 uint64_t* n_bubbles_out);
+po_status po_get_superbubble_stats(const po_handle* h, po_superbubble_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

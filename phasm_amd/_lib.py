@@ -32,6 +32,11 @@ COMPONENT_DTYPE = np.dtype([("first_node", "<u4"), ("n_nodes", "<u4"), ("n_edges
 SCC_DTYPE = np.dtype([("first_node", "<u4"), ("n_nodes", "<u4"), ("n_edges", "<u8"), ("n_r_in", "<u4"), ("n_re_out", "<u4")])
 # PO_PART_*: the bits of po_layout_partition's flag byte per node
 PART_R_IN, PART_RE_OUT, PART_START, PART_SINK = 1, 2, 4, 8
+# po_superbubble
+SUPERBUBBLE_DTYPE = np.dtype([("entrance", "<u4"), ("exit", "<u4"), ("n_inside", "<u4"), ("nested", "<u4")])
+# PO_SB_*: the bits of po_layout_superbubbles' flag byte per node; PO_NO_NODE
+SB_ENTRANCE, SB_EXIT, SB_NESTED, SB_SELF_LOOP = 1, 2, 4, 8
+NO_NODE = 0xFFFFFFFF
 
 
 class PoLayoutParams(ctypes.Structure):
@@ -159,6 +164,23 @@ class PoPartitionStats(ctypes.Structure):
         return d
 
 
+class PoSuperbubbleParams(ctypes.Structure):
+    _fields_ = [("reserved", ctypes.c_uint32)]
+
+
+class PoSuperbubbleStats(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("n_edges", ctypes.c_uint64), ("n_p_nodes", ctypes.c_uint64), ("n_p_edges", ctypes.c_uint64),
+                ("n_bubbles", ctypes.c_uint64), ("n_nested", ctypes.c_uint64), ("n_self_loop_nodes", ctypes.c_uint64),
+                ("n_discarded", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64), ("n_levels_forward", ctypes.c_uint32),
+                ("n_levels_backward", ctypes.c_uint32), ("n_scc_rounds", ctypes.c_uint32), ("n_level_rounds", ctypes.c_uint32),
+                ("n_discard_rounds", ctypes.c_uint32), ("n_batches", ctypes.c_uint32),
+                ("ms_partition", ctypes.c_float), ("ms_levels", ctypes.c_float), ("ms_dominators", ctypes.c_float),
+                ("ms_label", ctypes.c_float), ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -263,6 +285,9 @@ SYMBOLS = [
     ("po_layout_partition", ctypes.c_int, [_P, _P, ctypes.POINTER(PoPartitionParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_partition_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPartitionStats)]),
+    ("po_layout_superbubbles", ctypes.c_int, [_P, _P, ctypes.POINTER(PoSuperbubbleParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_superbubble_stats", ctypes.c_int, [_P, ctypes.POINTER(PoSuperbubbleStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

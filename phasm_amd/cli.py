@@ -290,13 +290,22 @@ def chain_components(args) -> int:
         logger.critical("No valid file formats specified.")
         sys.exit(1)
     logger.info("Reconstructing assembly graph...")
-    g = layout.chain_components(args.graph_gfa, device=args.device, partitions=args.partitions)
+    g = layout.chain_components(args.graph_gfa, device=args.device, partitions=args.partitions, superbubbles=args.superbubbles)
     logger.info("Enumerate weakly connected components in the graph...")
     n = layout.write_component_graphs(args.output_dir, g, formats)
     for parts in g.partitions or ():
         for part in parts:   # (find_superbubbles, phasm/bubbles.py:402-409, logs this line per partition)
             logger.info("Partition with %d nodes with in-degree 0, %d nodes with out-degree 0, acyclic: %s", part.num_sources,
                         part.num_sinks, part.acyclic)
+    if g.superbubbles is not None:
+        import numpy as np
+        entrances = g.superbubbles.table["entrance"].astype(np.int64)
+        comp_of = np.zeros(int(g.components.node_order.max()) + 1 if len(g.components.node_order) else 0, dtype=np.int64)
+        comp_of[g.components.node_order] = g.components.component_of_node
+        per = np.bincount(comp_of[entrances], minlength=len(g.components))
+        top = np.bincount(comp_of[entrances[g.superbubbles.table["nested"] == 0]], minlength=len(g.components))
+        for i in range(len(g.components)):
+            logger.info("Connected component %d: %d superbubbles in its acyclic partition, %d of them not nested.", i, per[i], top[i])
     logger.info("Wrote %d weakly connected components.", n)
     return 0
 
@@ -377,6 +386,8 @@ def main(argv=None) -> int:
     k.add_argument("-f", "--format", default="gfa2", help="comma separated: gfa1, gfa2, graphml (default: gfa2)")
     k.add_argument("-o", "--output-dir", required=True)
     k.add_argument("--device", type=int, default=None)
+    k.add_argument("--superbubbles", action="store_true",
+                   help="also log, per component, the number of superbubbles of its acyclic partition")
     k.add_argument("--partitions", action="store_true",
                    help="also log, per component, the partitions superbubble detection starts with (strongly connected components)")
     k.add_argument("graph_gfa", help="the graph file (S, F and E lines)")

@@ -43,6 +43,7 @@
 #include "coverage.hip.h"
 #include "components.hip.h"
 #include "partition.hip.h"
+#include "superbubbles.hip.h"
 
 namespace {
 
@@ -65,12 +66,15 @@ enum { RK_CNT, RK_RCNT, RK_KEY, RK_VAL, RK_RANKOF, RK_ENDS, RK_ROOT, RK_INDEX, R
 enum { KB_P, KB_COMP, KB_ECOMP, KB_TABLE, KB_N };
 // workspaces of po_layout_partition (partition.hip.h) beyond those
 enum { PB_LIVE, PB_SCC, PB_COLOUR, PB_MARK, PB_HASIN, PB_HASOUT, PB_NODESCC, PB_FLAGW, PB_FLAGS, PB_ECLASS, PB_TABLE, PB_N };
+// workspaces of po_layout_superbubbles (superbubbles.hip.h) beyond those of the rank scaffold and of po_layout_partition
+enum { UB_CNT, UB_W, UB_CIN, UB_COUT, UB_OFFIN, UB_OFFOUT, UB_CURIN, UB_CUROUT, UB_LISTIN, UB_LISTOUT, UB_LVLF, UB_LVLB, UB_IDOM, UB_IPDOM,
+       UB_DEPTH, UB_EXIT, UB_ENCL, UB_INSIDE, UB_TOTAL, UB_DEAD, UB_EXITOUT, UB_INSIDEOUT, UB_FLAGSOUT, UB_TABLE, UB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 38;
+constexpr int EV_LAY_N = 45;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
-       EV_PARTITION = 34 };
-static_assert(EV_PARTITION + 4 == EV_LAY_N, "the four events of po_layout_partition are the last of the layout events");
+       EV_PARTITION = 34, EV_SUPERBUBBLES = 38 };
+static_assert(EV_SUPERBUBBLES + 7 == EV_LAY_N, "the seven events of po_layout_superbubbles are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -420,6 +424,9 @@ struct po_handle {
     // strongly connected components and the superbubble partition (po_layout_partition, partition.hip.h)
     DevBuf d_scc[PB_N];
     po_partition_stats pstats = {};
+    // the superbubbles of the acyclic partitions (po_layout_superbubbles, superbubbles.hip.h)
+    DevBuf d_sb[UB_N];
+    po_superbubble_stats sbstats = {};
 };
 
 struct po_result {
@@ -3921,19 +3928,22 @@ struct SccOps : RoundOps {
     }
 };
 
-po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint8_t* flags_out, uint8_t* class_out, po_scc* table_out,
-                        uint64_t* n_sccs_out) {
+// The SCC stage on the device, as po_layout_partition and po_layout_superbubbles run it (`name`, the first of the caller's
+// events, the caller's stats): ranked_open with the workspaces of d_scc and the caller's `own`, the rounds of scc_drive,
+// the numbering of the roots, the table, the class byte per edge and the flag byte per rank, all left in d_scc; the
+// counters in R.cnt.  Records R.ev[2] behind the rounds.  W is filled whatever the outcome.  !R.ev: nothing to do.
+template <class Stats, class Own>
+po_status scc_stage(po_handle* h, po_result* graph, const std::string& name, int ev_first, Stats& S, Own&& own, RankedGraph& R,
+                    po::SccWork& W, uint32_t& n_scc) {
     hipStream_t st = h->stream;
-    po_partition_stats& S = h->pstats;
-    S = po_partition_stats();
     DevBuf* B = h->d_scc;
-    RankedGraph R;
     // (the identity words land in `colour`: colour[r] = r is where the first forward phase starts anyway)
-    PO_TRY(ranked_open(h, graph, "po_layout_partition", EV_PARTITION, po::PC_N, S, B[PB_COLOUR], [&](size_t nn, size_t ne) {
+    PO_TRY(ranked_open(h, graph, name, ev_first, po::PC_N, S, B[PB_COLOUR], [&](size_t nn, size_t ne) {
         for (int k : {PB_SCC, PB_COLOUR, PB_NODESCC, PB_FLAGW}) PO_TRY(ensure(h, B[k], nn * 4));
         for (int k : {PB_LIVE, PB_MARK, PB_HASIN, PB_HASOUT, PB_FLAGS}) PO_TRY(ensure(h, B[k], nn));
         PO_TRY(ensure(h, B[PB_TABLE], nn * sizeof(po::Scc)));
-        return ensure(h, B[PB_ECLASS], ne);
+        PO_TRY(ensure(h, B[PB_ECLASS], ne));
+        return own(nn, ne);
     }, R));
     if (!R.ev) return PO_OK;
     const uint32_t n = R.n, n_order = R.n_order;
@@ -3943,30 +3953,21 @@ po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint
             *has_out = B[PB_HASOUT].as<uint8_t>(), *flags = B[PB_FLAGS].as<uint8_t>(), *eclass = B[PB_ECLASS].as<uint8_t>();
     po::Scc* table = B[PB_TABLE].as<po::Scc>();
     // trim rounds, forward colouring, backward marking, again while live ranks remain: every bound is scc_drive's
-    po::SccWork W;
     if (n_order) {
         hipLaunchKernelGGL(po::k_scc_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, live, scc, has_in, has_out);
         SccOps ops{{h, st, R.rcnt}, R, live, mark, has_in, has_out, scc, colour};
         const int how = po::scc_drive(ops, n_order, W);
-        S.n_trimmed = W.n_trimmed;
-        S.n_outer = W.outer;
-        S.n_trim_rounds = W.trim_rounds;
-        S.n_forward_rounds = W.forward_rounds;
-        S.n_backward_rounds = W.backward_rounds;
-        S.n_batches = W.batches;
         if (how == po::SCC_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
-        if (how == po::SCC_ROUND_CAP) return fail(h, PO_ERR_HIP, "internal: a phase of po_layout_partition reached its bound of live + 2 rounds");
-        if (how == po::SCC_OUTER_CAP) return fail(h, PO_ERR_HIP, "internal: po_layout_partition reached its bound of n_order iterations");
-        if (how != po::SCC_DONE) return fail(h, PO_ERR_HIP, "internal: the live nodes of po_layout_partition do not add up");
+        if (how == po::SCC_ROUND_CAP) return fail(h, PO_ERR_HIP, "internal: a phase of " + name + " reached its bound of live + 2 rounds");
+        if (how == po::SCC_OUTER_CAP) return fail(h, PO_ERR_HIP, "internal: " + name + " reached its bound of n_order iterations");
+        if (how != po::SCC_DONE) return fail(h, PO_ERR_HIP, "internal: the live nodes of " + name + " do not add up");
     }
     HIP_TRY(h, hipEventRecord(R.ev[2], st));
     if (n_order) {
         hipLaunchKernelGGL(po::k_scc_roots, dim3(R.rank_grid), dim3(256), 0, st, scc, n_order, R.root, flagw);
         HIP_TRY(h, hipGetLastError());
     }
-    uint32_t n_scc = 0;
-    PO_TRY(ranked_roots(h, R, "po_layout_partition", n_scc));
-    S.n_sccs = n_scc;
+    PO_TRY(ranked_roots(h, R, name.c_str(), n_scc));
     if (n_scc) {
         HIP_TRY(h, hipMemsetAsync(table, 0, (size_t)n_scc * sizeof(po::Scc), st));
         hipLaunchKernelGGL(po::k_scc_label_nodes, dim3(R.rank_grid), dim3(256), 0, st, scc, R.index, R.val, n_order, n_scc, node_scc, table);
@@ -3977,10 +3978,32 @@ po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint
         hipLaunchKernelGGL(po::k_scc_max, dim3(stride_grid(h, n_scc)), dim3(256), 0, st, table, n_scc, R.cnt);
         HIP_TRY(h, hipGetLastError());
     }
-    HIP_TRY(h, hipEventRecord(R.ev[3], st));
+    return PO_OK;
+}
+
+po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint8_t* flags_out, uint8_t* class_out, po_scc* table_out,
+                        uint64_t* n_sccs_out) {
+    po_partition_stats& S = h->pstats;
+    S = po_partition_stats();
+    DevBuf* B = h->d_scc;
+    RankedGraph R;
+    po::SccWork W;
+    uint32_t n_scc = 0;
+    const po_status staged = scc_stage(h, graph, "po_layout_partition", EV_PARTITION, S, [](size_t, size_t) { return PO_OK; }, R, W, n_scc);
+    S.n_trimmed = W.n_trimmed;
+    S.n_outer = W.outer;
+    S.n_trim_rounds = W.trim_rounds;
+    S.n_forward_rounds = W.forward_rounds;
+    S.n_backward_rounds = W.backward_rounds;
+    S.n_batches = W.batches;
+    PO_TRY(staged);
+    if (!R.ev) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order;
+    S.n_sccs = n_scc;
+    HIP_TRY(h, hipEventRecord(R.ev[3], h->stream));
     static_assert(sizeof(po_scc) == sizeof(po::Scc) && sizeof(po_scc) == 24, "po_scc is the device's table entry");
-    PO_TRY(land_outputs(h, {{table, (size_t)n_scc * sizeof(po_scc), table_out}, {node_scc, (size_t)n_order * 4, node_out},
-                            {flags, n_order, flags_out}, {eclass, n, class_out}}, R.cnt, po::PC_N));
+    PO_TRY(land_outputs(h, {{B[PB_TABLE].p, (size_t)n_scc * sizeof(po_scc), table_out}, {B[PB_NODESCC].p, (size_t)n_order * 4, node_out},
+                            {B[PB_FLAGS].p, n_order, flags_out}, {B[PB_ECLASS].p, n, class_out}}, R.cnt, po::PC_N));
     S.n_singletons = h->pinned[16 + po::PC_SINGLE];
     S.n_nonsingleton_sccs = S.n_sccs - S.n_singletons;
     S.max_scc_nodes = h->pinned[16 + po::PC_MAXN];
@@ -3992,6 +4015,143 @@ po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint
     (void)hipEventElapsedTime(&S.ms_rounds, R.ev[1], R.ev[2]);
     (void)hipEventElapsedTime(&S.ms_label, R.ev[2], R.ev[3]);
     (void)hipEventElapsedTime(&S.ms_total, R.ev[0], R.ev[3]);
+    return PO_OK;
+}
+
+// ---- the superbubbles of the acyclic partitions (po_layout_superbubbles, superbubbles.hip.h) ------------------------------
+
+po_status run_superbubbles(po_handle* h, po_result* graph, uint32_t* exit_out, uint32_t* inside_out, uint8_t* flags_out,
+                           po_superbubble* table_out, uint64_t* n_bubbles_out) {
+    const char* const name = "po_layout_superbubbles";
+    hipStream_t st = h->stream;
+    po_superbubble_stats& S = h->sbstats;
+    S = po_superbubble_stats();
+    DevBuf* B = h->d_sb;
+    RankedGraph R;
+    po::SccWork W;
+    uint32_t n_scc = 0;
+    const po_status staged = scc_stage(h, graph, name, EV_SUPERBUBBLES, S, [&](size_t nn, size_t ne) {
+        PO_TRY(ensure(h, B[UB_CNT], 128));
+        for (int k : {UB_W, UB_CIN, UB_COUT, UB_OFFIN, UB_OFFOUT, UB_CURIN, UB_CUROUT, UB_LVLF, UB_LVLB, UB_IDOM, UB_IPDOM, UB_DEPTH, UB_EXIT,
+                      UB_ENCL, UB_INSIDE, UB_TOTAL, UB_EXITOUT, UB_INSIDEOUT})
+            PO_TRY(ensure(h, B[k], nn * 4));
+        for (int k : {UB_DEAD, UB_FLAGSOUT}) PO_TRY(ensure(h, B[k], nn));
+        for (int k : {UB_LISTIN, UB_LISTOUT}) PO_TRY(ensure(h, B[k], ne * 4));
+        return ensure(h, B[UB_TABLE], nn * sizeof(po::Bubble));
+    }, R, W, n_scc);
+    S.n_scc_rounds = W.trim_rounds + W.forward_rounds + W.backward_rounds;
+    S.n_batches = W.batches;
+    PO_TRY(staged);
+    if (!R.ev || !R.n_order) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order;
+    hipEvent_t* ev = R.ev;
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    unsigned long long* cnt = B[UB_CNT].as<unsigned long long>();
+    uint32_t *w = B[UB_W].as<uint32_t>(), *cin = B[UB_CIN].as<uint32_t>(), *cout = B[UB_COUT].as<uint32_t>(),
+             *off_in = B[UB_OFFIN].as<uint32_t>(), *off_out = B[UB_OFFOUT].as<uint32_t>(), *cur_in = B[UB_CURIN].as<uint32_t>(),
+             *cur_out = B[UB_CUROUT].as<uint32_t>(), *list_in = B[UB_LISTIN].as<uint32_t>(), *list_out = B[UB_LISTOUT].as<uint32_t>(),
+             *lvl_f = B[UB_LVLF].as<uint32_t>(), *lvl_b = B[UB_LVLB].as<uint32_t>(), *idom = B[UB_IDOM].as<uint32_t>(),
+             *ipdom = B[UB_IPDOM].as<uint32_t>(), *depth = B[UB_DEPTH].as<uint32_t>(), *exit_of = B[UB_EXIT].as<uint32_t>(),
+             *encl = B[UB_ENCL].as<uint32_t>(), *inside = B[UB_INSIDE].as<uint32_t>(), *total = B[UB_TOTAL].as<uint32_t>(),
+             *d_exit = B[UB_EXITOUT].as<uint32_t>(), *d_inside = B[UB_INSIDEOUT].as<uint32_t>();
+    uint8_t *dead = B[UB_DEAD].as<uint8_t>(), *d_flags = B[UB_FLAGSOUT].as<uint8_t>();
+    po::Bubble* table = B[UB_TABLE].as<po::Bubble>();
+    const uint8_t *eclass = h->d_scc[PB_ECLASS].as<uint8_t>(), *pflags = h->d_scc[PB_FLAGS].as<uint8_t>();
+    volatile uint64_t* C = h->pinned + 48;   // this stage's counters on the host (words 16.. and 32.. are the scaffold's)
+    auto counters_home = [&]() -> po_status {
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 48, cnt, po::BC_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        return PO_OK;
+    };
+    // the structure graph D: degrees, the parents and the children of every rank, sources and sinks
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    hipLaunchKernelGGL(po::k_sb_init, dim3(stride_grid(h, (uint64_t)n_order + 1)), dim3(256), 0, st, n_order, n_scc,
+                       h->d_scc[PB_NODESCC].as<uint32_t>(), h->d_scc[PB_TABLE].as<po::Scc>(), w, cin, cout, idom, ipdom, depth, exit_of, encl, total,
+                       dead);
+    if (n) hipLaunchKernelGGL(po::k_sb_degrees, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, eclass, w, cin, cout, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, cin, n_order, off_in, &h->pinned[2]));
+    PO_TRY(prefix_sum<uint32_t>(h, cout, n_order, off_out, &h->pinned[3]));
+    for (uint32_t* p : {cur_in, cur_out}) HIP_TRY(h, hipMemsetAsync(p, 0, (size_t)n_order * 4, st));
+    if (n)
+        hipLaunchKernelGGL(po::k_sb_fill, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, eclass, cin, cout, off_in, off_out, cur_in,
+                           cur_out, list_in, list_out);
+    hipLaunchKernelGGL(po::k_sb_nodes, dim3(R.rank_grid), dim3(256), 0, st, n_order, pflags, cin, cout, w, lvl_f, lvl_b, cnt);
+    PO_TRY(counters_home());
+    const uint64_t n_real = C[po::BC_REAL], n_dedges = C[po::BC_DEDGES];
+    if (h->pinned[2] != n_dedges || h->pinned[3] != n_dedges || n_dedges > n || n_real > n_order)
+        return fail(h, PO_ERR_HIP, std::string("internal: the degrees of ") + name + " do not add up");
+    S.n_self_loop_nodes = C[po::BC_LOOPS];
+    S.n_p_nodes = n_real + (C[po::BC_R_EDGES] != 0) + (C[po::BC_RE_EDGES] != 0);
+    S.n_p_edges = n_dedges + C[po::BC_LOOPS] + C[po::BC_R_EDGES] + C[po::BC_RE_EDGES];
+    // the longest-path levels from the sources and from the sinks: rounds over the edges of D, bounded by round_phase
+    RoundOps ops{h, st, R.rcnt};
+    uint64_t ignored = 0;
+    int how = po::round_phase(ops, n_real, [&](uint32_t j) {
+        if (n) hipLaunchKernelGGL(po::k_sb_level, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, eclass, lvl_f, lvl_b, R.rcnt + j);
+    }, S.n_level_rounds, S.n_batches, ignored);
+    if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+    if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, std::string("internal: the levels of ") + name + " reached their bound of live + 2 rounds");
+    hipLaunchKernelGGL(po::k_sb_level_max, dim3(R.rank_grid), dim3(256), 0, st, n_order, lvl_f, lvl_b, cnt);
+    PO_TRY(counters_home());
+    const uint64_t levels_f = C[po::BC_LEVF], levels_b = C[po::BC_LEVB];
+    if (levels_f > n_real || levels_b > n_real)   // (a level is the number of ranks on a path)
+        return fail(h, PO_ERR_HIP, std::string("internal: ") + name + " counted more levels than nodes");
+    S.n_levels_forward = (uint32_t)levels_f;
+    S.n_levels_backward = (uint32_t)levels_b;
+    HIP_TRY(h, hipEventRecord(ev[4], st));
+    // the dominator tree and the post-dominator tree, one launch per level; the pairs; the innermost enclosing bubble
+    for (uint32_t l = 1; l <= levels_f; ++l)
+        hipLaunchKernelGGL(po::k_sb_tree, dim3(R.rank_grid), dim3(256), 0, st, n_order, n, l, lvl_f, off_in, cin, list_in, w,
+                           (uint32_t)po::SBW_SOURCE, idom, depth, cnt);
+    for (uint32_t l = 1; l <= levels_b; ++l)
+        hipLaunchKernelGGL(po::k_sb_tree, dim3(R.rank_grid), dim3(256), 0, st, n_order, n, l, lvl_b, off_out, cout, list_out, w,
+                           (uint32_t)po::SBW_SINK, ipdom, depth, cnt);
+    hipLaunchKernelGGL(po::k_sb_pairs, dim3(R.rank_grid), dim3(256), 0, st, n_order, w, idom, ipdom, exit_of);
+    for (uint32_t l = 1; l <= levels_f; ++l)
+        hipLaunchKernelGGL(po::k_sb_encl, dim3(R.rank_grid), dim3(256), 0, st, n_order, l, lvl_f, idom, exit_of, encl);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[5], st));
+    // self-loops discard bubbles, and a discarded bubble the one around it: rounds, bounded by round_phase
+    if (S.n_self_loop_nodes) {
+        hipLaunchKernelGGL(po::k_sb_dead_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, w, idom, exit_of, encl, dead);
+        how = po::round_phase(ops, n_real, [&](uint32_t j) {
+            hipLaunchKernelGGL(po::k_sb_dead_round, dim3(R.rank_grid), dim3(256), 0, st, n_order, exit_of, encl, dead, R.rcnt + j);
+        }, S.n_discard_rounds, S.n_batches, ignored);
+        if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how != po::ROUNDS_DONE)
+            return fail(h, PO_ERR_HIP, std::string("internal: the discards of ") + name + " reached their bound of live + 2 rounds");
+    }
+    hipLaunchKernelGGL(po::k_sb_label, dim3(R.rank_grid), dim3(256), 0, st, n_order, R.val, w, idom, exit_of, encl, dead, inside, total, R.root,
+                       d_exit, d_inside, d_flags, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint8_t>(h, R.root, n_order, R.index, &h->pinned[2]));
+    PO_TRY(counters_home());
+    if (C[po::BC_WALK]) return fail(h, PO_ERR_HIP, std::string("internal: a walk along a dominator tree of ") + name + " reached its bound");
+    const uint64_t n64 = h->pinned[2];
+    if (n64 > n_real || C[po::BC_NESTED] > n64) return fail(h, PO_ERR_HIP, std::string("internal: the bubbles of ") + name + " do not add up");
+    const uint32_t n_bubbles = (uint32_t)n64;
+    S.n_bubbles = n_bubbles;
+    S.n_nested = C[po::BC_NESTED];
+    S.n_discarded = C[po::BC_DISCARDED];
+    if (S.n_nested)
+        for (uint32_t l = (uint32_t)levels_f; l >= 1; --l)
+            hipLaunchKernelGGL(po::k_sb_sum, dim3(R.rank_grid), dim3(256), 0, st, n_order, l, lvl_f, R.root, inside, total);
+    if (n_bubbles)
+        hipLaunchKernelGGL(po::k_sb_table, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_bubbles, R.val, R.root, R.index, exit_of, inside, total,
+                           table);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[6], st));
+    static_assert(sizeof(po_superbubble) == sizeof(po::Bubble) && sizeof(po_superbubble) == 16, "po_superbubble is the device's table entry");
+    PO_TRY(land_outputs(h, {{table, (size_t)n_bubbles * sizeof(po_superbubble), table_out}, {d_exit, (size_t)n_order * 4, exit_out},
+                            {d_inside, (size_t)n_order * 4, inside_out}, {d_flags, n_order, flags_out}}, cnt, po::BC_N));
+    *n_bubbles_out = n_bubbles;
+    (void)hipEventElapsedTime(&S.ms_partition, ev[0], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_levels, ev[3], ev[4]);
+    (void)hipEventElapsedTime(&S.ms_dominators, ev[4], ev[5]);
+    (void)hipEventElapsedTime(&S.ms_label, ev[5], ev[6]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[6]);
     return PO_OK;
 }
 
@@ -4467,6 +4627,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_rank) b.release();
         for (DevBuf& b : h->d_cc) b.release();
         for (DevBuf& b : h->d_scc) b.release();
+        for (DevBuf& b : h->d_sb) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -6309,6 +6470,15 @@ po_status po_get_merge_stats(const po_handle* h, po_merge_stats* out) { return g
 po_status po_get_coverage_stats(const po_handle* h, po_coverage_stats* out) { return get_stats(h, &po_handle::cstats, out); }
 po_status po_get_components_stats(const po_handle* h, po_components_stats* out) { return get_stats(h, &po_handle::ccstats, out); }
 po_status po_get_partition_stats(const po_handle* h, po_partition_stats* out) { return get_stats(h, &po_handle::pstats, out); }
+
+po_status po_layout_superbubbles(po_handle* h, po_result* graph, const po_superbubble_params* params, uint32_t* node_exit_out,
+                                 uint32_t* node_inside_out, uint8_t* node_flags_out, po_superbubble* bubbles_out, uint64_t* n_bubbles_out) {
+    return graph_call(h, graph, "po_layout_superbubbles", !params || params->reserved == 0, "superbubbles", n_bubbles_out, [&] {
+        return run_superbubbles(h, graph, node_exit_out, node_inside_out, node_flags_out, bubbles_out, n_bubbles_out);
+    });
+}
+
+po_status po_get_superbubble_stats(const po_handle* h, po_superbubble_stats* out) { return get_stats(h, &po_handle::sbstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

@@ -27,7 +27,8 @@ still in HBM, and ``write_graphml`` writes the graph with that attribute (the co
 (assembler.py:231-310): the components of a graph result by ``po_layout_components``, numbered as networkx yields them;
 ``chain_components`` runs it on a graph file and ``write_component_graphs`` writes ``component{i}.gfa`` / ``.graphml``.
 ``strongly_connected_components`` (``po_layout_partition``) and ``superbubble_partitions`` are what superbubble detection
-starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).
+starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).  ``superbubbles``
+(``po_layout_superbubbles``) are the superbubbles of the acyclic partitions: ``SuperBubbleFinderDAG`` (bubbles.py:174-381).
 What follows that point (bubble chains, contigs, phasing) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
@@ -576,21 +577,85 @@ def superbubble_partitions(sccs: StrongComponents, components: Components) -> Li
     return out
 
 
+# ---- the superbubbles of the acyclic partitions (SuperBubbleFinderDAG, phasm/bubbles.py:174-381) ------------------------------
+
+@dataclass
+class Superbubbles:
+    """The superbubbles of the acyclic partitions of a graph result (``po_layout_superbubbles``).  ``node_order``: the
+    graph's nodes in the reference's order; ``node_exit`` / ``node_inside`` (node ids, ``_lib.NO_NODE`` where there is
+    none) and ``node_flags`` (``_lib.SB_*`` bits): parallel to it; ``table``: structured (``entrance``, ``exit``,
+    ``n_inside``, ``nested``), one entry per superbubble in the order of the entrances' ranks (the reference's finder yields
+    them in another order); ``stats``: ``po_get_superbubble_stats``."""
+    node_order: np.ndarray
+    node_exit: np.ndarray
+    node_inside: np.ndarray
+    node_flags: np.ndarray
+    table: np.ndarray
+    stats: dict
+
+    def __len__(self) -> int:
+        return len(self.table)
+
+    def pairs(self, nested: bool = True) -> List[tuple]:
+        """The (entrance, exit) pairs: what ``SuperBubbleFinderDAG(partition, report_nested=nested)`` reports, in table order."""
+        t = self.table if nested else self.table[self.table["nested"] == 0]
+        return list(zip(t["entrance"].tolist(), t["exit"].tolist()))
+
+    def nodes(self, entrance: int) -> np.ndarray:
+        """``superbubble_nodes(g, entrance, exit)`` in node order: the two ends and every node whose chain of
+        ``node_inside`` reaches the entrance."""
+        from ._lib import NO_NODE, SB_ENTRANCE
+        if not hasattr(self, "_held"):
+            held = self.node_inside != NO_NODE
+            self._held = _groups_by_value(self.node_inside[held], np.flatnonzero(held))
+            self._rank = {int(n): r for r, n in enumerate(self.node_order.tolist())}
+        r = self._rank.get(int(entrance))
+        if r is None or not self.node_flags[r] & SB_ENTRANCE:
+            raise KeyError("node %d enters no superbubble" % entrance)
+        members, work = [r, self._rank[int(self.node_exit[r])]], [int(entrance)]
+        while work:   # (every node is held by one bubble: each is visited once)
+            for x in self._held.get(work.pop(), ()):
+                members.append(x)
+                if self.node_flags[x] & SB_ENTRANCE:
+                    work.append(int(self.node_order[x]))
+        return self.node_order[np.unique(np.asarray(members, dtype=np.int64))]
+
+
+def _groups_by_value(values: np.ndarray, ranks: np.ndarray) -> dict:
+    """{value: the ranks that carry it, ascending}."""
+    out = {}
+    for v, r in zip(values.tolist(), ranks.tolist()):
+        out.setdefault(v, []).append(r)
+    return out
+
+
+def superbubbles(ov: ExactOverlapper, graph_res: OverlapResult) -> Superbubbles:
+    """``po_layout_superbubbles`` on a graph result of ``ov`` (an edge result, a merged graph or a ``graph_from_edges``
+    result), which stays valid and in HBM."""
+    order = graph_res.node_order()
+    node_exit, node_inside, flags, table = ov.layout_superbubbles(graph_res, len(order))
+    return Superbubbles(order, node_exit, node_inside, flags, table, ov.superbubble_stats())
+
+
+_superbubbles = superbubbles   # (chain_components has an argument of that name)
+
+
 @dataclass
 class ChainGraph:
     """What ``chain_components`` hands to the writers: the graph file as read (``phasm_amd.io.gfa.GraphFile``) and its
     components; with ``partitions=True`` also the strongly connected components and, per component, the partitions that
-    superbubble detection starts with."""
+    superbubble detection starts with; with ``superbubbles=True`` also the superbubbles of the acyclic partitions."""
     graph: object
     components: Components
     sccs: Optional[StrongComponents] = None
     partitions: Optional[List[List[Partition]]] = None
+    superbubbles: Optional[Superbubbles] = None
 
 
-def chain_components(path: str, device: Optional[int] = None, partitions: bool = False) -> ChainGraph:
+def chain_components(path: str, device: Optional[int] = None, partitions: bool = False, superbubbles: bool = False) -> ChainGraph:
     """The start of `phasm chain` on a graph file: ``read_graph_gfa``, one segment per ``S`` line on a fresh handle, the
     graph on the device (``graph_from_edges``) and its weakly connected components; with ``partitions`` also
-    ``strongly_connected_components`` and ``superbubble_partitions``."""
+    ``strongly_connected_components`` and ``superbubble_partitions``; with ``superbubbles`` also ``superbubbles``."""
     from .io import gfa
     with open(path) as f:
         graph = gfa.read_graph_gfa(f)
@@ -600,11 +665,13 @@ def chain_components(path: str, device: Optional[int] = None, partitions: bool =
             ov.add_segment(name, n)
         res = ov.graph_from_edges(graph.edges, graph.node_order)
         try:
-            comps = weakly_connected_components(ov, res)
-            if not partitions:
-                return ChainGraph(graph, comps)
-            sccs = strongly_connected_components(ov, res)
-            return ChainGraph(graph, comps, sccs, superbubble_partitions(sccs, comps))
+            out = ChainGraph(graph, weakly_connected_components(ov, res))
+            if partitions:
+                out.sccs = strongly_connected_components(ov, res)
+                out.partitions = superbubble_partitions(out.sccs, out.components)
+            if superbubbles:
+                out.superbubbles = _superbubbles(ov, res)
+            return out
         finally:
             res.free()
     finally:

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -535,6 +535,20 @@ class ExactOverlapper:
 
     def partition_stats(self) -> dict:
         return self._stats(self._lib.po_get_partition_stats, PoPartitionStats)
+
+    def layout_superbubbles(self, graph: OverlapResult, n_order: Optional[int] = None):
+        """``po_layout_superbubbles``: the superbubbles of the acyclic partitions of a graph result (of the kinds
+        ``layout_components`` takes), which stays valid -- what the reference's ``SuperBubbleFinderDAG`` reports on every
+        acyclic partition (phasm/bubbles.py:174-381, 411-414).  Returns ``(node_exit, node_inside, node_flags, table)``:
+        per node, parallel to ``graph.node_order()`` (``n_order``: its length, if the caller has it), the exit of the
+        superbubble it enters, the entrance of the innermost superbubble that holds it strictly (``NO_NODE`` where there is
+        none) and the ``SB_*`` flag byte; one entry (``entrance``, ``exit``, ``n_inside``, ``nested``) per superbubble, in
+        the order of the entrances' ranks."""
+        return self._graph_stage(self._lib.po_layout_superbubbles, graph, PoSuperbubbleParams(0), n_order,
+                                 [(np.uint32, "node"), (np.uint32, "node"), (np.uint8, "node"), (SUPERBUBBLE_DTYPE, "node")])
+
+    def superbubble_stats(self) -> dict:
+        return self._stats(self._lib.po_get_superbubble_stats, PoSuperbubbleStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:
