@@ -424,8 +424,9 @@ typedef struct {
  * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds, the merging
  * of unambiguous paths with po_layout_merge, the average coverage per edge with po_layout_coverage; of `phasm chain`
  * this library has the weakly connected components (po_layout_components), the partition that superbubble detection
- * starts with (po_layout_partition) and the superbubbles of the acyclic partitions (po_layout_superbubbles).  graph_to_dag
- * and the superbubbles of the cyclic partitions, bubble chains, contigs and phasing are not part of it. */
+ * starts with (po_layout_partition), the superbubbles of the acyclic partitions (po_layout_superbubbles) and the bubble
+ * chains built from them (po_layout_bubblechains).  graph_to_dag and the superbubbles of the cyclic partitions, contigs and
+ * phasing are not part of it. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -744,6 +745,73 @@ po_status po_layout_superbubbles(po_handle* h, po_result* graph, const po_superb
                                  uint32_t* node_inside_out, uint8_t* node_flags_out, po_superbubble* bubbles_out,
                                  uint64_t* n_bubbles_out);
 po_status po_get_superbubble_stats(const po_handle* h, po_superbubble_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The bubble chains of `phasm chain`: build_bubblechains (phasm/assembly_graph.py:594-652), as cli/assembler.py:272
+ * calls it on every weakly connected component.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t min_nodes;          /* a chain with fewer nodes is not reported (the reference's default: 1); 0 is invalid */
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_bubblechain_params;
+
+typedef struct {
+    uint32_t first_entrance;     /* the head: the entrance of the chain's first bubble (node id)                 */
+    uint32_t last_exit;          /* the exit of the chain's last bubble (node id)                                */
+    uint32_t n_bubbles;          /* top-level bubbles of the chain                                               */
+    uint32_t n_nodes;            /* nodes of the chain                                                           */
+    uint64_t n_edges;            /* edges of the graph with both ends in the chain                               */
+} po_bubblechain;                /* 24 bytes                                                                     */
+
+typedef struct {
+    uint64_t n_nodes;            /* nodes of the graph (those in its node order)                                 */
+    uint64_t n_edges;
+    uint64_t n_bubbles;          /* superbubbles of the acyclic partitions, nested ones included                 */
+    uint64_t n_top;              /* ... of them not nested                                                       */
+    uint64_t n_chains;           /* chains reported                                                              */
+    uint64_t n_short;            /* chains dropped by min_nodes                                                  */
+    uint64_t n_chain_nodes, n_chain_edges;   /* nodes / edges of the graph in a reported chain                   */
+    uint64_t n_invalid;          /* edges with an end that is not in the node order (the call fails then)        */
+    uint32_t max_chain_bubbles;  /* bubbles of the longest chain, dropped chains included                        */
+    uint32_t n_nest_rounds, n_chain_rounds;  /* pointer-jumping rounds, each loop's closing round included       */
+    uint32_t n_batches;          /* readbacks of all round loops, those of the superbubble stage included        */
+    float ms_superbubbles, ms_chains, ms_label, ms_total;
+} po_bubblechain_stats;
+
+/* `graph` is a graph result of this handle, of the kinds po_layout_superbubbles takes; it stays valid and unchanged.  Ranks,
+ * superbubbles, `nested` and the node_inside chains are exactly those of po_layout_superbubbles.  A TOP-LEVEL bubble is a
+ * table entry with nested == 0: what find_superbubbles(g, report_nested=False) reports on an acyclic partition.  Bubble
+ * (s, t) is LINKED to bubble (t, w) when both are top-level; a BUBBLE CHAIN is a maximal sequence of linked top-level
+ * bubbles, its HEAD the entrance that is no top-level exit.  The links are acyclic (the structure graph is a DAG) and a node
+ * enters at most one bubble and exits at most one, so chains are disjoint and every node lies in at most one.  The NODES of
+ * a chain are the ends of its bubbles plus every node whose chain of node_inside reaches one of its entrances (nested
+ * bubbles form no chain of their own: their nodes belong to the chain of the top-level bubble around them); its EDGES are
+ * the graph's edges with both ends in the chain (the reference's networkx.subgraph).  A chain with fewer than min_nodes
+ * nodes is not reported and its nodes carry no chain.  Chains are numbered by the rank of their heads.
+ *   node_chain_out   the chain of the node, else PO_NO_NODE; parallel to the node order
+ *   node_bubble_out  the 0-based position in its chain of the top-level bubble that holds the node, else PO_NO_NODE: for an
+ *                    entrance the bubble it enters, for a chain's last exit the bubble it exits, for every other node the
+ *                    bubble that holds it strictly
+ *   edge_chain_out   in the graph's edge order: the chain when both ends carry the same one, else PO_NO_NODE
+ *   chains_out       one entry per chain, in chain order (room for n_order entries)
+ * Any of the four may be NULL; *n_chains_out is always written.  Not reproduced: the reference's numbering j, which follows
+ * the iteration order of a Python set of node objects; cyclic partitions (graph_to_dag), as in po_layout_superbubbles; where
+ * a component holds a non-singleton SCC or a self-loop the definition above applies, not the reference.  On a component
+ * in which every SCC is a singleton and no node has a self-loop the reference yields exactly these chains (DESIGN.md
+ * section 3.9k has the proof).  Only integers are involved: every output is the same on every run (the round counts of the
+ * stats are statistics).  An edge with an end that is not in the node order is counted in n_invalid; the call then fails
+ * with PO_ERR_INVALID and writes nothing.  Device memory beyond the inputs is linear: at most 260 bytes per node (168 of
+ * them po_layout_superbubbles', whose workspaces the call fills first; 92 its own) and 21 per edge (17 + 4).  params may
+ * be NULL (min_nodes 1).  An empty graph with an empty order: PO_OK, 0 chains.  Every round loop is bounded on the host (the
+ * pointer jumping by its live entries + 2 rounds, though it needs only logarithmically many; the rest as in
+ * po_layout_superbubbles); reaching a bound is PO_ERR_HIP with a message, never a result.  There is no CPU fallback: without
+ * a GPU the call returns PO_ERR_HIP.  A row result, a result of another handle, reserved != 0, min_nodes == 0, n_chains_out
+ * NULL: PO_ERR_INVALID. */
+po_status po_layout_bubblechains(po_handle* h, po_result* graph, const po_bubblechain_params* params, uint32_t* node_chain_out,
+                                 uint32_t* node_bubble_out, uint32_t* edge_chain_out, po_bubblechain* chains_out,
+                                 uint64_t* n_chains_out);
+po_status po_get_bubblechain_stats(const po_handle* h, po_bubblechain_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

@@ -37,6 +37,8 @@ SUPERBUBBLE_DTYPE = np.dtype([("entrance", "<u4"), ("exit", "<u4"), ("n_inside",
 # PO_SB_*: the bits of po_layout_superbubbles' flag byte per node; PO_NO_NODE
 SB_ENTRANCE, SB_EXIT, SB_NESTED, SB_SELF_LOOP = 1, 2, 4, 8
 NO_NODE = 0xFFFFFFFF
+# po_bubblechain
+BUBBLECHAIN_DTYPE = np.dtype([("first_entrance", "<u4"), ("last_exit", "<u4"), ("n_bubbles", "<u4"), ("n_nodes", "<u4"), ("n_edges", "<u8")])
 
 
 class PoLayoutParams(ctypes.Structure):
@@ -181,6 +183,22 @@ class PoSuperbubbleStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoBubblechainParams(ctypes.Structure):
+    _fields_ = [("min_nodes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class PoBubblechainStats(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("n_edges", ctypes.c_uint64), ("n_bubbles", ctypes.c_uint64), ("n_top", ctypes.c_uint64),
+                ("n_chains", ctypes.c_uint64), ("n_short", ctypes.c_uint64), ("n_chain_nodes", ctypes.c_uint64),
+                ("n_chain_edges", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64), ("max_chain_bubbles", ctypes.c_uint32),
+                ("n_nest_rounds", ctypes.c_uint32), ("n_chain_rounds", ctypes.c_uint32), ("n_batches", ctypes.c_uint32),
+                ("ms_superbubbles", ctypes.c_float), ("ms_chains", ctypes.c_float), ("ms_label", ctypes.c_float),
+                ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -288,6 +306,9 @@ SYMBOLS = [
     ("po_layout_superbubbles", ctypes.c_int, [_P, _P, ctypes.POINTER(PoSuperbubbleParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_superbubble_stats", ctypes.c_int, [_P, ctypes.POINTER(PoSuperbubbleStats)]),
+    ("po_layout_bubblechains", ctypes.c_int, [_P, _P, ctypes.POINTER(PoBubblechainParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_bubblechain_stats", ctypes.c_int, [_P, ctypes.POINTER(PoBubblechainStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

@@ -290,7 +290,8 @@ def chain_components(args) -> int:
         logger.critical("No valid file formats specified.")
         sys.exit(1)
     logger.info("Reconstructing assembly graph...")
-    g = layout.chain_components(args.graph_gfa, device=args.device, partitions=args.partitions, superbubbles=args.superbubbles)
+    g = layout.chain_components(args.graph_gfa, device=args.device, partitions=args.partitions, superbubbles=args.superbubbles,
+                                bubblechains=args.bubblechains, min_nodes=args.min_nodes)
     logger.info("Enumerate weakly connected components in the graph...")
     n = layout.write_component_graphs(args.output_dir, g, formats)
     for parts in g.partitions or ():
@@ -386,6 +387,10 @@ def main(argv=None) -> int:
     k.add_argument("-f", "--format", default="gfa2", help="comma separated: gfa1, gfa2, graphml (default: gfa2)")
     k.add_argument("-o", "--output-dir", required=True)
     k.add_argument("--device", type=int, default=None)
+    k.add_argument("--bubblechains", action="store_true",
+                   help="also build the bubble chains of every component: component{i}.bubblechain{j}.* and the node attribute "
+                        "bubblechain in component{i}.graphml")
+    k.add_argument("--min-nodes", type=int, default=1, help="with --bubblechains: drop chains with fewer nodes (default: 1)")
     k.add_argument("--superbubbles", action="store_true",
                    help="also log, per component, the number of superbubbles of its acyclic partition")
     k.add_argument("--partitions", action="store_true",

@@ -44,6 +44,7 @@
 #include "components.hip.h"
 #include "partition.hip.h"
 #include "superbubbles.hip.h"
+#include "bubblechains.hip.h"
 
 namespace {
 
@@ -69,12 +70,16 @@ enum { PB_LIVE, PB_SCC, PB_COLOUR, PB_MARK, PB_HASIN, PB_HASOUT, PB_NODESCC, PB_
 // workspaces of po_layout_superbubbles (superbubbles.hip.h) beyond those of the rank scaffold and of po_layout_partition
 enum { UB_CNT, UB_W, UB_CIN, UB_COUT, UB_OFFIN, UB_OFFOUT, UB_CURIN, UB_CUROUT, UB_LISTIN, UB_LISTOUT, UB_LVLF, UB_LVLB, UB_IDOM, UB_IPDOM,
        UB_DEPTH, UB_EXIT, UB_ENCL, UB_INSIDE, UB_TOTAL, UB_DEAD, UB_EXITOUT, UB_INSIDEOUT, UB_FLAGSOUT, UB_TABLE, UB_N };
+// workspaces of po_layout_bubblechains (bubblechains.hip.h) beyond those of the rank scaffold, po_layout_partition and
+// po_layout_superbubbles
+enum { HB_CNT, HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOPS1, HB_NHEAD, HB_NPOS, HB_CB, HB_CN, HB_LAST, HB_CE,
+       HB_CHAINOUT, HB_BUBBLEOUT, HB_EDGEOUT, HB_TABLE, HB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 45;
+constexpr int EV_LAY_N = 54;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
-       EV_PARTITION = 34, EV_SUPERBUBBLES = 38 };
-static_assert(EV_SUPERBUBBLES + 7 == EV_LAY_N, "the seven events of po_layout_superbubbles are the last of the layout events");
+       EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45 };
+static_assert(EV_BUBBLECHAINS + 9 == EV_LAY_N, "the nine events of po_layout_bubblechains are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -427,6 +432,9 @@ struct po_handle {
     // the superbubbles of the acyclic partitions (po_layout_superbubbles, superbubbles.hip.h)
     DevBuf d_sb[UB_N];
     po_superbubble_stats sbstats = {};
+    // the bubble chains (po_layout_bubblechains, bubblechains.hip.h)
+    DevBuf d_bc[HB_N];
+    po_bubblechain_stats bcstats = {};
 };
 
 struct po_result {
@@ -4020,24 +4028,33 @@ po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint
 
 // ---- the superbubbles of the acyclic partitions (po_layout_superbubbles, superbubbles.hip.h) ------------------------------
 
-po_status run_superbubbles(po_handle* h, po_result* graph, uint32_t* exit_out, uint32_t* inside_out, uint8_t* flags_out,
-                           po_superbubble* table_out, uint64_t* n_bubbles_out) {
-    const char* const name = "po_layout_superbubbles";
+// what the superbubble stage counts, for the stats of its callers
+struct SbWork {
+    uint64_t n_p_nodes = 0, n_p_edges = 0, n_bubbles = 0, n_nested = 0, n_self_loop_nodes = 0, n_discarded = 0;
+    uint32_t n_levels_forward = 0, n_levels_backward = 0, n_scc_rounds = 0, n_level_rounds = 0, n_discard_rounds = 0, n_batches = 0;
+};
+
+// The superbubble stage on the device, as po_layout_superbubbles and po_layout_bubblechains run it (`name`, the first of
+// the caller's events, the caller's stats for ranked_open): scc_stage with the workspaces of d_sb and the caller's `own`,
+// then everything up to the table, all left in d_sb -- the byte "enters a surviving bubble" per rank in R.root, the number
+// of every entrance in R.index, exit_of in UB_EXIT, the holder in UB_INSIDE; the counters in UB_CNT.  Records ev[3]..ev[6].
+// S is filled whatever the outcome.  !R.ev or !R.n_order: nothing to do.
+template <class Stats, class Own>
+po_status superbubble_stage(po_handle* h, po_result* graph, const char* const name, int ev_first, Stats& stats, Own&& own, RankedGraph& R,
+                            SbWork& S) {
     hipStream_t st = h->stream;
-    po_superbubble_stats& S = h->sbstats;
-    S = po_superbubble_stats();
     DevBuf* B = h->d_sb;
-    RankedGraph R;
     po::SccWork W;
     uint32_t n_scc = 0;
-    const po_status staged = scc_stage(h, graph, name, EV_SUPERBUBBLES, S, [&](size_t nn, size_t ne) {
+    const po_status staged = scc_stage(h, graph, name, ev_first, stats, [&](size_t nn, size_t ne) {
         PO_TRY(ensure(h, B[UB_CNT], 128));
         for (int k : {UB_W, UB_CIN, UB_COUT, UB_OFFIN, UB_OFFOUT, UB_CURIN, UB_CUROUT, UB_LVLF, UB_LVLB, UB_IDOM, UB_IPDOM, UB_DEPTH, UB_EXIT,
                       UB_ENCL, UB_INSIDE, UB_TOTAL, UB_EXITOUT, UB_INSIDEOUT})
             PO_TRY(ensure(h, B[k], nn * 4));
         for (int k : {UB_DEAD, UB_FLAGSOUT}) PO_TRY(ensure(h, B[k], nn));
         for (int k : {UB_LISTIN, UB_LISTOUT}) PO_TRY(ensure(h, B[k], ne * 4));
-        return ensure(h, B[UB_TABLE], nn * sizeof(po::Bubble));
+        PO_TRY(ensure(h, B[UB_TABLE], nn * sizeof(po::Bubble)));
+        return own(nn, ne);
     }, R, W, n_scc);
     S.n_scc_rounds = W.trim_rounds + W.forward_rounds + W.backward_rounds;
     S.n_batches = W.batches;
@@ -4143,15 +4160,153 @@ po_status run_superbubbles(po_handle* h, po_result* graph, uint32_t* exit_out, u
                            table);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[6], st));
+    return PO_OK;
+}
+
+po_status run_superbubbles(po_handle* h, po_result* graph, uint32_t* exit_out, uint32_t* inside_out, uint8_t* flags_out,
+                           po_superbubble* table_out, uint64_t* n_bubbles_out) {
+    po_superbubble_stats& S = h->sbstats;
+    S = po_superbubble_stats();
+    DevBuf* B = h->d_sb;
+    RankedGraph R;
+    SbWork W;
+    const po_status staged = superbubble_stage(h, graph, "po_layout_superbubbles", EV_SUPERBUBBLES, S, [](size_t, size_t) { return PO_OK; }, R, W);
+    S.n_p_nodes = W.n_p_nodes;
+    S.n_p_edges = W.n_p_edges;
+    S.n_bubbles = W.n_bubbles;
+    S.n_nested = W.n_nested;
+    S.n_self_loop_nodes = W.n_self_loop_nodes;
+    S.n_discarded = W.n_discarded;
+    S.n_levels_forward = W.n_levels_forward;
+    S.n_levels_backward = W.n_levels_backward;
+    S.n_scc_rounds = W.n_scc_rounds;
+    S.n_level_rounds = W.n_level_rounds;
+    S.n_discard_rounds = W.n_discard_rounds;
+    S.n_batches = W.n_batches;
+    PO_TRY(staged);
+    if (!R.ev || !R.n_order) return PO_OK;
+    const uint32_t n_order = R.n_order, n_bubbles = (uint32_t)W.n_bubbles;
+    hipEvent_t* ev = R.ev;
     static_assert(sizeof(po_superbubble) == sizeof(po::Bubble) && sizeof(po_superbubble) == 16, "po_superbubble is the device's table entry");
-    PO_TRY(land_outputs(h, {{table, (size_t)n_bubbles * sizeof(po_superbubble), table_out}, {d_exit, (size_t)n_order * 4, exit_out},
-                            {d_inside, (size_t)n_order * 4, inside_out}, {d_flags, n_order, flags_out}}, cnt, po::BC_N));
+    PO_TRY(land_outputs(h, {{B[UB_TABLE].p, (size_t)n_bubbles * sizeof(po_superbubble), table_out},
+                            {B[UB_EXITOUT].p, (size_t)n_order * 4, exit_out}, {B[UB_INSIDEOUT].p, (size_t)n_order * 4, inside_out},
+                            {B[UB_FLAGSOUT].p, n_order, flags_out}}, B[UB_CNT].as<unsigned long long>(), po::BC_N));
     *n_bubbles_out = n_bubbles;
     (void)hipEventElapsedTime(&S.ms_partition, ev[0], ev[3]);
     (void)hipEventElapsedTime(&S.ms_levels, ev[3], ev[4]);
     (void)hipEventElapsedTime(&S.ms_dominators, ev[4], ev[5]);
     (void)hipEventElapsedTime(&S.ms_label, ev[5], ev[6]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[6]);
+    return PO_OK;
+}
+
+// ---- the bubble chains (po_layout_bubblechains, bubblechains.hip.h) -------------------------------------------------------
+
+po_status run_bubblechains(po_handle* h, po_result* graph, uint32_t min_nodes, uint32_t* chain_out, uint32_t* bubble_out,
+                           uint32_t* edge_out, po_bubblechain* table_out, uint64_t* n_chains_out) {
+    const char* const name = "po_layout_bubblechains";
+    hipStream_t st = h->stream;
+    po_bubblechain_stats& S = h->bcstats;
+    S = po_bubblechain_stats();
+    DevBuf* B = h->d_bc;
+    RankedGraph R;
+    SbWork W;
+    const po_status staged = superbubble_stage(h, graph, name, EV_BUBBLECHAINS, S, [&](size_t nn, size_t ne) {
+        PO_TRY(ensure(h, B[HB_CNT], 128));
+        for (int k : {HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOPS1, HB_NHEAD, HB_NPOS, HB_CB, HB_CN, HB_LAST, HB_CHAINOUT,
+                      HB_BUBBLEOUT})
+            PO_TRY(ensure(h, B[k], nn * 4));
+        PO_TRY(ensure(h, B[HB_CE], nn * 8));
+        PO_TRY(ensure(h, B[HB_EDGEOUT], ne * 4));
+        return ensure(h, B[HB_TABLE], nn * sizeof(po::BubbleChain));
+    }, R, W);
+    S.n_bubbles = W.n_bubbles;
+    S.n_batches = W.n_batches;
+    PO_TRY(staged);
+    if (!R.ev || !R.n_order) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order;
+    hipEvent_t* ev = R.ev;
+    unsigned long long *cnt = B[HB_CNT].as<unsigned long long>(), *ce = B[HB_CE].as<unsigned long long>();
+    uint32_t *fw = B[HB_FW].as<uint32_t>(), *next = B[HB_NEXT].as<uint32_t>(), *pred = B[HB_PRED].as<uint32_t>(), *top = B[HB_TOP].as<uint32_t>(),
+             *jb[2] = {B[HB_JB0].as<uint32_t>(), B[HB_JB1].as<uint32_t>()}, *hops[2] = {B[HB_HOPS0].as<uint32_t>(), B[HB_HOPS1].as<uint32_t>()},
+             *nhead = B[HB_NHEAD].as<uint32_t>(), *npos = B[HB_NPOS].as<uint32_t>(), *cb = B[HB_CB].as<uint32_t>(), *cn = B[HB_CN].as<uint32_t>(),
+             *last = B[HB_LAST].as<uint32_t>(), *d_chain = B[HB_CHAINOUT].as<uint32_t>(), *d_bubble = B[HB_BUBBLEOUT].as<uint32_t>(),
+             *d_edge = B[HB_EDGEOUT].as<uint32_t>();
+    po::BubbleChain* table = B[HB_TABLE].as<po::BubbleChain>();
+    const uint32_t *exit_of = h->d_sb[UB_EXIT].as<uint32_t>(), *inside = h->d_sb[UB_INSIDE].as<uint32_t>();
+    volatile uint64_t* C = h->pinned + 48;   // this stage's counters on the host (words 16.. and 32.. are the scaffold's)
+    auto counters_home = [&]() -> po_status {
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 48, cnt, po::HK_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        return PO_OK;
+    };
+    // top-level entrances (R.root still holds the byte "enters a surviving bubble"), their links, the heads
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    hipLaunchKernelGGL(po::k_bc_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, R.root, inside, fw, next, pred, top, cb, cn, ce, last);
+    hipLaunchKernelGGL(po::k_bc_link, dim3(R.rank_grid), dim3(256), 0, st, n_order, fw, exit_of, next, pred, cnt);
+    hipLaunchKernelGGL(po::k_bc_heads, dim3(R.rank_grid), dim3(256), 0, st, n_order, pred, fw, jb[0], hops[0], cnt);
+    PO_TRY(counters_home());
+    const uint64_t n_top = C[po::HK_TOP], n_heads = C[po::HK_HEADS];
+    if (n_top + W.n_nested != W.n_bubbles || n_heads > n_top || (n_top && !n_heads))
+        return fail(h, PO_ERR_HIP, std::string("internal: the top-level bubbles of ") + name + " do not add up");
+    S.n_top = n_top;
+    RoundOps ops{h, st, R.rcnt};
+    uint64_t ignored = 0;
+    // the outermost holder of every rank inside a bubble: needed only where a bubble lies inside another
+    if (n_top && W.n_nested) {
+        const int how = po::round_phase(ops, W.n_nested, [&](uint32_t j) {
+            hipLaunchKernelGGL(po::k_bc_nest, dim3(R.rank_grid), dim3(256), 0, st, n_order, top, R.rcnt + j);
+        }, S.n_nest_rounds, S.n_batches, ignored);
+        if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, std::string("internal: the holders of ") + name + " reached their bound of nested + 2 rounds");
+    }
+    // list ranking of the top-level entrances toward their head: ping-pong, the last launch wrote jb[fin] / hops[fin]
+    uint32_t launched = 0;
+    if (n_top) {
+        const int how = po::round_phase(ops, n_top, [&](uint32_t j) {
+            const uint32_t a = launched & 1, b = a ^ 1;
+            hipLaunchKernelGGL(po::k_bc_jump, dim3(R.rank_grid), dim3(256), 0, st, n_order, jb[a], hops[a], jb[b], hops[b], R.rcnt + j);
+            ++launched;
+        }, S.n_chain_rounds, S.n_batches, ignored);
+        if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, std::string("internal: the ranking of ") + name + " reached its bound of top-level + 2 rounds");
+    }
+    const uint32_t fin = launched & 1;
+    HIP_TRY(h, hipEventRecord(ev[7], st));
+    // chain and position of every rank, the sums per head, the filter, the numbering of the surviving heads
+    hipLaunchKernelGGL(po::k_bc_place, dim3(R.rank_grid), dim3(256), 0, st, n_order, fw, next, pred, top, exit_of, jb[fin], hops[fin], nhead, npos,
+                       cb, cn, last, cnt);
+    if (n) hipLaunchKernelGGL(po::k_bc_edges, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, nhead, ce);
+    hipLaunchKernelGGL(po::k_bc_filter, dim3(R.rank_grid), dim3(256), 0, st, n_order, min_nodes, fw, cb, cn, ce, R.root, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint8_t>(h, R.root, n_order, R.index, &h->pinned[2]));
+    PO_TRY(counters_home());
+    if (C[po::HK_BAD]) return fail(h, PO_ERR_HIP, std::string("internal: a node of ") + name + " reached no head");
+    const uint64_t n64 = h->pinned[2];
+    if (n64 != C[po::HK_CHAINS] || n64 + C[po::HK_SHORT] != n_heads || C[po::HK_CNODES] > n_order || C[po::HK_CEDGES] > n ||
+        C[po::HK_MAXB] > n_top)
+        return fail(h, PO_ERR_HIP, std::string("internal: the chains of ") + name + " do not add up");
+    const uint32_t n_chains = (uint32_t)n64;
+    S.n_chains = n_chains;
+    S.n_short = C[po::HK_SHORT];
+    S.n_chain_nodes = C[po::HK_CNODES];
+    S.n_chain_edges = C[po::HK_CEDGES];
+    S.max_chain_bubbles = (uint32_t)C[po::HK_MAXB];
+    if (n_chains)
+        hipLaunchKernelGGL(po::k_bc_table, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_chains, R.val, R.root, R.index, last, cb, cn, ce, table);
+    hipLaunchKernelGGL(po::k_bc_nodes, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_chains, R.root, R.index, nhead, npos, d_chain, d_bubble);
+    if (n) hipLaunchKernelGGL(po::k_bc_edge_out, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, d_chain, d_edge);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[8], st));
+    static_assert(sizeof(po_bubblechain) == sizeof(po::BubbleChain) && sizeof(po_bubblechain) == 24, "po_bubblechain is the device's table entry");
+    PO_TRY(land_outputs(h, {{table, (size_t)n_chains * sizeof(po_bubblechain), table_out}, {d_chain, (size_t)n_order * 4, chain_out},
+                            {d_bubble, (size_t)n_order * 4, bubble_out}, {d_edge, (size_t)n * 4, edge_out}}, cnt, po::HK_N));
+    *n_chains_out = n_chains;
+    (void)hipEventElapsedTime(&S.ms_superbubbles, ev[0], ev[6]);
+    (void)hipEventElapsedTime(&S.ms_chains, ev[6], ev[7]);
+    (void)hipEventElapsedTime(&S.ms_label, ev[7], ev[8]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[8]);
     return PO_OK;
 }
 
@@ -4628,6 +4783,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_cc) b.release();
         for (DevBuf& b : h->d_scc) b.release();
         for (DevBuf& b : h->d_sb) b.release();
+        for (DevBuf& b : h->d_bc) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -6479,6 +6635,17 @@ po_status po_layout_superbubbles(po_handle* h, po_result* graph, const po_superb
 }
 
 po_status po_get_superbubble_stats(const po_handle* h, po_superbubble_stats* out) { return get_stats(h, &po_handle::sbstats, out); }
+
+po_status po_layout_bubblechains(po_handle* h, po_result* graph, const po_bubblechain_params* params, uint32_t* node_chain_out,
+                                 uint32_t* node_bubble_out, uint32_t* edge_chain_out, po_bubblechain* chains_out, uint64_t* n_chains_out) {
+    return graph_call(h, graph, "po_layout_bubblechains", !params || (params->reserved == 0 && params->min_nodes != 0), "bubble chains",
+                      n_chains_out, [&] {
+        return run_bubblechains(h, graph, params ? params->min_nodes : 1u, node_chain_out, node_bubble_out, edge_chain_out, chains_out,
+                                n_chains_out);
+    });
+}
+
+po_status po_get_bubblechain_stats(const po_handle* h, po_bubblechain_stats* out) { return get_stats(h, &po_handle::bcstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

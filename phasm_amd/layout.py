@@ -29,7 +29,10 @@ still in HBM, and ``write_graphml`` writes the graph with that attribute (the co
 ``strongly_connected_components`` (``po_layout_partition``) and ``superbubble_partitions`` are what superbubble detection
 starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).  ``superbubbles``
 (``po_layout_superbubbles``) are the superbubbles of the acyclic partitions: ``SuperBubbleFinderDAG`` (bubbles.py:174-381).
-What follows that point (bubble chains, contigs, phasing) is out of scope.
+``bubble_chains`` (``po_layout_bubblechains``) builds the chains of the bubbles that are not nested:
+``build_bubblechains`` (assembly_graph.py:594-652); with them ``write_component_graphs`` also writes
+``component{i}.bubblechain{j}.*`` and the node attribute ``bubblechain``.
+What follows that point (contigs, phasing) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -153,11 +156,12 @@ def average_coverage(ov: ExactOverlapper, graph_res: OverlapResult, rows_res: Ov
     return _quotients(ov.layout_coverage(graph_res, rows_res))
 
 
-def write_graphml(f, g: "AssemblyEdges") -> int:
+def write_graphml(f, g: "AssemblyEdges", bubblechain: Optional[dict] = None) -> int:
     """The graph ``g`` as GraphML with the reference's attribute names: nodes named by ``node_name`` (the nodes of
     ``node_order`` where the result carries one, else the ends of the edges in order of appearance), edge data ``weight``,
-    ``overlap_len`` and, when present, ``avg_coverage`` (written with ``repr``: it reads back to the same double).
-    Returns the number of edges."""
+    ``overlap_len`` and, when present, ``avg_coverage`` (written with ``repr``: it reads back to the same double).  With
+    ``bubblechain`` ({node name: number}, None: no such attribute) the nodes it names carry the node attribute
+    ``bubblechain`` (long), as `phasm chain` marks them (assembler.py:277-278).  Returns the number of edges."""
     from xml.sax.saxutils import escape, quoteattr
     names = g.edge_tuples()
     nodes = [g.node_name(n) for n in g.node_order.tolist()] if g.node_order is not None else []
@@ -175,8 +179,14 @@ def write_graphml(f, g: "AssemblyEdges") -> int:
             '  <key id="d1" for="edge" attr.name="overlap_len" attr.type="long" />\n')
     if cov is not None:
         f.write('  <key id="d2" for="edge" attr.name="avg_coverage" attr.type="double" />\n')
+    if bubblechain is not None:
+        f.write('  <key id="d3" for="node" attr.name="bubblechain" attr.type="long" />\n')
     f.write('  <graph edgedefault="directed">\n')
-    f.write("".join("    <node id=%s />\n" % quoteattr(n) for n in nodes))
+    if bubblechain is None:
+        f.write("".join("    <node id=%s />\n" % quoteattr(n) for n in nodes))
+    else:
+        f.write("".join('    <node id=%s>\n      <data key="d3">%d</data>\n    </node>\n' % (quoteattr(n), bubblechain[n])
+                        if n in bubblechain else "    <node id=%s />\n" % quoteattr(n) for n in nodes))
     for i, (u, v, w, o) in enumerate(names):
         f.write('    <edge source=%s target=%s>\n      <data key="d0">%d</data>\n      <data key="d1">%d</data>\n'
                 % (quoteattr(u), quoteattr(v), w, o))
@@ -640,22 +650,103 @@ def superbubbles(ov: ExactOverlapper, graph_res: OverlapResult) -> Superbubbles:
 _superbubbles = superbubbles   # (chain_components has an argument of that name)
 
 
+# ---- the bubble chains (build_bubblechains, phasm/assembly_graph.py:594-652) -------------------------------------------------
+
+@dataclass
+class BubbleChains:
+    """The bubble chains of a graph result (``po_layout_bubblechains``).  ``node_order``: the graph's nodes in the
+    reference's order; ``node_chain`` / ``node_bubble`` (``_lib.NO_NODE`` where there is none): parallel to it, the chain of
+    the node and the position in that chain of the top-level bubble that holds it; ``edge_chain``: the chain that holds both
+    ends of every edge, in the graph's edge order; ``table``: structured (``first_entrance``, ``last_exit``, ``n_bubbles``,
+    ``n_nodes``, ``n_edges``), one entry per chain in the order of the heads' ranks (the reference numbers them in the
+    iteration order of a Python set); ``node_exit``: ``Superbubbles.node_exit`` of the same graph; ``stats``:
+    ``po_get_bubblechain_stats``."""
+    node_order: np.ndarray
+    node_chain: np.ndarray
+    node_bubble: np.ndarray
+    edge_chain: np.ndarray
+    table: np.ndarray
+    node_exit: np.ndarray
+    stats: dict
+
+    def __len__(self) -> int:
+        return len(self.table)
+
+    def _among(self, of: np.ndarray):
+        from ._lib import NO_NODE
+        return _groups(of, len(self), np.flatnonzero(of != NO_NODE))
+
+    def nodes_of(self, j: int) -> np.ndarray:
+        """The nodes of chain ``j``, in node order: what ``build_bubblechains`` yields as a subgraph."""
+        if not hasattr(self, "_node_group"):
+            self._node_group = self._among(self.node_chain)
+        by, off = self._node_group
+        return self.node_order[by[off[j]:off[j + 1]]]
+
+    def edges_of(self, j: int) -> np.ndarray:
+        """The indices of the edges of chain ``j``, in the graph's edge order."""
+        if not hasattr(self, "_edge_group"):
+            self._edge_group = self._among(self.edge_chain)
+        by, off = self._edge_group
+        return by[off[j]:off[j + 1]]
+
+    def bubbles_of(self, j: int) -> List[tuple]:
+        """The (entrance, exit) pairs of the top-level bubbles of chain ``j``, in chain order."""
+        if not hasattr(self, "_rank"):
+            self._rank = {int(n): r for r, n in enumerate(self.node_order.tolist())}
+        out, s = [], int(self.table["first_entrance"][j])
+        for _ in range(int(self.table["n_bubbles"][j])):
+            t = int(self.node_exit[self._rank[s]])
+            out.append((s, t))
+            s = t
+        return out
+
+
+def bubble_chains(ov: ExactOverlapper, graph_res: OverlapResult, min_nodes: int = 1,
+                  superbubbles: Optional[Superbubbles] = None) -> BubbleChains:
+    """``po_layout_bubblechains`` on a graph result of ``ov`` (an edge result, a merged graph or a ``graph_from_edges``
+    result), which stays valid and in HBM; ``superbubbles``: ``layout.superbubbles`` of the same graph, if the caller has
+    them (computed here otherwise: ``bubbles_of`` reads the exits from them)."""
+    order = graph_res.node_order()
+    if superbubbles is None:
+        superbubbles = _superbubbles(ov, graph_res)
+    node_chain, node_bubble, edge_chain, table = ov.layout_bubblechains(graph_res, min_nodes, len(order))
+    return BubbleChains(order, node_chain, node_bubble, edge_chain, table, superbubbles.node_exit, ov.bubblechain_stats())
+
+
+def chains_by_component(chains: BubbleChains, components: Components) -> List[List[int]]:
+    """Per weakly connected component the chains in it, in chain order: chain ``out[i][j]`` is what `phasm chain` writes as
+    ``component{i}.bubblechain{j}`` (its own j follows the iteration order of a Python set)."""
+    out = [[] for _ in range(len(components))]
+    if len(chains):
+        rank = np.zeros(int(chains.node_order.max()) + 1, dtype=np.int64)
+        rank[chains.node_order] = np.arange(len(chains.node_order))
+        for c, i in enumerate(components.component_of_node[rank[chains.table["first_entrance"]]].tolist()):
+            out[i].append(c)
+    return out
+
+
 @dataclass
 class ChainGraph:
     """What ``chain_components`` hands to the writers: the graph file as read (``phasm_amd.io.gfa.GraphFile``) and its
     components; with ``partitions=True`` also the strongly connected components and, per component, the partitions that
-    superbubble detection starts with; with ``superbubbles=True`` also the superbubbles of the acyclic partitions."""
+    superbubble detection starts with; with ``superbubbles=True`` also the superbubbles of the acyclic partitions; with
+    ``bubblechains=True`` also the bubble chains and, per component, the chains in it (``chains_by_component``)."""
     graph: object
     components: Components
     sccs: Optional[StrongComponents] = None
     partitions: Optional[List[List[Partition]]] = None
     superbubbles: Optional[Superbubbles] = None
+    bubblechains: Optional[BubbleChains] = None
+    component_chains: Optional[List[List[int]]] = None
 
 
-def chain_components(path: str, device: Optional[int] = None, partitions: bool = False, superbubbles: bool = False) -> ChainGraph:
+def chain_components(path: str, device: Optional[int] = None, partitions: bool = False, superbubbles: bool = False,
+                     bubblechains: bool = False, min_nodes: int = 1) -> ChainGraph:
     """The start of `phasm chain` on a graph file: ``read_graph_gfa``, one segment per ``S`` line on a fresh handle, the
     graph on the device (``graph_from_edges``) and its weakly connected components; with ``partitions`` also
-    ``strongly_connected_components`` and ``superbubble_partitions``; with ``superbubbles`` also ``superbubbles``."""
+    ``strongly_connected_components`` and ``superbubble_partitions``; with ``superbubbles`` also ``superbubbles``; with
+    ``bubblechains`` also ``bubble_chains`` (``min_nodes`` as in ``build_bubblechains``) and ``chains_by_component``."""
     from .io import gfa
     with open(path) as f:
         graph = gfa.read_graph_gfa(f)
@@ -671,6 +762,9 @@ def chain_components(path: str, device: Optional[int] = None, partitions: bool =
                 out.partitions = superbubble_partitions(out.sccs, out.components)
             if superbubbles:
                 out.superbubbles = _superbubbles(ov, res)
+            if bubblechains:
+                out.bubblechains = bubble_chains(ov, res, min_nodes, out.superbubbles)
+                out.component_chains = chains_by_component(out.bubblechains, out.components)
             return out
         finally:
             res.free()
@@ -733,20 +827,34 @@ class _ComponentView:
 
 def write_component_graphs(out_dir: str, g: ChainGraph, formats: Sequence[str] = ("gfa2",)) -> int:
     """``component{i}.gfa`` and / or ``component{i}.graphml`` for every component, as ``_write_graphs`` writes them
-    (assembler.py:215-228, :303-304): ``gfa1`` and ``gfa2`` go to the same name, so with both the later one wins.
-    Returns the number of components."""
+    (assembler.py:215-228, :303-304): ``gfa1`` and ``gfa2`` go to the same name, so with both the later one wins.  Where
+    ``g`` carries bubble chains, before each component's own files also ``component{i}.bubblechain{j}.gfa`` / ``.graphml``
+    for every chain j of component i with the reference's log line (assembler.py:272-286), and the component's GraphML
+    carries the node attribute ``bubblechain`` = j.  Returns the number of components."""
     os.makedirs(out_dir, exist_ok=True)
     comps = g.components
+
+    def write(stem, nodes, edges, marks):
+        for file_format in formats:
+            if file_format.startswith("gfa"):
+                lines = (component_gfa1_lines if int(file_format[-1]) == 1 else component_gfa2_lines)(g.graph, nodes, edges)
+                with open(os.path.join(out_dir, stem + ".gfa"), "w") as f:
+                    f.write("".join(lines))
+            else:
+                with open(os.path.join(out_dir, stem + ".graphml"), "w") as f:
+                    write_graphml(f, _ComponentView(g.graph, nodes, edges), marks)
+
     for i in range(len(comps)):
         nodes, idx = comps.nodes_of(i).tolist(), comps.edges_of(i)
         edges = g.graph.edges[idx]
         logger.info("Connected component %d with %d nodes and %d edges.", i, len(nodes), len(edges))
-        for file_format in formats:
-            if file_format.startswith("gfa"):
-                lines = (component_gfa1_lines if int(file_format[-1]) == 1 else component_gfa2_lines)(g.graph, nodes, edges)
-                with open(os.path.join(out_dir, "component%d.gfa" % i), "w") as f:
-                    f.write("".join(lines))
-            else:
-                with open(os.path.join(out_dir, "component%d.graphml" % i), "w") as f:
-                    write_graphml(f, _ComponentView(g.graph, nodes, edges))
+        marks = None
+        if g.bubblechains is not None:
+            marks = {}
+            for j, c in enumerate(g.component_chains[i]):
+                c_nodes, c_edges = g.bubblechains.nodes_of(c).tolist(), g.graph.edges[g.bubblechains.edges_of(c)]
+                logger.info("Found bubblechain #%d with %d nodes and %d edges", j, len(c_nodes), len(c_edges))
+                marks.update((g.graph.node_name(n), j) for n in c_nodes)
+                write("component%d.bubblechain%d" % (i, j), c_nodes, c_edges, None)
+        write("component%d" % i, nodes, edges, marks)
     return len(comps)

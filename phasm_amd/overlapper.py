@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE
+from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -549,6 +549,22 @@ class ExactOverlapper:
 
     def superbubble_stats(self) -> dict:
         return self._stats(self._lib.po_get_superbubble_stats, PoSuperbubbleStats)
+
+    def layout_bubblechains(self, graph: OverlapResult, min_nodes: int = 1, n_order: Optional[int] = None):
+        """``po_layout_bubblechains``: the bubble chains of a graph result (of the kinds ``layout_components`` takes), which
+        stays valid -- what the reference's ``build_bubblechains(component, min_nodes)`` yields on every component
+        (phasm/assembly_graph.py:594-652).  Returns ``(node_chain, node_bubble, edge_chain, table)``: per node, parallel to
+        ``graph.node_order()`` (``n_order``: its length, if the caller has it), its chain and the position in that chain of
+        the top-level bubble that holds it (``NO_NODE`` where there is none); per edge, in the graph's edge order, the chain
+        that holds both ends; one entry (``first_entrance``, ``last_exit``, ``n_bubbles``, ``n_nodes``, ``n_edges``) per
+        chain, in the order of the heads' ranks."""
+        if not 0 <= int(min_nodes) <= 0xFFFFFFFF:
+            raise ValueError("min_nodes does not fit 32 bits")
+        return self._graph_stage(self._lib.po_layout_bubblechains, graph, PoBubblechainParams(int(min_nodes), 0), n_order,
+                                 [(np.uint32, "node"), (np.uint32, "node"), (np.uint32, "edge"), (BUBBLECHAIN_DTYPE, "node")])
+
+    def bubblechain_stats(self) -> dict:
+        return self._stats(self._lib.po_get_bubblechain_stats, PoBubblechainStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:
