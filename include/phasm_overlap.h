@@ -424,9 +424,9 @@ typedef struct {
  * is no edge result, reserved != 0: PO_ERR_INVALID.  Diamond tips follow with po_layout_diamonds, the merging
  * of unambiguous paths with po_layout_merge, the average coverage per edge with po_layout_coverage; of `phasm chain`
  * this library has the weakly connected components (po_layout_components), the partition that superbubble detection
- * starts with (po_layout_partition), the superbubbles of the acyclic partitions (po_layout_superbubbles) and the bubble
- * chains built from them (po_layout_bubblechains).  graph_to_dag and the superbubbles of the cyclic partitions, contigs and
- * phasing are not part of it. */
+ * starts with (po_layout_partition), the superbubbles of the acyclic partitions (po_layout_superbubbles), the bubble
+ * chains built from them (po_layout_bubblechains) and the contigs outside the chains (po_layout_contigs).  graph_to_dag, the
+ * superbubbles of the cyclic partitions and phasing are not part of it. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -812,6 +812,82 @@ po_status po_layout_bubblechains(po_handle* h, po_result* graph, const po_bubble
                                  uint32_t* node_bubble_out, uint32_t* edge_chain_out, po_bubblechain* chains_out,
                                  uint64_t* n_chains_out);
 po_status po_get_bubblechain_stats(const po_handle* h, po_bubblechain_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The contigs of `phasm chain` outside the bubble chains: identify_contigs (phasm/assembly_graph.py:655-718), as
+ * cli/assembler.py:289 calls it on every weakly connected component behind build_bubblechains.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint64_t min_contig_len;     /* a shorter path or node is not reported (the reference's default: 5000); 0 is valid  */
+    uint32_t min_nodes;          /* of the bubble chains whose nodes are excluded, as po_bubblechain_params; 0 is invalid */
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_contig_params;
+
+typedef struct {
+    uint32_t first_node;         /* the first node of the path (node id)                                         */
+    uint32_t last_node;          /* its last node; the first again on a path that ends where it began            */
+    uint32_t n_nodes;            /* nodes on the path, counted as often as they occur; 1 for a one-node contig   */
+    uint32_t first_edge;         /* the head edge, as an index in the graph's edge order; PO_NO_NODE for a one-node contig */
+    int64_t length;              /* sum of the weights of the path's edges + the length of the last node         */
+} po_contig;                     /* 24 bytes                                                                     */
+
+typedef struct {
+    uint64_t n_nodes;            /* nodes of the graph (those in its node order)                                 */
+    uint64_t n_edges;
+    uint64_t n_invalid;          /* edges with an end that is not in the node order (the call fails then)        */
+    uint64_t n_excluded;         /* nodes in the exclude set                                                     */
+    uint64_t n_root_starts;      /* edges (a, b) with in(a) != 1                                                 */
+    uint64_t n_late_starts;      /* edges (a, b) with in(a) == 1 and out(a) > 1                                  */
+    uint64_t n_blocked;          /* starts with both ends excluded                                               */
+    uint64_t n_covered_edges, n_uncovered_edges;   /* their sum is n_edges                                       */
+    uint64_t n_paths;            /* covered starts: each is the head edge of one path                            */
+    uint64_t n_short_paths;      /* ... of them dropped by min_contig_len                                        */
+    uint64_t n_isolated;         /* nodes without an edge                                                        */
+    uint64_t n_short_isolated;   /* ... of them dropped by min_contig_len                                        */
+    uint64_t n_contigs;          /* n_paths - n_short_paths + n_isolated - n_short_isolated                      */
+    uint64_t max_path_nodes;     /* nodes of the longest path, dropped ones included                             */
+    uint64_t n_chains;           /* bubble chains whose nodes were excluded (0 with exclude_in)                  */
+    uint32_t n_path_rounds, n_cover_rounds;   /* pointer-jumping rounds, each loop's closing round included      */
+    uint32_t n_batches;          /* readbacks of all round loops, those of the stages run first included         */
+    uint32_t reserved;
+    float ms_ranks, ms_bubblechains, ms_paths, ms_cover, ms_label, ms_total;
+} po_contig_stats;
+
+/* `graph` is a graph result of this handle, of the kinds po_layout_bubblechains takes; it stays valid and unchanged.  With
+ * in(x) / out(x) the degrees in the graph and X the excluded nodes, an edge (a, b) is a ROOT START when in(a) != 1, a LATE
+ * START when in(a) == 1 and out(a) > 1, an EXTENSION when in(a) == 1 and out(a) == 1; a start is BLOCKED when a and b are
+ * both in X.  COVERED is the least fixed point of: a root start is covered iff it is not blocked; a late start (a, .) iff the
+ * one in-edge of a is covered and the start is not blocked; an extension (a, .) iff the one in-edge of a is covered.  Rings
+ * of in-degree-1 nodes, and what hangs off them through in-degree-1 nodes, are never covered.  Every covered start (a, b) is
+ * the HEAD EDGE of one path [a, b, c, ...]: from cur = b the path takes the one out-edge of cur while out(cur) == 1 and
+ * in(cur) == 1 (extensions never look at X: a path that starts outside X runs on through it).  Every covered edge lies on
+ * exactly one path; a path may end at its own first node.  The LENGTH of a path is the signed 64-bit sum of the weights of
+ * its edges plus the length of its last node (a read's from the handle, a merged node's from the graph); a path is reported
+ * iff length >= min_contig_len, compared in 64 bits.  Every node without an edge whose length is >= min_contig_len is
+ * reported as a one-node contig.  This is what the reference's queue walk reports, as a set of paths (DESIGN.md section
+ * 3.9l has the argument).  Contigs are numbered: the reported paths by (rank of the head edge's first node, index of the
+ * head edge in the edge order), then the one-node contigs by rank.
+ *   exclude_in       NULL: the call runs po_layout_bubblechains' stages first, in their workspaces, and X = the nodes that
+ *                    carry a chain after the min_nodes filter (what `phasm chain` passes).  Else one byte per node,
+ *                    parallel to the node order, non-zero = in X; the bubble-chain stages are skipped, min_nodes is ignored
+ *   edge_contig_out  in the graph's edge order: the contig whose path holds the edge, else PO_NO_NODE (uncovered, or the
+ *                    path was dropped by its length)
+ *   edge_pos_out     the 0-based place of the edge on that path (the head edge 0), else PO_NO_NODE
+ *   contigs_out      one entry per contig, in contig order (room for n_order + n_edges entries)
+ * Any of the three may be NULL; *n_contigs_out is always written.  The two edge arrays identify every path completely; a
+ * node may end several paths, so there is no output per node.  Not reproduced: the reference's numbering j, the pop order
+ * of a queue filled in the iteration order of a Python set.  Only integers are involved: every output is the same on every
+ * run (the round counts of the stats are statistics).  An edge with an end that is not in the node order is counted in
+ * n_invalid; the call then fails with PO_ERR_INVALID and writes nothing.  Device memory beyond the inputs and the rank
+ * scaffold is linear: 49 bytes per node and at most 120 per edge of its own, plus with exclude_in == NULL what
+ * po_layout_bubblechains takes.  params may be NULL (5000, 1).  An empty graph with an empty order: PO_OK, 0 contigs.  Both
+ * pointer-jumping loops are bounded on the host (edges + 2 rounds, though they need ceil(log2(longest)) + 1); reaching a
+ * bound is PO_ERR_HIP with a message, never a result.  There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.
+ * A row result, a result of another handle, reserved != 0, min_nodes == 0, n_contigs_out NULL: PO_ERR_INVALID. */
+po_status po_layout_contigs(po_handle* h, po_result* graph, const po_contig_params* params, const uint8_t* exclude_in,
+                            uint32_t* edge_contig_out, uint32_t* edge_pos_out, po_contig* contigs_out, uint64_t* n_contigs_out);
+po_status po_get_contig_stats(const po_handle* h, po_contig_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

@@ -39,6 +39,8 @@ SB_ENTRANCE, SB_EXIT, SB_NESTED, SB_SELF_LOOP = 1, 2, 4, 8
 NO_NODE = 0xFFFFFFFF
 # po_bubblechain
 BUBBLECHAIN_DTYPE = np.dtype([("first_entrance", "<u4"), ("last_exit", "<u4"), ("n_bubbles", "<u4"), ("n_nodes", "<u4"), ("n_edges", "<u8")])
+# po_contig
+CONTIG_DTYPE = np.dtype([("first_node", "<u4"), ("last_node", "<u4"), ("n_nodes", "<u4"), ("first_edge", "<u4"), ("length", "<i8")])
 
 
 class PoLayoutParams(ctypes.Structure):
@@ -199,6 +201,22 @@ class PoBubblechainStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoContigParams(ctypes.Structure):
+    _fields_ = [("min_contig_len", ctypes.c_uint64), ("min_nodes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class PoContigStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+                    "n_nodes", "n_edges", "n_invalid", "n_excluded", "n_root_starts", "n_late_starts", "n_blocked", "n_covered_edges",
+                    "n_uncovered_edges", "n_paths", "n_short_paths", "n_isolated", "n_short_isolated", "n_contigs", "max_path_nodes",
+                    "n_chains")] + \
+               [(name, ctypes.c_uint32) for name in ("n_path_rounds", "n_cover_rounds", "n_batches", "reserved")] + \
+               [(name, ctypes.c_float) for name in ("ms_ranks", "ms_bubblechains", "ms_paths", "ms_cover", "ms_label", "ms_total")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -309,6 +327,9 @@ SYMBOLS = [
     ("po_layout_bubblechains", ctypes.c_int, [_P, _P, ctypes.POINTER(PoBubblechainParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_bubblechain_stats", ctypes.c_int, [_P, ctypes.POINTER(PoBubblechainStats)]),
+    ("po_layout_contigs", ctypes.c_int, [_P, _P, ctypes.POINTER(PoContigParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_contig_stats", ctypes.c_int, [_P, ctypes.POINTER(PoContigStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

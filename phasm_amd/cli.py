@@ -290,8 +290,10 @@ def chain_components(args) -> int:
         logger.critical("No valid file formats specified.")
         sys.exit(1)
     logger.info("Reconstructing assembly graph...")
+    contigs = getattr(args, "contigs", False)
     g = layout.chain_components(args.graph_gfa, device=args.device, partitions=args.partitions, superbubbles=args.superbubbles,
-                                bubblechains=args.bubblechains, min_nodes=args.min_nodes)
+                                bubblechains=args.bubblechains or contigs, min_nodes=args.min_nodes, contigs=contigs,
+                                min_length=args.min_length)
     logger.info("Enumerate weakly connected components in the graph...")
     n = layout.write_component_graphs(args.output_dir, g, formats)
     for parts in g.partitions or ():
@@ -307,7 +309,11 @@ def chain_components(args) -> int:
         top = np.bincount(comp_of[entrances[g.superbubbles.table["nested"] == 0]], minlength=len(g.components))
         for i in range(len(g.components)):
             logger.info("Connected component %d: %d superbubbles in its acyclic partition, %d of them not nested.", i, per[i], top[i])
-    logger.info("Wrote %d weakly connected components.", n)
+    if getattr(args, "as_chain", False):   # (the last line of `phasm chain`, assembler.py:308-310)
+        logger.info("Built %d bubblechains and %d contigs from %d weakly connected components.",
+                    sum(len(x) for x in g.component_chains), sum(len(x) for x in g.component_contigs), n)
+    else:
+        logger.info("Wrote %d weakly connected components.", n)
     return 0
 
 
@@ -391,12 +397,27 @@ def main(argv=None) -> int:
                    help="also build the bubble chains of every component: component{i}.bubblechain{j}.* and the node attribute "
                         "bubblechain in component{i}.graphml")
     k.add_argument("--min-nodes", type=int, default=1, help="with --bubblechains: drop chains with fewer nodes (default: 1)")
+    k.add_argument("--contigs", action="store_true",
+                   help="also build the contigs outside the bubble chains: component{i}.contig{j}.* and the edge attribute contig "
+                        "in component{i}.graphml (implies --bubblechains)")
+    k.add_argument("-l", "--min-length", type=_int_in(0, 2**63 - 1), default=5000,
+                   help="with --contigs: drop contigs shorter than this many bases (default: 5000)")
     k.add_argument("--superbubbles", action="store_true",
                    help="also log, per component, the number of superbubbles of its acyclic partition")
     k.add_argument("--partitions", action="store_true",
                    help="also log, per component, the partitions superbubble detection starts with (strongly connected components)")
     k.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
     k.set_defaults(func=chain_components)
+    # `phasm chain` itself, with its own arguments (assembler.py): chain-components --bubblechains --contigs
+    m = sub.add_parser("chain", help="`phasm chain`: per weakly connected component of a graph file its bubble chains and the "
+                                     "contigs outside them, one file each, then the component's own.")
+    m.add_argument("-l", "--min-length", type=_int_in(0, 2**63 - 1), default=5000,
+                   help="minimum length of a contig outside the bubble chains (default: 5000)")
+    m.add_argument("-f", "--format", default="gfa2", help="comma separated: gfa1, gfa2, graphml (default: gfa2)")
+    m.add_argument("-o", "--output-dir", required=True)
+    m.add_argument("--device", type=int, default=None)
+    m.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
+    m.set_defaults(func=chain_components, bubblechains=True, contigs=True, min_nodes=1, superbubbles=False, partitions=False, as_chain=True)
     args = parser.parse_args(argv)
     if not getattr(args, "func", None):
         parser.print_help()

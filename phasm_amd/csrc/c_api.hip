@@ -45,6 +45,7 @@
 #include "partition.hip.h"
 #include "superbubbles.hip.h"
 #include "bubblechains.hip.h"
+#include "contigs.hip.h"
 
 namespace {
 
@@ -74,12 +75,17 @@ enum { UB_CNT, UB_W, UB_CIN, UB_COUT, UB_OFFIN, UB_OFFOUT, UB_CURIN, UB_CUROUT, 
 // po_layout_superbubbles
 enum { HB_CNT, HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOPS1, HB_NHEAD, HB_NPOS, HB_CB, HB_CN, HB_LAST, HB_CE,
        HB_CHAINOUT, HB_BUBBLEOUT, HB_EDGEOUT, HB_TABLE, HB_N };
+// workspaces of po_layout_contigs (contigs.hip.h) beyond those of the rank scaffold and, without an exclude set from the caller,
+// of the three stages that po_layout_bubblechains runs
+enum { CB_CNT, CB_EXCL, CB_LEN, CB_INDEG, CB_OUTDEG, CB_INE, CB_NLEN, CB_CLS, CB_JB0, CB_JB1, CB_HOPS0, CB_HOPS1, CB_WS0, CB_WS1, CB_CJ0,
+       CB_CJ1, CB_OK0, CB_OK1, CB_HEADOF, CB_PN, CB_PLAST, CB_PLEN, CB_KEPT, CB_KEY, CB_VAL, CB_CONTIGOUT, CB_POSOUT, CB_TABLE, CB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 54;
+constexpr int EV_LAY_N = 67;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
-       EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45 };
-static_assert(EV_BUBBLECHAINS + 9 == EV_LAY_N, "the nine events of po_layout_bubblechains are the last of the layout events");
+       EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54 };
+static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
+static_assert(EV_CONTIGS + 13 == EV_LAY_N, "the thirteen events of po_layout_contigs are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -435,6 +441,9 @@ struct po_handle {
     // the bubble chains (po_layout_bubblechains, bubblechains.hip.h)
     DevBuf d_bc[HB_N];
     po_bubblechain_stats bcstats = {};
+    // the contigs outside the bubble chains (po_layout_contigs, contigs.hip.h)
+    DevBuf d_ct[CB_N];
+    po_contig_stats ctstats = {};
 };
 
 struct po_result {
@@ -4202,23 +4211,31 @@ po_status run_superbubbles(po_handle* h, po_result* graph, uint32_t* exit_out, u
 
 // ---- the bubble chains (po_layout_bubblechains, bubblechains.hip.h) -------------------------------------------------------
 
-po_status run_bubblechains(po_handle* h, po_result* graph, uint32_t min_nodes, uint32_t* chain_out, uint32_t* bubble_out,
-                           uint32_t* edge_out, po_bubblechain* table_out, uint64_t* n_chains_out) {
-    const char* const name = "po_layout_bubblechains";
+// what the bubble-chain stage counts, for the stats of its callers
+struct BcWork {
+    uint64_t n_bubbles = 0, n_top = 0, n_chains = 0, n_short = 0, n_chain_nodes = 0, n_chain_edges = 0;
+    uint32_t max_chain_bubbles = 0, n_nest_rounds = 0, n_chain_rounds = 0, n_batches = 0;
+};
+
+// The bubble-chain stage on the device, as po_layout_bubblechains and po_layout_contigs run it (`name`, the first of the
+// caller's events, the caller's stats for ranked_open): superbubble_stage with the workspaces of d_bc and the caller's `own`,
+// then everything up to the table and the three arrays, all left in d_bc -- the chain per rank in HB_CHAINOUT; the counters
+// in HB_CNT.  Records ev[7] and ev[8].  S is filled whatever the outcome.  !R.ev or !R.n_order: nothing to do.
+template <class Stats, class Own>
+po_status bubblechain_stage(po_handle* h, po_result* graph, const char* const name, int ev_first, Stats& stats, uint32_t min_nodes, Own&& own,
+                            RankedGraph& R, BcWork& S) {
     hipStream_t st = h->stream;
-    po_bubblechain_stats& S = h->bcstats;
-    S = po_bubblechain_stats();
     DevBuf* B = h->d_bc;
-    RankedGraph R;
     SbWork W;
-    const po_status staged = superbubble_stage(h, graph, name, EV_BUBBLECHAINS, S, [&](size_t nn, size_t ne) {
+    const po_status staged = superbubble_stage(h, graph, name, ev_first, stats, [&](size_t nn, size_t ne) {
         PO_TRY(ensure(h, B[HB_CNT], 128));
         for (int k : {HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOPS1, HB_NHEAD, HB_NPOS, HB_CB, HB_CN, HB_LAST, HB_CHAINOUT,
                       HB_BUBBLEOUT})
             PO_TRY(ensure(h, B[k], nn * 4));
         PO_TRY(ensure(h, B[HB_CE], nn * 8));
         PO_TRY(ensure(h, B[HB_EDGEOUT], ne * 4));
-        return ensure(h, B[HB_TABLE], nn * sizeof(po::BubbleChain));
+        PO_TRY(ensure(h, B[HB_TABLE], nn * sizeof(po::BubbleChain)));
+        return own(nn, ne);
     }, R, W);
     S.n_bubbles = W.n_bubbles;
     S.n_batches = W.n_batches;
@@ -4299,14 +4316,206 @@ po_status run_bubblechains(po_handle* h, po_result* graph, uint32_t min_nodes, u
     if (n) hipLaunchKernelGGL(po::k_bc_edge_out, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, d_chain, d_edge);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[8], st));
+    return PO_OK;
+}
+
+po_status run_bubblechains(po_handle* h, po_result* graph, uint32_t min_nodes, uint32_t* chain_out, uint32_t* bubble_out,
+                           uint32_t* edge_out, po_bubblechain* table_out, uint64_t* n_chains_out) {
+    po_bubblechain_stats& S = h->bcstats;
+    S = po_bubblechain_stats();
+    DevBuf* B = h->d_bc;
+    RankedGraph R;
+    BcWork W;
+    const po_status staged = bubblechain_stage(h, graph, "po_layout_bubblechains", EV_BUBBLECHAINS, S, min_nodes,
+                                               [](size_t, size_t) { return PO_OK; }, R, W);
+    S.n_bubbles = W.n_bubbles;
+    S.n_top = W.n_top;
+    S.n_chains = W.n_chains;
+    S.n_short = W.n_short;
+    S.n_chain_nodes = W.n_chain_nodes;
+    S.n_chain_edges = W.n_chain_edges;
+    S.max_chain_bubbles = W.max_chain_bubbles;
+    S.n_nest_rounds = W.n_nest_rounds;
+    S.n_chain_rounds = W.n_chain_rounds;
+    S.n_batches = W.n_batches;
+    PO_TRY(staged);
+    if (!R.ev || !R.n_order) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order, n_chains = (uint32_t)W.n_chains;
+    hipEvent_t* ev = R.ev;
     static_assert(sizeof(po_bubblechain) == sizeof(po::BubbleChain) && sizeof(po_bubblechain) == 24, "po_bubblechain is the device's table entry");
-    PO_TRY(land_outputs(h, {{table, (size_t)n_chains * sizeof(po_bubblechain), table_out}, {d_chain, (size_t)n_order * 4, chain_out},
-                            {d_bubble, (size_t)n_order * 4, bubble_out}, {d_edge, (size_t)n * 4, edge_out}}, cnt, po::HK_N));
+    PO_TRY(land_outputs(h, {{B[HB_TABLE].p, (size_t)n_chains * sizeof(po_bubblechain), table_out},
+                            {B[HB_CHAINOUT].p, (size_t)n_order * 4, chain_out}, {B[HB_BUBBLEOUT].p, (size_t)n_order * 4, bubble_out},
+                            {B[HB_EDGEOUT].p, (size_t)n * 4, edge_out}}, B[HB_CNT].as<unsigned long long>(), po::HK_N));
     *n_chains_out = n_chains;
     (void)hipEventElapsedTime(&S.ms_superbubbles, ev[0], ev[6]);
     (void)hipEventElapsedTime(&S.ms_chains, ev[6], ev[7]);
     (void)hipEventElapsedTime(&S.ms_label, ev[7], ev[8]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[8]);
+    return PO_OK;
+}
+
+// ---- the contigs outside the bubble chains (po_layout_contigs, contigs.hip.h) ----------------------------------------------
+
+po_status run_contigs(po_handle* h, po_result* graph, uint64_t min_len, uint32_t min_nodes, const uint8_t* exclude_in, uint32_t* contig_out,
+                      uint32_t* pos_out, po_contig* table_out, uint64_t* n_contigs_out) {
+    const char* const name = "po_layout_contigs";
+    hipStream_t st = h->stream;
+    po_contig_stats& S = h->ctstats;
+    S = po_contig_stats();
+    DevBuf* B = h->d_ct;
+    RankedGraph R;
+    const size_t n_ids = h->len.size();
+    uint32_t pad_e = 0;
+    auto own = [&](size_t nn, size_t ne) -> po_status {
+        pad_e = po::merge_sort_pad((uint32_t)ne);
+        PO_TRY(ensure(h, B[CB_CNT], 128));
+        PO_TRY(ensure(h, B[CB_EXCL], nn));
+        PO_TRY(ensure(h, B[CB_LEN], (n_ids + 1) * 4));
+        for (int k : {CB_INDEG, CB_OUTDEG, CB_INE}) PO_TRY(ensure(h, B[k], nn * 4));
+        PO_TRY(ensure(h, B[CB_NLEN], nn * 8));
+        for (int k : {CB_CLS, CB_OK0, CB_OK1, CB_KEPT}) PO_TRY(ensure(h, B[k], ne));
+        for (int k : {CB_JB0, CB_JB1, CB_HOPS0, CB_HOPS1, CB_CJ0, CB_CJ1, CB_HEADOF, CB_PN, CB_PLAST, CB_CONTIGOUT, CB_POSOUT})
+            PO_TRY(ensure(h, B[k], ne * 4));
+        for (int k : {CB_WS0, CB_WS1, CB_PLEN}) PO_TRY(ensure(h, B[k], ne * 8));
+        PO_TRY(ensure(h, B[CB_KEY], (size_t)pad_e * 8));
+        PO_TRY(ensure(h, B[CB_VAL], (size_t)pad_e * 4));
+        return ensure(h, B[CB_TABLE], (nn + ne) * sizeof(po::Contig));
+    };
+    // the ranks; without an exclude set the bubble chains too (their chain word per rank is the set)
+    int e0 = 1;   // the event behind the stage run first
+    if (exclude_in) {
+        PO_TRY(ranked_open(h, graph, name, EV_CONTIGS, po::KC_N, S, B[CB_INE], own, R));   // (the identity words: overwritten below)
+    } else {
+        BcWork W;
+        const po_status staged = bubblechain_stage(h, graph, name, EV_CONTIGS, S, min_nodes, own, R, W);
+        S.n_chains = W.n_chains;
+        S.n_batches = W.n_batches;
+        PO_TRY(staged);
+        e0 = 8;
+    }
+    if (!R.ev) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order;
+    if (!n_order) return PO_OK;
+    hipEvent_t* ev = R.ev;
+    unsigned long long *cnt = B[CB_CNT].as<unsigned long long>(), *ws[2] = {B[CB_WS0].as<unsigned long long>(), B[CB_WS1].as<unsigned long long>()},
+                       *key = B[CB_KEY].as<unsigned long long>();
+    uint8_t *excl = B[CB_EXCL].as<uint8_t>(), *cls = B[CB_CLS].as<uint8_t>(), *ok[2] = {B[CB_OK0].as<uint8_t>(), B[CB_OK1].as<uint8_t>()},
+            *kept = B[CB_KEPT].as<uint8_t>();
+    uint32_t *len = B[CB_LEN].as<uint32_t>(), *indeg = B[CB_INDEG].as<uint32_t>(), *outdeg = B[CB_OUTDEG].as<uint32_t>(),
+             *ine = B[CB_INE].as<uint32_t>(), *jb[2] = {B[CB_JB0].as<uint32_t>(), B[CB_JB1].as<uint32_t>()},
+             *hops[2] = {B[CB_HOPS0].as<uint32_t>(), B[CB_HOPS1].as<uint32_t>()}, *cj[2] = {B[CB_CJ0].as<uint32_t>(), B[CB_CJ1].as<uint32_t>()},
+             *head_of = B[CB_HEADOF].as<uint32_t>(), *pn = B[CB_PN].as<uint32_t>(), *plast = B[CB_PLAST].as<uint32_t>(),
+             *val = B[CB_VAL].as<uint32_t>(), *d_contig = B[CB_CONTIGOUT].as<uint32_t>(), *d_pos = B[CB_POSOUT].as<uint32_t>();
+    long long *nlen = B[CB_NLEN].as<long long>(), *plen = B[CB_PLEN].as<long long>();
+    po::Contig* table = B[CB_TABLE].as<po::Contig>();
+    const po::Edge* edges = graph->d_rows.as<po::Edge>();
+    volatile uint64_t* C = h->pinned + 48;   // this stage's counters on the host (words 16.. and 32.. are the scaffold's)
+    auto counters_home = [&]() -> po_status {
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 48, cnt, po::TK_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        return PO_OK;
+    };
+    // degrees, the one in-edge, node lengths, the exclude bytes; class and link of every edge
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    if (n_ids) HIP_TRY(h, hipMemcpyAsync(len, h->len.data(), n_ids * 4, hipMemcpyHostToDevice, st));
+    if (exclude_in) HIP_TRY(h, hipMemcpyAsync(excl, exclude_in, n_order, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(po::k_ct_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, R.val, (uint32_t)n_ids, R.n_total, len,
+                       graph->merged ? graph->d_mlen.as<long long>() : (const long long*)nullptr,
+                       exclude_in ? (const uint32_t*)nullptr : h->d_bc[HB_CHAINOUT].as<uint32_t>(), excl, indeg, outdeg, ine, nlen, cnt);
+    if (n) {
+        hipLaunchKernelGGL(po::k_ct_degrees, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, indeg, outdeg, ine);
+        hipLaunchKernelGGL(po::k_ct_classes, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, indeg, outdeg, excl, cls, cnt);
+        hipLaunchKernelGGL(po::k_ct_links, dim3(R.edge_grid), dim3(256), 0, st, R.ends, edges, n, n_order, ine, cls, jb[0], hops[0], ws[0]);
+        HIP_TRY(h, hipMemsetAsync(pn, 0, (size_t)n * 4, st));
+    }
+    HIP_TRY(h, hipGetLastError());
+    // (the caller's bytes were read by the copy above only once the stream got there)
+    if (exclude_in) HIP_TRY(h, hipStreamSynchronize(st));
+    RoundOps ops{h, st, R.rcnt};
+    uint64_t ignored = 0;
+    // list ranking of the extensions toward the head edge of their path: ping-pong, the last launch wrote buffer `fin`
+    uint32_t launched = 0;
+    if (n) {
+        const int how = po::round_phase(ops, n, [&](uint32_t j) {
+            const uint32_t a = launched & 1, b = a ^ 1;
+            hipLaunchKernelGGL(po::k_ct_jump, dim3(R.edge_grid), dim3(256), 0, st, n, jb[a], hops[a], ws[a], jb[b], hops[b], ws[b], R.rcnt + j);
+            ++launched;
+        }, S.n_path_rounds, S.n_batches, ignored);
+        if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, std::string("internal: the ranking of ") + name + " reached its bound of edges + 2 rounds");
+    }
+    const uint32_t fin = launched & 1;
+    HIP_TRY(h, hipEventRecord(ev[e0 + 1], st));
+    // which late starts are covered: the same between two buffer pairs, over the heads
+    launched = 0;
+    if (n) {
+        hipLaunchKernelGGL(po::k_ct_cover_init, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, ine, cls, jb[fin], cj[0], ok[0]);
+        const int how = po::round_phase(ops, n, [&](uint32_t j) {
+            const uint32_t a = launched & 1, b = a ^ 1;
+            hipLaunchKernelGGL(po::k_ct_cover_jump, dim3(R.edge_grid), dim3(256), 0, st, n, cj[a], ok[a], cj[b], ok[b], R.rcnt + j);
+            ++launched;
+        }, S.n_cover_rounds, S.n_batches, ignored);
+        if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, std::string("internal: the coverage of ") + name + " reached its bound of edges + 2 rounds");
+    }
+    const uint32_t cfin = launched & 1;
+    HIP_TRY(h, hipEventRecord(ev[e0 + 2], st));
+    // the sums at the heads, the filter, the numbering: the free halves of the two ping-pongs take the two index arrays
+    uint32_t *eidx = jb[fin ^ 1], *cidx = cj[cfin ^ 1];
+    if (n) {
+        hipLaunchKernelGGL(po::k_ct_paths, dim3(R.edge_grid), dim3(256), 0, st, R.ends, edges, n, n_order, indeg, outdeg, nlen, cls, jb[fin],
+                           hops[fin], ws[fin], cj[cfin], ok[cfin], head_of, pn, plast, plen, cnt);
+        hipLaunchKernelGGL(po::k_ct_filter, dim3(R.edge_grid), dim3(256), 0, st, n, (unsigned long long)min_len, head_of, pn, plen, kept, cnt);
+    }
+    hipLaunchKernelGGL(po::k_ct_isolated, dim3(R.rank_grid), dim3(256), 0, st, n_order, (unsigned long long)min_len, indeg, outdeg, nlen, R.root,
+                       cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint8_t>(h, kept, n, eidx, &h->pinned[2]));
+    PO_TRY(prefix_sum<uint8_t>(h, R.root, n_order, R.index, &h->pinned[3]));
+    PO_TRY(counters_home());
+    S.n_excluded = C[po::TK_EXCLUDED];
+    S.n_root_starts = C[po::TK_ROOT];
+    S.n_late_starts = C[po::TK_LATE];
+    S.n_blocked = C[po::TK_BLOCKED];
+    S.n_covered_edges = C[po::TK_COVERED];
+    S.n_uncovered_edges = C[po::TK_UNCOVERED];
+    S.n_paths = C[po::TK_PATHS];
+    S.n_short_paths = C[po::TK_SHORT];
+    S.n_isolated = C[po::TK_ISO];
+    S.n_short_isolated = C[po::TK_SHORTISO];
+    S.max_path_nodes = C[po::TK_MAXN];
+    const uint64_t n_kept64 = h->pinned[2], n_iso64 = h->pinned[3];
+    if (C[po::TK_BAD]) return fail(h, PO_ERR_HIP, std::string("internal: a path of ") + name + " has no last edge");
+    if (S.n_covered_edges + S.n_uncovered_edges != n || C[po::TK_PEDGES] != S.n_covered_edges || n_kept64 != C[po::TK_KEPT] ||
+        n_kept64 + S.n_short_paths != S.n_paths || n_iso64 + S.n_short_isolated != S.n_isolated || S.n_paths > S.n_root_starts + S.n_late_starts ||
+        S.n_root_starts + S.n_late_starts > n || S.n_isolated > n_order || S.max_path_nodes > (uint64_t)n + 1)
+        return fail(h, PO_ERR_HIP, std::string("internal: the paths of ") + name + " do not add up");
+    const uint32_t n_kept = (uint32_t)n_kept64, n_iso = (uint32_t)n_iso64;
+    S.n_contigs = (uint64_t)n_kept + n_iso;
+    if (n_kept) {
+        const uint32_t pad = po::merge_sort_pad(n_kept);   // (<= pad_e: n_kept <= n)
+        hipLaunchKernelGGL(po::k_ct_keys, dim3(stride_grid(h, std::max(n, pad))), dim3(256), 0, st, R.ends, n, n_kept, pad, kept, eidx, key, val);
+        po::merge_sort_steps(n_kept, [&](uint32_t j, uint32_t k) {
+            hipLaunchKernelGGL(po::k_merge_bitonic, dim3(cdiv(pad, 256)), dim3(256), 0, st, key, val, pad, j, k);
+        });
+        hipLaunchKernelGGL(po::k_ct_number, dim3(stride_grid(h, n_kept)), dim3(256), 0, st, R.ends, n, n_order, n_kept, val, R.val, pn, plast, plen,
+                           cidx, table);
+    }
+    if (n_iso) hipLaunchKernelGGL(po::k_ct_iso_table, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_kept, n_iso, R.root, R.index, R.val, nlen, table);
+    if (n) hipLaunchKernelGGL(po::k_ct_edge_out, dim3(R.edge_grid), dim3(256), 0, st, n, head_of, kept, cidx, hops[fin], d_contig, d_pos);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[e0 + 3], st));
+    static_assert(sizeof(po_contig) == sizeof(po::Contig) && sizeof(po_contig) == 24, "po_contig is the device's table entry");
+    PO_TRY(land_outputs(h, {{table, (size_t)S.n_contigs * sizeof(po_contig), table_out}, {d_contig, (size_t)n * 4, contig_out},
+                            {d_pos, (size_t)n * 4, pos_out}}, cnt, po::TK_N));
+    *n_contigs_out = S.n_contigs;
+    if (!exclude_in) (void)hipEventElapsedTime(&S.ms_bubblechains, ev[0], ev[e0]);
+    (void)hipEventElapsedTime(&S.ms_ranks, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&S.ms_paths, ev[e0], ev[e0 + 1]);
+    (void)hipEventElapsedTime(&S.ms_cover, ev[e0 + 1], ev[e0 + 2]);
+    (void)hipEventElapsedTime(&S.ms_label, ev[e0 + 2], ev[e0 + 3]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[e0 + 3]);
     return PO_OK;
 }
 
@@ -4784,6 +4993,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_scc) b.release();
         for (DevBuf& b : h->d_sb) b.release();
         for (DevBuf& b : h->d_bc) b.release();
+        for (DevBuf& b : h->d_ct) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -6646,6 +6856,16 @@ po_status po_layout_bubblechains(po_handle* h, po_result* graph, const po_bubble
 }
 
 po_status po_get_bubblechain_stats(const po_handle* h, po_bubblechain_stats* out) { return get_stats(h, &po_handle::bcstats, out); }
+
+po_status po_layout_contigs(po_handle* h, po_result* graph, const po_contig_params* params, const uint8_t* exclude_in,
+                            uint32_t* edge_contig_out, uint32_t* edge_pos_out, po_contig* contigs_out, uint64_t* n_contigs_out) {
+    return graph_call(h, graph, "po_layout_contigs", !params || (params->reserved == 0 && params->min_nodes != 0), "contigs", n_contigs_out, [&] {
+        return run_contigs(h, graph, params ? params->min_contig_len : 5000ull, params ? params->min_nodes : 1u, exclude_in, edge_contig_out,
+                           edge_pos_out, contigs_out, n_contigs_out);
+    });
+}
+
+po_status po_get_contig_stats(const po_handle* h, po_contig_stats* out) { return get_stats(h, &po_handle::ctstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

@@ -32,7 +32,10 @@ starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).
 ``bubble_chains`` (``po_layout_bubblechains``) builds the chains of the bubbles that are not nested:
 ``build_bubblechains`` (assembly_graph.py:594-652); with them ``write_component_graphs`` also writes
 ``component{i}.bubblechain{j}.*`` and the node attribute ``bubblechain``.
-What follows that point (contigs, phasing) is out of scope.
+``identify_contigs`` (``po_layout_contigs``) reports the non-branching paths and single nodes outside the chains:
+``identify_contigs`` (assembly_graph.py:655-718); with them ``write_component_graphs`` also writes
+``component{i}.contig{j}.*`` and the edge attribute ``contig``: every file `phasm chain` writes.
+What follows that point (``graph_to_dag`` for the cyclic partitions, phasing) is out of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -156,12 +159,14 @@ def average_coverage(ov: ExactOverlapper, graph_res: OverlapResult, rows_res: Ov
     return _quotients(ov.layout_coverage(graph_res, rows_res))
 
 
-def write_graphml(f, g: "AssemblyEdges", bubblechain: Optional[dict] = None) -> int:
+def write_graphml(f, g: "AssemblyEdges", bubblechain: Optional[dict] = None, contig: Optional[dict] = None) -> int:
     """The graph ``g`` as GraphML with the reference's attribute names: nodes named by ``node_name`` (the nodes of
     ``node_order`` where the result carries one, else the ends of the edges in order of appearance), edge data ``weight``,
     ``overlap_len`` and, when present, ``avg_coverage`` (written with ``repr``: it reads back to the same double).  With
     ``bubblechain`` ({node name: number}, None: no such attribute) the nodes it names carry the node attribute
-    ``bubblechain`` (long), as `phasm chain` marks them (assembler.py:277-278).  Returns the number of edges."""
+    ``bubblechain`` (long), as `phasm chain` marks them (assembler.py:277-278); with ``contig`` ({index of the edge in
+    ``g.edge_tuples()``: number}, None: no such attribute) the edges it names carry the edge attribute ``contig`` (long,
+    assembler.py:293-295).  Returns the number of edges."""
     from xml.sax.saxutils import escape, quoteattr
     names = g.edge_tuples()
     nodes = [g.node_name(n) for n in g.node_order.tolist()] if g.node_order is not None else []
@@ -181,6 +186,8 @@ def write_graphml(f, g: "AssemblyEdges", bubblechain: Optional[dict] = None) -> 
         f.write('  <key id="d2" for="edge" attr.name="avg_coverage" attr.type="double" />\n')
     if bubblechain is not None:
         f.write('  <key id="d3" for="node" attr.name="bubblechain" attr.type="long" />\n')
+    if contig is not None:
+        f.write('  <key id="d4" for="edge" attr.name="contig" attr.type="long" />\n')
     f.write('  <graph edgedefault="directed">\n')
     if bubblechain is None:
         f.write("".join("    <node id=%s />\n" % quoteattr(n) for n in nodes))
@@ -192,6 +199,8 @@ def write_graphml(f, g: "AssemblyEdges", bubblechain: Optional[dict] = None) -> 
                 % (quoteattr(u), quoteattr(v), w, o))
         if cov is not None:
             f.write('      <data key="d2">%s</data>\n' % escape(repr(cov[i])))
+        if contig is not None and i in contig:
+            f.write('      <data key="d4">%d</data>\n' % contig[i])
         f.write("    </edge>\n")
     f.write("  </graph>\n</graphml>\n")
     return len(names)
@@ -726,12 +735,90 @@ def chains_by_component(chains: BubbleChains, components: Components) -> List[Li
     return out
 
 
+# ---- the contigs outside the bubble chains (identify_contigs, phasm/assembly_graph.py:655-718) --------------------------------
+
+@dataclass
+class Contigs:
+    """The contigs of a graph result (``po_layout_contigs``).  ``node_order``: the graph's nodes in the reference's order;
+    ``edge_contig`` / ``edge_pos`` (``_lib.NO_NODE`` where there is none): per edge, in the graph's edge order, the contig
+    whose path holds it and its 0-based place on that path; ``table``: structured (``first_node``, ``last_node``,
+    ``n_nodes``, ``first_edge``, ``length``), one entry per contig: the paths by (rank of the first node, head edge), then
+    the one-node contigs by rank (the reference numbers them in the pop order of a queue filled in the iteration order of a
+    Python set); ``stats``: ``po_get_contig_stats``; ``edge_ends``: (u, v) of every edge of the graph, [n, 2]."""
+    node_order: np.ndarray
+    edge_contig: np.ndarray
+    edge_pos: np.ndarray
+    table: np.ndarray
+    stats: dict
+    edge_ends: Optional[np.ndarray] = None
+
+    def __len__(self) -> int:
+        return len(self.table)
+
+    def edges_of(self, j: int) -> np.ndarray:
+        """The indices of the edges of the path of contig ``j``, in path order (none for a one-node contig)."""
+        if not hasattr(self, "_edge_group"):
+            from ._lib import NO_NODE
+            on = np.flatnonzero(self.edge_contig != NO_NODE)
+            on = on[np.lexsort((self.edge_pos[on], self.edge_contig[on]))]          # by contig, then by place
+            self._edge_group = (on, np.concatenate(([0], np.cumsum(np.bincount(self.edge_contig[on], minlength=len(self))))))
+        by, off = self._edge_group
+        return by[off[j]:off[j + 1]]
+
+    def path_of(self, j: int) -> List[int]:
+        """The node ids of contig ``j`` in path order (a node as often as the path meets it); ``[n]`` for a one-node contig."""
+        idx = self.edges_of(j)
+        if not len(idx):
+            return [int(self.table["first_node"][j])]
+        ends = self.edge_ends[idx]
+        return [int(ends[0, 0])] + ends[:, 1].astype(np.int64).tolist()
+
+
+def identify_contigs(ov: ExactOverlapper, graph_res: OverlapResult, min_contig_len: int = 5000, min_nodes: int = 1,
+                     exclude=None) -> Contigs:
+    """``po_layout_contigs`` on a graph result of ``ov`` (an edge result, a merged graph or a ``graph_from_edges`` result),
+    which stays valid and in HBM.  ``exclude`` None: the nodes of the bubble chains (``min_nodes`` as in ``bubble_chains``),
+    built on the device by the same call; else one flag per node, parallel to the node order."""
+    order = graph_res.node_order()
+    edge_contig, edge_pos, table = ov.layout_contigs(graph_res, min_contig_len, min_nodes, exclude, len(order))
+    rows = graph_res.rows()
+    ends = np.stack([rows["u"], rows["v"]], axis=1) if len(rows) else np.zeros((0, 2), dtype=np.uint32)
+    return Contigs(order, edge_contig, edge_pos, table, ov.contig_stats(), ends)
+
+
+def contigs_by_component(contigs: Contigs, components: Components) -> List[List[int]]:
+    """Per weakly connected component the contigs in it, in contig order: contig ``out[i][j]`` is what `phasm chain` writes as
+    ``component{i}.contig{j}`` (its own j follows the pop order of its queue)."""
+    out = [[] for _ in range(len(components))]
+    if len(contigs):
+        rank = np.zeros(int(contigs.node_order.max()) + 1, dtype=np.int64)
+        rank[contigs.node_order] = np.arange(len(contigs.node_order))
+        for c, i in enumerate(components.component_of_node[rank[contigs.table["first_node"]]].tolist()):
+            out[i].append(c)
+    return out
+
+
+def induced_edges(graph_edges: np.ndarray, nodes: Sequence[int]) -> np.ndarray:
+    """The indices of the edges of ``g.subgraph(nodes)`` in the order networkx yields them: per node of ``nodes`` (each
+    once, at its first place) its out-edges in the graph's edge order, those with both ends among the nodes."""
+    e = np.asarray(graph_edges).reshape(-1, 4)
+    inside, out = set(), []
+    first = [n for n in nodes if not (n in inside or inside.add(n))]
+    by = np.argsort(e[:, 0], kind="stable")
+    lo = np.searchsorted(e[by, 0], first, side="left")
+    hi = np.searchsorted(e[by, 0], first, side="right")
+    for a, b in zip(lo.tolist(), hi.tolist()):
+        out += [int(i) for i in by[a:b].tolist() if int(e[i, 1]) in inside]
+    return np.asarray(out, dtype=np.int64)
+
+
 @dataclass
 class ChainGraph:
     """What ``chain_components`` hands to the writers: the graph file as read (``phasm_amd.io.gfa.GraphFile``) and its
     components; with ``partitions=True`` also the strongly connected components and, per component, the partitions that
     superbubble detection starts with; with ``superbubbles=True`` also the superbubbles of the acyclic partitions; with
-    ``bubblechains=True`` also the bubble chains and, per component, the chains in it (``chains_by_component``)."""
+    ``bubblechains=True`` also the bubble chains and, per component, the chains in it (``chains_by_component``); with
+    ``contigs=True`` also the contigs outside the chains and, per component, the contigs in it (``contigs_by_component``)."""
     graph: object
     components: Components
     sccs: Optional[StrongComponents] = None
@@ -739,14 +826,18 @@ class ChainGraph:
     superbubbles: Optional[Superbubbles] = None
     bubblechains: Optional[BubbleChains] = None
     component_chains: Optional[List[List[int]]] = None
+    contigs: Optional[Contigs] = None
+    component_contigs: Optional[List[List[int]]] = None
 
 
 def chain_components(path: str, device: Optional[int] = None, partitions: bool = False, superbubbles: bool = False,
-                     bubblechains: bool = False, min_nodes: int = 1) -> ChainGraph:
+                     bubblechains: bool = False, min_nodes: int = 1, contigs: bool = False, min_length: int = 5000) -> ChainGraph:
     """The start of `phasm chain` on a graph file: ``read_graph_gfa``, one segment per ``S`` line on a fresh handle, the
     graph on the device (``graph_from_edges``) and its weakly connected components; with ``partitions`` also
     ``strongly_connected_components`` and ``superbubble_partitions``; with ``superbubbles`` also ``superbubbles``; with
-    ``bubblechains`` also ``bubble_chains`` (``min_nodes`` as in ``build_bubblechains``) and ``chains_by_component``."""
+    ``bubblechains`` also ``bubble_chains`` (``min_nodes`` as in ``build_bubblechains``) and ``chains_by_component``; with
+    ``contigs`` also ``identify_contigs`` outside those chains (``min_length`` as `phasm chain -l`) and
+    ``contigs_by_component``."""
     from .io import gfa
     with open(path) as f:
         graph = gfa.read_graph_gfa(f)
@@ -765,6 +856,9 @@ def chain_components(path: str, device: Optional[int] = None, partitions: bool =
             if bubblechains:
                 out.bubblechains = bubble_chains(ov, res, min_nodes, out.superbubbles)
                 out.component_chains = chains_by_component(out.bubblechains, out.components)
+            if contigs:
+                out.contigs = identify_contigs(ov, res, min_length, min_nodes)
+                out.component_contigs = contigs_by_component(out.contigs, out.components)
             return out
         finally:
             res.free()
@@ -830,11 +924,15 @@ def write_component_graphs(out_dir: str, g: ChainGraph, formats: Sequence[str] =
     (assembler.py:215-228, :303-304): ``gfa1`` and ``gfa2`` go to the same name, so with both the later one wins.  Where
     ``g`` carries bubble chains, before each component's own files also ``component{i}.bubblechain{j}.gfa`` / ``.graphml``
     for every chain j of component i with the reference's log line (assembler.py:272-286), and the component's GraphML
-    carries the node attribute ``bubblechain`` = j.  Returns the number of components."""
+    carries the node attribute ``bubblechain`` = j.  Where ``g`` carries contigs, behind the chain files the reference's log
+    line and ``component{i}.contig{j}.gfa`` / ``.graphml`` for every contig j of component i -- what ``g.subgraph(path)``
+    holds: the nodes of the path in path order, and every edge of the graph with both ends among them --, and the
+    component's GraphML carries the edge attribute ``contig`` = j on the edges of the reported paths (assembler.py:288-301).
+    Returns the number of components."""
     os.makedirs(out_dir, exist_ok=True)
     comps = g.components
 
-    def write(stem, nodes, edges, marks):
+    def write(stem, nodes, edges, marks, edge_marks=None):
         for file_format in formats:
             if file_format.startswith("gfa"):
                 lines = (component_gfa1_lines if int(file_format[-1]) == 1 else component_gfa2_lines)(g.graph, nodes, edges)
@@ -842,7 +940,7 @@ def write_component_graphs(out_dir: str, g: ChainGraph, formats: Sequence[str] =
                     f.write("".join(lines))
             else:
                 with open(os.path.join(out_dir, stem + ".graphml"), "w") as f:
-                    write_graphml(f, _ComponentView(g.graph, nodes, edges), marks)
+                    write_graphml(f, _ComponentView(g.graph, nodes, edges), marks, edge_marks)
 
     for i in range(len(comps)):
         nodes, idx = comps.nodes_of(i).tolist(), comps.edges_of(i)
@@ -856,5 +954,14 @@ def write_component_graphs(out_dir: str, g: ChainGraph, formats: Sequence[str] =
                 logger.info("Found bubblechain #%d with %d nodes and %d edges", j, len(c_nodes), len(c_edges))
                 marks.update((g.graph.node_name(n), j) for n in c_nodes)
                 write("component%d.bubblechain%d" % (i, j), c_nodes, c_edges, None)
-        write("component%d" % i, nodes, edges, marks)
+        edge_marks = None
+        if g.contigs is not None:
+            logger.info("Building contigs not part of a bubble chain...")
+            edge_marks, place = {}, {int(e): k for k, e in enumerate(idx.tolist())}
+            for j, c in enumerate(g.component_contigs[i]):
+                path, seen = g.contigs.path_of(c), set()
+                edge_marks.update((place[int(e)], j) for e in g.contigs.edges_of(c).tolist())
+                p_nodes = [n for n in path if not (n in seen or seen.add(n))]
+                write("component%d.contig%d" % (i, j), p_nodes, g.graph.edges[induced_edges(g.graph.edges, p_nodes)], None)
+        write("component%d" % i, nodes, edges, marks, edge_marks)
     return len(comps)

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, EDGE_DTYPE, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE
+from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -565,6 +565,38 @@ class ExactOverlapper:
 
     def bubblechain_stats(self) -> dict:
         return self._stats(self._lib.po_get_bubblechain_stats, PoBubblechainStats)
+
+    def layout_contigs(self, graph: OverlapResult, min_contig_len: int = 5000, min_nodes: int = 1, exclude=None,
+                       n_order: Optional[int] = None):
+        """``po_layout_contigs``: the contigs of a graph result (of the kinds ``layout_components`` takes), which stays
+        valid -- the paths and single nodes that the reference's ``identify_contigs(component, exclude_nodes, min_contig_len)``
+        reports on every component (phasm/assembly_graph.py:655-718).  ``exclude`` None: the nodes of the bubble chains the
+        call builds first (``min_nodes`` as in ``layout_bubblechains``), what `phasm chain` passes; else one byte per node,
+        parallel to ``graph.node_order()`` (``n_order``: its length, if the caller has it), non-zero = excluded.  Returns
+        ``(edge_contig, edge_pos, table)``: per edge, in the graph's edge order, its contig and its 0-based place on that
+        contig's path (``NO_NODE`` where there is none); one entry (``first_node``, ``last_node``, ``n_nodes``,
+        ``first_edge``, ``length``) per contig: the paths by (rank of the first node, head edge), then the one-node contigs
+        by rank."""
+        if not 0 <= int(min_nodes) <= 0xFFFFFFFF:
+            raise ValueError("min_nodes does not fit 32 bits")
+        if not 0 <= int(min_contig_len) < 2**64:
+            raise ValueError("min_contig_len does not fit 64 bits")
+        if n_order is None:
+            n_order = len(graph.node_order())
+        if exclude is not None:
+            exclude = np.ascontiguousarray(np.asarray(exclude) != 0, dtype=np.uint8)
+            if exclude.shape != (int(n_order),):
+                raise ValueError("exclude needs one entry per node of the order")
+        prm = PoContigParams(int(min_contig_len), int(min_nodes), 0)
+        edge_contig, edge_pos = np.zeros(len(graph), dtype=np.uint32), np.zeros(len(graph), dtype=np.uint32)
+        table = np.zeros(int(n_order) + len(graph), dtype=CONTIG_DTYPE)
+        n = ctypes.c_uint64()
+        _check(self._h, self._lib.po_layout_contigs(self._h, graph._ptr, ctypes.byref(prm), _ptr(exclude) if exclude is not None else None,
+                                                    _ptr(edge_contig), _ptr(edge_pos), _ptr(table), ctypes.byref(n)))
+        return edge_contig, edge_pos, table[:int(n.value)].copy()
+
+    def contig_stats(self) -> dict:
+        return self._stats(self._lib.po_get_contig_stats, PoContigStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:

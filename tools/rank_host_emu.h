@@ -12,14 +12,19 @@ struct RankedInput {
     unsigned long long cnt[16] = {};
 };
 
-// stdin: n_total n_edges n_order, one "u v" line per edge, the nodes in node order.  The identity words go to `ident`.
-// Returns -1 to go on, else the exit status ("invalid N" or "order" is on stdout then).
-static int ranked_input(RankedInput& g, std::vector<uint32_t>& ident) {
+// stdin: n_total n_edges n_order, one "u v" line per edge ("u v weight" with `weights`), the nodes in node order.  The
+// identity words go to `ident`.  Returns -1 to go on, else the exit status ("invalid N" or "order" is on stdout then).
+static int ranked_input(RankedInput& g, std::vector<uint32_t>& ident, bool weights = false) {
     uint32_t n_order_in;
     if (scanf("%u %u %u", &g.n_total, &g.n, &n_order_in) != 3) return 1;
     const uint32_t n_total = g.n_total, n = g.n;
     g.e.resize(n + 1);
-    for (uint32_t i = 0; i < n; ++i) { if (scanf("%u %u", &g.e[i].u, &g.e[i].v) != 2) return 1; g.e[i].weight = 100; g.e[i].overlap_len = 17; }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (scanf("%u %u", &g.e[i].u, &g.e[i].v) != 2) return 1;
+        g.e[i].weight = 100;
+        if (weights && scanf("%d", &g.e[i].weight) != 1) return 1;
+        g.e[i].overlap_len = 17;
+    }
     std::vector<unsigned long long> nrank(n_total + 1, NODE_NO_RANK);
     for (uint32_t i = 0; i < n_order_in; ++i) { uint32_t x; if (scanf("%u", &x) != 1 || x >= n_total) return 1; nrank[x] = ((unsigned long long)(3u * i + 5) << 2) | (i & 3); }
     const uint32_t pad = g.pad = merge_sort_pad(n_total), nn = g.nn = n_total + 2;
