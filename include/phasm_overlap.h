@@ -194,8 +194,9 @@ po_status po_overlaps_to_host(po_handle* h, uint32_t min_length, po_result** out
  *   B  all of b against a prefix of a[p:]  -> row (a, b, p, aend, 0, len(b))
  * longest-only for A per ordered pair, every B occurrence, as in the exact contract.  max_diff = 0 returns exactly the
  * rows of po_overlaps (checked against the reference goldens); max_diff > 0 has no reference counterpart -- its checker
- * is the build's own CPU restatement, oracle/extend_oracle.c ("parity unpinned").  Needs pure ACGT (2-bit) or 8-bit reads
- * when max_diff > 0. */
+ * is the build's own CPU restatement, oracle/extend_oracle.c, itself held against an independent definition and rows
+ * known by construction (tests/test_extend_definition.py).  Needs pure ACGT (2-bit) or 8-bit reads when max_diff > 0,
+ * and always anchors on the prefix K-mer (the narrow index), whatever the size of the read set. */
 po_status po_overlaps_ex(po_handle* h, uint32_t min_length, uint32_t max_diff, uint32_t band, po_result** out);
 
 /* Multi-GPU form: only the rows whose `a` read lies in shard `shard` of `nshards` (contiguous

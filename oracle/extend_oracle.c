@@ -1,11 +1,15 @@
 /* TEST INFRASTRUCTURE ONLY -- CPU restatement of the banded seed-extension mode (po_overlaps_ex).
  *
- * PARITY UNPINNED for max_diff > 0: the reference overlapper is exact (/root/reference/src/overlapper.cpp:28-150 has
- * no error tolerance anywhere), so nothing of the reference can check an inexact overlap.  This file is the build's
- * own statement of what that mode computes, written as the plainest possible row-by-row DP so that the HIP kernel
- * (phasm_amd/csrc/extend.hip.h: antidiagonal sweep, one lane per diagonal) has something independent to agree with.
- * With max_diff = 0 it reduces to the exact contract, and THAT is pinned: tests/test_oracle.py checks this file with
- * max_diff = 0 against every reference golden.
+ * NO REFERENCE for max_diff > 0: the reference overlapper is exact (its src/overlapper.cpp:28-150 has no error
+ * tolerance anywhere), so nothing of the reference can check an inexact overlap.  This file is the build's own
+ * statement of what that mode computes, written as the plainest possible row-by-row DP so that the HIP kernels
+ * (phasm_amd/csrc/extend.hip.h) have something independent to agree with.  What holds IT:
+ *   - max_diff = 0 reduces to the exact contract, pinned by every reference golden (tests/test_oracle.py);
+ *   - max_diff > 0: a second, independent statement of the Definition below (tests/extend_definition.py: plain numpy,
+ *     the full matrix with the band as a mask, ties as tuples) gives the same rows on every band 0..30, on tandem and
+ *     two-letter sequence and on seeded fuzz, and both give the rows that tests/extend_cases.py knows by construction
+ *     (cost at max_diff / one above, indel runs of W / W + 1, the canA / canB edges, tied end cells, two anchors of
+ *     a pair): tests/test_extend_definition.py.
  *
  * Definition.  Anchor: b's K-byte prefix occurs at a[p..p+K), p <= la - m, lb >= m, a != b (index).  x = a[p:],
  * y = b, rem = la - p.  D[i][j] = unit-cost edit distance of x[:i], y[:j] over cells with |j - i| <= W only.

@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- Python face of oracle/extend_oracle.c, the CPU restatement of the banded
-seed-extension mode (``po_overlaps_ex``).  PARITY UNPINNED for ``max_diff > 0`` (the reference is exact:
-/root/reference/src/overlapper.cpp:28-150); with ``max_diff = 0`` it is the exact contract and is pinned by the
-reference goldens (tests/test_oracle.py)."""
+seed-extension mode (``po_overlaps_ex``).  No reference for ``max_diff > 0`` (the reference is exact: its
+src/overlapper.cpp:28-150); there the restatement is held against an independent definition in plain numpy and against
+rows known by construction (tests/test_extend_definition.py).  With ``max_diff = 0`` it is the exact contract and is
+pinned by the reference goldens (tests/test_oracle.py)."""
 from __future__ import annotations
 
 import ctypes

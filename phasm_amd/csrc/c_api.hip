@@ -1807,13 +1807,19 @@ struct IndexFlavour {
     bool wide;
     uint32_t ww;
 };
-IndexFlavour index_flavour(po_handle* h, uint32_t m, bool streamed, uint32_t lead, const OverlapSwitches& sw) {
+// inexact (po_overlaps_ex with max_diff > 0): always narrow.  That mode is DEFINED on the narrow index's anchors -- b's prefix
+// K-mer at a[p..p+K) (extend.hip.h) -- and the wide index finds a pair through another K-mer of b, the one at offset (-p) mod W
+// (or a window minimiser further in) facing a word of a: the same candidates only while every base up to there matches.  With
+// differences it would miss anchors whose first difference lies before that K-mer's end and list others whose prefix K-mer
+// is not intact (tests/test_gpu_extend_edges.py: two anchors of one pair, the longer one 2 bases out of phase).
+IndexFlavour index_flavour(po_handle* h, uint32_t m, bool streamed, uint32_t lead, const OverlapSwitches& sw, bool inexact = false) {
     const uint32_t W = 64 / h->bits;
     bool wide = count_eligible(h, m) > 160000 && m >= 2 * W - 1;
     if (sw.index) {
         if (!strcmp(sw.index, "wide")) wide = m >= 2 * W - 1;
         if (!strcmp(sw.index, "narrow")) wide = false;
     }
+    if (inexact) wide = false;
     uint32_t ww = 1;
     if (wide && h->bits == 2) {
         ww = m >= W * 16 + W - 1 ? 16u : m >= W * 4 + W - 1 ? 4u : 1u;
@@ -1967,7 +1973,7 @@ struct OverlapCall {
         res->count = 0;
         if (n == 0 || n_elig == 0 || ntiles == 0) return PO_OK;
 
-        const IndexFlavour f = index_flavour(h, m, a.streamed, h->st_lead, sw);
+        const IndexFlavour f = index_flavour(h, m, a.streamed, h->st_lead, sw, dpE != 0);
         wide = f.wide;
         ww = f.ww;
         S.wide_index = wide ? 1u : 0u;

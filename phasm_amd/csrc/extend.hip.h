@@ -1,11 +1,15 @@
 // Banded seed-extension DP (po_overlaps_ex): the verify step of kernels.hip.h with up to `max_diff` differences.
 //
-// The reference overlapper is exact (/root/reference/src/overlapper.cpp:28-150: suffix-tree matches only), so this
-// mode has no reference to be checked against for max_diff > 0 -- PARITY UNPINNED there; its checker is the CPU
-// restatement oracle/extend_oracle.c.  With max_diff = 0 it must (and does, tests/test_gpu_extend.py) give exactly
-// the rows of po_overlaps, which the reference goldens pin.
+// The reference overlapper is exact (its src/overlapper.cpp:28-150: suffix-tree matches only), so this mode has no
+// reference to be checked against for max_diff > 0; its checker is the CPU restatement oracle/extend_oracle.c, which is
+// itself held against an independent definition (tests/extend_definition.py) and against rows known by construction
+// (tests/extend_cases.py) -- on the CPU in tests/test_extend_definition.py, on the device, through all three mappings
+// below, in tests/test_gpu_extend_edges.py: every band 0..30, costs at max_diff and one above, indel runs of W and W + 1,
+// the canA / canB edges, the rows where k_extend_bits changes phase, tied end cells, repeats.  With max_diff = 0 it must
+// (and does, tests/test_gpu_extend.py) give exactly the rows of po_overlaps, which the reference goldens pin.
 //
-// One candidate (a, p, b) = b's K-base prefix occurs at a[p..p+K) (the same anchors as the exact path).  Let
+// One candidate (a, p, b) = b's K-base prefix occurs at a[p..p+K) (the anchors of the narrow index; an inexact call
+// always builds that one -- the wide index anchors a pair at another K-mer of b, c_api.hip index_flavour).  Let
 // x = a[p:] (length rem) and y = b (length lb).  D[i][j] = edit distance (unit costs) of x[:i] and y[:j] restricted to
 // the band |j - i| <= W:
 //   A (suffix-prefix)  costA = min over j of D[rem][j] <= max_diff   -> row (a, b, p, la, 0, j*)

@@ -1944,12 +1944,16 @@ __global__ __launch_bounds__(VER_BLOCK) void k_verify_a(const uint64_t* __restri
 // ----------------------------------------------------------------------------------------
 // select: rows per candidate.  B rows: every occurrence.  A rows: only the longest per (a,b),
 // i.e. the smallest p = the smallest candidate index (candidates of one a come in ascending p).
-// Two A hits for one (a,b) force b's prefix K-mer to recur inside b (period p-p'), so only
+// EXACT mode: two A hits for one (a,b) force b's prefix K-mer to recur inside b (period p-p'), so only
 // candidates whose b has selfrep[b] set can be duplicates -- none at all in non-repetitive data,
 // where the host skips this machinery.  Where they exist, k_select_mark records the smallest
-// verified-A candidate index per (a,b) in an open-addressed table (size 2x the number of such
+// verified-A candidate POSITION per (a,b) in an open-addressed table (size 2x the number of such
 // candidates: O(1) per candidate, also for tandem repeats with thousands of hits per pair) and
 // k_select drops every other one.
+// INEXACT mode (po_overlaps_ex, max_diff > 0): the argument does not hold -- a = U (AC)^17 Z', b = (AC)^16 Z
+// has two accepted anchors two bases apart and b never repeats its prefix -- so selfrep[] says nothing there
+// and the host runs k_select_local over EVERY read's list (c_api.hip, `own_lists || dpE`); a list too long for
+// its table marks its b's itself and comes here (tests/test_gpu_extend_edges.py has both cases).
 // ----------------------------------------------------------------------------------------
 // one slot of the (a, b) -> smallest verified-A candidate table: key and minimum share 16 bytes, so the claim, the
 // atomicMin and k_select's lookup touch one cache line (memset 0xFF = empty key, "infinite" minimum)

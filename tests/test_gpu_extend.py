@@ -3,9 +3,11 @@
 * max_diff = 0: the DP kernel in place of the packed compare must return exactly the rows of po_overlaps -- checked
   against the REFERENCE goldens (toy, adversarial incl. N / lower case, repeats, the synthetic ladders).  This half is
   pinned by the reference.
-* max_diff > 0: the reference is exact (src/overlapper.cpp:28-150) and cannot check an inexact overlap -- PARITY
-  UNPINNED.  The checker is the build's own CPU restatement (oracle/extend_oracle.c, a plain row-by-row banded DP,
-  run in the checker process), on seeded read sets with substitutions and indels.  Bit-exact rows, sorted multisets.
+* max_diff > 0: the reference is exact (src/overlapper.cpp:28-150) and cannot check an inexact overlap.  The checker is
+  the build's own CPU restatement (oracle/extend_oracle.c, a plain row-by-row banded DP, run in the checker process), on
+  seeded read sets with substitutions and indels.  Bit-exact rows, sorted multisets.  That restatement is itself held
+  against an independent definition and rows known by construction (tests/test_extend_definition.py); the bands,
+  thresholds, end rows, ties and repeats that seeded noise does not reach are in tests/test_gpu_extend_edges.py.
 """
 import numpy as np
 import pytest

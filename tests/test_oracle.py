@@ -77,9 +77,10 @@ def test_c_oracle_matches_live_reference_random():
 
 
 def test_extension_oracle_with_zero_differences_is_the_exact_contract():
-    """oracle/extend_oracle.c (the CPU restatement of po_overlaps_ex) is PARITY UNPINNED for max_diff > 0 -- the
-    reference is exact -- but with max_diff = 0 it must be the exact contract, and that is pinned here by every
-    reference golden (the band is ignored without differences)."""
+    """oracle/extend_oracle.c (the CPU restatement of po_overlaps_ex) has no reference for max_diff > 0 -- the
+    reference is exact; there it is held against an independent definition and rows known by construction
+    (tests/test_extend_definition.py) -- but with max_diff = 0 it must be the exact contract, and that is pinned here
+    by every reference golden (the band is ignored without differences)."""
     from oracle import extend_oracle as eo
     for name, seqs, m, want in gu.all_small_cases() + gu.repeats_cases():
         assert np.array_equal(eo.oracle_overlaps_ex(seqs, m, 0, 5), want), name
