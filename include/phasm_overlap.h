@@ -263,7 +263,9 @@ po_status po_result_copy_prefix_to_device(po_result* r, void* dst_device, uint64
 void po_result_free(po_result* r);
 
 /* Write one GFA2 edge line per row to the file descriptor, byte-identical to the reference's
- * gfa_line("E", "*", a_id, b_id, astart, aend, bstart, bend, "*")  (assembler.py:46-48, gfa.py:230-231). */
+ * gfa_line("E", "*", a_id, b_id, astart, aend, bstart, bend, "*")  (assembler.py:46-48, gfa.py:230-231).  The lines go
+ * behind the descriptor's position, in row order, whatever the descriptor is: a regular file opened without O_APPEND is
+ * written in parallel at computed offsets, anything else (a pipe, a descriptor opened for appending) in order. */
 po_status po_write_gfa_edges(po_result* r, int fd, uint64_t* lines_out);
 /* The segment lines that go before them: `S <name> <length> *` per read pair (assembler.py:38; the handle's reads
  * must have been added as name+"+" / name+"-" pairs). */

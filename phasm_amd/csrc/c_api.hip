@@ -6335,7 +6335,12 @@ po_status po_write_gfa_edges(po_result* r, int fd, uint64_t* lines_out) {
     const uint64_t n_chunks = (r->count + chunk - 1) / chunk;
     const size_t line_max = 2 * max_id + 4 * 11 + 16;
     const off_t base_off = ::lseek(fd, 0, SEEK_CUR);
-    const bool seekable = base_off >= 0;
+    // pwrite at a computed offset needs a regular file that honours the offset: on an O_APPEND descriptor Linux ignores it
+    // and appends, so the chunks would land in the order the threads finish (`>> out.gfa`, a file opened in mode "a");
+    // lseek also succeeds on descriptors that are no files at all.  Those take the ordered write() like a pipe.
+    struct stat fd_st;
+    const int fd_fl = ::fcntl(fd, F_GETFL);
+    const bool seekable = base_off >= 0 && fd_fl >= 0 && !(fd_fl & O_APPEND) && ::fstat(fd, &fd_st) == 0 && S_ISREG(fd_st.st_mode);
     static const char digits2[201] =
         "00010203040506070809101112131415161718192021222324252627282930313233343536373839404142434445464748495051525354555657585960616263646566676869707172737475767778798081828384858687888990919293949596979899";
     auto put_int = [&](char* q, long long v) -> char* {

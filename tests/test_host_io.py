@@ -2,6 +2,7 @@
 import io
 
 import numpy as np
+import pytest
 
 from phasm_amd import synth
 from phasm_amd._lib import ROW_DTYPE
@@ -190,5 +191,89 @@ def test_native_edge_writer_many_chunks_file_and_pipe(tmp_path):
     t.join()
     os.close(rd)
     assert got[0] == want
+    res.free()
+    ov.close()
+
+
+def _union_text(layout, min_bytes):
+    """GFA2 text of a union of the row cases of tests/union_cases.py, at least ``min_bytes`` long: (text, segments, rows)."""
+    import union_cases as uc
+    import union_utils as uu
+    cases = uc.row_cases()
+    U0, _, _, seq0 = uu.row_union(cases, uc.alternating(len(cases), 1), layout)
+    per_round = len(uu.gfa_text(cases, U0, seq0))
+    U, lengths, rows, seq = uu.row_union(cases, uc.alternating(len(cases), -(-min_bytes // per_round) + 1), layout)
+    return uu.gfa_text(cases, U, seq), len(lengths), rows
+
+
+@pytest.mark.parametrize("layout", ["copy_major", "interleaved"])
+def test_threaded_gfa_reader_joins_its_ranges_in_file_order(layout, tmp_path):
+    """po_add_gfa cuts a file of 8 MB or more into byte ranges at line starts and parses them on several threads: the rows
+    come back in file order, none lost or doubled at a cut, and of two malformed lines the first in file order is the one
+    reported.  17 MB of text: four ranges where four threads are to be had."""
+    from phasm_amd.overlapper import ExactOverlapper
+    text, n_segments, rows = _union_text(layout, 17 << 20)
+    assert len(text) >= 16 << 20
+    p = tmp_path / "union.gfa"
+    p.write_text(text)
+    ov = ExactOverlapper()
+    n, res = ov.add_gfa(str(p))
+    got = res.rows()
+    assert n == n_segments and len(ov) == 2 * n_segments and len(got) == len(rows)
+    assert np.array_equal(np.stack([got[k] for k in ROW_DTYPE.names], 1).astype(np.int64), rows)
+    res.free()
+    ov.close()
+    # two malformed E lines: one in the first tenth of the edge lines, one in the last range
+    first_e = text.index("\nE\t") + 1
+    cut = lambda frac: text.index("\n", first_e + int((len(text) - first_e) * frac)) + 1   # noqa: E731
+    a, b = cut(0.05), cut(0.97)
+    bad = text[:a] + "E\t*\tearly\n" + text[a:b] + "E\t*\tlate\n" + text[b:]
+    p.write_text(bad)
+    ov = ExactOverlapper()
+    with pytest.raises(ValueError) as err:
+        ov.add_gfa(str(p))
+    assert "early" in str(err.value) and "late" not in str(err.value)
+    ov.close()
+
+
+def test_native_edge_writer_into_append_mode_descriptors(tmp_path):
+    """A descriptor opened for appending ignores the offset of pwrite (Linux appends): po_write_gfa_edges must take the
+    ordered write() there, or the 32 k-row chunks land in the order the threads finish.  400 000 rows (13 chunks) behind a
+    header line, through ``open(path, "a")`` and through ``os.open(..., O_WRONLY | O_APPEND)``: the bytes are header + the
+    per-row reference format, and a line written afterwards through the same descriptor lands behind the edges."""
+    import os
+    from phasm_amd.overlapper import ExactOverlapper
+    rng = np.random.default_rng(21)
+    ov = ExactOverlapper()
+    for i in range(40):
+        ov.add_segment("seg%d" % i, 500 + i)
+    ids = ov.ids()
+    n = 400_000
+    rows = np.zeros(n, dtype=ROW_DTYPE)
+    rows["a_idx"] = rng.integers(0, len(ids), n)
+    rows["b_idx"] = rng.integers(0, len(ids), n)
+    rows["astart"] = np.arange(n)                     # (every line differs from its neighbours: a swapped chunk shows)
+    rows["aend"] = rng.integers(0, 20_000, n)
+    rows["bstart"] = rng.integers(0, 500, n)
+    rows["bend"] = rng.integers(0, 120, n)
+    res = ov.result_from_rows(rows)
+    py = io.StringIO()
+    gfa.write_edges(py, rows, ids)
+    head, tail = b"H\tVN:z:2.0\n", b"S\tafter\t1\t*\n"
+    want = head + py.getvalue().encode() + tail
+    for how in ("python_a", "os_append"):
+        path = tmp_path / (how + ".gfa")
+        path.write_bytes(head)
+        if how == "python_a":
+            with open(path, "a") as f:
+                assert res.write_gfa_edges(f) == n
+                f.write(tail.decode())
+        else:
+            fd = os.open(str(path), os.O_WRONLY | os.O_APPEND)
+            with os.fdopen(fd, "w") as f:
+                assert res.write_gfa_edges(f) == n
+                f.write(tail.decode())
+        got = path.read_bytes()
+        assert len(got) == len(want) and got == want, how
     res.free()
     ov.close()

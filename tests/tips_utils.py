@@ -27,9 +27,10 @@ def new_counts():
 
 # ---- the node order ------------------------------------------------------------------------------------------------
 
-def node_order(rows, lengths, min_read_length=0, min_overlap_length=0, max_overhang_abs=1000, max_overhang_rel=0.8):
+def node_order(rows, lengths, min_read_length=0, min_overlap_length=0, max_overhang_abs=1000, max_overhang_rel=0.8, with_rows=False):
     """Oriented nodes in the order the reference's graph first saw them, without the nodes of contained reads.
-    rows: (a, b, astart, aend, bstart, bend) in file order; lengths per oriented node."""
+    rows: (a, b, astart, aend, bstart, bend) in file order; lengths per oriented node.  ``with_rows``: the pair (that
+    order, the index of the row that brought each node in)."""
     rows = [tuple(int(x) for x in r) for r in rows]
     first_c, types, passes = {}, [], []
     for r, (a, b, s, e, bs, be) in enumerate(rows):
@@ -59,7 +60,8 @@ def node_order(rows, lengths, min_read_length=0, min_overlap_length=0, max_overh
         for s, n in enumerate(slots):
             if (n >> 1) not in contained_reads:
                 rank.setdefault(n, (r, s))
-    return sorted(rank, key=rank.get)
+    order = sorted(rank, key=rank.get)
+    return (order, [rank[n][0] for n in order]) if with_rows else order
 
 
 # ---- the contract, sequential --------------------------------------------------------------------------------------
