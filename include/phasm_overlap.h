@@ -428,8 +428,9 @@ typedef struct {
  * of unambiguous paths with po_layout_merge, the average coverage per edge with po_layout_coverage; of `phasm chain`
  * this library has the weakly connected components (po_layout_components), the partition that superbubble detection
  * starts with (po_layout_partition), the superbubbles of the acyclic partitions (po_layout_superbubbles), the bubble
- * chains built from them (po_layout_bubblechains) and the contigs outside the chains (po_layout_contigs).  graph_to_dag, the
- * superbubbles of the cyclic partitions and phasing are not part of it. */
+ * chains built from them (po_layout_bubblechains) and the contigs outside the chains (po_layout_contigs); of `phasm phase`
+ * the scoring and pruning of the haplotype extensions at one bubble (po_phase_branch).  graph_to_dag, the superbubbles of the
+ * cyclic partitions and the rest of phasing (the bubble walk, the relevant reads, new blocks, spelling) are not part of it. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -891,6 +892,94 @@ typedef struct {
 po_status po_layout_contigs(po_handle* h, po_result* graph, const po_contig_params* params, const uint8_t* exclude_in,
                             uint32_t* edge_contig_out, uint32_t* edge_pos_out, po_contig* contigs_out, uint64_t* n_contigs_out);
 po_status po_get_contig_stats(const po_handle* h, po_contig_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The hot loop of `phasm phase`: BubbleChainPhaser.branch -- generate_new_hsets and calculate_rl, phasm/phasing.py:421-480,
+ * 564-631 -- and prune (phasing.py:482-539) at ONE bubble, given as plain arrays.  The call needs neither reads nor a graph on
+ * the handle.  Not part of it: the bubble walk of phase(), get_relevant_read_info, new_block and the final prune(.., 1.0) with
+ * its random.choice among ties, spelling sequences, CoverageModel (which the reference never uses), and the superbubbles of
+ * cyclic partitions.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t ploidy;             /* k, 1..8                                                                         */
+    uint32_t n_paths;            /* P, 1..64: the possible paths through the bubble                                 */
+    uint32_t n_cands;            /* C >= 1: the candidate haplotype sets                                            */
+    uint32_t n_reads;            /* R >= 0: the relevant reads                                                      */
+    uint32_t n_b;                /* local read ids are 0..n_b-1: the graph reads that are b read of an alignment    */
+    uint32_t start_of_block;     /* non-zero: only the non-decreasing k-tuples (combinations_with_replacement)      */
+    uint32_t min_spanning_reads; /* R below it: every rl is -inf                                                    */
+    uint32_t prune;              /* non-zero: the kept list goes through prune before it comes out                  */
+    uint32_t max_candidates;     /* prune: stop raising the level once this many or fewer survive                   */
+    uint32_t n_levels;           /* prune: the number of levels in po_phase_input.levels, at most 1024              */
+    double threshold;            /* linear, >= 0; 0 stands for log10 = -inf                                         */
+    uint32_t reserved;           /* must be 0                                                                       */
+    uint32_t reserved2;          /* must be 0                                                                       */
+} po_phase_params;
+
+typedef struct {
+    const int32_t* overlap_max;  /* [n_reads]; may be <= 0 (the reference computes edge_length - la.arange[0])      */
+    const uint32_t* aln_off;     /* [n_reads + 1]: the alignments of read r are aln_off[r] .. aln_off[r+1]-1        */
+    const uint32_t* aln_b;       /* per alignment: local id of its b read                                           */
+    const int32_t* aln_a0;       /* per alignment: arange[0]                                                        */
+    const int32_t* aln_a1;       /* per alignment: arange[1]                                                        */
+    const uint32_t* path_off;    /* [n_paths + 1]                                                                   */
+    const uint32_t* path_ids;    /* per path the local ids of its interior reads (MergedReads expanded, entrance
+                                    and exit left out)                                                              */
+    const uint32_t* set_off;     /* [n_cands * ploidy + 1]: list c * ploidy + i is read_sets[i] of candidate c      */
+    const uint32_t* set_ids;     /* the local ids of those reads (reads outside 0..n_b-1 can never match: the
+                                    caller leaves them out)                                                         */
+    const double* levels;        /* [n_levels]: log10 of the prune factors f0, f0 + step, ... in the order the
+                                    reference's loop would reach them (it accumulates in float and stops at
+                                    factor >= 1.0 or after max_prune_rounds rounds)                                 */
+} po_phase_input;
+
+typedef struct {
+    uint64_t n_extensions;       /* extensions enumerated: C * P^k, at the start of a block C * (P+k-1 choose k)     */
+    uint64_t n_kept;             /* of them with rl >= log10(threshold)                                             */
+    uint64_t n_survivors;        /* what prune left of those (= n_kept without prune or at its early returns)       */
+    uint64_t level_counts[16];   /* survivors of the first 16 levels, each as if the loop had got there             */
+    double max_rl;               /* greatest rl of the kept list (NaN: the list is empty)                           */
+    int32_t level_used;          /* index of the level prune stopped at; -1: it did not filter                      */
+    uint32_t n_levels;
+    float ms_intervals, ms_table, ms_extend, ms_filter, ms_prune, ms_total;
+} po_phase_stats;
+
+/* 1. TABLE.  For candidate c, haplotype slot i and path p, in float64,
+ *      S[c][i][p] = sum over the relevant reads r of f(r; read_sets[i] of c + interior of p)
+ *      f = (E - S0) / overlap_max_r if S0 < E, else 0
+ *    where S0 is the least arange[0] and E the greatest min(overlap_max_r, arange[1]), never below 0, of the alignments of r
+ *    whose b read is in the set (S0 < E fails when none is).  The sum runs in the implementation's order, which is fixed (per
+ *    tile of 2048 reads: per thread in index order, lanes by a butterfly, waves in order; tiles in order): there are no
+ *    floating-point atomics, the same input gives the same bits on every run.
+ * 2. EXTENSIONS.  Not at the start of a block all P^k tuples (p_0 .. p_{k-1}) in itertools.product order; at the start of a
+ *    block only the non-decreasing ones, in combinations_with_replacement order.  The ID of an extension is its product index
+ *    in both modes: digits base P, slot 0 most significant.
+ * 3. SCORE.  tot = (S[c][0][p_0] + ... + S[c][k-1][p_{k-1}]) / (k * R), added in slot order; p_sr = log10(tot), -inf when
+ *    tot == 0 (and when R == 0); prior = log10(multinomial / P^k) with multinomial = k! / prod m_j! over the multiplicities m_j
+ *    by path INDEX; rl = p_sr + prior.  R < min_spanning_reads: rl = -inf for every extension.
+ * 4. FILTER.  An extension is kept iff rl >= log10(threshold) (threshold 0: -inf >= -inf keeps the all-zero ones, as in the
+ *    reference).  The kept entries (cand, ext, rl) come out in (cand ascending, ext ascending) order -- the order of the list
+ *    branch returns.  Compaction is by prefix sum, not by atomics.
+ * 5. PRUNE (params.prune != 0): the reference's prune on the kept list with its early returns -- fewer than 2 entries, no
+ *    levels (the caller passes none for a factor <= 0), greatest rl = -inf: the list comes out as it is.  Otherwise an entry
+ *    survives level j iff rl - max >= levels[0..j] all hold; the call counts the survivors of every level in one pass, takes
+ *    the first level j with count <= max_candidates, else the last, and the survivors of that level come out in the same
+ *    order.  A level above 0 removes everything, as in the reference.
+ * 6. OUTPUTS.  Up to `cap` entries are written to cand_out / ext_out / rl_out (each may be NULL); *n_out is always the full
+ *    count (the convention of po_result_node_order).  table_out (may be NULL) receives S as C * k * P doubles; with C = 1 and
+ *    empty sets S[0][0][p] / R is the score of phase_large_bubble (phasing.py:633-685).  po_get_phase_stats has the counts.
+ * 7. REJECTIONS, each PO_ERR_INVALID with a sentence in po_last_error, checked on the host before the device is touched, the
+ *    outputs untouched (*n_out = 0 where it is given): n_out NULL; params or input NULL; reserved != 0, a threshold that is
+ *    negative or NaN, more than 1024 levels; ploidy outside 1..8; n_paths outside 1..64; n_cands == 0; C * P^k >= 2^31 (the id
+ *    space, in both modes); a missing array; offsets that do not start at 0 or that decrease; a local id >= n_b.
+ * Where the reference would raise (overlap_max == 0 under a negative arange[0]: ZeroDivisionError; a negative sum: log10
+ * domain error; R == 0 with min_spanning_reads == 0) the call computes in IEEE arithmetic; a NaN rl is never kept.  Device
+ * memory is linear in (C*k + P) * (R + n_b/8), C*k*P and C * P^k (13 bytes per extension id, 21 per kept entry, 16 per survivor).  There is no
+ * CPU fallback: without a GPU a valid call returns PO_ERR_HIP. */
+po_status po_phase_branch(po_handle* h, const po_phase_params* params, const po_phase_input* input, uint32_t* cand_out,
+                          uint32_t* ext_out, double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out);
+po_status po_get_phase_stats(const po_handle* h, po_phase_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

@@ -217,6 +217,30 @@ class PoContigStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoPhaseParams(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint32) for name in (
+                    "ploidy", "n_paths", "n_cands", "n_reads", "n_b", "start_of_block", "min_spanning_reads", "prune", "max_candidates",
+                    "n_levels")] + \
+               [("threshold", ctypes.c_double), ("reserved", ctypes.c_uint32), ("reserved2", ctypes.c_uint32)]
+
+
+class PoPhaseInput(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+                    "overlap_max", "aln_off", "aln_b", "aln_a0", "aln_a1", "path_off", "path_ids", "set_off", "set_ids", "levels")]
+
+
+class PoPhaseStats(ctypes.Structure):
+    _fields_ = [("n_extensions", ctypes.c_uint64), ("n_kept", ctypes.c_uint64), ("n_survivors", ctypes.c_uint64),
+                ("level_counts", ctypes.c_uint64 * 16), ("max_rl", ctypes.c_double), ("level_used", ctypes.c_int32),
+                ("n_levels", ctypes.c_uint32)] + \
+               [(name, ctypes.c_float) for name in ("ms_intervals", "ms_table", "ms_extend", "ms_filter", "ms_prune", "ms_total")]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["level_counts"] = list(self.level_counts)
+        return d
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -330,6 +354,9 @@ SYMBOLS = [
     ("po_layout_contigs", ctypes.c_int, [_P, _P, ctypes.POINTER(PoContigParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_contig_stats", ctypes.c_int, [_P, ctypes.POINTER(PoContigStats)]),
+    ("po_phase_branch", ctypes.c_int, [_P, ctypes.POINTER(PoPhaseParams), ctypes.POINTER(PoPhaseInput), ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_phase_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPhaseStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

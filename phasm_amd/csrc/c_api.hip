@@ -46,6 +46,7 @@
 #include "superbubbles.hip.h"
 #include "bubblechains.hip.h"
 #include "contigs.hip.h"
+#include "phase.hip.h"
 
 namespace {
 
@@ -79,13 +80,19 @@ enum { HB_CNT, HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOP
 // of the three stages that po_layout_bubblechains runs
 enum { CB_CNT, CB_EXCL, CB_LEN, CB_INDEG, CB_OUTDEG, CB_INE, CB_NLEN, CB_CLS, CB_JB0, CB_JB1, CB_HOPS0, CB_HOPS1, CB_WS0, CB_WS1, CB_CJ0,
        CB_CJ1, CB_OK0, CB_OK1, CB_HEADOF, CB_PN, CB_PLAST, CB_PLEN, CB_KEPT, CB_KEY, CB_VAL, CB_CONTIGOUT, CB_POSOUT, CB_TABLE, CB_N };
+// workspaces of po_phase_branch (phase.hip.h): counters (the greatest key behind them), the level histogram, the levels, the inputs,
+// bitsets and intervals of the read sets and of the paths, the table, rl / keep byte / place per extension id, the kept list,
+// keep byte / place per kept entry, the survivors
+enum { FB_CNT, FB_HIST, FB_LEVELS, FB_OM, FB_ALNOFF, FB_ALNB, FB_A0, FB_A1, FB_POFF, FB_PIDS, FB_SOFF, FB_SIDS, FB_SBITS, FB_PBITS, FB_SIV,
+       FB_PIV, FB_TABLE, FB_RL, FB_KEEP, FB_PLACE, FB_KCAND, FB_KEXT, FB_KRL, FB_KEEP2, FB_PLACE2, FB_SCAND, FB_SEXT, FB_SRL, FB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 67;
+constexpr int EV_LAY_N = 73;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
-       EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54 };
+       EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
-static_assert(EV_CONTIGS + 13 == EV_LAY_N, "the thirteen events of po_layout_contigs are the last of the layout events");
+static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
+static_assert(EV_PHASE + 6 == EV_LAY_N, "the six events of po_phase_branch are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -444,6 +451,9 @@ struct po_handle {
     // the contigs outside the bubble chains (po_layout_contigs, contigs.hip.h)
     DevBuf d_ct[CB_N];
     po_contig_stats ctstats = {};
+    // scoring and pruning of the haplotype extensions at one bubble (po_phase_branch, phase.hip.h)
+    DevBuf d_ph[FB_N];
+    po_phase_stats phstats = {};
 };
 
 struct po_result {
@@ -4525,6 +4535,232 @@ po_status run_contigs(po_handle* h, po_result* graph, uint64_t min_len, uint32_t
     return PO_OK;
 }
 
+// ---- scoring and pruning of the haplotype extensions at one bubble (po_phase_branch, phase.hip.h) ----------------------------
+
+// offsets of a CSR: they start at 0 and never decrease
+bool phase_offsets_ok(const uint32_t* off, uint64_t n_lists) {
+    if (off[0] != 0) return false;
+    for (uint64_t i = 0; i < n_lists; ++i)
+        if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
+// The checks of po_phase_branch in front of the device, in the order the header lists them: the sentence of the first one
+// that fails, empty when the call may go on (Pk = P^k then).
+std::string phase_check(const po_phase_params& p, const po_phase_input& in, uint64_t& Pk) {
+    const std::string name = "po_phase_branch: ";
+    if (p.reserved || p.reserved2 || !(p.threshold >= 0.0) || p.n_levels > po::PH_MAX_LEVELS) return name + "bad parameters";
+    if (p.ploidy < 1 || p.ploidy > po::PH_MAX_K) return name + "the ploidy must be 1 to 8";
+    if (p.n_paths < 1 || p.n_paths > po::PH_MAX_P) return name + "the number of paths must be 1 to 64";
+    if (!p.n_cands) return name + "there must be at least one candidate set";
+    Pk = 1;
+    for (uint32_t i = 0; i < p.ploidy; ++i) Pk *= p.n_paths;   // (at most 2^48)
+    if (Pk >= (1ull << 31) || Pk * p.n_cands >= (1ull << 31)) return name + "too many extensions for one call";
+    const uint64_t n_slots = (uint64_t)p.n_cands * p.ploidy;
+    if ((p.n_reads && (!in.overlap_max || !in.aln_off)) || !in.path_off || !in.set_off || (p.prune && p.n_levels && !in.levels))
+        return name + "an input array is missing";
+    if (p.n_reads && !phase_offsets_ok(in.aln_off, p.n_reads)) return name + "the offsets of the alignments do not start at 0 or decrease";
+    if (!phase_offsets_ok(in.path_off, p.n_paths)) return name + "the offsets of the paths do not start at 0 or decrease";
+    if (!phase_offsets_ok(in.set_off, n_slots)) return name + "the offsets of the read sets do not start at 0 or decrease";
+    const uint32_t n_aln = p.n_reads ? in.aln_off[p.n_reads] : 0, n_pids = in.path_off[p.n_paths], n_sids = in.set_off[n_slots];
+    if ((n_aln && (!in.aln_b || !in.aln_a0 || !in.aln_a1)) || (n_pids && !in.path_ids) || (n_sids && !in.set_ids))
+        return name + "an input array is missing";
+    for (uint32_t j = 0; j < n_aln; ++j)
+        if (in.aln_b[j] >= p.n_b) return name + "a local read id is not below n_b";
+    for (uint32_t j = 0; j < n_pids; ++j)
+        if (in.path_ids[j] >= p.n_b) return name + "a local read id is not below n_b";
+    for (uint32_t j = 0; j < n_sids; ++j)
+        if (in.set_ids[j] >= p.n_b) return name + "a local read id is not below n_b";
+    return std::string();
+}
+
+po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input& in, uint32_t Pk, uint32_t* cand_out, uint32_t* ext_out,
+                    double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out) {
+    const char* const name = "po_phase_branch";
+    hipStream_t st = h->stream;
+    po_phase_stats& S = h->phstats;
+    S = po_phase_stats();
+    S.level_used = -1;
+    S.max_rl = std::nan("");
+    S.n_levels = p.prune ? p.n_levels : 0;
+    DevBuf* B = h->d_ph;
+    const uint32_t k = p.ploidy, P = p.n_paths, C = p.n_cands, R = p.n_reads, nb = p.n_b, W = std::max(1u, cdiv(nb, 32));
+    const uint32_t N = C * Pk, n_slots = C * k;   // (both below 2^31: phase_check)
+    const uint32_t n_aln = R ? in.aln_off[R] : 0, n_pids = in.path_off[P], n_sids = in.set_off[n_slots];
+    const size_t Rr = std::max<size_t>(R, 1);
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_PHASE;
+    // everything whose size the inputs give, before the first launch (the two lists follow once their lengths are known)
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[FB_CNT], 128));
+    PO_TRY(ensure(h, B[FB_HIST], (po::PH_MAX_LEVELS + 1) * 8));
+    PO_TRY(ensure(h, B[FB_LEVELS], po::PH_MAX_LEVELS * 8));
+    for (int b : {FB_OM, FB_ALNOFF}) PO_TRY(ensure(h, B[b], ((size_t)R + 1) * 4));
+    for (int b : {FB_ALNB, FB_A0, FB_A1}) PO_TRY(ensure(h, B[b], ((size_t)n_aln + 1) * 4));
+    PO_TRY(ensure(h, B[FB_POFF], ((size_t)P + 1) * 4));
+    PO_TRY(ensure(h, B[FB_PIDS], ((size_t)n_pids + 1) * 4));
+    PO_TRY(ensure(h, B[FB_SOFF], ((size_t)n_slots + 1) * 4));
+    PO_TRY(ensure(h, B[FB_SIDS], ((size_t)n_sids + 1) * 4));
+    PO_TRY(ensure(h, B[FB_SBITS], (size_t)n_slots * W * 4));
+    PO_TRY(ensure(h, B[FB_PBITS], (size_t)P * W * 4));
+    PO_TRY(ensure(h, B[FB_SIV], (size_t)n_slots * Rr * sizeof(po::PhInterval)));
+    PO_TRY(ensure(h, B[FB_PIV], (size_t)P * Rr * sizeof(po::PhInterval)));
+    PO_TRY(ensure(h, B[FB_TABLE], (size_t)n_slots * P * 8));
+    PO_TRY(ensure(h, B[FB_RL], (size_t)N * 8));
+    PO_TRY(ensure(h, B[FB_KEEP], N));
+    PO_TRY(ensure(h, B[FB_PLACE], (size_t)N * 4));
+    unsigned long long *cnt = B[FB_CNT].as<unsigned long long>(), *hist = B[FB_HIST].as<unsigned long long>();
+    int32_t *om = B[FB_OM].as<int32_t>(), *a0 = B[FB_A0].as<int32_t>(), *a1 = B[FB_A1].as<int32_t>();
+    uint32_t *aln_off = B[FB_ALNOFF].as<uint32_t>(), *aln_b = B[FB_ALNB].as<uint32_t>(), *poff = B[FB_POFF].as<uint32_t>(),
+             *pids = B[FB_PIDS].as<uint32_t>(), *soff = B[FB_SOFF].as<uint32_t>(), *sids = B[FB_SIDS].as<uint32_t>(),
+             *sbits = B[FB_SBITS].as<uint32_t>(), *pbits = B[FB_PBITS].as<uint32_t>(), *place = B[FB_PLACE].as<uint32_t>();
+    po::PhInterval *siv = B[FB_SIV].as<po::PhInterval>(), *piv = B[FB_PIV].as<po::PhInterval>();
+    double *table = B[FB_TABLE].as<double>(), *rl = B[FB_RL].as<double>(), *levels = B[FB_LEVELS].as<double>();
+    uint8_t* keep = B[FB_KEEP].as<uint8_t>();
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    HIP_TRY(h, hipMemsetAsync(sbits, 0, (size_t)n_slots * W * 4, st));
+    HIP_TRY(h, hipMemsetAsync(pbits, 0, (size_t)P * W * 4, st));
+    auto up = [&](void* dst, const void* src, size_t bytes) -> po_status {
+        if (bytes) HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+        return PO_OK;
+    };
+    PO_TRY(up(om, in.overlap_max, (size_t)R * 4));
+    PO_TRY(up(aln_off, in.aln_off, R ? ((size_t)R + 1) * 4 : 0));
+    PO_TRY(up(aln_b, in.aln_b, (size_t)n_aln * 4));
+    PO_TRY(up(a0, in.aln_a0, (size_t)n_aln * 4));
+    PO_TRY(up(a1, in.aln_a1, (size_t)n_aln * 4));
+    PO_TRY(up(poff, in.path_off, ((size_t)P + 1) * 4));
+    PO_TRY(up(pids, in.path_ids, (size_t)n_pids * 4));
+    PO_TRY(up(soff, in.set_off, ((size_t)n_slots + 1) * 4));
+    PO_TRY(up(sids, in.set_ids, (size_t)n_sids * 4));
+    // the bitsets, the interval of every (read set, read) and (path, read)
+    hipLaunchKernelGGL(po::k_ph_bits, dim3(stride_grid(h, n_slots)), dim3(256), 0, st, n_slots, soff, sids, nb, W, sbits);
+    hipLaunchKernelGGL(po::k_ph_bits, dim3(stride_grid(h, P)), dim3(256), 0, st, P, poff, pids, nb, W, pbits);
+    if (R) {
+        hipLaunchKernelGGL(po::k_ph_intervals, dim3(stride_grid(h, (uint64_t)n_slots * R)), dim3(256), 0, st, n_slots, R, nb, W, sbits, aln_off,
+                           aln_b, a0, a1, om, siv);
+        hipLaunchKernelGGL(po::k_ph_intervals, dim3(stride_grid(h, (uint64_t)P * R)), dim3(256), 0, st, P, R, nb, W, pbits, aln_off, aln_b, a0, a1,
+                           om, piv);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    const uint32_t wg_cap = (uint32_t)h->n_cu * 8;
+    hipLaunchKernelGGL(po::k_ph_table, dim3(std::min(n_slots, wg_cap)), dim3(256), 0, st, n_slots, P, R, siv, piv, om, table);
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    // rl and keep byte of every extension id
+    po::PhExtend X;
+    X.C = C;
+    X.P = P;
+    X.k = k;
+    X.Pk = Pk;
+    X.chunks = cdiv(Pk, 256);
+    X.start_mode = p.start_of_block != 0;
+    X.dead = R < p.min_spanning_reads;
+    X.kfact = 1;
+    for (uint32_t i = 2; i <= k; ++i) X.kfact *= i;
+    X.denom = (double)k * (double)R;
+    X.log_thr = p.threshold == 0.0 ? -(double)INFINITY : std::log10(p.threshold);
+    hipLaunchKernelGGL(po::k_ph_extend, dim3(std::min(C * X.chunks, wg_cap)), dim3(256), 0, st, X, table, rl, keep, cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    // the kept list: places by prefix sum, the entries to their places, the greatest rl on the way
+    PO_TRY(prefix_sum<uint8_t>(h, keep, N, place, &h->pinned[2]));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::PK_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_kept64 = h->pinned[2];
+    S.n_extensions = h->pinned[16 + po::PK_ENUM];
+    S.n_kept = S.n_survivors = n_kept64;
+    if (n_kept64 != h->pinned[16 + po::PK_KEPT] || n_kept64 > S.n_extensions || S.n_extensions > N)
+        return fail(h, PO_ERR_HIP, std::string("internal: the extensions of ") + name + " do not add up");
+    const uint32_t n_kept = (uint32_t)n_kept64;
+    for (int b : {FB_KCAND, FB_KEXT, FB_PLACE2}) PO_TRY(ensure(h, B[b], ((size_t)n_kept + 1) * 4));
+    PO_TRY(ensure(h, B[FB_KRL], ((size_t)n_kept + 1) * 8));
+    PO_TRY(ensure(h, B[FB_KEEP2], (size_t)n_kept + 1));
+    uint32_t *kcand = B[FB_KCAND].as<uint32_t>(), *kext = B[FB_KEXT].as<uint32_t>(), *place2 = B[FB_PLACE2].as<uint32_t>();
+    double* krl = B[FB_KRL].as<double>();
+    uint8_t* keep2 = B[FB_KEEP2].as<uint8_t>();
+    double max_rl = std::nan("");
+    if (n_kept) {
+        hipLaunchKernelGGL(po::k_ph_gather, dim3(stride_grid(h, N)), dim3(256), 0, st, N, n_kept, Pk, keep, place, (const uint32_t*)nullptr,
+                           (const uint32_t*)nullptr, rl, kcand, kext, krl, cnt + po::PK_N);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 18, cnt + po::PK_N, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipEventRecord(ev[4], st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        const uint64_t key = h->pinned[18];
+        if (!key) return fail(h, PO_ERR_HIP, std::string("internal: the kept list of ") + name + " has no greatest entry");
+        const uint64_t bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
+        std::memcpy(&max_rl, &bits, 8);
+    } else {
+        HIP_TRY(h, hipEventRecord(ev[4], st));
+    }
+    S.max_rl = max_rl;
+    // prune: the survivors of every level in one pass, the level the reference's loop stops at, its survivors in order
+    const uint32_t *fcand = kcand, *fext = kext;
+    const double* frl = krl;
+    uint32_t n_final = n_kept;
+    if (p.prune && n_kept >= 2 && p.n_levels && max_rl != -(double)INFINITY) {
+        const uint32_t L = p.n_levels;
+        std::vector<double> lv(in.levels, in.levels + L);
+        for (uint32_t j = 1; j < L; ++j) lv[j] = lv[j] >= lv[j - 1] ? lv[j] : lv[j - 1];   // surviving levels 0..j = surviving their greatest
+        HIP_TRY(h, hipMemcpyAsync(levels, lv.data(), (size_t)L * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemsetAsync(hist, 0, ((size_t)L + 1) * 8, st));
+        PO_TRY(ensure_host(h, h->scratch_host, ((size_t)L + 1) * 8));
+        hipLaunchKernelGGL(po::k_ph_levels, dim3(stride_grid(h, n_kept)), dim3(256), 0, st, n_kept, krl, max_rl, levels, L, hist);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, hist, ((size_t)L + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        const uint64_t* hh = static_cast<const uint64_t*>(h->scratch_host.p);   // hh[t]: the entries that survive exactly t levels
+        std::vector<uint64_t> left(L);
+        uint64_t behind = 0, all = hh[0];
+        for (uint32_t j = L; j-- > 0;) {
+            behind += hh[j + 1];
+            left[j] = behind;
+            all += hh[j + 1];
+        }
+        if (all != n_kept) return fail(h, PO_ERR_HIP, std::string("internal: the prune levels of ") + name + " do not add up");
+        uint32_t used = L - 1;
+        for (uint32_t j = 0; j < L; ++j)
+            if (left[j] <= p.max_candidates) {
+                used = j;
+                break;
+            }
+        for (uint32_t j = 0; j < L && j < 16; ++j) S.level_counts[j] = left[j];
+        S.level_used = (int32_t)used;
+        hipLaunchKernelGGL(po::k_ph_survive, dim3(stride_grid(h, n_kept)), dim3(256), 0, st, n_kept, krl, max_rl, lv[used], keep2);
+        HIP_TRY(h, hipGetLastError());
+        PO_TRY(prefix_sum<uint8_t>(h, keep2, n_kept, place2, &h->pinned[3]));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        const uint64_t n_left = h->pinned[3];
+        if (n_left != left[used]) return fail(h, PO_ERR_HIP, std::string("internal: the survivors of ") + name + " do not add up");
+        for (int b : {FB_SCAND, FB_SEXT}) PO_TRY(ensure(h, B[b], ((size_t)n_left + 1) * 4));
+        PO_TRY(ensure(h, B[FB_SRL], ((size_t)n_left + 1) * 8));
+        if (n_left)
+            hipLaunchKernelGGL(po::k_ph_gather, dim3(stride_grid(h, n_kept)), dim3(256), 0, st, n_kept, (uint32_t)n_left, Pk, keep2, place2, kcand,
+                               kext, krl, B[FB_SCAND].as<uint32_t>(), B[FB_SEXT].as<uint32_t>(), B[FB_SRL].as<double>(),
+                               (unsigned long long*)nullptr);
+        HIP_TRY(h, hipGetLastError());
+        fcand = B[FB_SCAND].as<uint32_t>();
+        fext = B[FB_SEXT].as<uint32_t>();
+        frl = B[FB_SRL].as<double>();
+        n_final = (uint32_t)n_left;
+        S.n_survivors = n_left;
+    }
+    HIP_TRY(h, hipEventRecord(ev[5], st));
+    const size_t n_give = (size_t)std::min<uint64_t>(cap, n_final);
+    PO_TRY(land_outputs(h, {{fcand, n_give * 4, cand_out}, {fext, n_give * 4, ext_out}, {frl, n_give * 8, rl_out},
+                            {table, (size_t)n_slots * P * 8, table_out}}, cnt, po::PK_N));
+    *n_out = n_final;
+    (void)hipEventElapsedTime(&S.ms_intervals, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&S.ms_table, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&S.ms_extend, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_filter, ev[3], ev[4]);
+    (void)hipEventElapsedTime(&S.ms_prune, ev[4], ev[5]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[5]);
+    return PO_OK;
+}
+
 // ---- what the po_layout_* entry points share ------------------------------------------------------------------------
 
 // Everything an edge-producing entry point does behind its checks: `run(result)` fills a new result of handle h, which
@@ -5000,6 +5236,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_sb) b.release();
         for (DevBuf& b : h->d_bc) b.release();
         for (DevBuf& b : h->d_ct) b.release();
+        for (DevBuf& b : h->d_ph) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -6877,6 +7114,24 @@ po_status po_layout_contigs(po_handle* h, po_result* graph, const po_contig_para
 }
 
 po_status po_get_contig_stats(const po_handle* h, po_contig_stats* out) { return get_stats(h, &po_handle::ctstats, out); }
+
+po_status po_phase_branch(po_handle* h, const po_phase_params* params, const po_phase_input* input, uint32_t* cand_out, uint32_t* ext_out,
+                          double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out) {
+    if (!h) return PO_ERR_INVALID;
+    if (!n_out) return fail(h, PO_ERR_INVALID, "po_phase_branch: no room for the number of entries");
+    *n_out = 0;
+    if (!params || !input) return fail(h, PO_ERR_INVALID, "po_phase_branch: no parameters");
+    uint64_t Pk = 0;
+    const std::string said = phase_check(*params, *input, Pk);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return guarded_run(h, "po_phase_branch", [&] {
+        return run_phase(h, *params, *input, (uint32_t)Pk, cand_out, ext_out, rl_out, cap, table_out, n_out);
+    });
+}
+
+po_status po_get_phase_stats(const po_handle* h, po_phase_stats* out) { return get_stats(h, &po_handle::phstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE
+from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -597,6 +597,48 @@ class ExactOverlapper:
 
     def contig_stats(self) -> dict:
         return self._stats(self._lib.po_get_contig_stats, PoContigStats)
+
+    def phase_branch(self, bubble, start_of_block, min_spanning_reads: int = 0, threshold: float = 0.0, levels=None,
+                     max_candidates: int = 0, cap: Optional[int] = None, want_table: bool = False):
+        """``po_phase_branch``: the haplotype extensions of one bubble scored, filtered and -- with ``levels`` -- pruned.
+        ``bubble``: a ``phasm_amd.phasing.PackedBubble`` (``pack_bubble``).  ``threshold``: linear, 0 = keep everything;
+        ``levels``: None for the kept list as ``branch`` returns it, else the log10 prune levels of
+        ``phasing.prune_levels`` (an empty list prunes nothing, as a factor <= 0 does) with ``max_candidates``.  Returns
+        ``(cand, ext, rl)`` -- candidate set, extension id (``phasing.ext_digits``) and log10 relative likelihood of every
+        entry, in the reference's order -- and with ``want_table`` also S as C * k * P doubles.  ``cap``: write at most this
+        many entries (``phase_stats()`` has the full counts); None: all of them."""
+        b = bubble
+        if not 0 <= int(min_spanning_reads) < 2**32 or not 0 <= int(max_candidates) < 2**32:
+            raise ValueError("min_spanning_reads and max_candidates must fit 32 bits")
+        lv = np.ascontiguousarray(levels if levels is not None else [], dtype=np.float64)
+        arrays = [np.ascontiguousarray(a, dtype=dt) for a, dt in (
+            (b.overlap_max, np.int32), (b.aln_off, np.uint32), (b.aln_b, np.uint32), (b.aln_a0, np.int32), (b.aln_a1, np.int32),
+            (b.path_off, np.uint32), (b.path_ids, np.uint32), (b.set_off, np.uint32), (b.set_ids, np.uint32), (lv, np.float64))]
+        if len(arrays[0]) != b.n_reads or len(arrays[1]) != b.n_reads + 1 or len(arrays[5]) != b.n_paths + 1 or \
+                len(arrays[7]) != b.n_cands * b.ploidy + 1:
+            raise ValueError("the arrays of the bubble do not have the lengths its sizes give")
+        if len({len(arrays[2]), len(arrays[3]), len(arrays[4])}) != 1 or (b.n_reads and len(arrays[2]) != int(arrays[1][-1])) or \
+                len(arrays[6]) != int(arrays[5][-1]) or len(arrays[8]) != int(arrays[7][-1]):
+            raise ValueError("the arrays of the bubble do not have the lengths its offsets give")
+        prm = PoPhaseParams(int(b.ploidy), int(b.n_paths), int(b.n_cands), int(b.n_reads), int(b.n_b), int(bool(start_of_block)),
+                            int(min_spanning_reads), int(levels is not None), int(max_candidates), len(lv), float(threshold), 0, 0)
+        inp = PoPhaseInput(*[a.ctypes.data if len(a) else None for a in arrays])
+        table = np.zeros(b.n_cands * b.ploidy * b.n_paths if want_table else 0, dtype=np.float64)
+        room = min(b.n_cands * b.n_paths ** b.ploidy, 1 << 20) if cap is None else int(cap)
+        n = ctypes.c_uint64()
+        while True:
+            cand, ext, rl = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.float64)
+            _check(self._h, self._lib.po_phase_branch(self._h, ctypes.byref(prm), ctypes.byref(inp), _ptr(cand), _ptr(ext), _ptr(rl), room,
+                                                      _ptr(table), ctypes.byref(n)))
+            if cap is not None or n.value <= room:
+                break
+            room = int(n.value)   # (more than the first guess held: once more, with room for all)
+        k = min(room, int(n.value))
+        out = (cand[:k].copy(), ext[:k].copy(), rl[:k].copy())
+        return out + (table,) if want_table else out
+
+    def phase_stats(self) -> dict:
+        return self._stats(self._lib.po_get_phase_stats, PoPhaseStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:

@@ -1,0 +1,282 @@
+"""The hot loop of `phasm phase` on the device: scoring and pruning the haplotype extensions at one bubble.
+
+What the reference's ``BubbleChainPhaser.branch`` (``generate_new_hsets`` + ``calculate_rl``, phasm/phasing.py:421-480, 564-631),
+``prune`` (phasing.py:482-539) and the per-path score of ``phase_large_bubble`` (phasing.py:633-685) compute, through
+``po_phase_branch`` (include/phasm_overlap.h):
+
+    bubble = pack_bubble(possible_paths, [hs.read_sets for hs in candidate_sets], relevant_reads)
+    cand, ext, rl = branch(ov, bubble, start_of_block, threshold, min_spanning_reads)
+    cand, ext, rl = branch_and_prune(ov, bubble, start_of_block, threshold, min_spanning_reads,
+                                     prune_factor, prune_step_size, max_candidates, max_prune_rounds)
+    scores = score_paths(ov, bubble)
+
+Entry j of the result is candidate set ``cand[j]`` extended by the paths ``ext_digits(ext[j], P, k)``, with relative likelihood
+``rl[j]`` (log10), in the order of the list the reference returns.
+
+``ov`` is a SCORER: anything with ``phase_branch(bubble, start_of_block, min_spanning_reads, threshold, levels,
+max_candidates, want_table)`` and ``phase_stats()`` -- an ``ExactOverlapper`` (the device) or a ``HostScorer`` (the same
+decomposition in numpy, for machines without a GPU and for the tests; it is no fallback: nothing here picks it on its own).
+
+Not here: the bubble walk of ``phase()``, ``get_relevant_read_info``, ``new_block`` and the final ``prune(.., 1.0)`` with its
+``random.choice`` among ties, spelling sequences, a ``phase`` command, ``CoverageModel`` (unused by the reference)."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field, replace
+from typing import Callable, Iterable, List, Optional, Sequence
+
+import numpy as np
+
+NO_START = 0x7FFFFFFF
+
+
+@dataclass
+class PackedBubble:
+    """One bubble as ``po_phase_branch`` takes it: local read ids 0..n_b-1 and CSR arrays (include/phasm_overlap.h)."""
+    ploidy: int
+    n_paths: int
+    n_cands: int
+    n_reads: int
+    n_b: int
+    overlap_max: np.ndarray      # int32 [R]
+    aln_off: np.ndarray          # uint32 [R + 1]
+    aln_b: np.ndarray            # uint32
+    aln_a0: np.ndarray           # int32
+    aln_a1: np.ndarray           # int32
+    path_off: np.ndarray         # uint32 [P + 1]
+    path_ids: np.ndarray         # uint32
+    set_off: np.ndarray          # uint32 [C * k + 1]
+    set_ids: np.ndarray          # uint32
+    b_reads: list = field(default_factory=list)   # local id -> the caller's read object (empty when packed from arrays)
+
+    def path_reads(self, p: int) -> np.ndarray:
+        return self.path_ids[self.path_off[p]:self.path_off[p + 1]]
+
+    def set_reads(self, c: int, i: int) -> np.ndarray:
+        s = c * self.ploidy + i
+        return self.set_ids[self.set_off[s]:self.set_off[s + 1]]
+
+
+def _csr(lists: Sequence[Sequence[int]], dtype=np.uint32):
+    off = np.zeros(len(lists) + 1, dtype=np.uint32)
+    if len(lists):
+        off[1:] = np.cumsum([len(x) for x in lists])
+    flat = np.asarray([v for x in lists for v in x], dtype=dtype)
+    return off, np.ascontiguousarray(flat)
+
+
+def bubble_from_arrays(ploidy: int, overlap_max, alignments, paths, read_sets, n_b: Optional[int] = None) -> PackedBubble:
+    """A bubble from local ids: ``alignments[r]`` the (b, arange0, arange1) triples of read r, ``paths[p]`` the interior ids of
+    path p, ``read_sets[c][i]`` the ids of slot i of candidate c."""
+    alignments = [list(a) for a in alignments]
+    aln_off, aln_b = _csr([[t[0] for t in a] for a in alignments])
+    _, a0 = _csr([[t[1] for t in a] for a in alignments], np.int32)
+    _, a1 = _csr([[t[2] for t in a] for a in alignments], np.int32)
+    path_off, path_ids = _csr([sorted(set(p)) for p in paths])
+    flat_sets = [sorted(set(s)) for c in read_sets for s in c]
+    if any(len(c) != ploidy for c in read_sets):
+        raise ValueError("every candidate needs one read set per haplotype")
+    set_off, set_ids = _csr(flat_sets)
+    if n_b is None:
+        n_b = int(max([-1] + aln_b.tolist() + path_ids.tolist() + set_ids.tolist())) + 1
+    return PackedBubble(int(ploidy), len(paths), len(read_sets), len(alignments), int(n_b),
+                        np.ascontiguousarray(np.asarray(overlap_max, dtype=np.int64).astype(np.int32)), aln_off, aln_b, a0, a1,
+                        path_off, path_ids, set_off, set_ids)
+
+
+def _default_expand(node) -> Iterable:
+    """``get_all_reads`` of one node (phasing.py:552-562): the reads of a merged node, else the node itself."""
+    reads = getattr(node, "reads", None)
+    return reads if reads is not None else (node,)
+
+
+def _triple(la):
+    if hasattr(la, "arange"):
+        return la.get_oriented_reads()[1], int(la.arange[0]), int(la.arange[1])
+    b, a0, a1 = la
+    return b, int(a0), int(a1)
+
+
+def pack_bubble(paths, cand_read_sets, relevant, expand: Optional[Callable] = None) -> PackedBubble:
+    """Objects to local ids and CSR arrays.  ``paths``: the possible paths through the bubble, each a tuple of nodes WITH its
+    entrance and exit (they are left out here, as ``hap_ext[1:-1]``); ``expand(node)`` yields the reads of a node (default:
+    ``node.reads`` where there is one, else the node).  ``cand_read_sets[c][i]``: ``read_sets[i]`` of candidate set c.
+    ``relevant``: read -> (alignments, overlap_max), alignments being (b, arange0, arange1) triples or objects with ``.arange``
+    and ``.get_oriented_reads()``.  Objects need ``__hash__`` and ``__eq__`` only.  The local id of a read is its place in the
+    order in which the alignments first name it as b read; reads that no alignment names can never match and are dropped."""
+    expand = expand or _default_expand
+    local = {}
+    overlap_max, alignments = [], []
+    for _read, info in relevant.items():
+        las, om = info[0], info[1]
+        mine = []
+        for la in las:
+            b, a0, a1 = _triple(la)
+            mine.append((local.setdefault(b, len(local)), a0, a1))
+        alignments.append(mine)
+        overlap_max.append(int(om))
+    ids = lambda reads: [local[r] for r in reads if r in local]   # noqa: E731
+    path_lists = [ids(r for node in tuple(p)[1:-1] for r in expand(node)) for p in paths]
+    cand_read_sets = [list(c) for c in cand_read_sets]
+    if not cand_read_sets:
+        raise ValueError("there must be at least one candidate set")
+    ploidy = len(cand_read_sets[0])
+    out = bubble_from_arrays(ploidy, overlap_max, alignments, path_lists, [[ids(s) for s in c] for c in cand_read_sets], len(local))
+    out.b_reads = list(local)
+    return out
+
+
+def ext_digits(ext: int, n_paths: int, ploidy: int) -> tuple:
+    """The path index of every haplotype slot of extension id ``ext``: digits base P, slot 0 most significant."""
+    out = []
+    for _ in range(ploidy):
+        out.append(int(ext) % n_paths)
+        ext = int(ext) // n_paths
+    return tuple(reversed(out))
+
+
+def prune_levels(prune_factor: float, step: float, max_rounds: int) -> List[float]:
+    """log10 of the prune factors the reference's loop can reach, in its order (phasing.py:496-521): the factor itself, then
+    ``factor += step`` in float while fewer than ``max_rounds`` rounds have run and the factor is below 1.0.  A factor <= 0
+    gives no level (``prune`` returns its input).  Whether the loop GOES on to a level also depends on how many candidates the
+    level before left -- that is decided where the counts are."""
+    if prune_factor <= 0.0:
+        return []
+    levels = [math.log10(prune_factor)]
+    rounds = 1
+    while rounds < max_rounds and prune_factor < 1.0:
+        prune_factor += step
+        levels.append(math.log10(prune_factor))
+        rounds += 1
+    return levels
+
+
+def log_threshold(threshold: float) -> float:
+    return -math.inf if threshold == 0.0 else math.log10(threshold)
+
+
+def branch(ov, bubble: PackedBubble, start_of_block: bool, threshold: float = 0.0, min_spanning_reads: int = 0):
+    """The kept extensions of every candidate set, as ``BubbleChainPhaser.branch`` lists them: ``(cand, ext, rl)``."""
+    return ov.phase_branch(bubble, start_of_block, min_spanning_reads, threshold)
+
+
+def branch_and_prune(ov, bubble: PackedBubble, start_of_block: bool, threshold: float = 0.0, min_spanning_reads: int = 0,
+                     prune_factor: float = 0.1, prune_step_size: float = 0.1, max_candidates: int = 500, max_prune_rounds: int = 9):
+    """``prune(branch(...), prune_factor)`` of the reference: the survivors ``(cand, ext, rl)`` in the order of the kept list.
+    ``prune_factor`` is a number (a callable of the reference's depends on the length of the kept list: call ``branch``, then
+    this with the number)."""
+    levels = prune_levels(float(prune_factor), float(prune_step_size), int(max_prune_rounds))
+    return ov.phase_branch(bubble, start_of_block, min_spanning_reads, threshold, levels=levels, max_candidates=int(max_candidates))
+
+
+def score_paths(ov, bubble: PackedBubble) -> np.ndarray:
+    """The score of every path as ``phase_large_bubble`` computes it: the sum over the relevant reads of the overlap with the
+    path's interior alone, divided by their number."""
+    if bubble.n_reads == 0:
+        raise ZeroDivisionError("no relevant reads")
+    alone = replace(bubble, ploidy=1, n_cands=1, set_off=np.zeros(2, dtype=np.uint32), set_ids=np.zeros(0, dtype=np.uint32))
+    *_, table = ov.phase_branch(alone, False, 0, 0.0, want_table=True, cap=0)
+    return table.reshape(bubble.n_paths) / bubble.n_reads
+
+
+def best_paths(scores: np.ndarray, ploidy: int) -> List[int]:
+    """``sorted(scored_paths, key=scored_paths.get, reverse=True)[:ploidy]`` on path indices (a stable sort: ties keep the
+    order of the paths)."""
+    return sorted(range(len(scores)), key=lambda p: scores[p], reverse=True)[:ploidy]
+
+
+class HostScorer:
+    """The scheme of ``po_phase_branch`` in numpy: the table S[c][i][p], then every extension from it.  The same contract as
+    the device's, up to the order of the float64 sums."""
+
+    def __init__(self):
+        self._stats = {}
+
+    def phase_stats(self) -> dict:
+        return dict(self._stats)
+
+    @staticmethod
+    def _intervals(b: PackedBubble, off, ids, n_sets):
+        R, A = b.n_reads, len(b.aln_b)
+        member = np.zeros((n_sets, max(b.n_b, 1)), dtype=bool)
+        for s in range(n_sets):
+            member[s, ids[off[s]:off[s + 1]]] = True
+        s0 = np.full((n_sets, R), NO_START, dtype=np.int64)
+        e = np.zeros((n_sets, R), dtype=np.int64)
+        if A == 0 or R == 0:
+            return s0, e
+        read_of = np.repeat(np.arange(R), np.diff(b.aln_off.astype(np.int64)))
+        match = member[:, b.aln_b]                                                  # [set, alignment]
+        lo = np.where(match, b.aln_a0.astype(np.int64)[None, :], NO_START)
+        hi = np.where(match, np.minimum(b.aln_a1.astype(np.int64), b.overlap_max.astype(np.int64)[read_of])[None, :], 0)
+        some = np.flatnonzero(np.diff(b.aln_off.astype(np.int64)) > 0)
+        starts = b.aln_off.astype(np.int64)[some]
+        s0[:, some] = np.minimum.reduceat(lo, starts, axis=1)
+        e[:, some] = np.maximum(np.maximum.reduceat(hi, starts, axis=1), 0)
+        return s0, e
+
+    def table(self, b: PackedBubble) -> np.ndarray:
+        C, k, P, R = b.n_cands, b.ploidy, b.n_paths, b.n_reads
+        ss0, se = self._intervals(b, b.set_off, b.set_ids, C * k)
+        ps0, pe = self._intervals(b, b.path_off, b.path_ids, P)
+        s0 = np.minimum(ss0[:, None, :], ps0[None, :, :])
+        e = np.maximum(se[:, None, :], pe[None, :, :])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f = np.where(s0 < e, (e - s0) / b.overlap_max.astype(np.float64)[None, None, :], 0.0)
+        return f.sum(axis=2).reshape(C, k, P)
+
+    def phase_branch(self, bubble: PackedBubble, start_of_block, min_spanning_reads: int = 0, threshold: float = 0.0, levels=None,
+                     max_candidates: int = 0, cap: Optional[int] = None, want_table: bool = False):
+        b = bubble
+        C, k, P, R = b.n_cands, b.ploidy, b.n_paths, b.n_reads
+        if not 1 <= k <= 8 or not 1 <= P <= 64 or C < 1 or C * P ** k >= 2 ** 31:
+            raise ValueError("po_phase_branch: bad sizes")
+        S = self.table(b)
+        Pk = P ** k
+        digits = np.stack(np.unravel_index(np.arange(Pk), (P,) * k), axis=1)       # [ext, slot], slot 0 most significant
+        tot = np.zeros((C, Pk))
+        for i in range(k):
+            tot = tot + S[:, i, digits[:, i]]
+        den = np.ones(Pk, dtype=np.int64)
+        for i in range(k):
+            same = np.ones(Pk, dtype=np.int64)
+            for j in range(i):
+                same += digits[:, j] == digits[:, i]
+            den *= same
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tot = tot / float(k * R) if R else np.zeros_like(tot)
+            p_sr = np.where(tot == 0.0, -np.inf, np.log10(tot))
+            prior = np.log10((math.factorial(k) // den).astype(np.float64) / float(Pk))
+        rl = p_sr + prior[None, :]
+        if R < min_spanning_reads:
+            rl = np.full_like(rl, -np.inf)
+        listed = np.ones(Pk, dtype=bool)
+        if start_of_block:
+            listed = np.all(digits[:, 1:] >= digits[:, :-1], axis=1)
+        keep = (rl >= log_threshold(threshold)) & listed[None, :]
+        cand, ext = np.nonzero(keep)
+        rls = rl[cand, ext]
+        st = {"n_extensions": int(C * listed.sum()), "n_kept": len(rls), "n_survivors": len(rls), "level_used": -1,
+              "max_rl": float(rls.max()) if len(rls) else math.nan, "level_counts": [], "n_levels": len(levels) if levels is not None else 0}
+        if levels is not None and len(levels) and len(rls) >= 2 and rls.max() != -np.inf:
+            with np.errstate(invalid="ignore"):
+                d = rls - rls.max()
+            alive = np.ones(len(rls), dtype=bool)
+            for j, level in enumerate(levels):
+                alive &= d >= level
+                st["level_counts"].append(int(alive.sum()))
+                st["level_used"] = j
+                if alive.sum() <= max_candidates:
+                    break
+            # (the counts of the levels the loop did not reach, as if it had)
+            rest = alive.copy()
+            for level in levels[st["level_used"] + 1:]:
+                rest &= d >= level
+                st["level_counts"].append(int(rest.sum()))
+            cand, ext, rls = cand[alive], ext[alive], rls[alive]
+            st["n_survivors"] = len(rls)
+        st["level_counts"] = (st["level_counts"] + [0] * 16)[:16]
+        self._stats = st
+        n = len(rls) if cap is None else min(int(cap), len(rls))
+        out = (cand[:n].astype(np.uint32), ext[:n].astype(np.uint32), rls[:n].astype(np.float64))
+        return out + (S.reshape(-1).copy(),) if want_table else out
