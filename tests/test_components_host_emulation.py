@@ -2,31 +2,21 @@
 after another) against the goldens, with AddressSanitizer + UBSan: the sort of the rank words, the ranks of the edge ends,
 the hook and jump rounds with the host's cap and batches, the numbering of the roots, the labels and the table, checked
 without a GPU.  The edges go in scrambled.  Every loop is bounded: a subprocess that runs into its timeout fails the test."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import components_utils as cu
+import emu_utils
 from test_components_oracle import CASES, stage_inputs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c["name"] for c in CASES if c.get("direct")] + \
         ["tangle_3", "selfish_2", "reduced_hub_1025", "reduced_line_101", "ring_40", "lasso_70_6"] + \
         [c["name"] for c in CASES if c["name"].startswith("union_")]
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "components_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "components_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("components")
 
 
 def run_emu(emu, uv, order, n_total, perm):

@@ -4,32 +4,22 @@ every edge, the ranking rounds between two buffer triples, the coverage rounds b
 heads, the filter, the sort of the surviving heads, the table and the two arrays, with the host's caps and batches
 (round_phase of components.hip.h, which the library launches by), checked without a GPU.  The edges go in scrambled.  Every
 loop is bounded: a subprocess that runs into its timeout fails the test."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import contig_utils as ct
+import emu_utils
 from test_contigs_oracle import CASES, check_reference, exclude_of, stage_inputs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c["name"] for c in CASES if c.get("direct")] + \
         ["tangle_3", "selfish_2", "reduced_hub_1025", "reduced_line_101", "ring_40", "lasso_70_6"] + \
         [c["name"] for c in CASES if c["name"].startswith("union_")]
 NO_NODE = 0xFFFFFFFF
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "contigs_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "contigs_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("contigs")
 
 
 def run_emu(emu, edges, order, n_total, n_ids, lengths, exclude, min_len):

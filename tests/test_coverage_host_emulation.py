@@ -2,30 +2,20 @@
 after another) against the reference's goldens, with AddressSanitizer + UBSan: node_of, the pair table and its bounded
 probes, the sums, the lists and inclusion-exclusion per edge, checked without a GPU.  The rows go in scrambled.  A
 subprocess that runs into its timeout fails the test."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import coverage_utils as cu
+import emu_utils
 from test_coverage_oracle import CASES, application
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["_".join(str(v) for v in s.values()) for s in cu.NEW_CASES] + \
         ["tangle_11", "selfish_2", "reduced_hub_1025", "reduced_line_101", "union_21_1", "ring_40", "lasso_12_8", "lasso_70_6"]
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "coverage_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "coverage_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("coverage")
 
 
 def run_emu(emu, rows, e, members, L, n_ids):

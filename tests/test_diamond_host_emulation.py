@@ -3,31 +3,21 @@ after another) against the reference's goldens, with AddressSanitizer + UBSan: d
 rounds with the candidates handed over in scrambled order and the node pass, checked without a GPU.  The direct cases
 bring what no GFA case of the file has: node 0 as pred1, self-loops on a gt1, a predecessor that is the end node's own
 mirror, fans that settle one end node per round."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_utils
 import reduce_utils as ru
 from test_diamond_oracle import CASES, GOLDEN, input_edges
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c["name"] for c in CASES if c.get("direct")] + \
         ["tangle_3", "selfish_2", "reduced_hub_129", "reduced_hub_1025", "reduced_stagger_1100"] + \
         [c["name"] for c in CASES if c["name"].startswith("union_")]
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "diamond_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "diamond_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("diamond")
 
 
 def run_emu(emu, e, order, perm):

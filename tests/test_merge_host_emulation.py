@@ -3,32 +3,22 @@ another) against the reference's goldens, with AddressSanitizer + UBSan: degrees
 the sort of the heads (handed over in scrambled order), the tables, the renamed edges and the ranks of the result,
 checked without a GPU.  The edges go in scrambled.  The cycles of the direct cases (a self-loop, 2, 3, 64 and 65 nodes),
 the ring and the lasso show that every loop is bounded: a subprocess that runs into its timeout fails the test."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_utils
 import merge_utils as mu
 import reduce_utils as ru
 from test_merge_oracle import CASES, input_edges, node_lengths
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c["name"] for c in CASES if c.get("direct")] + \
         ["tangle_3", "selfish_2", "reduced_hub_1025", "reduced_line_101", "ring_40", "lasso_70_6"] + \
         [c["name"] for c in CASES if c["name"].startswith("union_")]
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "merge_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "merge_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("merge")
 
 
 def run_emu(emu, e, order, lengths, n_nodes, perm):

@@ -3,28 +3,18 @@ threads one after another) against the goldens, with AddressSanitizer + UBSan: t
 tile, the digits of an extension id, the start-of-block test, the multinomial, the filter, the places, the level histogram and
 the survivors, launched as run_phase of c_api.hip launches them, checked without a GPU.  The program is a stand-alone
 executable run as a subprocess; every loop is bounded: a subprocess that runs into its timeout fails the test."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
+import emu_utils
 import phase_utils as pu
 from phasm_amd import phasing
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = pu.load_golden()["cases"]
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "phase_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "phase_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("phase")
 
 
 def run_emu(emu, case, pruned):

@@ -2,32 +2,22 @@
 after another) against the reference's goldens, with AddressSanitizer + UBSan: indexing and logic of the CSR build,
 of k_reduce_mark with its states in "LDS" and in the global workspace (the hubs, on both sides of the switch at 1024 out-edges), and of the symmetry pass, checked
 without a GPU.  The edges go in shuffled with their insertion rank beside them, as the table path hands them over."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_utils
 import layout_utils as lu
 import reduce_utils as ru
 from oracle import layout_oracle as lo
 from phasm_amd.io import gfa
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["ladder_varlen", "ladder_cfg2_mini", "layout_random_1008", "layout_daligner_form_2003", "line_100", "line_105",
          "line_111", "hub_5200", "hub_1023", "hub_1024", "hub_1025", "stagger_1100", "dense_260", "tie_8"]
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "reduce_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "reduce_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("reduce")
 
 
 GOLDEN = ru.load_golden()

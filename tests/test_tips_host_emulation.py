@@ -2,31 +2,21 @@
 another) against the reference's goldens, with AddressSanitizer + UBSan: degrees and id sums, the rounds of both tip
 passes with the candidates handed over in scrambled order, the hash table of the symmetry pass and the node pass,
 checked without a GPU.  The direct cases bring what no GFA case of the file has: weights <= 0, self-loops, the edge (a, a^1), 2-cycles."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_utils
 import reduce_utils as ru
 import tips_utils as tu
 from test_tips_oracle import CASES, input_edges
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c["name"] for c in CASES if c.get("direct") or "synth" in c] + \
         ["reduced_" + n for n in ("ladder_varlen", "cfg2_1k", "layout_random_1008", "line_109", "hub_129", "hub_1025", "stagger_1100", "tie_8")]
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("emu") / "tips_host_emu")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-o", exe, os.path.join(ROOT, "tools", "tips_host_emu.cpp")])
-    return exe
+emu = emu_utils.emu_fixture("tips")
 
 
 def run_emu(emu, e, order, L, B, perm):
