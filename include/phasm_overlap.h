@@ -429,8 +429,9 @@ typedef struct {
  * this library has the weakly connected components (po_layout_components), the partition that superbubble detection
  * starts with (po_layout_partition), the superbubbles of the acyclic partitions (po_layout_superbubbles), the bubble
  * chains built from them (po_layout_bubblechains) and the contigs outside the chains (po_layout_contigs); of `phasm phase`
- * the scoring and pruning of the haplotype extensions at one bubble (po_phase_branch).  graph_to_dag, the superbubbles of the
- * cyclic partitions and the rest of phasing (the bubble walk, the relevant reads, new blocks, spelling) are not part of it. */
+ * the scoring and pruning of the haplotype extensions at one bubble (po_phase_branch) and the relevant reads of a bubble
+ * (po_phase_index, po_phase_relevant).  graph_to_dag, the superbubbles of the cyclic partitions and the rest of phasing (the
+ * bubble walk, new blocks, spelling) are not part of it. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -896,7 +897,7 @@ po_status po_get_contig_stats(const po_handle* h, po_contig_stats* out);
 /* ---------------------------------------------------------------------------------------------
  * The hot loop of `phasm phase`: BubbleChainPhaser.branch -- generate_new_hsets and calculate_rl, phasm/phasing.py:421-480,
  * 564-631 -- and prune (phasing.py:482-539) at ONE bubble, given as plain arrays.  The call needs neither reads nor a graph on
- * the handle.  Not part of it: the bubble walk of phase(), get_relevant_read_info, new_block and the final prune(.., 1.0) with
+ * the handle.  Not part of it: the bubble walk of phase(), new_block and the final prune(.., 1.0) with
  * its random.choice among ties, spelling sequences, CoverageModel (which the reference never uses), and the superbubbles of
  * cyclic partitions.
  * --------------------------------------------------------------------------------------------- */
@@ -980,6 +981,100 @@ typedef struct {
 po_status po_phase_branch(po_handle* h, const po_phase_params* params, const po_phase_input* input, uint32_t* cand_out,
                           uint32_t* ext_out, double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out);
 po_status po_get_phase_stats(const po_handle* h, po_phase_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The relevant reads of a bubble of `phasm phase`: the arrays po_phase_branch takes, from the rows.
+ *   _get_read_alignments (phasm/cli/assembler.py:313-328), get_aligning_reads (phasm/phasing.py:541-550), the spanning-read
+ *   intersection (phasing.py:263-286), get_relevant_read_info and _get_max_possible_overlap (phasing.py:366-419).
+ * Not part of it: the bubble walk itself, all_simple_paths, new_block, the final random.choice, spelling; the outputs of the
+ * gather come to the host (they are bubble-sized), po_phase_branch takes them from there.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t b;                  /* y: the oriented read the entry of (x, y) aligns x to                            */
+    int32_t a0, a1;              /* arange of the winning write                                                     */
+    uint32_t seq;                /* its sequence number: 2 * row for m[a][b], 2 * row + 1 for m[b][a]               */
+} po_alignment;
+
+typedef struct {
+    uint64_t n_rows, n_keys, max_degree, n_invalid;
+    float ms_insert, ms_fill, ms_place, ms_total;
+} po_phase_index_stats;
+
+/* THE INDEX: the reference's read_alignments mapping of a row result, on the device.  For every row
+ * i = (a, b, astart, aend, bstart, bend), in row order, the reference writes m[a][b] = (astart, aend) -- sequence number 2i --
+ * and then m[b][a] = (bstart, bend) -- 2i + 1; a later write replaces an earlier one, so the entry of key (x, y) is the write
+ * with the greatest sequence number.  x+ and x- are different keys.  A later row (b, a, ..) therefore replaces what an
+ * earlier (a, b, ..) wrote under both keys, and a row (x, x, ..) leaves (bstart, bend) under (x, x).
+ * Form: CSR over the handle's oriented read ids (< po_num_sequences): per x the distinct y as po_alignment, ascending in y;
+ * beside it the open-addressing table of the 64-bit keys (x, y) for point look-ups.  Two runs give the same bytes.
+ * The result is of a kind of its own: it holds no rows (po_result_count is 0), it is freed with po_result_free, and it stays
+ * valid after `rows` is freed.  It describes the reads the handle held when it was built: after more reads are added the
+ * gather refuses it.
+ * Limits: 2 * rows < 2^31, else PO_ERR_CAPACITY.  A row that names a read the handle does not hold: PO_ERR_INVALID (counted in
+ * n_invalid).  Device memory of the index: at most 80 bytes per row + 8 per read; while it is built another 40 per row + 8 per
+ * read in workspaces of the handle.  There is no CPU fallback. */
+po_status po_phase_index(po_handle* h, po_result* rows, po_result** index_out);
+/* For tests and tools: the offsets (n_ids + 1 of them, n_ids = po_num_sequences when the index was built) and up to `cap`
+ * entries in ascending (x, y); *n_out is always the number of keys (the convention of po_result_node_order).  Either array
+ * may be NULL. */
+po_status po_phase_index_copy(po_result* index, uint64_t* off_out, po_alignment* entries_out, uint64_t cap, uint64_t* n_out);
+po_status po_get_phase_index_stats(const po_handle* h, po_phase_index_stats* out);
+
+typedef struct {
+    uint32_t mode;               /* 0 = spanning (not the start of a block), 1 = all (the start of a block)         */
+    uint32_t min_spanning_reads;
+    uint32_t reserved, reserved2; /* must be 0                                                                      */
+} po_relevant_params;
+
+typedef struct {
+    const uint32_t* cur_graph;     uint64_t n_cur_graph;     /* interior reads of the bubble, MergedReads expanded  */
+    const uint32_t* prev_graph;    uint64_t n_prev_graph;    /* self.prev_graph_reads                               */
+    const uint32_t* prev_aligning; uint64_t n_prev_aligning; /* self.prev_aligning_reads                            */
+    /* the predecessors of the exit that are PLAIN reads, with g[pred][exit][edge_len].  A MergedReads predecessor is never
+     * a key of the mapping (`pred in self.alignments` is false for it), so it contributes len(read), which is where the
+     * minimum starts: the caller leaves it out. */
+    const uint32_t* pred_read; const int32_t* pred_edge_len; uint64_t n_pred;
+} po_relevant_input;
+
+/* what po_relevant_sizes gives (C has one name space for types and functions, so the struct has a name of its own) */
+typedef struct {
+    uint64_t n_cur_aligning, n_spanning, n_relevant, n_alignments, n_b;
+    uint32_t fell_back, reserved;
+} po_relevant_dims;
+
+typedef struct {
+    uint64_t n_cur_aligning, n_spanning, n_relevant, n_alignments, n_b;
+    uint32_t fell_back, reserved;
+    float ms_mark, ms_lists, ms_alignments, ms_total;
+} po_relevant_stats;
+
+/* THE GATHER for one bubble.  All lists are oriented read ids; duplicates are allowed and count once.
+ *   cur_aligning = cur_graph + { y : (x, y) in the index, x in cur_graph }, ascending.
+ *   n_spanning   = |prev_aligning & cur_aligning|.
+ *   The relevant reads: mode 1: cur_aligning.  Mode 0 with n_spanning >= min_spanning_reads: the intersection.  Mode 0 with
+ *   n_spanning < min_spanning_reads: fell_back = 1 and the call computes what the reference computes after new_block()
+ *   (phasing.py:266-286): cur_aligning, with prev_graph taken as empty.
+ *   G = cur_graph + prev_graph (after the fallback rule); b_reads is G ascending, n_b = |G|, the local id of a read its place
+ *   in b_reads.
+ *   For relevant read r, in ascending order of id: its alignments are the entries (r, y) with y in G, as (local(y), a0, a1), in
+ *   ascending y; overlap_max[r] = min(len(r), min over the given preds p with (p, r) in the index of pred_edge_len[p] -
+ *   a0(p, r)), as int32; it may be <= 0.
+ * overlap_max, aln_off, aln_b, aln_a0, aln_a1 are exactly those fields of po_phase_input.  The result is of a kind of its own,
+ * freed with po_result_free; po_relevant_sizes gives the lengths (cur_aligning: n_cur_aligning; rel_reads, overlap_max:
+ * n_relevant; aln_off: n_relevant + 1; aln_b, aln_a0, aln_a1: n_alignments; b_reads: n_b), po_relevant_copy the arrays, each
+ * of which may be NULL.
+ * Rejections, each PO_ERR_INVALID with a sentence in po_last_error, checked on the host before the device is touched (*out
+ * stays NULL): NULL out, params or input; reserved != 0; mode > 1; a NULL list with a non-zero count; an id >=
+ * po_num_sequences; a result of another handle or of the wrong kind; an index built before reads were added.  An empty
+ * cur_graph is PO_OK with every size 0.  Work per call is proportional to the segments of cur_graph and of the relevant reads
+ * plus n_ids / 32 words, not to the rows.  There is no CPU fallback: without a GPU a valid call returns PO_ERR_HIP. */
+po_status po_phase_relevant(po_handle* h, po_result* index, const po_relevant_params* params, const po_relevant_input* input,
+                            po_result** out);
+po_status po_relevant_sizes(const po_result* out, po_relevant_dims* sizes);
+po_status po_relevant_copy(po_result* out, uint32_t* cur_aligning, uint32_t* rel_reads, int32_t* overlap_max, uint32_t* aln_off,
+                           uint32_t* aln_b, int32_t* aln_a0, int32_t* aln_a1, uint32_t* b_reads);
+po_status po_get_relevant_stats(const po_handle* h, po_relevant_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

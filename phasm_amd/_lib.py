@@ -241,6 +241,42 @@ class PoPhaseStats(ctypes.Structure):
         return d
 
 
+ALIGNMENT_DTYPE = np.dtype([("b", np.uint32), ("a0", np.int32), ("a1", np.int32), ("seq", np.uint32)])
+
+
+class PoPhaseIndexStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_rows", "n_keys", "max_degree", "n_invalid")] + \
+               [(name, ctypes.c_float) for name in ("ms_insert", "ms_fill", "ms_place", "ms_total")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PoRelevantParams(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint32) for name in ("mode", "min_spanning_reads", "reserved", "reserved2")]
+
+
+class PoRelevantInput(ctypes.Structure):
+    _fields_ = [("cur_graph", ctypes.c_void_p), ("n_cur_graph", ctypes.c_uint64), ("prev_graph", ctypes.c_void_p),
+                ("n_prev_graph", ctypes.c_uint64), ("prev_aligning", ctypes.c_void_p), ("n_prev_aligning", ctypes.c_uint64),
+                ("pred_read", ctypes.c_void_p), ("pred_edge_len", ctypes.c_void_p), ("n_pred", ctypes.c_uint64)]
+
+
+class PoRelevantDims(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_cur_aligning", "n_spanning", "n_relevant", "n_alignments", "n_b")] + \
+               [("fell_back", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class PoRelevantStats(ctypes.Structure):
+    _fields_ = PoRelevantDims._fields_ + [(name, ctypes.c_float) for name in ("ms_mark", "ms_lists", "ms_alignments", "ms_total")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -357,6 +393,13 @@ SYMBOLS = [
     ("po_phase_branch", ctypes.c_int, [_P, ctypes.POINTER(PoPhaseParams), ctypes.POINTER(PoPhaseInput), ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_phase_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPhaseStats)]),
+    ("po_phase_index", ctypes.c_int, [_P, _P, ctypes.POINTER(_P)]),
+    ("po_phase_index_copy", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_phase_index_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPhaseIndexStats)]),
+    ("po_phase_relevant", ctypes.c_int, [_P, _P, ctypes.POINTER(PoRelevantParams), ctypes.POINTER(PoRelevantInput), ctypes.POINTER(_P)]),
+    ("po_relevant_sizes", ctypes.c_int, [_P, ctypes.POINTER(PoRelevantDims)]),
+    ("po_relevant_copy", ctypes.c_int, [_P] + [ctypes.c_void_p] * 8),
+    ("po_get_relevant_stats", ctypes.c_int, [_P, ctypes.POINTER(PoRelevantStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

@@ -47,6 +47,7 @@
 #include "bubblechains.hip.h"
 #include "contigs.hip.h"
 #include "phase.hip.h"
+#include "relevant.hip.h"
 
 namespace {
 
@@ -85,14 +86,22 @@ enum { CB_CNT, CB_EXCL, CB_LEN, CB_INDEG, CB_OUTDEG, CB_INE, CB_NLEN, CB_CLS, CB
 // keep byte / place per kept entry, the survivors
 enum { FB_CNT, FB_HIST, FB_LEVELS, FB_OM, FB_ALNOFF, FB_ALNB, FB_A0, FB_A1, FB_POFF, FB_PIDS, FB_SOFF, FB_SIDS, FB_SBITS, FB_PBITS, FB_SIV,
        FB_PIV, FB_TABLE, FB_RL, FB_KEEP, FB_PLACE, FB_KCAND, FB_KEXT, FB_KRL, FB_KEEP2, FB_PLACE2, FB_SCAND, FB_SEXT, FB_SRL, FB_N };
+// workspaces of po_phase_index and po_phase_relevant (relevant.hip.h).  The index: counters, keys per read, fill cursors, the
+// unsorted entries and their x.  The gather: the uploaded lists, the six bitsets, the three popcounts and ranks per word, the
+// three lists, count / offset / overlap_max per relevant read, the alignments
+enum { XB_CNT, XB_DEG, XB_CUR, XB_TMP, XB_EX, XB_LISTS, XB_BITS, XB_WCNT, XB_WRANK, XB_CA, XB_REL, XB_B, XB_ALNCNT, XB_ALNOFF, XB_OM,
+       XB_ALNB, XB_A0, XB_A1, XB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 73;
+constexpr int EV_LAY_N = 81;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
-       EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67 };
+       EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
+       EV_RELEVANT = 77 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
-static_assert(EV_PHASE + 6 == EV_LAY_N, "the six events of po_phase_branch are the last of the layout events");
+static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
+static_assert(EV_PHASE_INDEX + 4 == EV_RELEVANT, "po_phase_index has four events");
+static_assert(EV_RELEVANT + 4 == EV_LAY_N, "the four events of po_phase_relevant are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -454,6 +463,10 @@ struct po_handle {
     // scoring and pruning of the haplotype extensions at one bubble (po_phase_branch, phase.hip.h)
     DevBuf d_ph[FB_N];
     po_phase_stats phstats = {};
+    // the alignment index and the relevant reads of a bubble (po_phase_index, po_phase_relevant, relevant.hip.h)
+    DevBuf d_rr[XB_N];
+    po_phase_index_stats pxstats = {};
+    po_relevant_stats rvstats = {};
 };
 
 struct po_result {
@@ -486,6 +499,16 @@ struct po_result {
     void* ext_dst = nullptr;
     uint64_t ext_cap = 0;
     bool wrote_ext = false;
+    // po_phase_index (special == 1) and po_phase_relevant (special == 2): results of a kind of their own -- elem is 1 and
+    // count 0, so every call that wants rows, candidates or edges refuses them by its own check.
+    // The index: key table, value words (the place of the key's entry), offsets per read, entries, read lengths.
+    uint8_t special = 0;
+    uint32_t ix_n_ids = 0, ix_n_slots = 0, ix_n_keys = 0;
+    DevBuf d_ixtable, d_ixval, d_ixoff, d_ixent, d_ixlen;
+    // The relevant reads of one bubble, on the host (they are bubble-sized)
+    po_relevant_dims rv = {};
+    std::vector<uint32_t> rv_ca, rv_rel, rv_alnoff, rv_alnb, rv_b;
+    std::vector<int32_t> rv_om, rv_a0, rv_a1;
     bool compact = false;   // (inside po_overlaps_to_host only) d_rows holds the verified-candidate records of `count` ROWS
 };
 
@@ -2943,7 +2966,9 @@ po_status fill_nrank_tail(po_handle* h, po_result* res, size_t n_nodes, size_t n
 
 // every buffer a result may hold on the device (an empty one releases nothing)
 void release_device(po_result* r) {
-    for (DevBuf* b : {&r->d_rows, &r->d_rank, &r->d_nrank, &r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen}) b->release();
+    for (DevBuf* b : {&r->d_rows, &r->d_rank, &r->d_nrank, &r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen, &r->d_ixtable, &r->d_ixval,
+                      &r->d_ixoff, &r->d_ixent, &r->d_ixlen})
+        b->release();
 }
 
 // the grid of a kernel that strides over n items: eight workgroups of 256 per CU at the most
@@ -4761,6 +4786,226 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     return PO_OK;
 }
 
+// ---- the alignment index and the relevant reads of a bubble (po_phase_index, po_phase_relevant, relevant.hip.h) ---------------
+
+po_status run_phase_index(po_handle* h, po_result* rows, po_result* r) {
+    const char* const name = "po_phase_index";
+    hipStream_t st = h->stream;
+    po_phase_index_stats& S = h->pxstats;
+    S = po_phase_index_stats();
+    const uint32_t n_ids = (uint32_t)h->len.size(), n_rows = (uint32_t)rows->count;   // (2 * rows < 2^31: the entry point)
+    S.n_rows = n_rows;
+    r->special = 1;
+    r->elem = 1;
+    r->ix_n_ids = n_ids;
+    const uint32_t n_slots = po::rr_table_slots(n_rows);
+    r->ix_n_slots = n_slots;
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_PHASE_INDEX;
+    PO_TRY(rows_to_device(h, rows));
+    DevBuf* B = h->d_rr;
+    const size_t nn = (size_t)n_ids + 2;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[XB_CNT], 128));
+    for (int k : {XB_DEG, XB_CUR}) PO_TRY(ensure(h, B[k], nn * 4));
+    // (what leaves the handle with the result is not carved out of the handle's arena)
+    PO_TRY(ensure(h, r->d_ixtable, (size_t)n_slots * 8, 1.0, false));
+    PO_TRY(ensure(h, r->d_ixval, (size_t)n_slots * 4, 1.0, false));
+    PO_TRY(ensure(h, r->d_ixoff, nn * 4, 1.0, false));
+    PO_TRY(ensure(h, r->d_ixlen, nn * 4, 1.0, false));
+    unsigned long long *cnt = B[XB_CNT].as<unsigned long long>(), *table = r->d_ixtable.as<unsigned long long>();
+    uint32_t *deg = B[XB_DEG].as<uint32_t>(), *cur = B[XB_CUR].as<uint32_t>(), *tval = r->d_ixval.as<uint32_t>(),
+             *off = r->d_ixoff.as<uint32_t>(), *d_len = r->d_ixlen.as<uint32_t>();
+    const po::Row* d_rows = rows->d_rows.as<po::Row>();
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    for (uint32_t* p : {deg, cur, off}) HIP_TRY(h, hipMemsetAsync(p, 0, nn * 4, st));
+    HIP_TRY(h, hipMemsetAsync(table, 0xFF, (size_t)n_slots * 8, st));
+    HIP_TRY(h, hipMemsetAsync(tval, 0, (size_t)n_slots * 4, st));
+    if (n_ids) HIP_TRY(h, hipMemcpyAsync(d_len, h->len.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, st));
+    if (n_rows) hipLaunchKernelGGL(po::k_rr_insert, dim3(stride_grid(h, n_rows)), dim3(256), 0, st, d_rows, n_rows, n_ids, table, tval, n_slots, deg, cnt);
+    if (n_ids) hipLaunchKernelGGL(po::k_rr_degree, dim3(stride_grid(h, n_ids)), dim3(256), 0, st, deg, n_ids, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, deg, n_ids, off, &h->pinned[2]));   // (off[n_ids] is the closing sentinel: the number of keys)
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::RX_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    S.n_invalid = h->pinned[16 + po::RX_INVALID];
+    S.n_keys = h->pinned[16 + po::RX_KEYS];
+    S.max_degree = h->pinned[16 + po::RX_MAXDEG];
+    if (S.n_invalid) return fail(h, PO_ERR_INVALID, std::string(name) + ": a row names a read the handle does not hold");
+    if (h->pinned[2] != S.n_keys || S.n_keys > 2ull * n_rows)
+        return fail(h, PO_ERR_HIP, std::string("internal: the segments of ") + name + " do not add up");
+    const uint32_t n_keys = (uint32_t)S.n_keys;
+    r->ix_n_keys = n_keys;
+    PO_TRY(ensure(h, r->d_ixent, ((size_t)n_keys + 1) * sizeof(po::RrEntry), 1.0, false));
+    PO_TRY(ensure(h, B[XB_TMP], ((size_t)n_keys + 1) * sizeof(po::RrEntry)));
+    PO_TRY(ensure(h, B[XB_EX], ((size_t)n_keys + 1) * 4));
+    po::RrEntry *tmp = B[XB_TMP].as<po::RrEntry>(), *entries = r->d_ixent.as<po::RrEntry>();
+    uint32_t* ex = B[XB_EX].as<uint32_t>();
+    if (n_keys) {
+        hipLaunchKernelGGL(po::k_rr_fill, dim3(stride_grid(h, n_slots)), dim3(256), 0, st, table, tval, n_slots, d_rows, n_rows, n_ids, off, cur, tmp,
+                           ex, n_keys);
+        hipLaunchKernelGGL(po::k_rr_sort, dim3(stride_grid(h, n_keys)), dim3(256), 0, st, tmp, ex, off, n_keys, n_ids, entries);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    if (n_keys) hipLaunchKernelGGL(po::k_rr_place, dim3(stride_grid(h, n_keys)), dim3(256), 0, st, entries, ex, n_keys, table, tval, n_slots);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&S.ms_insert, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&S.ms_fill, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&S.ms_place, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
+    return PO_OK;
+}
+
+// The checks of po_phase_relevant in front of the device, in the order the header lists them: the sentence of the first one
+// that fails, empty when the call may go on.
+std::string relevant_check(const po_handle* h, const po_result* index, const po_relevant_params* p, const po_relevant_input* in) {
+    const std::string name = "po_phase_relevant: ";
+    if (!p || !in) return name + "no parameters";
+    if (p->reserved || p->reserved2) return name + "bad parameters";
+    if (p->mode > 1) return name + "the mode must be 0 (spanning) or 1 (all)";
+    if ((!in->cur_graph && in->n_cur_graph) || (!in->prev_graph && in->n_prev_graph) || (!in->prev_aligning && in->n_prev_aligning) ||
+        ((!in->pred_read || !in->pred_edge_len) && in->n_pred))
+        return name + "a list is missing";
+    const uint64_t n_ids = h->len.size();
+    if (in->n_cur_graph + in->n_prev_graph + in->n_prev_aligning + in->n_pred >= (1ull << 31)) return name + "the lists are too long for one call";
+    for (const auto& l : {std::make_pair(in->cur_graph, in->n_cur_graph), std::make_pair(in->prev_graph, in->n_prev_graph),
+                          std::make_pair(in->prev_aligning, in->n_prev_aligning), std::make_pair(in->pred_read, in->n_pred)})
+        for (uint64_t i = 0; i < l.second; ++i)
+            if (l.first[i] >= n_ids) return name + "a list names a read the handle does not hold";
+    if (index->h != h) return name + "the index belongs to another handle";
+    if (index->special != 1) return name + "needs the result of po_phase_index";
+    if (index->ix_n_ids != n_ids) return name + "reads were added to the handle after the index was built";
+    return std::string();
+}
+
+po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_params& p, const po_relevant_input& in, po_result* r) {
+    const char* const name = "po_phase_relevant";
+    hipStream_t st = h->stream;
+    po_relevant_stats& S = h->rvstats;
+    S = po_relevant_stats();
+    r->special = 2;
+    r->elem = 1;
+    r->rv = po_relevant_dims();
+    const uint32_t n_cur = (uint32_t)in.n_cur_graph, n_pg = (uint32_t)in.n_prev_graph, n_pa = (uint32_t)in.n_prev_aligning,
+                   n_pred = (uint32_t)in.n_pred;
+    if (!n_cur) return PO_OK;   // (every size 0)
+    const uint32_t n_ids = index->ix_n_ids, n_keys = index->ix_n_keys, n_slots = index->ix_n_slots, W = cdiv(n_ids, 32);
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_RELEVANT;
+    DevBuf* B = h->d_rr;
+    // the five lists behind one another, as one upload
+    const size_t n_lists = (size_t)n_cur + n_pg + n_pa + 2 * (size_t)n_pred;
+    std::vector<uint32_t> lists(n_lists);
+    {
+        uint32_t* at = lists.data();
+        for (const auto& l : {std::make_pair((const void*)in.cur_graph, n_cur), std::make_pair((const void*)in.prev_graph, n_pg),
+                              std::make_pair((const void*)in.prev_aligning, n_pa), std::make_pair((const void*)in.pred_read, n_pred),
+                              std::make_pair((const void*)in.pred_edge_len, n_pred)}) {
+            if (l.second) std::memcpy(at, l.first, (size_t)l.second * 4);
+            at += l.second;
+        }
+    }
+    const size_t Wp = (size_t)W + 1;   // (a scan writes a closing sentinel)
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[XB_CNT], 128));
+    PO_TRY(ensure(h, B[XB_LISTS], n_lists * 4));
+    PO_TRY(ensure(h, B[XB_BITS], 6 * Wp * 4));
+    PO_TRY(ensure(h, B[XB_WCNT], 3 * Wp * 4));
+    PO_TRY(ensure(h, B[XB_WRANK], 3 * Wp * 4));
+    unsigned long long* cnt = B[XB_CNT].as<unsigned long long>();
+    uint32_t* d_lists = B[XB_LISTS].as<uint32_t>();
+    const uint32_t *d_cur = d_lists, *d_pg = d_cur + n_cur, *d_pa = d_pg + n_pg, *d_pred = d_pa + n_pa;
+    const int32_t* d_plen = reinterpret_cast<const int32_t*>(d_pred + n_pred);
+    uint32_t* bits = B[XB_BITS].as<uint32_t>();
+    uint32_t *ca = bits, *pa = bits + Wp, *gc = bits + 2 * Wp, *gp = bits + 3 * Wp, *rel = bits + 4 * Wp, *g = bits + 5 * Wp;
+    uint32_t *wcnt = B[XB_WCNT].as<uint32_t>(), *wrank = B[XB_WRANK].as<uint32_t>();
+    const uint32_t* off = index->d_ixoff.as<uint32_t>();
+    const po::RrEntry* entries = index->d_ixent.as<po::RrEntry>();
+    const uint32_t cap = (uint32_t)h->n_cu * 8, word_grid = stride_grid(h, W);
+    auto wave_grid = [&](uint32_t n) { return std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 4), cap)); };   // one wave per item, four to a workgroup
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    HIP_TRY(h, hipMemsetAsync(bits, 0, 4 * Wp * 4, st));
+    HIP_TRY(h, hipMemcpyAsync(d_lists, lists.data(), n_lists * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(po::k_rr_mark, dim3(stride_grid(h, n_cur)), dim3(256), 0, st, d_cur, n_cur, n_ids, ca);
+    hipLaunchKernelGGL(po::k_rr_mark, dim3(stride_grid(h, n_cur)), dim3(256), 0, st, d_cur, n_cur, n_ids, gc);
+    if (n_pg) hipLaunchKernelGGL(po::k_rr_mark, dim3(stride_grid(h, n_pg)), dim3(256), 0, st, d_pg, n_pg, n_ids, gp);
+    if (n_pa) hipLaunchKernelGGL(po::k_rr_mark, dim3(stride_grid(h, n_pa)), dim3(256), 0, st, d_pa, n_pa, n_ids, pa);
+    hipLaunchKernelGGL(po::k_rr_mark_seg, dim3(wave_grid(n_cur)), dim3(256), 0, st, d_cur, n_cur, n_ids, off, entries, n_keys, ca);
+    hipLaunchKernelGGL(po::k_rr_count, dim3(word_grid), dim3(256), 0, st, ca, pa, W, cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, cnt, po::RG_N * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    HIP_TRY(h, hipStreamSynchronize(st));   // (the lists are on the device: `lists` may go)
+    const uint64_t n_ca = h->pinned[16 + po::RG_CA], n_span = h->pinned[16 + po::RG_SPAN];
+    if (n_ca > n_ids || n_span > n_ca) return fail(h, PO_ERR_HIP, std::string("internal: the aligning reads of ") + name + " do not add up");
+    const bool fell_back = p.mode == 0 && n_span < p.min_spanning_reads, use_pa = p.mode == 0 && !fell_back;
+    const uint32_t n_rel = (uint32_t)(use_pa ? n_span : n_ca), g_room = fell_back ? n_cur : n_cur + n_pg;
+    PO_TRY(ensure(h, B[XB_CA], (n_ca + 1) * 4));
+    PO_TRY(ensure(h, B[XB_REL], ((size_t)n_rel + 1) * 4));
+    PO_TRY(ensure(h, B[XB_B], ((size_t)g_room + 1) * 4));
+    for (int k : {XB_ALNCNT, XB_ALNOFF, XB_OM}) PO_TRY(ensure(h, B[k], ((size_t)n_rel + 2) * 4));
+    uint32_t *l_ca = B[XB_CA].as<uint32_t>(), *l_rel = B[XB_REL].as<uint32_t>(), *l_b = B[XB_B].as<uint32_t>(),
+             *aln_cnt = B[XB_ALNCNT].as<uint32_t>(), *aln_off = B[XB_ALNOFF].as<uint32_t>();
+    int32_t* om = B[XB_OM].as<int32_t>();
+    HIP_TRY(h, hipMemsetAsync(aln_off, 0, ((size_t)n_rel + 2) * 4, st));   // (no relevant read: the scan writes nothing)
+    hipLaunchKernelGGL(po::k_rr_select, dim3(word_grid), dim3(256), 0, st, ca, pa, gc, gp, W, (uint32_t)use_pa, (uint32_t)!fell_back, rel, g, wcnt,
+                       wcnt + Wp, wcnt + 2 * Wp);
+    HIP_TRY(h, hipGetLastError());
+    for (int k = 0; k < 3; ++k) PO_TRY(prefix_sum<uint32_t>(h, wcnt + k * Wp, W, wrank + k * Wp, &h->pinned[2 + k]));
+    hipLaunchKernelGGL(po::k_rr_list, dim3(word_grid), dim3(256), 0, st, ca, wrank, W, l_ca, (uint32_t)n_ca);
+    hipLaunchKernelGGL(po::k_rr_list, dim3(word_grid), dim3(256), 0, st, rel, wrank + Wp, W, l_rel, n_rel);
+    hipLaunchKernelGGL(po::k_rr_list, dim3(word_grid), dim3(256), 0, st, g, wrank + 2 * Wp, W, l_b, g_room);
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    if (n_rel) {
+        hipLaunchKernelGGL(po::k_rr_alncount, dim3(wave_grid(n_rel)), dim3(256), 0, st, l_rel, n_rel, n_ids, off, entries, n_keys, g, aln_cnt);
+        hipLaunchKernelGGL(po::k_rr_omax, dim3(stride_grid(h, n_rel)), dim3(256), 0, st, l_rel, n_rel, n_ids, index->d_ixlen.as<uint32_t>(), d_pred,
+                           d_plen, n_pred, index->d_ixtable.as<unsigned long long>(), index->d_ixval.as<uint32_t>(), n_slots, entries, n_keys,
+                           om);
+    }
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, aln_cnt, n_rel, aln_off, &h->pinned[5]));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_b = h->pinned[4], n_aln = h->pinned[5];
+    if (h->pinned[2] != n_ca || h->pinned[3] != n_rel || n_b > g_room || n_aln > n_keys)
+        return fail(h, PO_ERR_HIP, std::string("internal: the lists of ") + name + " do not add up");
+    for (int k : {XB_ALNB, XB_A0, XB_A1}) PO_TRY(ensure(h, B[k], (n_aln + 1) * 4));
+    uint32_t* aln_b = B[XB_ALNB].as<uint32_t>();
+    int32_t *a0 = B[XB_A0].as<int32_t>(), *a1 = B[XB_A1].as<int32_t>();
+    if (n_aln)
+        hipLaunchKernelGGL(po::k_rr_alnwrite, dim3(wave_grid(n_rel)), dim3(256), 0, st, l_rel, n_rel, n_ids, off, entries, n_keys, g, wrank + 2 * Wp,
+                           aln_off, (uint32_t)n_aln, aln_b, a0, a1);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    r->rv_ca.resize(n_ca);
+    r->rv_rel.resize(n_rel);
+    r->rv_om.resize(n_rel);
+    r->rv_alnoff.resize((size_t)n_rel + 1);
+    r->rv_alnb.resize(n_aln);
+    r->rv_a0.resize(n_aln);
+    r->rv_a1.resize(n_aln);
+    r->rv_b.resize(n_b);
+    PO_TRY(land_outputs(h, {{l_ca, n_ca * 4, r->rv_ca.data()}, {l_rel, (size_t)n_rel * 4, r->rv_rel.data()}, {om, (size_t)n_rel * 4, r->rv_om.data()},
+                            {aln_off, ((size_t)n_rel + 1) * 4, r->rv_alnoff.data()}, {aln_b, n_aln * 4, r->rv_alnb.data()},
+                            {a0, n_aln * 4, r->rv_a0.data()}, {a1, n_aln * 4, r->rv_a1.data()}, {l_b, n_b * 4, r->rv_b.data()}}, cnt, po::RG_N));
+    r->rv.n_cur_aligning = S.n_cur_aligning = n_ca;
+    r->rv.n_spanning = S.n_spanning = n_span;
+    r->rv.n_relevant = S.n_relevant = n_rel;
+    r->rv.n_alignments = S.n_alignments = n_aln;
+    r->rv.n_b = S.n_b = n_b;
+    r->rv.fell_back = S.fell_back = fell_back;
+    (void)hipEventElapsedTime(&S.ms_mark, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&S.ms_lists, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&S.ms_alignments, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
+    return PO_OK;
+}
+
 // ---- what the po_layout_* entry points share ------------------------------------------------------------------------
 
 // Everything an edge-producing entry point does behind its checks: `run(result)` fills a new result of handle h, which
@@ -5237,6 +5482,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_bc) b.release();
         for (DevBuf& b : h->d_ct) b.release();
         for (DevBuf& b : h->d_ph) b.release();
+        for (DevBuf& b : h->d_rr) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -7132,6 +7378,84 @@ po_status po_phase_branch(po_handle* h, const po_phase_params* params, const po_
 }
 
 po_status po_get_phase_stats(const po_handle* h, po_phase_stats* out) { return get_stats(h, &po_handle::phstats, out); }
+
+po_status po_phase_index(po_handle* h, po_result* rows, po_result** index_out) {
+    if (!h || !rows || !index_out) return PO_ERR_INVALID;
+    *index_out = nullptr;
+    if (rows->h != h) return fail(h, PO_ERR_INVALID, "po_phase_index: the rows belong to another handle");
+    if (rows->elem != sizeof(po_row) || rows->kind_edges || rows->special) return fail(h, PO_ERR_INVALID, "po_phase_index needs a row result");
+    if (2 * rows->count >= (1ull << 31)) return fail(h, PO_ERR_CAPACITY, "po_phase_index: more than 2^30 - 1 rows in one call");
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return new_edge_result(h, "po_phase_index", index_out, [&](po_result* r) { return run_phase_index(h, rows, r); });
+}
+
+po_status po_phase_index_copy(po_result* index, uint64_t* off_out, po_alignment* entries_out, uint64_t cap, uint64_t* n_out) {
+    if (!index) return PO_ERR_INVALID;
+    po_handle* h = index->h;
+    if (!n_out) return fail(h, PO_ERR_INVALID, "po_phase_index_copy: no room for the number of entries");
+    *n_out = 0;
+    if (index->special != 1) return fail(h, PO_ERR_INVALID, "po_phase_index_copy needs the result of po_phase_index");
+    static_assert(sizeof(po_alignment) == sizeof(po::RrEntry), "an entry of the index is a po_alignment");
+    const size_t n_off = (size_t)index->ix_n_ids + 1, n_give = (size_t)std::min<uint64_t>(cap, index->ix_n_keys);
+    return guarded_run(h, "po_phase_index_copy", [&] {
+        if (off_out) {
+            std::vector<uint32_t> off(n_off);
+            HIP_TRY(h, hipMemcpyAsync(off.data(), index->d_ixoff.p, n_off * 4, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            for (size_t i = 0; i < n_off; ++i) off_out[i] = off[i];
+        }
+        if (entries_out && n_give) {
+            HIP_TRY(h, hipMemcpyAsync(entries_out, index->d_ixent.p, n_give * sizeof(po_alignment), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        }
+        *n_out = index->ix_n_keys;
+        return PO_OK;
+    });
+}
+
+po_status po_get_phase_index_stats(const po_handle* h, po_phase_index_stats* out) { return get_stats(h, &po_handle::pxstats, out); }
+
+po_status po_phase_relevant(po_handle* h, po_result* index, const po_relevant_params* params, const po_relevant_input* input,
+                            po_result** out) {
+    if (!h) return PO_ERR_INVALID;
+    if (!out) return fail(h, PO_ERR_INVALID, "po_phase_relevant: no room for the result");
+    *out = nullptr;
+    if (!index) return fail(h, PO_ERR_INVALID, "po_phase_relevant: no index");
+    const std::string said = relevant_check(h, index, params, input);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return new_edge_result(h, "po_phase_relevant", out, [&](po_result* r) { return run_relevant(h, index, *params, *input, r); });
+}
+
+po_status po_relevant_sizes(const po_result* out, po_relevant_dims* sizes) {
+    if (!out || !sizes) return PO_ERR_INVALID;
+    if (out->special != 2) return fail(out->h, PO_ERR_INVALID, "po_relevant_sizes needs the result of po_phase_relevant");
+    *sizes = out->rv;
+    return PO_OK;
+}
+
+po_status po_relevant_copy(po_result* out, uint32_t* cur_aligning, uint32_t* rel_reads, int32_t* overlap_max, uint32_t* aln_off,
+                           uint32_t* aln_b, int32_t* aln_a0, int32_t* aln_a1, uint32_t* b_reads) {
+    if (!out) return PO_ERR_INVALID;
+    if (out->special != 2) return fail(out->h, PO_ERR_INVALID, "po_relevant_copy needs the result of po_phase_relevant");
+    auto give = [](void* dst, const void* src, size_t n) {
+        if (dst && n) std::memcpy(dst, src, n * 4);
+    };
+    give(cur_aligning, out->rv_ca.data(), out->rv_ca.size());
+    give(rel_reads, out->rv_rel.data(), out->rv_rel.size());
+    give(overlap_max, out->rv_om.data(), out->rv_om.size());
+    if (aln_off && out->rv_alnoff.empty()) aln_off[0] = 0;   // (an empty cur_graph: one offset, 0)
+    give(aln_off, out->rv_alnoff.data(), out->rv_alnoff.size());
+    give(aln_b, out->rv_alnb.data(), out->rv_alnb.size());
+    give(aln_a0, out->rv_a0.data(), out->rv_a0.size());
+    give(aln_a1, out->rv_a1.data(), out->rv_a1.size());
+    give(b_reads, out->rv_b.data(), out->rv_b.size());
+    return PO_OK;
+}
+
+po_status po_get_relevant_stats(const po_handle* h, po_relevant_stats* out) { return get_stats(h, &po_handle::rvstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

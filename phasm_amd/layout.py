@@ -36,8 +36,9 @@ starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).
 ``identify_contigs`` (assembly_graph.py:655-718); with them ``write_component_graphs`` also writes
 ``component{i}.contig{j}.*`` and the edge attribute ``contig``: every file `phasm chain` writes.
 What follows that point: of `phasm phase` the scoring and pruning of the haplotype extensions at one bubble is
-``phasm_amd.phasing`` (``po_phase_branch``); ``graph_to_dag`` for the cyclic partitions and the rest of phasing (the bubble
-walk, the relevant reads, new blocks, spelling sequences) are out of scope.
+``phasm_amd.phasing`` (``po_phase_branch``), as are the relevant reads of a bubble (``po_phase_index``, ``po_phase_relevant``);
+``graph_to_dag`` for the cyclic partitions and the rest of phasing (the bubble walk, new blocks, spelling sequences) are out
+of scope.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations

@@ -25,7 +25,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats
+from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats
+from .phasing import RelevantReads
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -639,6 +640,59 @@ class ExactOverlapper:
 
     def phase_stats(self) -> dict:
         return self._stats(self._lib.po_get_phase_stats, PoPhaseStats)
+
+    def phase_index(self, rows: OverlapResult) -> OverlapResult:
+        """``po_phase_index``: the reference's ``read_alignments`` mapping of a row result, on the device.  The result holds
+        no rows; it stays valid after ``rows`` is freed and goes to ``phase_relevant``."""
+        r = ctypes.c_void_p()
+        _check(self._h, self._lib.po_phase_index(self._h, rows._ptr, ctypes.byref(r)))
+        return OverlapResult(self, r, ALIGNMENT_DTYPE)
+
+    def phase_index_entries(self, index: OverlapResult):
+        """``po_phase_index_copy``: ``(offsets, entries)`` -- the entries of read x are ``entries[offsets[x]:offsets[x + 1]]``
+        (ALIGNMENT_DTYPE: b, a0, a1, seq), ascending in b."""
+        n = ctypes.c_uint64()
+        off = np.zeros(len(self) + 1, dtype=np.uint64)
+        _check(self._h, self._lib.po_phase_index_copy(index._ptr, _ptr(off), None, 0, ctypes.byref(n)))
+        entries = np.zeros(int(n.value), dtype=ALIGNMENT_DTYPE)
+        _check(self._h, self._lib.po_phase_index_copy(index._ptr, None, _ptr(entries), len(entries), ctypes.byref(n)))
+        return off, entries
+
+    def phase_index_stats(self) -> dict:
+        return self._stats(self._lib.po_get_phase_index_stats, PoPhaseIndexStats)
+
+    def phase_relevant(self, index: OverlapResult, cur_graph, prev_graph=(), prev_aligning=(), preds=(), mode: int = 0,
+                       min_spanning_reads: int = 0) -> "RelevantReads":
+        """``po_phase_relevant``: the relevant reads of one bubble with their alignments and overlap_max, in the arrays
+        ``po_phase_branch`` takes.  The lists are oriented read ids (duplicates count once); ``preds``: (read, edge_len) of
+        the predecessors of the exit that are plain reads; ``mode`` 0 = spanning, 1 = all."""
+        if not 0 <= int(mode) < 2**32 or not 0 <= int(min_spanning_reads) < 2**32:
+            raise ValueError("mode and min_spanning_reads must fit 32 bits")
+        preds = list(preds)
+        lists = [np.ascontiguousarray(a, dtype=np.uint32) for a in (
+            list(cur_graph), list(prev_graph), list(prev_aligning), [p[0] for p in preds])]
+        plen = np.ascontiguousarray([p[1] for p in preds], dtype=np.int32)
+        as_p = lambda a: a.ctypes.data if len(a) else None   # noqa: E731
+        prm = PoRelevantParams(int(mode), int(min_spanning_reads), 0, 0)
+        inp = PoRelevantInput(as_p(lists[0]), len(lists[0]), as_p(lists[1]), len(lists[1]), as_p(lists[2]), len(lists[2]),
+                              as_p(lists[3]), as_p(plen), len(plen))
+        r = ctypes.c_void_p()
+        _check(self._h, self._lib.po_phase_relevant(self._h, index._ptr, ctypes.byref(prm), ctypes.byref(inp), ctypes.byref(r)))
+        try:
+            d = PoRelevantDims()
+            _check(self._h, self._lib.po_relevant_sizes(r, ctypes.byref(d)))
+            R, A = int(d.n_relevant), int(d.n_alignments)
+            out = RelevantReads(np.zeros(int(d.n_cur_aligning), np.uint32), np.zeros(R, np.uint32), np.zeros(R, np.int32),
+                                np.zeros(R + 1, np.uint32), np.zeros(A, np.uint32), np.zeros(A, np.int32), np.zeros(A, np.int32),
+                                np.zeros(int(d.n_b), np.uint32), int(d.n_spanning), bool(d.fell_back))
+            _check(self._h, self._lib.po_relevant_copy(r, _ptr(out.cur_aligning), _ptr(out.rel_reads), _ptr(out.overlap_max), _ptr(out.aln_off),
+                                                       _ptr(out.aln_b), _ptr(out.aln_a0), _ptr(out.aln_a1), _ptr(out.b_reads)))
+        finally:
+            self._lib.po_result_free(r)
+        return out
+
+    def relevant_stats(self) -> dict:
+        return self._stats(self._lib.po_get_relevant_stats, PoRelevantStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:

@@ -17,8 +17,18 @@ Entry j of the result is candidate set ``cand[j]`` extended by the paths ``ext_d
 max_candidates, want_table)`` and ``phase_stats()`` -- an ``ExactOverlapper`` (the device) or a ``HostScorer`` (the same
 decomposition in numpy, for machines without a GPU and for the tests; it is no fallback: nothing here picks it on its own).
 
-Not here: the bubble walk of ``phase()``, ``get_relevant_read_info``, ``new_block`` and the final ``prune(.., 1.0)`` with its
-``random.choice`` among ties, spelling sequences, a ``phase`` command, ``CoverageModel`` (unused by the reference)."""
+What feeds that call -- the reference's ``read_alignments`` mapping (phasm/cli/assembler.py:313-328), ``get_aligning_reads``
+(phasing.py:541-550), the spanning-read intersection (phasing.py:263-286) and ``get_relevant_read_info`` (phasing.py:366-419) --
+through ``po_phase_index`` and ``po_phase_relevant``, on oriented read ids:
+
+    index = ov.phase_index(rows)                                                     # once
+    rel = relevant_reads(ov, index, cur_graph, prev_graph, prev_aligning, preds, start_of_block, min_spanning_reads)
+    bubble = bubble_from_relevant(rel, ploidy, paths, read_sets)                     # then branch(...) as above
+
+Here ``ov`` is anything with ``phase_relevant``: an ``ExactOverlapper`` or a ``HostIndex`` (numpy, like ``HostScorer``).
+
+Not here: the bubble walk of ``phase()``, ``new_block`` and the final ``prune(.., 1.0)`` with its ``random.choice`` among ties,
+spelling sequences, a ``phase`` command, ``CoverageModel`` (unused by the reference)."""
 from __future__ import annotations
 
 import math
@@ -280,3 +290,142 @@ class HostScorer:
         n = len(rls) if cap is None else min(int(cap), len(rls))
         out = (cand[:n].astype(np.uint32), ext[:n].astype(np.uint32), rls[:n].astype(np.float64))
         return out + (S.reshape(-1).copy(),) if want_table else out
+
+
+# ---- the relevant reads of a bubble (po_phase_index, po_phase_relevant) -------------------------------------------------------
+
+ALIGNMENT_DTYPE = np.dtype([("b", np.uint32), ("a0", np.int32), ("a1", np.int32), ("seq", np.uint32)])
+
+
+@dataclass
+class RelevantReads:
+    """What ``po_phase_relevant`` gives for one bubble.  ``overlap_max`` .. ``aln_a1`` are those fields of ``PackedBubble``;
+    the local id of a read is its place in ``b_reads`` (ascending global ids)."""
+    cur_aligning: np.ndarray     # uint32, ascending
+    rel_reads: np.ndarray        # uint32 [R], ascending
+    overlap_max: np.ndarray      # int32 [R]
+    aln_off: np.ndarray          # uint32 [R + 1]
+    aln_b: np.ndarray            # uint32, local ids
+    aln_a0: np.ndarray           # int32
+    aln_a1: np.ndarray           # int32
+    b_reads: np.ndarray          # uint32 [n_b], ascending
+    n_spanning: int = 0
+    fell_back: bool = False
+
+    def alignments_of(self, r: int) -> list:
+        """The (global b read, a0, a1) triples of relevant read number ``r``."""
+        lo, hi = int(self.aln_off[r]), int(self.aln_off[r + 1])
+        return [(int(self.b_reads[b]), int(a0), int(a1)) for b, a0, a1 in zip(self.aln_b[lo:hi], self.aln_a0[lo:hi], self.aln_a1[lo:hi])]
+
+
+def relevant_reads(src, index, cur_graph, prev_graph=(), prev_aligning=(), preds=(), start_of_block: bool = False,
+                   min_spanning_reads: int = 0) -> RelevantReads:
+    """The relevant reads of one bubble as ``phase()`` collects them: all aligning reads at the start of a block, else the
+    spanning ones -- and if those are fewer than ``min_spanning_reads``, what the reference computes after ``new_block()``
+    (``fell_back``: the caller starts its new block).  ``src``: anything with ``phase_relevant``."""
+    return src.phase_relevant(index, cur_graph, prev_graph, prev_aligning, preds, 1 if start_of_block else 0, int(min_spanning_reads))
+
+
+def bubble_from_relevant(rel: RelevantReads, ploidy: int, paths, read_sets) -> PackedBubble:
+    """A ``PackedBubble`` from GLOBAL read ids: ``paths[p]`` the interior reads of path p (MergedReads expanded),
+    ``read_sets[c][i]`` the reads of slot i of candidate c.  Ids go through ``rel.b_reads``; ids outside it can never match
+    and are dropped, as ``pack_bubble`` drops the reads no alignment names."""
+    b_reads = np.asarray(rel.b_reads, dtype=np.int64)
+
+    def local(ids):
+        ids = np.unique(np.asarray(list(ids), dtype=np.int64))
+        at = np.searchsorted(b_reads, ids)
+        ok = at < len(b_reads)
+        ok[ok] = b_reads[at[ok]] == ids[ok]
+        return at[ok].tolist()
+
+    read_sets = [list(c) for c in read_sets]
+    if not read_sets:
+        raise ValueError("there must be at least one candidate set")
+    if any(len(c) != ploidy for c in read_sets):
+        raise ValueError("every candidate needs one read set per haplotype")
+    path_off, path_ids = _csr([local(p) for p in paths])
+    set_off, set_ids = _csr([local(s) for c in read_sets for s in c])
+    out = PackedBubble(int(ploidy), len(paths), len(read_sets), len(rel.rel_reads), len(b_reads),
+                       np.ascontiguousarray(rel.overlap_max, dtype=np.int32), np.ascontiguousarray(rel.aln_off, dtype=np.uint32),
+                       np.ascontiguousarray(rel.aln_b, dtype=np.uint32), np.ascontiguousarray(rel.aln_a0, dtype=np.int32),
+                       np.ascontiguousarray(rel.aln_a1, dtype=np.int32), path_off, path_ids, set_off, set_ids)
+    out.b_reads = [int(x) for x in b_reads]
+    return out
+
+
+class HostIndex:
+    """The contract of ``po_phase_index`` / ``po_phase_relevant`` in numpy, for machines without a GPU and for the tests; it is
+    no fallback: nothing here picks it on its own.  ``lengths``: the length of every oriented read id."""
+
+    def __init__(self, lengths):
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+
+    def __len__(self) -> int:
+        return len(self.lengths)
+
+    def phase_index(self, rows):
+        """``rows``: structured (a_idx, b_idx, astart, aend, bstart, bend) or an int array [n, 6]."""
+        rows = np.asarray(rows)
+        if rows.dtype.names:
+            rows = np.stack([rows[name].astype(np.int64) for name in rows.dtype.names], axis=1) if len(rows) else np.zeros((0, 6), np.int64)
+        rows = rows.astype(np.int64).reshape(-1, 6)
+        n, n_ids = len(rows), len(self)
+        if 2 * n >= 2 ** 31:
+            raise RuntimeError("po_phase_index: more than 2^30 - 1 rows in one call")
+        if n and (rows[:, :2].min() < 0 or rows[:, :2].max() >= n_ids):
+            raise ValueError("po_phase_index: a row names a read the handle does not hold")
+        x, y, a0, a1 = (np.zeros(2 * n, dtype=np.int64) for _ in range(4))
+        x[0::2], x[1::2], y[0::2], y[1::2] = rows[:, 0], rows[:, 1], rows[:, 1], rows[:, 0]
+        a0[0::2], a1[0::2], a0[1::2], a1[1::2] = rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5]
+        key = (x << 32) | y
+        order = np.lexsort((np.arange(2 * n), key))             # by key, then by sequence number
+        last = np.ones(2 * n, dtype=bool)
+        last[:-1] = key[order][1:] != key[order][:-1]           # the greatest sequence number of every key
+        sel = order[last]
+        entries = np.zeros(len(sel), dtype=ALIGNMENT_DTYPE)
+        entries["b"], entries["a0"], entries["a1"], entries["seq"] = y[sel], a0[sel], a1[sel], sel
+        off = np.searchsorted(x[sel], np.arange(n_ids + 1)).astype(np.uint64)
+        return {"off": off, "entries": entries, "n_ids": n_ids}
+
+    def phase_index_entries(self, index):
+        return index["off"], index["entries"]
+
+    def phase_relevant(self, index, cur_graph, prev_graph=(), prev_aligning=(), preds=(), mode: int = 0,
+                       min_spanning_reads: int = 0) -> RelevantReads:
+        off, entries, n_ids = index["off"], index["entries"], index["n_ids"]
+        if mode not in (0, 1):
+            raise ValueError("po_phase_relevant: the mode must be 0 (spanning) or 1 (all)")
+        preds = [(int(p), int(e)) for p, e in preds]
+        cur, prev_g, prev_a = (sorted({int(v) for v in l}) for l in (cur_graph, prev_graph, prev_aligning))
+        if any(not 0 <= v < n_ids for l in (cur, prev_g, prev_a, [p for p, _ in preds]) for v in l) or n_ids != len(self):
+            raise ValueError("po_phase_relevant: a list names a read the handle does not hold")
+        u32, i32 = (lambda v: np.asarray(v, dtype=np.uint32)), (lambda v: np.asarray(v, dtype=np.int32))
+        if not cur:
+            return RelevantReads(u32([]), u32([]), i32([]), u32([0]), u32([]), i32([]), i32([]), u32([]), 0, False)
+        seg = lambda v: entries[int(off[v]):int(off[v + 1])]   # noqa: E731
+        ca = set(cur)
+        for v in cur:
+            ca.update(seg(v)["b"].tolist())
+        spanning = ca & set(prev_a)
+        fell_back = mode == 0 and len(spanning) < min_spanning_reads
+        rel = sorted(spanning if mode == 0 and not fell_back else ca)
+        G = np.asarray(sorted(set(cur) | (set() if fell_back else set(prev_g))), dtype=np.int64)
+        om, aln_off, aln_b, a0, a1 = [], [0], [], [], []
+        for r in rel:
+            s = seg(r)
+            at = np.searchsorted(G, s["b"])
+            ok = at < len(G)
+            ok[ok] = G[at[ok]] == s["b"][ok]
+            aln_b += at[ok].tolist()
+            a0 += s["a0"][ok].tolist()
+            a1 += s["a1"][ok].tolist()
+            aln_off.append(len(aln_b))
+            m = int(self.lengths[r])
+            for p, edge_len in preds:
+                sp = seg(p)
+                j = int(np.searchsorted(sp["b"], r))
+                if j < len(sp) and int(sp["b"][j]) == r:
+                    m = min(m, edge_len - int(sp["a0"][j]))
+            om.append(m)
+        return RelevantReads(u32(sorted(ca)), u32(rel), i32(om), u32(aln_off), u32(aln_b), i32(a0), i32(a1), u32(G), len(spanning), fell_back)
