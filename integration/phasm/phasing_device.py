@@ -15,9 +15,29 @@ With an alignment index the subclass also replaces ``get_aligning_reads`` and ``
     phaser = device_phaser(BubbleChainPhaser, ov, index=index, read_id=read_id)(g, ploidy, ...)
 
 ``read_id`` maps a read object to its oriented id on the handle (a dict or a callable).  Both methods then go through
-``po_phase_relevant``; ``get_relevant_read_info`` returns ``{read: (list of (b read, a0, a1), overlap_max)}``, which
-``pack_bubble`` accepts.  Without ``index`` and ``read_id`` nothing changes."""
+``po_phase_relevant``; ``get_relevant_read_info`` returns ``{read: RelevantReadInfo(list of (b read, a0, a1), overlap_max)}``, which
+``pack_bubble`` accepts.  The inherited ``phase_large_bubble`` reads the same mapping (phasm/phasing.py:649-662), so the info
+also has ``.alignments`` and ``.overlap_max`` and every triple ``.arange`` and ``.get_oriented_reads()``, as the reference's
+``RelevantReadInfo`` and ``LocalAlignment`` have.  Without ``index`` and ``read_id`` nothing changes."""
+from collections import namedtuple
+
 from phasm_amd import phasing
+
+RelevantReadInfo = namedtuple("RelevantReadInfo", "alignments overlap_max")
+
+
+class Alignment(tuple):
+    """``(b read, a0, a1)`` of a relevant read, with what the reference's loops ask of a ``LocalAlignment``."""
+
+    def __new__(cls, a, b, a0, a1):
+        self = super().__new__(cls, (b, a0, a1))
+        self.a = a
+        return self
+
+    arange = property(lambda self: (self[1], self[2]))
+
+    def get_oriented_reads(self):
+        return self.a, self[0]
 
 
 def device_phaser(phaser_class, scorer, index=None, read_id=None, source=None):
@@ -85,7 +105,7 @@ def _with_relevant(base, source, index, read_id):
             relevant_reads = list(relevant_reads)
             cur = list(cur_bubble_graph_reads)
             if not relevant_reads or not cur:
-                return {r: ([], len(r)) for r in relevant_reads}
+                return {r: RelevantReadInfo([], len(r)) for r in relevant_reads}
             prev = list(self.prev_graph_reads)
             preds = [(p, self.g[p][bubble_exit][self.g.edge_len]) for p in self.g.predecessors_iter(bubble_exit)
                      if not hasattr(p, "prefix_lengths")]                       # (a MergedReads predecessor yields len(read))
@@ -93,8 +113,8 @@ def _with_relevant(base, source, index, read_id):
             # mode 0 with the wanted reads as prev_aligning: the relevant reads are those of them that align to the bubble
             rel = phasing.relevant_reads(self.relevant_source, self.alignment_index, [to_id(r) for r in cur], [to_id(r) for r in prev],
                                          [to_id(r) for r in relevant_reads], [(to_id(p), int(e)) for p, e in preds], False, 0)
-            out = {back[int(x)]: ([(back[b], a0, a1) for b, a0, a1 in rel.alignments_of(j)], int(rel.overlap_max[j]))
-                   for j, x in enumerate(rel.rel_reads)}
+            out = {back[int(x)]: RelevantReadInfo([Alignment(back[int(x)], back[b], a0, a1) for b, a0, a1 in rel.alignments_of(j)],
+                                                  int(rel.overlap_max[j])) for j, x in enumerate(rel.rel_reads)}
             missing = [r for r in relevant_reads if r not in out]
             if missing:
                 raise ValueError("get_relevant_read_info: %d reads that do not align to the bubble" % len(missing))

@@ -141,8 +141,18 @@ STAGES = {
         "kernels": each(("k_ph_bits", "k_ph_intervals", "k_ph_table", "k_ph_extend", "k_ph_gather", "k_ph_levels",
                          "k_ph_survive"), (None, "")),
     },
+    "relevant": {  # po_phase_index and po_phase_relevant (phasm_amd/csrc/relevant.hip.h): no scratch, at most 64 VGPRs --
+        # nothing is unrolled over data -- and static LDS within a workgroup's 64 KB (they use none)
+        "exact": True, "family": "k_rr_",
+        "forbid": ("k_ph_", "k_cov_", "k_ct_", "k_bc_", "k_sb_", "k_scc_", "k_cc_", "k_merge_", "k_diamond_", "k_tips_", "k_reduce_"),
+        "why": "one thread or one wave per item: a few indices, one entry {b, a0, a1, seq}, one 64-bit key",
+        "kernels": each(("k_rr_insert", "k_rr_degree", "k_rr_fill", "k_rr_sort", "k_rr_place", "k_rr_mark", "k_rr_mark_seg",
+                         "k_rr_count", "k_rr_select", "k_rr_list", "k_rr_alncount", "k_rr_alnwrite", "k_rr_omax"),
+                        (64, "one thread or one wave per item: a few indices, one entry {b, a0, a1, seq}, one 64-bit key")),
+    },
 }
-STAGES["phase"]["lds"] = dict.fromkeys(STAGES["phase"]["kernels"], 64 * 1024)
+for _stage in ("phase", "relevant"):
+    STAGES[_stage]["lds"] = dict.fromkeys(STAGES[_stage]["kernels"], 64 * 1024)
 
 
 def test_hot_kernels_stay_in_registers():
