@@ -1076,6 +1076,40 @@ po_status po_relevant_copy(po_result* out, uint32_t* cur_aligning, uint32_t* rel
                            uint32_t* aln_b, int32_t* aln_a0, int32_t* aln_a1, uint32_t* b_reads);
 po_status po_get_relevant_stats(const po_handle* h, po_relevant_stats* out);
 
+/* ---- SPELLING: the sequences of graph paths out of the reads the handle holds (phasm_amd/csrc/spell.hip.h) ----
+ * What AssemblyGraph.sequence_for_path and SequenceSource.get_sequence of the reference return, once the caller has reduced
+ * every path to PIECES: piece p = (piece_read[p], piece_take[p]) stands for the first piece_take[p] bytes of oriented read
+ * piece_read[p] as it was added (po_add_sequence, po_add_fasta), 0 <= take <= the read's length.  Sequence s is the
+ * concatenation of the pieces seq_off[s] .. seq_off[s + 1] - 1, with ASCII a-z as A-Z and every other byte unchanged.  The
+ * arrays are host memory; seq_off has n_seqs + 1 entries, begins with 0, ascends and ends with n_pieces. */
+typedef struct {
+    uint64_t n_seqs, n_pieces;
+    const uint64_t* seq_off;
+    const uint32_t* piece_read;
+    const uint32_t* piece_take;
+} po_spell_input;
+
+typedef struct {
+    uint64_t n_seqs, n_pieces, n_bytes;
+    uint64_t n_patched;   /* exception records of a 2-bit store that lay inside a piece */
+    float device_ms;      /* upload of the pieces, scan, decode and patch; not the copy of the bytes to the host */
+    uint32_t reserved;
+} po_spell_stats;
+
+/* po_spell uploads the reads first if the read set changed since the last upload; the bytes stay on the device with the
+ * result, which is of a kind of its own and freed with po_result_free.  po_spell_sizes gives the number of sequences and of
+ * bytes; po_spell_copy the n_seqs + 1 byte offsets of the sequences and the first min(cap, n_bytes) bytes, all sequences back
+ * to back; either array may be NULL.  Zero sequences, zero pieces and sequences of zero bytes are valid.
+ * Rejections, checked on the host before the device is touched (*out stays NULL): PO_ERR_INVALID for a NULL argument, a read
+ * id >= po_num_sequences, a take greater than the read's length, a seq_off that does not begin with 0, ascend and end with
+ * n_pieces, and a handle whose sequences were added by po_add_segment or po_add_gfa (lengths, no bases); PO_ERR_CAPACITY for
+ * more than 2^32 - 16 bytes or 2^32 - 2 pieces in one call: the caller splits the call.  Offsets are 64-bit throughout.
+ * There is no CPU fallback: without a GPU a valid call returns PO_ERR_HIP. */
+po_status po_spell(po_handle* h, const po_spell_input* in, po_result** out);
+po_status po_spell_sizes(const po_result* out, uint64_t* n_seqs, uint64_t* n_bytes);
+po_status po_spell_copy(po_result* out, uint64_t* seq_byte_off, uint8_t* bytes, uint64_t cap);
+po_status po_get_spell_stats(const po_handle* h, po_spell_stats* out);
+
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the
  * device, each violation PO_ERR_INVALID with a message: u, v < po_num_sequences; node_order entries in range and

@@ -277,6 +277,19 @@ class PoRelevantStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class PoSpellInput(ctypes.Structure):
+    _fields_ = [("n_seqs", ctypes.c_uint64), ("n_pieces", ctypes.c_uint64), ("seq_off", ctypes.c_void_p), ("piece_read", ctypes.c_void_p),
+                ("piece_take", ctypes.c_void_p)]
+
+
+class PoSpellStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_seqs", "n_pieces", "n_bytes", "n_patched")] + \
+               [("device_ms", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -400,6 +413,10 @@ SYMBOLS = [
     ("po_relevant_sizes", ctypes.c_int, [_P, ctypes.POINTER(PoRelevantDims)]),
     ("po_relevant_copy", ctypes.c_int, [_P] + [ctypes.c_void_p] * 8),
     ("po_get_relevant_stats", ctypes.c_int, [_P, ctypes.POINTER(PoRelevantStats)]),
+    ("po_spell", ctypes.c_int, [_P, ctypes.POINTER(PoSpellInput), ctypes.POINTER(_P)]),
+    ("po_spell_sizes", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_spell_copy", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    ("po_get_spell_stats", ctypes.c_int, [_P, ctypes.POINTER(PoSpellStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

@@ -317,6 +317,32 @@ def chain_components(args) -> int:
     return 0
 
 
+def spell_contigs(args) -> int:
+    """Per graph file one FASTA entry, named after the file: what the no-bubble branch of the reference's ``phase`` writes
+    (phasm/cli/assembler.py:368-383).  The reads go on the handle once, all files are spelled in one device call."""
+    from . import spelling
+    graphs = []
+    for path in args.graph_gfa:
+        with open(path) as f:
+            graphs.append((path, gfa.read_graph_gfa(f)))
+    overlapper = ExactOverlapper(device=getattr(args, "device", None))
+    overlapper.add_fasta(args.fasta_input, both_strands=True)
+    reads_of = spelling.ReadMap.of(overlapper)
+    piece_lists = []
+    for path, gf in graphs:
+        try:
+            piece_lists.append(spelling.contig_pieces(gf, reads_of))
+        except (ValueError, KeyError) as e:
+            raise SystemExit("%s: %s (a graph with bubbles needs `phase`)" % (path, e.args[0] if e.args else e))
+    logger.info("Spelling %d contigs of %d pieces on the GPU...", len(piece_lists), sum(map(len, piece_lists)))
+    seqs = spelling.spell_pieces(overlapper, piece_lists)
+    for (path, _), seq in zip(graphs, seqs):
+        args.output.write(b">" + spelling.contig_name(path).encode("utf-8") + b"\n" + seq + b"\n")
+    args.output.flush()
+    overlapper.close()
+    return len(seqs)
+
+
 def main(argv=None) -> int:
     parser = argparse.ArgumentParser(prog="phasm-amd", description="MI355X-native PHASM overlap step")
     parser.add_argument("-v", "--verbose", action="count", default=0)
@@ -418,6 +444,15 @@ def main(argv=None) -> int:
     m.add_argument("--device", type=int, default=None)
     m.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
     m.set_defaults(func=chain_components, bubblechains=True, contigs=True, min_nodes=1, superbubbles=False, partitions=False, as_chain=True)
+    sc = sub.add_parser("spell-contigs", help="Per graph file that is one simple path (or one node) its sequence as one FASTA entry "
+                                              "named after the file: the no-bubble branch of `phasm phase`.  The line format is "
+                                              "this tool's own (`>name`, then the sequence on ONE line): the reference writes through "
+                                              "dinopy, whose line width is not pinned here.")
+    sc.add_argument("-o", "--output", type=argparse.FileType("wb"), required=True, help="the FASTA file to write")
+    sc.add_argument("--device", type=int, default=None)
+    sc.add_argument("fasta_input", help="the reads (FASTA); both strands go on the handle, as `overlap` adds them")
+    sc.add_argument("graph_gfa", nargs="+", help="graph files (S, F and E lines), each one simple path or a single node")
+    sc.set_defaults(func=spell_contigs)
     args = parser.parse_args(argv)
     if not getattr(args, "func", None):
         parser.print_help()

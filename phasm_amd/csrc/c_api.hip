@@ -48,6 +48,7 @@
 #include "contigs.hip.h"
 #include "phase.hip.h"
 #include "relevant.hip.h"
+#include "spell.hip.h"
 
 namespace {
 
@@ -91,17 +92,21 @@ enum { FB_CNT, FB_HIST, FB_LEVELS, FB_OM, FB_ALNOFF, FB_ALNB, FB_A0, FB_A1, FB_P
 // three lists, count / offset / overlap_max per relevant read, the alignments
 enum { XB_CNT, XB_DEG, XB_CUR, XB_TMP, XB_EX, XB_LISTS, XB_BITS, XB_WCNT, XB_WRANK, XB_CA, XB_REL, XB_B, XB_ALNCNT, XB_ALNOFF, XB_OM,
        XB_ALNB, XB_A0, XB_A1, XB_N };
+// workspaces of po_spell (spell.hip.h): the uploaded input (seq_off, piece_read, piece_take behind one another), the 32-bit scan
+// of the takes, the 64-bit offsets of the pieces and of the sequences
+enum { SB_IN, SB_SCAN, SB_POFF, SB_SOFF, SB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 81;
+constexpr int EV_LAY_N = 83;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
        EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
-       EV_RELEVANT = 77 };
+       EV_RELEVANT = 77, EV_SPELL = 81 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
 static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
 static_assert(EV_PHASE_INDEX + 4 == EV_RELEVANT, "po_phase_index has four events");
-static_assert(EV_RELEVANT + 4 == EV_LAY_N, "the four events of po_phase_relevant are the last of the layout events");
+static_assert(EV_RELEVANT + 4 == EV_SPELL, "po_phase_relevant has four events");
+static_assert(EV_SPELL + 2 == EV_LAY_N, "the two events of po_spell are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -308,6 +313,7 @@ struct po_handle {
     DevBuf spare_cands;  // 50-170 MB buffer costs ~0.2 ms each and synchronises the device)
     DevBuf spare_edges;
     DevBuf spare_nrank;   // the node-order buffer of the last edge result that was freed (po_result::d_nrank)
+    DevBuf spare_spell;   // the byte buffer of the last po_spell result that was freed
     HostBuf spare_host;    // pinned row buffer of a freed result, kept for the next po_result_rows
     HostBuf scratch_host;  // pinned landing zone for small device->host copies into caller memory
     // pinned result pool sized while the reads are added (result_pool_grow): bytes of total_bases it was sized for
@@ -467,6 +473,9 @@ struct po_handle {
     DevBuf d_rr[XB_N];
     po_phase_index_stats pxstats = {};
     po_relevant_stats rvstats = {};
+    // the sequences of graph paths out of the resident reads (po_spell, spell.hip.h)
+    DevBuf d_sp[SB_N];
+    po_spell_stats spstats = {};
 };
 
 struct po_result {
@@ -509,6 +518,9 @@ struct po_result {
     po_relevant_dims rv = {};
     std::vector<uint32_t> rv_ca, rv_rel, rv_alnoff, rv_alnb, rv_b;
     std::vector<int32_t> rv_om, rv_a0, rv_a1;
+    // po_spell (special == 3): d_rows holds the bytes of all sequences back to back (padded to whole 16-byte chunks), sp_off
+    // the n_seqs + 1 byte offsets of the sequences
+    std::vector<uint64_t> sp_off;
     bool compact = false;   // (inside po_overlaps_to_host only) d_rows holds the verified-candidate records of `count` ROWS
 };
 
@@ -5006,6 +5018,103 @@ po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_p
     return PO_OK;
 }
 
+// ---- the sequences of graph paths (po_spell): pieces (oriented read, take) -> the bytes of every sequence ------------------
+
+// What po_spell refuses, checked on the host before the device is touched: "" when the input is a valid one.  *n_bytes gets
+// the sum of the takes, *n_patched the exception records that lie inside a piece.
+std::string spell_check(const po_handle* h, const po_spell_input& in, uint64_t* n_bytes, uint64_t* n_patched) {
+    const std::string name = "po_spell: ";
+    *n_bytes = *n_patched = 0;
+    if (h->segments_only) return name + "the sequences of this handle were added by po_add_segment: they have lengths and no bases";
+    if (!in.seq_off || (in.n_pieces && (!in.piece_read || !in.piece_take))) return name + "an input array is missing";
+    if (in.seq_off[0] != 0 || in.seq_off[in.n_seqs] != in.n_pieces) return name + "seq_off does not run from 0 to n_pieces";
+    for (uint64_t s = 0; s < in.n_seqs; ++s)
+        if (in.seq_off[s] > in.seq_off[s + 1]) return name + "seq_off is not ascending at sequence " + std::to_string(s);
+    const uint64_t n_reads = h->len.size();
+    const bool exc = h->bits == 2 && !h->exc_pos.empty();
+    for (uint64_t p = 0; p < in.n_pieces; ++p) {
+        const uint32_t r = in.piece_read[p], take = in.piece_take[p];
+        if (r >= n_reads) return name + "piece " + std::to_string(p) + " names read " + std::to_string(r) + ", the handle holds " + std::to_string(n_reads);
+        if (take > h->len[r])
+            return name + "piece " + std::to_string(p) + " takes " + std::to_string(take) + " bytes of a read of " + std::to_string(h->len[r]);
+        *n_bytes += take;
+        if (exc && h->exc_off[r] != h->exc_off[r + 1]) {
+            const uint32_t* e0 = h->exc_pos.data() + h->exc_off[r];
+            *n_patched += (uint64_t)(std::lower_bound(e0, h->exc_pos.data() + h->exc_off[r + 1], take) - e0);
+        }
+    }
+    return "";
+}
+
+constexpr uint64_t SPELL_MAX_BYTES = 0xFFFFFFFFull - 15;   // 2^32 - 16: the scan of the takes is the library's 32-bit one
+
+po_status run_spell(po_handle* h, const po_spell_input& in, uint64_t n_bytes, uint64_t n_patched, po_result* r) {
+    hipStream_t st = h->stream;
+    po_spell_stats& S = h->spstats;
+    S = po_spell_stats();
+    r->special = 3;
+    r->elem = 1;
+    const uint32_t n_seqs = (uint32_t)in.n_seqs, n = (uint32_t)in.n_pieces;
+    if (n) PO_TRY(upload(h));   // (the reads, if they changed since the last upload)
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_SPELL;
+    DevBuf* B = h->d_sp;
+    // the input as one upload out of page-locked memory: [seq_off | piece_read | piece_take]
+    const size_t soff_bytes = ((size_t)n_seqs + 1) * 8, in_bytes = soff_bytes + (size_t)n * 8;
+    const uint64_t n_chunks = (n_bytes + 15) / 16;
+    PO_TRY(ensure_host(h, h->scratch_host, std::max(in_bytes, soff_bytes)));
+    char* land = static_cast<char*>(h->scratch_host.p);
+    std::memcpy(land, in.seq_off, soff_bytes);
+    if (n) {
+        std::memcpy(land + soff_bytes, in.piece_read, (size_t)n * 4);
+        std::memcpy(land + soff_bytes + (size_t)n * 4, in.piece_take, (size_t)n * 4);
+    }
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, B[SB_IN], in_bytes));
+    PO_TRY(ensure(h, B[SB_SCAN], ((size_t)n + 1) * 4));
+    PO_TRY(ensure(h, B[SB_POFF], ((size_t)n + 1) * 8));
+    PO_TRY(ensure(h, B[SB_SOFF], soff_bytes));
+    if (h->spare_spell.p && h->spare_spell.cap >= n_chunks * 16) {
+        r->d_rows = h->spare_spell;
+        h->spare_spell = DevBuf();
+    }
+    PO_TRY(ensure(h, r->d_rows, std::max<size_t>(n_chunks * 16, 256), 1.0, false));
+    const uint64_t* d_seq_off = B[SB_IN].as<uint64_t>();
+    const uint32_t* d_read = reinterpret_cast<const uint32_t*>(B[SB_IN].as<char>() + soff_bytes);
+    const uint32_t* d_take = d_read + n;
+    uint32_t* scan = B[SB_SCAN].as<uint32_t>();
+    uint64_t *poff = B[SB_POFF].as<uint64_t>(), *soff = B[SB_SOFF].as<uint64_t>();
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    HIP_TRY(h, hipMemcpyAsync(B[SB_IN].p, land, in_bytes, hipMemcpyHostToDevice, st));
+    PO_TRY(prefix_sum<uint32_t>(h, d_take, n, scan, &h->pinned[2]));
+    hipLaunchKernelGGL(po::k_spell_offsets, dim3(stride_grid(h, (uint64_t)std::max(n, n_seqs) + 1)), dim3(256), 0, st, n ? scan : nullptr, n, d_seq_off,
+                       n_seqs, poff, soff);
+    if (n_chunks) {
+        const uint64_t* words = h->d_words.as<uint64_t>();
+        const uint64_t* woff = h->d_woff.as<uint64_t>();
+        po::SpellChunk* out = r->d_rows.as<po::SpellChunk>();
+        const dim3 grid(stride_grid(h, n_chunks));
+        hipLaunchKernelGGL(po::k_spell_decode, grid, dim3(256), 0, st, words, woff, (uint32_t)h->bits, d_read, d_take, poff, n, 0ull, n_chunks, out);
+        if (h->bits == 2 && h->n_exc_uploaded)
+            hipLaunchKernelGGL(po::k_spell_patch, dim3(stride_grid(h, n)), dim3(256), 0, st, d_read, d_take, poff, n, h->d_exc_off.as<uint32_t>(),
+                               h->d_exc_pos.as<uint32_t>(), h->d_exc_byte.as<uint8_t>(), 0ull, n_chunks * 16, r->d_rows.as<uint8_t>());
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    // (the input has left the landing zone: the stream is in order)
+    HIP_TRY(h, hipMemcpyAsync(land, soff, soff_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    r->sp_off.assign(reinterpret_cast<const uint64_t*>(land), reinterpret_cast<const uint64_t*>(land) + n_seqs + 1);
+    if ((n && h->pinned[2] != n_bytes) || r->sp_off[0] != 0 || r->sp_off[n_seqs] != n_bytes)
+        return fail(h, PO_ERR_HIP, "internal: the offsets of po_spell do not add up");
+    S.n_seqs = n_seqs;
+    S.n_pieces = n;
+    S.n_bytes = n_bytes;
+    S.n_patched = n_patched;
+    (void)hipEventElapsedTime(&S.device_ms, ev[0], ev[1]);
+    return PO_OK;
+}
+
 // ---- what the po_layout_* entry points share ------------------------------------------------------------------------
 
 // Everything an edge-producing entry point does behind its checks: `run(result)` fills a new result of handle h, which
@@ -5463,7 +5572,7 @@ void po_destroy(po_handle* h) {
                           &h->d_table, &h->d_slot_cnt, &h->d_slot_cur, &h->d_slot_start, &h->d_read_slot, &h->d_chain,
                           &h->d_chain_tmp, &h->d_long_list, &h->d_entry_off, &h->d_bloom, &h->d_selfrep, &h->d_tile_count, &h->d_tile_off,
                           &h->d_ps_blocks, &h->d_scalars, &h->d_cand_a, &h->d_cand_p, &h->d_cand_b, &h->d_type,
-                          &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key, &h->d_pair_min, &h->spare_rows, &h->spare_cands, &h->spare_edges, &h->spare_nrank,
+                          &h->d_rowcnt, &h->d_row_off, &h->d_flag, &h->d_pair_key, &h->d_pair_min, &h->spare_rows, &h->spare_cands, &h->spare_edges, &h->spare_nrank, &h->spare_spell,
                           &h->d_vlabel, &h->d_vrank, &h->d_vperm, &h->d_end_a, &h->d_end_b, &h->d_dpcnt, &h->d_lay_len, &h->d_lay_cnt, &h->d_rflag, &h->d_removed, &h->d_ekey, &h->d_ecnt,
                           &h->d_ewin, &h->d_eoff, &h->d_chain_state, &h->d_tail_state, &h->d_efirst, &h->d_lay_firstc};
         // every stream idle before anything the device (or a copy) may still touch is given back
@@ -5483,6 +5592,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_ct) b.release();
         for (DevBuf& b : h->d_ph) b.release();
         for (DevBuf& b : h->d_rr) b.release();
+        for (DevBuf& b : h->d_sp) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -6778,7 +6888,8 @@ void po_result_free(po_result* r) {
     if (h) {
         --h->live_results;
         // keep the larger buffer for the next call
-        DevBuf* spare = r->elem == sizeof(po_row) ? &h->spare_rows : (r->kind_edges ? &h->spare_edges : &h->spare_cands);
+        DevBuf* spare = r->special == 3 ? &h->spare_spell
+                        : r->elem == sizeof(po_row) ? &h->spare_rows : (r->kind_edges ? &h->spare_edges : &h->spare_cands);
         if (r->d_rows.p && r->d_rows.cap > spare->cap) {
             spare->release();
             *spare = r->d_rows;
@@ -7456,6 +7567,55 @@ po_status po_relevant_copy(po_result* out, uint32_t* cur_aligning, uint32_t* rel
 }
 
 po_status po_get_relevant_stats(const po_handle* h, po_relevant_stats* out) { return get_stats(h, &po_handle::rvstats, out); }
+
+po_status po_spell(po_handle* h, const po_spell_input* in, po_result** out) {
+    if (!h) return PO_ERR_INVALID;
+    if (!out) return fail(h, PO_ERR_INVALID, "po_spell: no room for the result");
+    *out = nullptr;
+    if (!in) return fail(h, PO_ERR_INVALID, "po_spell: no input");
+    if (in->n_pieces >= 0xFFFFFFFFull || in->n_seqs >= 0xFFFFFFFFull)
+        return fail(h, PO_ERR_CAPACITY, "po_spell: more than 2^32 - 2 pieces or sequences in one call");
+    uint64_t n_bytes = 0, n_patched = 0;
+    const std::string said = spell_check(h, *in, &n_bytes, &n_patched);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    // (decided from the host's sum, before anything is allocated: the caller splits the call)
+    if (n_bytes > SPELL_MAX_BYTES)
+        return fail(h, PO_ERR_CAPACITY, "po_spell: " + std::to_string(n_bytes) + " bytes in one call, at most 2^32 - 16");
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return new_edge_result(h, "po_spell", out, [&](po_result* r) { return run_spell(h, *in, n_bytes, n_patched, r); });
+}
+
+po_status po_spell_sizes(const po_result* out, uint64_t* n_seqs, uint64_t* n_bytes) {
+    if (!out || !n_seqs || !n_bytes) return PO_ERR_INVALID;
+    if (out->special != 3) return fail(out->h, PO_ERR_INVALID, "po_spell_sizes needs the result of po_spell");
+    *n_seqs = out->sp_off.size() - 1;
+    *n_bytes = out->sp_off.back();
+    return PO_OK;
+}
+
+po_status po_spell_copy(po_result* out, uint64_t* seq_byte_off, uint8_t* bytes, uint64_t cap) {
+    if (!out) return PO_ERR_INVALID;
+    po_handle* h = out->h;
+    if (out->special != 3) return fail(h, PO_ERR_INVALID, "po_spell_copy needs the result of po_spell");
+    if (seq_byte_off) std::memcpy(seq_byte_off, out->sp_off.data(), out->sp_off.size() * 8);
+    const uint64_t n_give = bytes ? std::min<uint64_t>(cap, out->sp_off.back()) : 0;
+    if (!n_give) return PO_OK;
+    // through the page-locked landing zone, 64 MB at a time
+    constexpr uint64_t STEP = 64ull << 20;
+    return guarded_run(h, "po_spell_copy", [&] {
+        PO_TRY(ensure_host(h, h->scratch_host, (size_t)std::min(n_give, STEP)));
+        for (uint64_t at = 0; at < n_give; at += STEP) {
+            const size_t k = (size_t)std::min(STEP, n_give - at);
+            HIP_TRY(h, hipMemcpyAsync(h->scratch_host.p, out->d_rows.as<char>() + at, k, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            std::memcpy(bytes + at, h->scratch_host.p, k);
+        }
+        return PO_OK;
+    });
+}
+
+po_status po_get_spell_stats(const po_handle* h, po_spell_stats* out) { return get_stats(h, &po_handle::spstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

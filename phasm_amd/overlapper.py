@@ -25,8 +25,9 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats
+from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats, PoSpellInput, PoSpellStats
 from .phasing import RelevantReads
+from .spelling import spell_arrays
 
 OverlapT = Tuple[str, str, int, int, int, int]
 
@@ -693,6 +694,34 @@ class ExactOverlapper:
 
     def relevant_stats(self) -> dict:
         return self._stats(self._lib.po_get_relevant_stats, PoRelevantStats)
+
+    def spell(self, seq_off, piece_read, piece_take) -> List[bytes]:
+        """``po_spell``: the sequences of pieces ``(oriented read, take)`` out of the reads on the device (phasm_amd/spelling.py
+        builds the pieces of graph paths).  Sequence s is the concatenation, over the pieces ``seq_off[s]:seq_off[s + 1]``, of
+        the first ``take`` bytes of the read, a-z upper-cased.  More than 2^32 - 16 bytes in one call: OverflowError (split
+        the call); anything else that is refused: ValueError."""
+        seq_off, piece_read, piece_take = spell_arrays(seq_off, piece_read, piece_take)
+        inp = PoSpellInput(len(seq_off) - 1, len(piece_read), seq_off.ctypes.data, piece_read.ctypes.data if len(piece_read) else None,
+                           piece_take.ctypes.data if len(piece_take) else None)
+        r = ctypes.c_void_p()
+        st = self._lib.po_spell(self._h, ctypes.byref(inp), ctypes.byref(r))
+        if st == _lib.PO_ERR_CAPACITY:
+            msg = self._lib.po_last_error(self._h)
+            raise OverflowError(msg.decode("utf-8", "replace") if msg else "po_spell: too many bytes in one call")
+        _check(self._h, st)
+        try:
+            n_seqs, n_bytes = ctypes.c_uint64(), ctypes.c_uint64()
+            _check(self._h, self._lib.po_spell_sizes(r, ctypes.byref(n_seqs), ctypes.byref(n_bytes)))
+            off = np.zeros(int(n_seqs.value) + 1, dtype=np.uint64)
+            data = np.zeros(int(n_bytes.value), dtype=np.uint8)
+            _check(self._h, self._lib.po_spell_copy(r, _ptr(off), _ptr(data), len(data)))
+        finally:
+            self._lib.po_result_free(r)
+        blob, off = data.tobytes(), off.tolist()
+        return [blob[off[s]:off[s + 1]] for s in range(len(off) - 1)]
+
+    def spell_stats(self) -> dict:
+        return self._stats(self._lib.po_get_spell_stats, PoSpellStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:
