@@ -7,6 +7,7 @@ import pytest
 
 import checker as ck
 import golden_utils as gu
+import spell_store_utils as ssu
 from oracle import overlap_oracle as oo   # row helpers only
 from phasm_amd.overlapper import ExactOverlapper
 
@@ -218,6 +219,8 @@ def test_other_entry_points_after_a_streamed_step(monkeypatch):
         assert ov.stats()["streamed"] == 1
         ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(res.rows_view())), want, seqs, m, "%s streamed" % name)
         res.free()
+        whole = ssu.whole_reads_call(seqs)   # po_spell: the byte-for-byte read-back of the store the streamed step left
+        assert ov.spell(*whole) == ssu.plain_spell(seqs, *whole), "%s spell after streamed" % name
         res = ov.overlaps_result(m)
         st = ov.stats()
         ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(res.rows())), want, seqs, m, "%s resident after streamed" % name)
@@ -231,6 +234,7 @@ def test_other_entry_points_after_a_streamed_step(monkeypatch):
         parts = np.concatenate([ov.overlaps_shard_array(m, k, 3) for k in range(3)])
         ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(parts)), want, seqs, m, "%s shards after streamed" % name)
         ck.assert_same_rows(oo.sort_rows(oo.struct_to_rows(ov.overlaps_ex_array(m, 0, 0))), want, seqs, m, "%s DP after streamed" % name)
+        assert ov.spell(*whole) == ssu.plain_spell(seqs, *whole), "%s spell after the DP call" % name
         if name == "ladder_varlen":
             _modes_after_the_dp_call(ov, seqs, m, want, monkeypatch)
         ov.close()

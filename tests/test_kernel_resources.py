@@ -150,6 +150,18 @@ STAGES = {
                          "k_rr_count", "k_rr_select", "k_rr_list", "k_rr_alncount", "k_rr_alnwrite", "k_rr_omax"),
                         (64, "one thread or one wave per item: a few indices, one entry {b, a0, a1, seq}, one 64-bit key")),
     },
+    "spell": {     # po_spell (phasm_amd/csrc/spell.hip.h)
+        "exact": True, "family": "k_spell_",
+        "why": "k_spell_decode is bound by the latency of its dependent loads -- the binary search over the piece offsets, then the "
+               "read's offset, then its words -- which only resident waves hide; it holds 16 output bytes and a few counters per "
+               "lane and needs neither LDS nor scratch.",
+        "kernels": {
+            "k_spell_offsets": (64, "8 waves per SIMD"),
+            "k_spell_decode": (64, "same"),
+            "k_spell_patch": (64, "same"),
+        },
+        "lds": {"k_spell_offsets": 0, "k_spell_decode": 0, "k_spell_patch": 0},
+    },
 }
 for _stage in ("phase", "relevant"):
     STAGES[_stage]["lds"] = dict.fromkeys(STAGES[_stage]["kernels"], 64 * 1024)

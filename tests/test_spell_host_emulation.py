@@ -1,13 +1,15 @@
 """The kernels of po_spell compiled for the HOST (tools/spell_host_emu.cpp: threads one after another) against the goldens, with
 AddressSanitizer + UBSan: the search for a chunk's piece, the walk over short and empty pieces, the words a fetch loads (the
 emulator's store has no byte behind a read's guard word to spare), the letters, the upper-casing in the word, the bound of the
-patch, launched as c_api.hip launches them, checked without a GPU.  The program is a stand-alone executable run as a
+patch, launched as c_api.hip launches them, checked without a GPU; and against plain Python slicing on the sweep and the odd
+bytes of tests/spell_store_utils.py.  The program is a stand-alone executable run as a
 subprocess on a case file; every loop is bounded: a subprocess that runs into its timeout fails the test."""
 import subprocess
 
 import pytest
 
 import emu_utils
+import spell_store_utils as ssu
 import spell_utils as su
 from phasm_amd import spelling
 
@@ -82,3 +84,36 @@ def test_offsets_just_below_and_beyond_2_to_the_32(emu, tmp_path, bits):
                                first_byte=first, n_out=64, offsets=off)
     assert off[1] < 2**32 < off[5] and soff == [off[0], off[-1]]
     assert blob == want[first - start:first - start + 64]
+
+
+# ---- against plain slicing: the sweep and the odd bytes (tests/spell_store_utils.py) -----------------------------------------
+
+def emu_spelled(emu, tmp_path, reads, call, bits):
+    seq_off, pr, pt = call
+    head, soff, blob = run_emu(emu, tmp_path, reads, seq_off, pr, pt, bits=bits)
+    return head, [blob[soff[i]:soff[i + 1]] for i in range(len(soff) - 1)]
+
+
+@pytest.mark.parametrize("bits", [2, 8])
+def test_the_sweep_on_host_compiled_kernels(emu, tmp_path, bits):
+    """Output-offset residue x read x take around the 32-base and 8-byte word edges, in both encodings (the whole sweep in
+    one run: a fifth of a second under the sanitizers)."""
+    reads = ssu.edge_reads()
+    call = ssu.sweep_call(reads)
+    want = ssu.plain_spell(reads, *call)
+    head, got = emu_spelled(emu, tmp_path, reads, call, bits)
+    assert (len(want), len(call[1]), head[1]) == ssu.SWEEP_SIZE
+    assert head == [bits, sum(map(len, want)), ssu.count_patched(reads, call[1], call[2], bits)]
+    assert ssu.first_difference(got, want) is None
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["2-bit", "8-bit"])
+def test_the_bytes_next_to_a_z_on_host_compiled_kernels(emu, tmp_path, which):
+    """@ [ ` { 0x80 0xE1 0xFA 0xFF and a z A Z N n as exception records of a 2-bit store (k_spell_patch, spell_upper) and in
+    the words of an 8-bit one (spell_upper8), at the width the library itself would choose for the set."""
+    reads = ssu.odd_bytes_reads()[which]
+    bits = (2, 8)[which]
+    for call in (ssu.whole_reads_call(reads), ssu.random_call(reads, 23)):
+        head, got = emu_spelled(emu, tmp_path, reads, call, 0)
+        assert head[0] == bits and head[2] == ssu.count_patched(reads, call[1], call[2], bits)
+        assert ssu.first_difference(got, ssu.plain_spell(reads, *call)) is None
