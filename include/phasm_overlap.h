@@ -986,7 +986,8 @@ po_status po_get_phase_stats(const po_handle* h, po_phase_stats* out);
  * The relevant reads of a bubble of `phasm phase`: the arrays po_phase_branch takes, from the rows.
  *   _get_read_alignments (phasm/cli/assembler.py:313-328), get_aligning_reads (phasm/phasing.py:541-550), the spanning-read
  *   intersection (phasing.py:263-286), get_relevant_read_info and _get_max_possible_overlap (phasing.py:366-419).
- * Not part of it: the bubble walk itself, all_simple_paths, new_block, the final random.choice, spelling; the outputs of the
+ * Not part of it: the bubble walk itself, new_block, the final random.choice (all_simple_paths, the interior and the exit
+ * predecessors of every bubble: po_phase_paths; spelling: po_spell); the outputs of the
  * gather come to the host (they are bubble-sized), po_phase_branch takes them from there.
  * --------------------------------------------------------------------------------------------- */
 
@@ -1109,6 +1110,90 @@ po_status po_spell(po_handle* h, const po_spell_input* in, po_result** out);
 po_status po_spell_sizes(const po_result* out, uint64_t* n_seqs, uint64_t* n_bytes);
 po_status po_spell_copy(po_result* out, uint64_t* seq_byte_off, uint8_t* bytes, uint64_t cap);
 po_status po_get_spell_stats(const po_handle* h, po_spell_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * What BubbleChainPhaser.phase() of `phasm phase` computes per bubble before it looks at a read (phasm/phasing.py:196-234, 396),
+ * for every top-level bubble of a graph in one call (phasm_amd/csrc/paths.hip.h):
+ *   the order of the bubbles along their chain; networkx.all_simple_paths(g, entrance, exit);
+ *   superbubble_nodes(g, entrance, exit) - {entrance, exit}; the predecessors of the exit with g[p][exit]['weight'].
+ * Not part of it: the walk loop itself, new_block, the final random.choice, the reads of a node (get_all_reads).
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint64_t max_paths;          /* the paths of a bubble are listed iff n_paths <= max_paths; 0: counts only           */
+    uint32_t reserved;           /* must be 0                                                                       */
+} po_paths_params;
+
+#define PO_PATHS_MANY 0xFFFFFFFFFFFFFFFFull   /* n_paths of a bubble with at least 2^64 - 1 paths                  */
+#define PO_PATHS_BARE 1u         /* no interior node: non_branching_bubble drops the bubble, the walk of its chain ends */
+#define PO_PATHS_UNLISTED 2u     /* more than max_paths paths: the count only                                       */
+#define PO_PATHS_SATURATED 4u    /* the count hit PO_PATHS_MANY; implies PO_PATHS_UNLISTED                          */
+
+typedef struct {
+    uint32_t entrance, exit;     /* node ids                                                                        */
+    uint32_t chain, position;    /* as po_layout_bubblechains with min_nodes = 1 numbers them                       */
+    uint32_t n_inside;           /* interior nodes, those of nested bubbles included (n_inside of po_superbubble)   */
+    uint32_t flags;              /* PO_PATHS_*                                                                      */
+    uint64_t n_paths;            /* simple paths from entrance to exit, saturating at PO_PATHS_MANY                 */
+    uint64_t n_path_nodes;       /* nodes of its listed paths together, both ends of each included; 0 when unlisted */
+} po_bubble_paths;               /* 40 bytes                                                                        */
+
+/* what po_paths_sizes gives */
+typedef struct {
+    uint64_t n_bubbles, n_inside_nodes, n_preds, n_listed_paths, n_path_nodes;
+} po_paths_dims;
+
+typedef struct {
+    uint64_t n_nodes, n_edges;   /* of the graph (the nodes: those in its node order)                               */
+    uint64_t n_invalid;          /* edges with an end that is not in the node order (the call fails then)           */
+    uint64_t n_bubbles, n_bare, n_unlisted, n_saturated, n_listed_paths, n_path_nodes;
+    uint64_t max_paths_seen;     /* the greatest n_paths of a bubble                                                */
+    uint64_t max_path_nodes;     /* nodes of the longest listed path                                                */
+    uint64_t n_stray_edges;      /* out-edges of a bubble member that leave U + {t}: 0 by the definition            */
+    uint32_t n_count_rounds;     /* counting rounds, the closing round included                                     */
+    uint32_t n_batches;          /* readbacks of all round loops, those of the stages before included               */
+    float ms_chains, ms_count, ms_list, ms_total;
+} po_paths_stats;
+
+/* `graph` is a graph result of this handle, of the kinds po_layout_bubblechains takes; it stays valid and unchanged.
+ * BUBBLES: every top-level superbubble of the acyclic partitions (the nested == 0 entries of po_layout_superbubbles: what
+ * find_superbubbles(g, report_nested=False) reports), one table entry each, ordered by (chain, position) as
+ * po_layout_bubblechains with min_nodes = 1 defines them: within a chain the order in which phase() visits them.  Nested
+ * bubbles get no entry; their nodes are interior nodes of the top-level bubble around them.  Cyclic partitions stay out.
+ * SUCCESSOR ORDER: the successors of a node are ordered by the position of the edges with that tail in the graph's edge
+ * order (the adjacency order of the networkx graph that gfa2_reconstruct_assembly_graph builds from the E lines).
+ * COUNT: with U the interior of bubble (s, t): cnt[t] = 1, cnt[v] = sum of cnt[w] over the out-edges (v, w) of every v in
+ * U + {s}, in 64 bits, saturating at PO_PATHS_MANY (a sum never wraps); n_paths = cnt[s].  t may enter the next bubble: as
+ * an end its count is 1.
+ * PATH ORDER: path j of a bubble is the j-th in lexicographic order of successor positions -- the index j unranked through
+ * the counts: at v the first successor w with j < cnt[w] once the counts of the successors before it are subtracted.  On a
+ * DAG this is the list networkx.all_simple_paths gives, path for path.  A path is listed with both ends: s, .., t.  The
+ * paths of a bubble are listed iff n_paths <= max_paths and the count is not saturated.
+ * INTERIOR: the nodes strictly inside, ascending in rank of the node order; n_inside of them.
+ * EXIT PREDECESSORS: every edge (p, t) as (p, weight), in the graph's edge order.
+ * PO_PATHS_BARE: n_inside == 0.  The reference's non_branching_bubble drops a bubble iff out_degree(s) == 1, in_degree(t) == 1
+ * and successors(s)[0] == t, and its walk of the chain ends at the first dropped bubble.  The three conditions hold iff the
+ * interior is empty: if the only out-edge of s goes to t, no node is reached from s without passing t; and a superbubble is
+ * closed -- every out-edge of s ends in U + {t}, every in-edge of t starts in U + {s} -- so with U empty s has the one
+ * successor t and t the one predecessor s (an edge (u, v) is in the graph once).  DESIGN.md section 3.9r.
+ * The result is of a kind of its own and stays in HBM until po_result_free.  po_paths_sizes gives the lengths; po_paths_copy
+ * the arrays, any of which may be NULL: bubbles (n_bubbles); inside_off, pred_off, bubble_path_off (n_bubbles + 1 each:
+ * offsets into inside_nodes, into pred_node / pred_weight, and the number of the bubble's first listed path); path_off
+ * (n_listed_paths + 1, offsets into path_nodes).
+ * Limits: as po_layout_bubblechains; and when the paths to list number 2^30 or more, or their nodes together reach 2^31, the
+ * call fails with PO_ERR_CAPACITY and a message and writes nothing -- the first from the counts alone, before anything is
+ * listed.  Device memory beyond the inputs and the result is linear: what po_layout_bubblechains takes plus at most 60 bytes
+ * per node and 32 per edge (two key arrays, padded to a power of two), and 4 bytes per listed path.  The counting rounds are
+ * bounded on the host by the largest n_inside + 2, the walk of a path by n_inside + 1 steps; reaching a bound is PO_ERR_HIP,
+ * never a result.  Only integers are involved: every output is the same on every run.  params may be NULL (max_paths 0).
+ * An empty graph: PO_OK, every size 0.  Rejections, each PO_ERR_INVALID with a message: a row result; a result of another
+ * handle; reserved != 0; out NULL; an edge with an end that is not in the node order (counted in n_invalid).  There is no CPU
+ * fallback: without a GPU a valid call returns PO_ERR_HIP. */
+po_status po_phase_paths(po_handle* h, po_result* graph, const po_paths_params* params, po_result** out);
+po_status po_paths_sizes(const po_result* out, po_paths_dims* dims);
+po_status po_paths_copy(po_result* out, po_bubble_paths* bubbles, uint64_t* inside_off, uint32_t* inside_nodes, uint64_t* pred_off,
+                        uint32_t* pred_node, int32_t* pred_weight, uint64_t* bubble_path_off, uint64_t* path_off, uint32_t* path_nodes);
+po_status po_get_paths_stats(const po_handle* h, po_paths_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

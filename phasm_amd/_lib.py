@@ -39,6 +39,11 @@ SB_ENTRANCE, SB_EXIT, SB_NESTED, SB_SELF_LOOP = 1, 2, 4, 8
 NO_NODE = 0xFFFFFFFF
 # po_bubblechain
 BUBBLECHAIN_DTYPE = np.dtype([("first_entrance", "<u4"), ("last_exit", "<u4"), ("n_bubbles", "<u4"), ("n_nodes", "<u4"), ("n_edges", "<u8")])
+# po_bubble_paths; PO_PATHS_*
+BUBBLE_PATHS_DTYPE = np.dtype([("entrance", "<u4"), ("exit", "<u4"), ("chain", "<u4"), ("position", "<u4"), ("n_inside", "<u4"),
+                               ("flags", "<u4"), ("n_paths", "<u8"), ("n_path_nodes", "<u8")])
+PATHS_BARE, PATHS_UNLISTED, PATHS_SATURATED = 1, 2, 4
+PATHS_MANY = 0xFFFFFFFFFFFFFFFF
 # po_contig
 CONTIG_DTYPE = np.dtype([("first_node", "<u4"), ("last_node", "<u4"), ("n_nodes", "<u4"), ("first_edge", "<u4"), ("length", "<i8")])
 
@@ -290,6 +295,28 @@ class PoSpellStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class PoPathsParams(ctypes.Structure):
+    _fields_ = [("max_paths", ctypes.c_uint64), ("reserved", ctypes.c_uint32)]
+
+
+class PoPathsDims(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_bubbles", "n_inside_nodes", "n_preds", "n_listed_paths", "n_path_nodes")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PoPathsStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+                    "n_nodes", "n_edges", "n_invalid", "n_bubbles", "n_bare", "n_unlisted", "n_saturated", "n_listed_paths", "n_path_nodes",
+                    "max_paths_seen", "max_path_nodes", "n_stray_edges")] + \
+               [(name, ctypes.c_uint32) for name in ("n_count_rounds", "n_batches")] + \
+               [(name, ctypes.c_float) for name in ("ms_chains", "ms_count", "ms_list", "ms_total")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -417,6 +444,10 @@ SYMBOLS = [
     ("po_spell_sizes", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     ("po_spell_copy", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     ("po_get_spell_stats", ctypes.c_int, [_P, ctypes.POINTER(PoSpellStats)]),
+    ("po_phase_paths", ctypes.c_int, [_P, _P, ctypes.POINTER(PoPathsParams), ctypes.POINTER(_P)]),
+    ("po_paths_sizes", ctypes.c_int, [_P, ctypes.POINTER(PoPathsDims)]),
+    ("po_paths_copy", ctypes.c_int, [_P] + [ctypes.c_void_p] * 9),
+    ("po_get_paths_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPathsStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

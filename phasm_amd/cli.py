@@ -317,6 +317,34 @@ def chain_components(args) -> int:
     return 0
 
 
+def bubble_paths_lines(graph, paths, max_bubble_size: int, listing: bool):
+    """The lines of ``bubble-paths``: one per top-level bubble -- chain, position, entrance, exit, interior nodes, paths, and
+    the arm ``phase()`` would take (``bare``: the walk of the chain ends here; ``large``: more than ``max_bubble_size`` paths,
+    ``phase_large_bubble``; ``branch``) --, with ``listing`` behind each listed bubble its paths by segment name."""
+    from .phasing import paths_text
+    yield "#chain\tposition\tentrance\texit\tinterior_nodes\tpaths\tarm\n"
+    for b in range(len(paths)):
+        row = paths.bubbles[b]
+        arm = "bare" if paths.is_bare(b) else "large" if paths.is_large(b, max_bubble_size) else "branch"
+        yield "%d\t%d\t%s\t%s\t%d\t%s\t%s\n" % (row["chain"], row["position"], graph.node_name(int(row["entrance"])),
+                                               graph.node_name(int(row["exit"])), row["n_inside"], paths_text(row["n_paths"]), arm)
+        if listing and paths.is_listed(b):
+            for j, p in enumerate(paths.paths_of(b)):
+                yield "P\t%d\t%d\t%d\t%s\n" % (row["chain"], row["position"], j, ",".join(graph.node_name(n) for n in p))
+
+
+def bubble_paths(args) -> int:
+    """What ``BubbleChainPhaser.phase()`` computes per bubble before it looks at a read, for every top-level bubble of a graph
+    file in one device call: the paths are counted there, and listed only with --list and only up to MAX_BUBBLE_SIZE."""
+    from . import layout
+    graph, paths, stats = layout.graph_file_bubble_paths(args.graph_gfa, args.max_bubble_size if args.list else 0, device=args.device)
+    logger.info("%d top-level bubbles (%d bare, %d with more than %d paths); %d paths listed; %.3f ms on the device.", stats["n_bubbles"],
+                stats["n_bare"], sum(paths.is_large(b, args.max_bubble_size) for b in range(len(paths))), args.max_bubble_size,
+                stats["n_listed_paths"], stats["ms_total"])
+    args.output.writelines(bubble_paths_lines(graph, paths, args.max_bubble_size, args.list))
+    return len(paths)
+
+
 def spell_contigs(args) -> int:
     """Per graph file one FASTA entry, named after the file: what the no-bubble branch of the reference's ``phase`` writes
     (phasm/cli/assembler.py:368-383).  The reads go on the handle once, all files are spelled in one device call."""
@@ -453,6 +481,17 @@ def main(argv=None) -> int:
     sc.add_argument("fasta_input", help="the reads (FASTA); both strands go on the handle, as `overlap` adds them")
     sc.add_argument("graph_gfa", nargs="+", help="graph files (S, F and E lines), each one simple path or a single node")
     sc.set_defaults(func=spell_contigs)
+    # -b as `phasm phase` names it (assembler.py)
+    bp = sub.add_parser("bubble-paths", help="Per top-level bubble of a graph file what `phasm phase` computes before it looks at a "
+                                             "read: chain, position, entrance, exit, interior nodes, the number of simple paths, "
+                                             "and the arm phase() would take, as TSV.")
+    bp.add_argument("-b", "--max-bubble-size", type=_int_in(0, 2**64 - 1), default=10,
+                    help="a bubble with more paths is `large` and its paths are not listed (default: 10)")
+    bp.add_argument("--list", action="store_true", help="also the paths of every bubble that is not large, by segment name (P lines)")
+    bp.add_argument("-o", "--output", type=argparse.FileType("w"), default=sys.stdout)
+    bp.add_argument("--device", type=int, default=None)
+    bp.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
+    bp.set_defaults(func=bubble_paths)
     args = parser.parse_args(argv)
     if not getattr(args, "func", None):
         parser.print_help()

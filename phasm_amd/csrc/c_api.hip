@@ -49,6 +49,7 @@
 #include "phase.hip.h"
 #include "relevant.hip.h"
 #include "spell.hip.h"
+#include "paths.hip.h"
 
 namespace {
 
@@ -95,18 +96,27 @@ enum { XB_CNT, XB_DEG, XB_CUR, XB_TMP, XB_EX, XB_LISTS, XB_BITS, XB_WCNT, XB_WRA
 // workspaces of po_spell (spell.hip.h): the uploaded input (seq_off, piece_read, piece_take behind one another), the 32-bit scan
 // of the takes, the 64-bit offsets of the pieces and of the sequences
 enum { SB_IN, SB_SCAN, SB_POFF, SB_SOFF, SB_N };
+// workspaces of po_phase_paths (paths.hip.h) beyond those of the rank scaffold and of the three stages that
+// po_layout_bubblechains runs: counters, bubbles per chain and their offsets, home / bubble number / done word / count per rank,
+// entrance per bubble, the two sorted key arrays of the edges, first and last place of every tail and of every head, the three
+// counts per bubble, the length of every listed path
+enum { QB_CNT, QB_NB, QB_COFF, QB_HOME, QB_BIDX, QB_BENT, QB_DONE, QB_COUNT, QB_KEYOUT, QB_KEYIN, QB_OFIRST, QB_OLAST, QB_IFIRST, QB_ILAST,
+       QB_NLIST, QB_NPRED, QB_NIN, QB_PLEN, QB_N };
+// what a po_phase_paths result holds in HBM (po_result::d_pp): the table, the three CSR pairs, the offsets of the paths
+enum { PR_TABLE, PR_INOFF, PR_INNODES, PR_PREDOFF, PR_PREDNODE, PR_PREDW, PR_BPO, PR_POFF, PR_PATHS, PR_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 83;
+constexpr int EV_LAY_N = 94;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
        EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
-       EV_RELEVANT = 77, EV_SPELL = 81 };
+       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
 static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
 static_assert(EV_PHASE_INDEX + 4 == EV_RELEVANT, "po_phase_index has four events");
 static_assert(EV_RELEVANT + 4 == EV_SPELL, "po_phase_relevant has four events");
-static_assert(EV_SPELL + 2 == EV_LAY_N, "the two events of po_spell are the last of the layout events");
+static_assert(EV_SPELL + 2 == EV_PATHS, "po_spell has two events");
+static_assert(EV_PATHS + 11 == EV_LAY_N, "the eleven events of po_phase_paths are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -476,6 +486,9 @@ struct po_handle {
     // the sequences of graph paths out of the resident reads (po_spell, spell.hip.h)
     DevBuf d_sp[SB_N];
     po_spell_stats spstats = {};
+    // paths, interior and exit predecessors of every top-level bubble (po_phase_paths, paths.hip.h)
+    DevBuf d_pp[QB_N];
+    po_paths_stats ppstats = {};
 };
 
 struct po_result {
@@ -521,6 +534,9 @@ struct po_result {
     // po_spell (special == 3): d_rows holds the bytes of all sequences back to back (padded to whole 16-byte chunks), sp_off
     // the n_seqs + 1 byte offsets of the sequences
     std::vector<uint64_t> sp_off;
+    // po_phase_paths (special == 4): everything stays in HBM (d_pp, 32-bit offsets: the call refuses what does not fit them)
+    DevBuf d_pp[PR_N];
+    po_paths_dims pp = {};
     bool compact = false;   // (inside po_overlaps_to_host only) d_rows holds the verified-candidate records of `count` ROWS
 };
 
@@ -2981,6 +2997,7 @@ void release_device(po_result* r) {
     for (DevBuf* b : {&r->d_rows, &r->d_rank, &r->d_nrank, &r->d_moff, &r->d_member, &r->d_prefix, &r->d_mlen, &r->d_ixtable, &r->d_ixval,
                       &r->d_ixoff, &r->d_ixent, &r->d_ixlen})
         b->release();
+    for (DevBuf& b : r->d_pp) b.release();
 }
 
 // the grid of a kernel that strides over n items: eight workgroups of 256 per CU at the most
@@ -4407,6 +4424,177 @@ po_status run_bubblechains(po_handle* h, po_result* graph, uint32_t min_nodes, u
     return PO_OK;
 }
 
+// ---- paths, interior and exit predecessors of every top-level bubble (po_phase_paths, paths.hip.h) ---------------------------
+
+constexpr uint64_t PATHS_MAX_LISTED = 1ull << 30;   // listed paths of one call (each has two nodes at the least)
+constexpr uint64_t PATHS_MAX_NODES = 1ull << 31;    // their nodes together
+
+po_status run_paths(po_handle* h, po_result* graph, uint64_t max_paths, po_result* r) {
+    const char* const name = "po_phase_paths";
+    hipStream_t st = h->stream;
+    po_paths_stats& S = h->ppstats;
+    S = po_paths_stats();
+    r->special = 4;
+    r->elem = 1;
+    r->pp = po_paths_dims();
+    DevBuf* B = h->d_pp;
+    DevBuf* O = r->d_pp;
+    RankedGraph R;
+    BcWork W;
+    uint32_t pad_e = 1;
+    const po_status staged = bubblechain_stage(h, graph, name, EV_PATHS, S, 1u, [&](size_t nn, size_t ne) {
+        pad_e = po::merge_sort_pad((uint32_t)ne);
+        PO_TRY(ensure(h, B[QB_CNT], 128));
+        for (int k : {QB_NB, QB_COFF, QB_HOME, QB_BIDX, QB_BENT, QB_DONE, QB_OFIRST, QB_OLAST, QB_IFIRST, QB_ILAST, QB_NLIST, QB_NPRED, QB_NIN})
+            PO_TRY(ensure(h, B[k], nn * 4));
+        PO_TRY(ensure(h, B[QB_COUNT], nn * 8));
+        for (int k : {QB_KEYOUT, QB_KEYIN}) PO_TRY(ensure(h, B[k], (size_t)pad_e * 8));
+        return PO_OK;
+    }, R, W);
+    S.n_batches = W.n_batches;
+    PO_TRY(staged);
+    if (!R.ev || !R.n_order || !W.n_top) return PO_OK;   // (no bubble: every size 0)
+    const uint32_t n = R.n, n_order = R.n_order, n_chains = (uint32_t)W.n_chains, n_b = (uint32_t)W.n_top;
+    if (!n) return fail(h, PO_ERR_HIP, std::string("internal: ") + name + " found bubbles in a graph without edges");
+    hipEvent_t* ev = R.ev;
+    unsigned long long *cnt = B[QB_CNT].as<unsigned long long>(), *count = B[QB_COUNT].as<unsigned long long>(),
+                       *key_out = B[QB_KEYOUT].as<unsigned long long>(), *key_in = B[QB_KEYIN].as<unsigned long long>(),
+                       *key_inside = h->d_rank[RK_KEY].as<unsigned long long>();   // (the rank sort is over: pad(n_total) words)
+    uint32_t *nb = B[QB_NB].as<uint32_t>(), *coff = B[QB_COFF].as<uint32_t>(), *home = B[QB_HOME].as<uint32_t>(),
+             *bidx = B[QB_BIDX].as<uint32_t>(), *bent = B[QB_BENT].as<uint32_t>(), *done = B[QB_DONE].as<uint32_t>(),
+             *ofirst = B[QB_OFIRST].as<uint32_t>(), *olast = B[QB_OLAST].as<uint32_t>(), *ifirst = B[QB_IFIRST].as<uint32_t>(),
+             *ilast = B[QB_ILAST].as<uint32_t>(), *n_list = B[QB_NLIST].as<uint32_t>(), *n_pred = B[QB_NPRED].as<uint32_t>(),
+             *n_in = B[QB_NIN].as<uint32_t>();
+    const uint32_t *fw = h->d_bc[HB_FW].as<uint32_t>(), *top = h->d_bc[HB_TOP].as<uint32_t>(), *pred = h->d_bc[HB_PRED].as<uint32_t>(),
+                   *chain = h->d_bc[HB_CHAINOUT].as<uint32_t>(), *pos = h->d_bc[HB_BUBBLEOUT].as<uint32_t>(),
+                   *exit_of = h->d_sb[UB_EXIT].as<uint32_t>(), *total = h->d_sb[UB_TOTAL].as<uint32_t>();
+    const po::BubbleChain* chains = h->d_bc[HB_TABLE].as<po::BubbleChain>();
+    const uint32_t pad_n = po::merge_sort_pad(n);   // (<= pad_e)
+    const uint32_t bubble_grid = stride_grid(h, (uint64_t)n_b + 1);
+    volatile uint64_t* C = h->pinned + 48;   // this stage's counters on the host (words 16.. and 32.. are the scaffold's)
+    auto counters_home = [&]() -> po_status {
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 48, cnt, po::QK_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        return PO_OK;
+    };
+    auto sort_keys = [&](unsigned long long* key, uint32_t count_, uint32_t pad) {
+        po::merge_sort_steps(count_, [&](uint32_t j, uint32_t k) {
+            hipLaunchKernelGGL(po::k_pp_bitonic, dim3(stride_grid(h, pad)), dim3(256), 0, st, key, pad, j, k);
+        });
+    };
+    static_assert(sizeof(po_bubble_paths) == sizeof(po::BubblePaths) && sizeof(po_bubble_paths) == 40, "po_bubble_paths is the device's table entry");
+    // the result's table and its three offset arrays: sized by the bubbles
+    PO_TRY(ensure(h, O[PR_TABLE], (size_t)n_b * sizeof(po::BubblePaths), 1.0, false));
+    for (int k : {PR_INOFF, PR_PREDOFF, PR_BPO}) PO_TRY(ensure(h, O[k], ((size_t)n_b + 1) * 4, 1.0, false));
+    po::BubblePaths* table = O[PR_TABLE].as<po::BubblePaths>();
+    uint32_t *in_off = O[PR_INOFF].as<uint32_t>(), *pred_off = O[PR_PREDOFF].as<uint32_t>(), *bpo = O[PR_BPO].as<uint32_t>();
+    // the bubbles numbered by (chain, position); home of every rank; the edges by tail and, into exits, by head
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    hipLaunchKernelGGL(po::k_pp_chain_counts, dim3(stride_grid(h, (uint64_t)n_chains + 1)), dim3(256), 0, st, n_chains, chains, nb);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, nb, (uint64_t)n_chains + 1, coff, &h->pinned[2]));
+    HIP_TRY(h, hipMemsetAsync(bent, 0xFF, (size_t)n_order * 4, st));
+    for (uint32_t* p : {ofirst, olast, ifirst, ilast}) HIP_TRY(h, hipMemsetAsync(p, 0, (size_t)n_order * 4, st));
+    hipLaunchKernelGGL(po::k_pp_bubbles, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_chains, n_b, fw, top, chain, pos, coff, total, home, bidx,
+                       bent, done, count, cnt);
+    hipLaunchKernelGGL(po::k_pp_keys, dim3(stride_grid(h, pad_n)), dim3(256), 0, st, R.ends, n, n_order, pad_n, home, exit_of, pred, key_out, key_in,
+                       cnt);
+    sort_keys(key_out, n, pad_n);
+    sort_keys(key_in, n, pad_n);
+    hipLaunchKernelGGL(po::k_pp_segments, dim3(R.edge_grid), dim3(256), 0, st, key_out, n, n_order, ofirst, olast);
+    hipLaunchKernelGGL(po::k_pp_segments, dim3(R.edge_grid), dim3(256), 0, st, key_in, n, n_order, ifirst, ilast);
+    PO_TRY(counters_home());
+    if (h->pinned[2] != n_b || C[po::QK_BAD] || C[po::QK_MAXIN] > n_order)
+        return fail(h, PO_ERR_HIP, std::string("internal: the bubbles of ") + name + " do not add up");
+    S.n_bubbles = n_b;
+    S.n_stray_edges = C[po::QK_STRAY];
+    const uint64_t max_inside = C[po::QK_MAXIN];
+    // the counts: a member sums its successors once an earlier launch has finished them all; bounded by round_phase
+    {
+        RoundOps ops{h, st, R.rcnt};
+        uint64_t ignored = 0;
+        uint32_t launch = 0;
+        const int how = po::round_phase(ops, max_inside, [&](uint32_t j) {
+            ++launch;
+            hipLaunchKernelGGL(po::k_pp_count, dim3(R.rank_grid), dim3(256), 0, st, n_order, n, launch, home, exit_of, ofirst, olast, key_out, R.ends,
+                               done, count, R.rcnt + j);
+        }, S.n_count_rounds, S.n_batches, ignored);
+        if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+        if (how != po::ROUNDS_DONE)
+            return fail(h, PO_ERR_HIP, std::string("internal: the counts of ") + name + " reached their bound of the largest n_inside + 2 rounds");
+    }
+    HIP_TRY(h, hipEventRecord(ev[9], st));
+    // the table; how many paths, predecessors and interior nodes every bubble adds, and where they go
+    hipLaunchKernelGGL(po::k_pp_table, dim3(bubble_grid), dim3(256), 0, st, n_b, n_order, (unsigned long long)max_paths, bent, exit_of, R.val, chain,
+                       pos, total, count, ifirst, ilast, table, n_list, n_pred, n_in, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, n_list, (uint64_t)n_b + 1, bpo, &h->pinned[2]));
+    PO_TRY(prefix_sum<uint32_t>(h, n_pred, (uint64_t)n_b + 1, pred_off, &h->pinned[3]));
+    PO_TRY(prefix_sum<uint32_t>(h, n_in, (uint64_t)n_b + 1, in_off, &h->pinned[4]));
+    PO_TRY(counters_home());
+    S.n_bare = C[po::QK_BARE];
+    S.n_unlisted = C[po::QK_UNLISTED];
+    S.n_saturated = C[po::QK_SATURATED];
+    S.max_paths_seen = C[po::QK_MAXPATHS];
+    const uint64_t listed64 = C[po::QK_LISTED], preds64 = h->pinned[3], inside64 = h->pinned[4];
+    // (decided from the counts alone, before anything is listed: the caller lowers max_paths)
+    if (listed64 >= PATHS_MAX_LISTED)
+        return fail(h, PO_ERR_CAPACITY, std::string(name) + ": at least " + std::to_string(listed64) + " paths to list in one call, at most 2^30 - 1");
+    if (h->pinned[2] != listed64 || preds64 > n || inside64 > n_order)
+        return fail(h, PO_ERR_HIP, std::string("internal: the offsets of ") + name + " do not add up");
+    const uint32_t n_listed = (uint32_t)listed64, n_preds = (uint32_t)preds64, n_inside = (uint32_t)inside64;
+    PO_TRY(ensure(h, B[QB_PLEN], ((size_t)n_listed + 1) * 4));
+    PO_TRY(ensure(h, O[PR_POFF], ((size_t)n_listed + 1) * 4, 1.0, false));
+    PO_TRY(ensure(h, O[PR_PREDNODE], std::max<size_t>((size_t)n_preds * 4, 256), 1.0, false));
+    PO_TRY(ensure(h, O[PR_PREDW], std::max<size_t>((size_t)n_preds * 4, 256), 1.0, false));
+    PO_TRY(ensure(h, O[PR_INNODES], std::max<size_t>((size_t)n_inside * 4, 256), 1.0, false));
+    uint32_t *plen = B[QB_PLEN].as<uint32_t>(), *poff = O[PR_POFF].as<uint32_t>(), *pred_node = O[PR_PREDNODE].as<uint32_t>(),
+             *inside_nodes = O[PR_INNODES].as<uint32_t>();
+    int32_t* pred_weight = O[PR_PREDW].as<int32_t>();
+    // the predecessors of the exits; the interior of every bubble by (bubble, rank)
+    hipLaunchKernelGGL(po::k_pp_preds, dim3(R.edge_grid), dim3(256), 0, st, n, n_order, n_preds, key_in, R.ends, graph->d_rows.as<po::Edge>(), pred,
+                       bidx, ifirst, pred_off, R.val, pred_node, pred_weight, cnt);
+    const uint32_t pad_o = po::merge_sort_pad(n_order);   // (<= pad(n_total), what RK_KEY holds)
+    hipLaunchKernelGGL(po::k_pp_inside_keys, dim3(stride_grid(h, pad_o)), dim3(256), 0, st, n_order, pad_o, home, bidx, key_inside, cnt);
+    sort_keys(key_inside, n_order, pad_o);
+    if (n_inside) hipLaunchKernelGGL(po::k_pp_inside, dim3(stride_grid(h, n_inside)), dim3(256), 0, st, n_inside, n_order, key_inside, R.val, inside_nodes);
+    // the length of every listed path, their offsets, then the nodes
+    const uint32_t path_grid = stride_grid(h, (uint64_t)n_listed + 1);
+    hipLaunchKernelGGL(po::k_pp_walk<false>, dim3(path_grid), dim3(256), 0, st, n_listed, n_b, n_order, n, 0u, bpo, bent, exit_of, total, home, ofirst,
+                       olast, key_out, R.ends, count, R.val, plen, (const uint32_t*)nullptr, (uint32_t*)nullptr, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, plen, (uint64_t)n_listed + 1, poff, &h->pinned[5]));
+    PO_TRY(counters_home());
+    if (C[po::QK_BAD] || C[po::QK_INSIDE] != n_inside)
+        return fail(h, PO_ERR_HIP, std::string("internal: the interior nodes or the predecessors of ") + name + " do not add up");
+    if (C[po::QK_WALK]) return fail(h, PO_ERR_HIP, std::string("internal: a path of ") + name + " did not reach its exit within n_inside + 1 steps");
+    const uint64_t nodes64 = h->pinned[5];
+    if (nodes64 >= PATHS_MAX_NODES)
+        return fail(h, PO_ERR_CAPACITY, std::string(name) + ": the listed paths hold " + std::to_string(nodes64) + " nodes together, at most 2^31 - 1");
+    if (nodes64 < 2 * listed64 || C[po::QK_MAXLEN] > max_inside + 2)
+        return fail(h, PO_ERR_HIP, std::string("internal: the path lengths of ") + name + " do not add up");
+    const uint32_t n_path_nodes = (uint32_t)nodes64;
+    PO_TRY(ensure(h, O[PR_PATHS], std::max<size_t>((size_t)n_path_nodes * 4, 256), 1.0, false));
+    uint32_t* path_nodes = O[PR_PATHS].as<uint32_t>();
+    if (n_listed)
+        hipLaunchKernelGGL(po::k_pp_walk<true>, dim3(path_grid), dim3(256), 0, st, n_listed, n_b, n_order, n, n_path_nodes, bpo, bent, exit_of, total,
+                           home, ofirst, olast, key_out, R.ends, count, R.val, (uint32_t*)nullptr, poff, path_nodes, cnt);
+    hipLaunchKernelGGL(po::k_pp_bubble_nodes, dim3(stride_grid(h, n_b)), dim3(256), 0, st, n_b, bpo, poff, table);
+    HIP_TRY(h, hipEventRecord(ev[10], st));
+    PO_TRY(counters_home());
+    if (C[po::QK_WALK]) return fail(h, PO_ERR_HIP, std::string("internal: a path of ") + name + " does not fill its row");
+    S.n_listed_paths = n_listed;
+    S.n_path_nodes = n_path_nodes;
+    S.max_path_nodes = C[po::QK_MAXLEN];
+    r->pp = po_paths_dims{n_b, n_inside, n_preds, n_listed, n_path_nodes};
+    (void)hipEventElapsedTime(&S.ms_chains, ev[0], ev[8]);
+    (void)hipEventElapsedTime(&S.ms_count, ev[8], ev[9]);
+    (void)hipEventElapsedTime(&S.ms_list, ev[9], ev[10]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[10]);
+    return PO_OK;
+}
+
 // ---- the contigs outside the bubble chains (po_layout_contigs, contigs.hip.h) ----------------------------------------------
 
 po_status run_contigs(po_handle* h, po_result* graph, uint64_t min_len, uint32_t min_nodes, const uint8_t* exclude_in, uint32_t* contig_out,
@@ -5593,6 +5781,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_ph) b.release();
         for (DevBuf& b : h->d_rr) b.release();
         for (DevBuf& b : h->d_sp) b.release();
+        for (DevBuf& b : h->d_pp) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -7616,6 +7805,70 @@ po_status po_spell_copy(po_result* out, uint64_t* seq_byte_off, uint8_t* bytes, 
 }
 
 po_status po_get_spell_stats(const po_handle* h, po_spell_stats* out) { return get_stats(h, &po_handle::spstats, out); }
+
+po_status po_phase_paths(po_handle* h, po_result* graph, const po_paths_params* params, po_result** out) {
+    const char* const name = "po_phase_paths";
+    if (!h) return PO_ERR_INVALID;
+    if (!out) return fail(h, PO_ERR_INVALID, std::string(name) + ": no room for the result");
+    *out = nullptr;
+    if (!graph) return fail(h, PO_ERR_INVALID, std::string(name) + ": no graph");
+    if (graph->h != h) return fail(h, PO_ERR_INVALID, std::string(name) + ": the graph belongs to another handle");
+    if (params && params->reserved != 0) return fail(h, PO_ERR_INVALID, std::string(name) + ": bad parameters");
+    if (graph->elem != sizeof(po_edge) || !graph->kind_edges)
+        return fail(h, PO_ERR_INVALID, std::string(name) + " needs an edge result, a merged graph or a po_graph_from_edges result");
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return new_edge_result(h, name, out, [&](po_result* r) { return run_paths(h, graph, params ? params->max_paths : 0, r); });
+}
+
+po_status po_paths_sizes(const po_result* out, po_paths_dims* dims) {
+    if (!out || !dims) return PO_ERR_INVALID;
+    if (out->special != 4) return fail(out->h, PO_ERR_INVALID, "po_paths_sizes needs the result of po_phase_paths");
+    *dims = out->pp;
+    return PO_OK;
+}
+
+po_status po_paths_copy(po_result* out, po_bubble_paths* bubbles, uint64_t* inside_off, uint32_t* inside_nodes, uint64_t* pred_off,
+                        uint32_t* pred_node, int32_t* pred_weight, uint64_t* bubble_path_off, uint64_t* path_off, uint32_t* path_nodes) {
+    if (!out) return PO_ERR_INVALID;
+    po_handle* h = out->h;
+    if (out->special != 4) return fail(h, PO_ERR_INVALID, "po_paths_copy needs the result of po_phase_paths");
+    const po_paths_dims& D = out->pp;
+    if (!D.n_bubbles) {   // (nothing on the device: one offset each, 0)
+        for (uint64_t* p : {inside_off, pred_off, bubble_path_off, path_off})
+            if (p) p[0] = 0;
+        return PO_OK;
+    }
+    return guarded_run(h, "po_paths_copy", [&] {
+        hipStream_t st = h->stream;
+        // straight into the caller's arrays; the device holds the offsets in 32 bits: they are widened from a staging copy
+        auto give = [&](void* dst, int k, size_t bytes) -> po_status {
+            if (dst && bytes) HIP_TRY(h, hipMemcpyAsync(dst, out->d_pp[k].p, bytes, hipMemcpyDeviceToHost, st));
+            return PO_OK;
+        };
+        const size_t nb1 = (size_t)D.n_bubbles + 1, np1 = (size_t)D.n_listed_paths + 1;
+        std::vector<uint32_t> stage[4];
+        const struct { uint64_t* dst; int k; size_t n; } offs[4] = {{inside_off, PR_INOFF, nb1}, {pred_off, PR_PREDOFF, nb1},
+                                                                    {bubble_path_off, PR_BPO, nb1}, {path_off, PR_POFF, np1}};
+        for (int i = 0; i < 4; ++i)
+            if (offs[i].dst) {
+                stage[i].resize(offs[i].n);
+                PO_TRY(give(stage[i].data(), offs[i].k, offs[i].n * 4));
+            }
+        PO_TRY(give(bubbles, PR_TABLE, (size_t)D.n_bubbles * sizeof(po_bubble_paths)));
+        PO_TRY(give(inside_nodes, PR_INNODES, (size_t)D.n_inside_nodes * 4));
+        PO_TRY(give(pred_node, PR_PREDNODE, (size_t)D.n_preds * 4));
+        PO_TRY(give(pred_weight, PR_PREDW, (size_t)D.n_preds * 4));
+        PO_TRY(give(path_nodes, PR_PATHS, (size_t)D.n_path_nodes * 4));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        for (int i = 0; i < 4; ++i)
+            if (offs[i].dst)
+                for (size_t j = 0; j < offs[i].n; ++j) offs[i].dst[j] = stage[i][j];
+        return PO_OK;
+    });
+}
+
+po_status po_get_paths_stats(const po_handle* h, po_paths_stats* out) { return get_stats(h, &po_handle::ppstats, out); }
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

@@ -869,6 +869,27 @@ def chain_components(path: str, device: Optional[int] = None, partitions: bool =
         ov.close()
 
 
+def graph_file_bubble_paths(path: str, max_paths: int = 0, device: Optional[int] = None):
+    """A graph file by the route of ``chain_components`` -- ``read_graph_gfa``, one segment per ``S`` line on a fresh handle,
+    the graph on the device (``graph_from_edges``) -- then ``po_phase_paths``: ``(graph file, phasing.BubblePaths, stats)``.
+    The successor order is that of the file's ``E`` lines, as in the graph ``gfa2_reconstruct_assembly_graph`` builds."""
+    from .io import gfa
+    from .phasing import bubble_paths
+    with open(path) as f:
+        graph = gfa.read_graph_gfa(f)
+    ov = ExactOverlapper(device=device)
+    try:
+        for name, n in zip(graph.names, graph.lengths.tolist()):
+            ov.add_segment(name, n)
+        res = ov.graph_from_edges(graph.edges, graph.node_order)
+        try:
+            return graph, bubble_paths(ov, res, max_paths), ov.paths_stats()
+        finally:
+            res.free()
+    finally:
+        ov.close()
+
+
 def component_gfa2_lines(graph, nodes: Sequence[int], edges: np.ndarray) -> List[str]:
     """What ``gfa2_write_graph`` (phasm/io/gfa.py:281-326) writes for the subgraph of ``nodes`` (in node order) with
     ``edges`` (rows of ``graph.edges``, input order)."""

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats, PoSpellInput, PoSpellStats
-from .phasing import RelevantReads
+from .phasing import BubblePaths, RelevantReads
 from .spelling import spell_arrays
 
 OverlapT = Tuple[str, str, int, int, int, int]
@@ -722,6 +722,38 @@ class ExactOverlapper:
 
     def spell_stats(self) -> dict:
         return self._stats(self._lib.po_get_spell_stats, PoSpellStats)
+
+    def phase_paths(self, graph: OverlapResult, max_paths: int = 0) -> "BubblePaths":
+        """``po_phase_paths``: for every top-level bubble of a graph result (of the kinds ``layout_bubblechains`` takes, which
+        stays valid) its chain and position, the number of simple paths from entrance to exit, the paths themselves where
+        they number at most ``max_paths`` (0: counts only), the interior nodes and the predecessors of the exit with their
+        edge weights -- a ``phasm_amd.phasing.BubblePaths``.  Too many paths to list in one call: OverflowError (lower
+        ``max_paths``)."""
+        if not 0 <= int(max_paths) < 2**64:
+            raise ValueError("max_paths does not fit 64 bits")
+        prm = _lib.PoPathsParams(int(max_paths), 0)
+        r = ctypes.c_void_p()
+        st = self._lib.po_phase_paths(self._h, graph._ptr, ctypes.byref(prm), ctypes.byref(r))
+        if st == _lib.PO_ERR_CAPACITY:
+            msg = self._lib.po_last_error(self._h)
+            raise OverflowError(msg.decode("utf-8", "replace") if msg else "po_phase_paths: too many paths in one call")
+        _check(self._h, st)
+        try:
+            d = _lib.PoPathsDims()
+            _check(self._h, self._lib.po_paths_sizes(r, ctypes.byref(d)))
+            nb, npaths = int(d.n_bubbles), int(d.n_listed_paths)
+            out = BubblePaths(np.zeros(nb, _lib.BUBBLE_PATHS_DTYPE), np.zeros(nb + 1, np.uint64), np.zeros(int(d.n_inside_nodes), np.uint32),
+                              np.zeros(nb + 1, np.uint64), np.zeros(int(d.n_preds), np.uint32), np.zeros(int(d.n_preds), np.int32),
+                              np.zeros(nb + 1, np.uint64), np.zeros(npaths + 1, np.uint64), np.zeros(int(d.n_path_nodes), np.uint32))
+            _check(self._h, self._lib.po_paths_copy(r, _ptr(out.bubbles), _ptr(out.inside_off), _ptr(out.inside_nodes), _ptr(out.pred_off),
+                                                    _ptr(out.pred_node), _ptr(out.pred_weight), _ptr(out.bubble_path_off), _ptr(out.path_off),
+                                                    _ptr(out.path_nodes)))
+        finally:
+            self._lib.po_result_free(r)
+        return out
+
+    def paths_stats(self) -> dict:
+        return self._stats(self._lib.po_get_paths_stats, _lib.PoPathsStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:

@@ -27,8 +27,20 @@ through ``po_phase_index`` and ``po_phase_relevant``, o
 
 Here ``ov`` is anything with ``phase_relevant``: an ``ExactOverlapper`` or a ``HostIndex`` (numpy, like ``HostScorer``).
 
-Not here: the bubble walk of ``phase()``, ``new_block`` and the final ``prune(.., 1.0)`` with its ``random.choice`` among ties,
-spelling sequences, a ``phase`` command, ``CoverageModel`` (unused by the reference)."""
+What ``phase()`` computes per bubble before any of that (phasing.py:196-234, 396) -- the order of the bubbles along their chain,
+``networkx.all_simple_paths(g, entrance, exit)``, ``superbubble_nodes(g, entrance, exit) - {entrance, exit}`` and the
+predecessors of the exit with their edge weights -- for every top-level bubble of a graph in one call, through
+``po_phase_paths``:
+
+    paths = bubble_paths(ov, graph_res, max_paths)                                   # once per graph: a BubblePaths
+    for b in paths.chain_bubbles(chain):                                             # the order of phase()'s walk
+        if paths.is_large(b, max_bubble_size): ...                                   # from the count alone
+        paths.paths_of(b), paths.interior_of(b), paths.preds_of(b)
+
+Here ``ov`` is anything with ``phase_paths``: an ``ExactOverlapper`` or a ``HostPaths`` (plain Python, like ``HostScorer``).
+
+Not here: the walk loop of ``phase()`` itself, ``new_block`` and the final ``prune(.., 1.0)`` with its ``random.choice`` among
+ties, expanding nodes to reads (``get_all_reads``), a ``phase`` command, ``CoverageModel`` (unused by the reference)."""
 from __future__ import annotations
 
 import math
@@ -36,6 +48,8 @@ from dataclasses import dataclass, field, replace
 from typing import Callable, Iterable, List, Optional, Sequence
 
 import numpy as np
+
+from ._lib import BUBBLE_PATHS_DTYPE, PATHS_BARE, PATHS_MANY, PATHS_SATURATED, PATHS_UNLISTED
 
 NO_START = 0x7FFFFFFF
 
@@ -429,3 +443,292 @@ class HostIndex:
                     m = min(m, edge_len - int(sp["a0"][j]))
             om.append(m)
         return RelevantReads(u32(sorted(ca)), u32(rel), i32(om), u32(aln_off), u32(aln_b), i32(a0), i32(a1), u32(G), len(spanning), fell_back)
+
+
+# ---- paths, interior and exit predecessors of every top-level bubble (po_phase_paths) ---------------
+
+@dataclass
+class BubblePaths:
+    """What ``po_phase_paths`` gives: one table entry per top-level bubble, ordered by (chain, position), and CSR arrays.
+    ``bubbles``: BUBBLE_PATHS_DTYPE (entrance, exit, chain, position, n_inside, flags, n_paths, n_path_nodes)."""
+    bubbles: np.ndarray            # BUBBLE_PATHS_DTYPE [B]
+    inside_off: np.ndarray         # uint64 [B + 1] into inside_nodes
+    inside_nodes: np.ndarray       # uint32: interior nodes, ascending in rank of the node order
+    pred_off: np.ndarray           # uint64 [B + 1] into pred_node / pred_weight
+    pred_node: np.ndarray          # uint32: the predecessors of the exit, in the graph's edge order
+    pred_weight: np.ndarray        # int32: g[pred][exit]['weight']
+    bubble_path_off: np.ndarray    # uint64 [B + 1]: the number of the bubble's first listed path
+    path_off: np.ndarray           # uint64 [P + 1] into path_nodes
+    path_nodes: np.ndarray         # uint32: the listed paths, both ends included
+
+    def __len__(self) -> int:
+        return len(self.bubbles)
+
+    def is_listed(self, b: int) -> bool:
+        return not int(self.bubbles["flags"][b]) & PATHS_UNLISTED
+
+    def is_bare(self, b: int) -> bool:
+        return bool(int(self.bubbles["flags"][b]) & PATHS_BARE)
+
+    def paths_of(self, b: int) -> List[tuple]:
+        """``[tuple(p) for p in networkx.all_simple_paths(g, entrance, exit)]`` of bubble b, in that order."""
+        if not self.is_listed(b):
+            raise ValueError("bubble %d has %s paths: more than max_paths, they were not listed" % (b, paths_text(self.bubbles["n_paths"][b])))
+        off, nodes = self.path_off, self.path_nodes
+        return [tuple(nodes[int(off[p]):int(off[p + 1])].tolist())
+                for p in range(int(self.bubble_path_off[b]), int(self.bubble_path_off[b + 1]))]
+
+    def interior_of(self, b: int) -> List[int]:
+        """``superbubble_nodes(g, entrance, exit) - {entrance, exit}`` of bubble b, in node order."""
+        return self.inside_nodes[int(self.inside_off[b]):int(self.inside_off[b + 1])].tolist()
+
+    def preds_of(self, b: int) -> List[tuple]:
+        """``[(p, g[p][exit]['weight']) for p in g.predecessors_iter(exit)]`` of bubble b, in the graph's edge order."""
+        lo, hi = int(self.pred_off[b]), int(self.pred_off[b + 1])
+        return list(zip(self.pred_node[lo:hi].tolist(), self.pred_weight[lo:hi].tolist()))
+
+    def chain_bubbles(self, chain: int) -> List[int]:
+        """The bubbles ``phase()`` visits on chain ``chain``, in its order: those of the chain by position, up to the first
+        bare one (``non_branching_bubble`` drops it, and ``while entrance in self.bubble_entrances`` ends there)."""
+        out = []
+        for b in np.flatnonzero(self.bubbles["chain"] == chain).tolist():   # (the table is ordered by (chain, position))
+            if self.is_bare(b):
+                break
+            out.append(b)
+        return out
+
+    def is_large(self, b: int, max_bubble_size: int) -> bool:
+        """``len(possible_paths) > max_bubble_size``, from the count alone."""
+        return int(self.bubbles["n_paths"][b]) > int(max_bubble_size)
+
+
+def paths_text(n_paths) -> str:
+    """A path count as the tools print it: a saturated one as a lower bound."""
+    return ">=2^64-1" if int(n_paths) == PATHS_MANY else str(int(n_paths))
+
+
+def bubble_paths(src, graph, max_paths: int = 0) -> BubblePaths:
+    """``src.phase_paths(graph, max_paths)``: ``src`` is an ``ExactOverlapper`` with one of its graph results, or a ``HostPaths``
+    (then ``graph`` is ignored: it holds its own)."""
+    return src.phase_paths(graph, max_paths)
+
+
+class HostPaths:
+    """``po_phase_paths`` in plain Python / numpy, on ``edges`` (rows that start with u, v, weight) and the graph's node
+    order: for machines without a GPU and for the tests.  It is no fallback: nothing here picks it on its own.  The bubbles
+    are found the way the device finds them (DESIGN.md sections 3.9j, 3.9k): the singleton SCCs, immediate dominators and
+    post-dominators of their DAG under one virtual root and one virtual sink, the pairs (s, t) with t = ipdom[s] and
+    s = idom[t], the discards for self-loops, the top-level ones, their chains."""
+
+    def __init__(self, edges, node_order):
+        e = np.asarray(edges, dtype=np.int64).reshape(len(edges), -1) if len(edges) else np.zeros((0, 3), np.int64)
+        self.order = [int(x) for x in node_order]
+        rank = {x: r for r, x in enumerate(self.order)}
+        if len(rank) != len(self.order):
+            raise ValueError("po_phase_paths: the node order repeats a node")
+        try:
+            self.eu = [rank[int(u)] for u in e[:, 0]]
+            self.ev = [rank[int(v)] for v in e[:, 1]]
+        except KeyError:
+            raise ValueError("po_phase_paths: an edge has an end that is not in the node order")
+        self.weight = e[:, 2].tolist() if e.shape[1] > 2 else [0] * len(e)
+        n = len(self.order)
+        self.succ = [[] for _ in range(n)]       # (head rank, edge index), in edge order
+        self.pred = [[] for _ in range(n)]
+        for k, (a, b) in enumerate(zip(self.eu, self.ev)):
+            self.succ[a].append((b, k))
+            self.pred[b].append((a, k))
+        self._bubbles()
+        self.stats = {}
+
+    def _sccs(self):
+        """Tarjan, iterative: the SCC number of every rank."""
+        n = len(self.order)
+        index, low, comp, on = [-1] * n, [0] * n, [-1] * n, [False] * n
+        stack, count, n_comp = [], 0, 0
+        for root in range(n):
+            if index[root] != -1:
+                continue
+            work = [(root, 0)]
+            while work:
+                v, i = work.pop()
+                if i == 0:
+                    index[v] = low[v] = count
+                    count += 1
+                    stack.append(v)
+                    on[v] = True
+                if i < len(self.succ[v]):
+                    w = self.succ[v][i][0]
+                    work.append((v, i + 1))
+                    if index[w] == -1:
+                        work.append((w, 0))
+                    elif on[w]:
+                        low[v] = min(low[v], index[w])
+                    continue
+                if low[v] == index[v]:
+                    while True:
+                        w = stack.pop()
+                        on[w] = False
+                        comp[w] = n_comp
+                        if w == v:
+                            break
+                    n_comp += 1
+                if work:
+                    u = work[-1][0]
+                    low[u] = min(low[u], low[v])
+        return comp, n_comp
+
+    @staticmethod
+    def _idoms(n, parents, topo):
+        """Immediate dominators on a DAG with root n (``parents[v]`` empty: v hangs on the root), in topological order."""
+        idom, depth = [n] * (n + 1), [0] * (n + 1)
+        for v in topo:
+            ps = parents[v]
+            a = ps[0] if ps else n
+            for b in ps[1:]:
+                while a != b:
+                    if depth[a] >= depth[b]:
+                        a = idom[a]
+                    else:
+                        b = idom[b]
+            idom[v], depth[v] = a, depth[a] + 1
+        return idom
+
+    def _bubbles(self):
+        n = len(self.order)
+        comp, n_comp = self._sccs()
+        size = [0] * n_comp
+        for c in comp:
+            size[c] += 1
+        real = [size[comp[r]] == 1 for r in range(n)]
+        loop = [False] * n
+        parents, children = [[] for _ in range(n)], [[] for _ in range(n)]
+        from_root, to_sink = [False] * n, [False] * n
+        for a, b in zip(self.eu, self.ev):
+            if a == b:
+                loop[a] = True
+            elif real[a] and real[b]:
+                parents[b].append(a)
+                children[a].append(b)
+            else:
+                from_root[b] = from_root[b] or not real[a]
+                to_sink[a] = to_sink[a] or not real[b]
+        reals = [r for r in range(n) if real[r]]
+        indeg = {r: len(parents[r]) for r in reals}
+        topo = [r for r in reals if indeg[r] == 0]
+        for v in topo:
+            for c in children[v]:
+                indeg[c] -= 1
+                if indeg[c] == 0:
+                    topo.append(c)
+        idom = self._idoms(n, [[] if from_root[r] else parents[r] for r in range(n)], topo)
+        ipdom = self._idoms(n, [[] if to_sink[r] else children[r] for r in range(n)], topo[::-1])
+        cand = {s: ipdom[s] for s in reals if ipdom[s] < n and idom[ipdom[s]] == s}
+        interior = {}
+        for s, t in cand.items():                # the nodes reached from s without passing t
+            seen, todo = {s, t}, [s]
+            while todo:
+                for w, _ in self.succ[todo.pop()]:
+                    if w not in seen:
+                        seen.add(w)
+                        todo.append(w)
+            interior[s] = seen - {s, t}
+        alive = {s: t for s, t in cand.items() if not (loop[s] or loop[t] or any(loop[x] for x in interior[s]))}
+        held = set().union(*[interior[s] for s in alive]) if alive else set()
+        self.top = {s: t for s, t in alive.items() if s not in held}
+        self.interior = {s: sorted(interior[s]) for s in self.top}
+        exits = set(self.top.values())
+        self.table = []                          # (entrance rank, chain, position), by (chain, position)
+        for chain, head in enumerate(s for s in sorted(self.top) if s not in exits):
+            s, position = head, 0
+            while s in self.top:
+                self.table.append((s, chain, position))
+                s, position = self.top[s], position + 1
+
+    def _counts(self, s):
+        """cnt of every member of the bubble that s enters, saturating."""
+        t, members = self.top[s], [s] + self.interior[s]
+        inside = set(self.interior[s])
+        cnt, stray = {}, 0
+        todo = [(s, 0)]
+        while todo:                              # post-order over the members
+            v, i = todo.pop()
+            if i < len(self.succ[v]):
+                todo.append((v, i + 1))
+                w = self.succ[v][i][0]
+                if w != t and w in inside and w not in cnt:
+                    todo.append((w, 0))
+                continue
+            total = 0
+            for w, _ in self.succ[v]:
+                if w == t:
+                    total += 1
+                elif w in inside:
+                    total += cnt[w]
+                else:
+                    stray += 1
+            cnt[v] = min(total, PATHS_MANY)
+        for v in members:                        # (a member that no path from s reaches: cannot happen in a superbubble)
+            cnt.setdefault(v, 0)
+        return cnt, stray
+
+    def _unrank(self, s, cnt, j):
+        t, inside, path, v = self.top[s], set(self.interior[s]), [s], s
+        while v != t:
+            for w, _ in self.succ[v]:
+                c = 1 if w == t else (cnt[w] if w in inside else 0)
+                if j < c:
+                    break
+                j -= c
+            else:
+                raise RuntimeError("the counts of bubble %d do not add up" % self.order[s])
+            path.append(w)
+            v = w
+        return path
+
+    def phase_paths(self, graph=None, max_paths: int = 0) -> BubblePaths:
+        if not 0 <= int(max_paths) < 2**64:
+            raise ValueError("max_paths does not fit 64 bits")
+        order = self.order
+        table = np.zeros(len(self.table), dtype=BUBBLE_PATHS_DTYPE)
+        inside_off, pred_off, bpo, path_off = [0], [0], [0], [0]
+        inside_nodes, pred_node, pred_weight, path_nodes = [], [], [], []
+        n_stray, n_listed = 0, 0
+        for b, (s, chain, position) in enumerate(self.table):
+            t = self.top[s]
+            cnt, stray = self._counts(s)
+            n_stray += stray
+            n_paths = cnt[s]
+            saturated = n_paths == PATHS_MANY
+            unlisted = saturated or n_paths > max_paths
+            n_listed += 0 if unlisted else n_paths
+            if n_listed >= 2**30:
+                raise OverflowError("po_phase_paths: at least %d paths to list in one call, at most 2^30 - 1" % n_listed)
+            first = len(path_nodes)
+            if not unlisted:
+                for j in range(n_paths):
+                    path_nodes += [order[v] for v in self._unrank(s, cnt, j)]
+                    path_off.append(len(path_nodes))
+                if len(path_nodes) >= 2**31:
+                    raise OverflowError("po_phase_paths: the listed paths hold %d nodes together, at most 2^31 - 1" % len(path_nodes))
+            flags = (PATHS_BARE if not self.interior[s] else 0) | (PATHS_UNLISTED if unlisted else 0) | (PATHS_SATURATED if saturated else 0)
+            table[b] = (order[s], order[t], chain, position, len(self.interior[s]), flags, n_paths, len(path_nodes) - first)
+            inside_nodes += [order[v] for v in self.interior[s]]
+            inside_off.append(len(inside_nodes))
+            for p, k in self.pred[t]:
+                pred_node.append(order[p])
+                pred_weight.append(self.weight[k])
+            pred_off.append(len(pred_node))
+            bpo.append(len(path_off) - 1)
+        u64, u32 = (lambda v: np.asarray(v, dtype=np.uint64)), (lambda v: np.asarray(v, dtype=np.uint32))
+        flags = table["flags"]
+        self.stats = {"n_nodes": len(order), "n_edges": len(self.eu), "n_invalid": 0, "n_bubbles": len(table),
+                      "n_bare": int((flags & PATHS_BARE != 0).sum()), "n_unlisted": int((flags & PATHS_UNLISTED != 0).sum()),
+                      "n_saturated": int((flags & PATHS_SATURATED != 0).sum()), "n_listed_paths": len(path_off) - 1,
+                      "n_path_nodes": len(path_nodes), "max_paths_seen": int(table["n_paths"].max()) if len(table) else 0,
+                      "max_path_nodes": int(np.diff(path_off).max()) if len(path_off) > 1 else 0, "n_stray_edges": n_stray}
+        return BubblePaths(table, u64(inside_off), u32(inside_nodes), u64(pred_off), u32(pred_node), np.asarray(pred_weight, dtype=np.int32),
+                           u64(bpo), u64(path_off), u32(path_nodes))
+
+    def paths_stats(self) -> dict:
+        return dict(self.stats)
