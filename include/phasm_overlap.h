@@ -897,9 +897,9 @@ po_status po_get_contig_stats(const po_handle* h, po_contig_stats* out);
 /* ---------------------------------------------------------------------------------------------
  * The hot loop of `phasm phase`: BubbleChainPhaser.branch -- generate_new_hsets and calculate_rl, phasm/phasing.py:421-480,
  * 564-631 -- and prune (phasing.py:482-539) at ONE bubble, given as plain arrays.  The call needs neither reads nor a graph on
- * the handle.  Not part of it: the bubble walk of phase(), new_block and the final prune(.., 1.0) with
- * its random.choice among ties, spelling sequences, CoverageModel (which the reference never uses), and the superbubbles of
- * cyclic partitions.
+ * the handle.  Not part of it: the state the bubble walk of phase() carries, new_block and the final prune(.., 1.0) (po_walk_*
+ * below), its random.choice among ties, spelling sequences (po_spell), CoverageModel (which the reference never uses), and the
+ * superbubbles of cyclic partitions.
  * --------------------------------------------------------------------------------------------- */
 
 typedef struct {
@@ -1194,6 +1194,80 @@ po_status po_paths_sizes(const po_result* out, po_paths_dims* dims);
 po_status po_paths_copy(po_result* out, po_bubble_paths* bubbles, uint64_t* inside_off, uint32_t* inside_nodes, uint64_t* pred_off,
                         uint32_t* pred_node, int32_t* pred_weight, uint64_t* bubble_path_off, uint64_t* path_off, uint32_t* path_nodes);
 po_status po_get_paths_stats(const po_handle* h, po_paths_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The walk of `phasm phase` along a bubble chain with the candidate sets RESIDENT on the device: what
+ * BubbleChainPhaser carries from bubble to bubble (candidate_sets with their read sets and log_rl, phasm/phasing.py:125-142),
+ * the take-over of the survivors (phasing.py:311-319), new_block's reset (phasing.py:343-364) and prune(.., 1.0) of new_block
+ * and of the end of phase() (phasing.py:335-339, 347).  phasm_amd/csrc/walk.hip.h, DESIGN.md section 3.9s.
+ * Not part of it: the loop itself and its arms (phasm_amd/phasing.py, phase_chain), prev_graph_reads / prev_aligning_reads
+ * (host lists of the caller), the choice among ties.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t ploidy;             /* k of po_walk_create                                                             */
+    uint32_t n_cands;            /* the candidate sets of the state; 1 after po_walk_create and po_walk_reset       */
+    uint32_t depth;              /* bubbles advanced since the reset                                                */
+    uint32_t start_of_block;     /* depth == 0                                                                      */
+    uint64_t n_block_reads;      /* reads that a step since the reset named in b_reads and then advanced            */
+} po_walk_info;
+
+typedef struct {
+    uint64_t n_cands_in, n_cands_out;   /* candidates before the step and after it (equal where it did not advance) */
+    uint64_t depth, n_block_reads;      /* after the step                                                           */
+    uint64_t n_new_reads;        /* reads of b_reads that were new to the block (they joined it iff the step advanced) */
+    uint32_t words_per_slot;     /* W of the state's rows after the step                                            */
+    uint32_t advanced;           /* the step took its final list over                                               */
+    float ms_bits;               /* path bitsets and the intervals of slots and paths (ms_intervals of the phase stats) */
+    float ms_advance;            /* k_wk_advance                                                                    */
+    float ms_total;              /* ms_total of the phase stats + ms_advance                                        */
+    uint32_t reserved;
+} po_walk_stats;
+
+/* A WALK is a result of a kind of its own: it belongs to one handle, po_result_count is 0, po_result_free frees it; every
+ * call that wants rows, candidates, edges or another special result refuses it.  Creating, resetting and asking a walk that
+ * has not advanced touch no device.
+ * po_walk_create: ploidy 1..8.  The state is that of BubbleChainPhaser.__init__ / new_block: ONE candidate with k empty
+ *   read sets and log_rl = -inf, depth 0, no block reads, start of block.
+ * po_walk_reset: back to that state (the reset half of new_block; its prune(.., 1.0) is po_walk_best, called before).
+ * po_walk_step: po_phase_branch on the bubble whose read-set list c * k + i is: the interior reads of every path that slot i
+ *   of candidate c took at the advanced bubbles of the block, as far as they are in b_reads.  params and input are those of
+ *   po_phase_branch except: input.set_off and input.set_ids must be NULL; params.n_cands must equal the walk's count,
+ *   params.start_of_block its flag, params.ploidy its ploidy (a caller whose idea of the state has drifted is told).
+ *   b_reads[params.n_b]: the global oriented read ids behind the local ids 0..n_b-1, strictly ascending, as po_relevant_copy
+ *   gives them.  The entries, their order, every level of prune and po_get_phase_stats are those of po_phase_branch; since
+ *   (S0, E) are a least and a greatest value and the table's sums run over the relevant reads in index order, neither of
+ *   which the numbering of the b reads touches, (cand, ext, rl) are byte-equal to po_phase_branch's on the same handle.  A
+ *   block read that b_reads leaves out can match nothing.
+ *   advance != 0 and at least one entry in the final list: the state becomes that list -- candidate j takes over slot i of
+ *   candidate cand[j] and adds to it the interior of path digit_i(ext[j]) (digits base P, slot 0 most significant), its
+ *   log_rl is rl[j]; depth grows by 1; the reads of b_reads that are new to the block join the block reads.  advance == 0,
+ *   or no entry: the state is untouched (advance == 0 is the peek a callable prune factor needs).
+ *   cap bounds only what is copied home: *n_out is always the full count, and the state takes the whole list.
+ *   Rejections as po_phase_branch's (PO_ERR_INVALID with a sentence, checked on the host before the device is touched,
+ *   outputs and state untouched), and: a walk of another handle or a result of another kind; non-NULL set_off / set_ids; the
+ *   three mismatches; b_reads NULL with n_b > 0, or not strictly ascending.  A call that fails later (PO_ERR_HIP,
+ *   PO_ERR_NOMEM) leaves the state as it was.
+ * po_walk_best: prune(candidate_sets, 1.0) with its early returns -- fewer than two candidates, or greatest log_rl = -inf:
+ *   every candidate; else the candidates with log_rl - max >= log10(1.0), ascending (no further round: 1.0 < 1.0 is false).
+ *   Up to cap of them go to cands_out, *n_out is the full count, *max_rl_out (may be NULL) the greatest log_rl.
+ * po_walk_history: for each of the n named candidates its extension id at every advanced bubble of the block,
+ *   ext_out[q * depth + d], oldest first (room for n * depth entries).
+ * po_walk_read_sets: the k read sets of each named candidate as global read ids, ascending, in CSR form: off_out[n * k + 1],
+ *   up to cap ids to ids_out, *n_ids_out the full count.  For the yielded block and for tests: the bit rows of the named
+ *   candidates come home and are expanded on the host.
+ * A candidate >= n_cands, a NULL count: PO_ERR_INVALID.  There is no CPU fallback: without a GPU a valid step returns
+ * PO_ERR_HIP.  Device memory of a walk: 2 x 4 W bytes per slot, 2 x 8 per candidate, 8 per survivor of every advanced bubble. */
+po_status po_walk_create(po_handle* h, uint32_t ploidy, po_result** walk_out);
+po_status po_walk_reset(po_result* walk);
+po_status po_walk_info_get(const po_result* walk, po_walk_info* info);
+po_status po_walk_step(po_handle* h, po_result* walk, const po_phase_params* params, const po_phase_input* input, const uint32_t* b_reads,
+                       uint32_t advance, uint32_t* cand_out, uint32_t* ext_out, double* rl_out, uint64_t cap, uint64_t* n_out);
+po_status po_walk_best(po_result* walk, uint32_t* cands_out, uint64_t cap, uint64_t* n_out, double* max_rl_out);
+po_status po_walk_history(po_result* walk, const uint32_t* cands, uint64_t n, uint32_t* ext_out);
+po_status po_walk_read_sets(po_result* walk, const uint32_t* cands, uint64_t n, uint64_t* off_out, uint32_t* ids_out, uint64_t cap,
+                            uint64_t* n_ids_out);
+po_status po_get_walk_stats(const po_handle* h, po_walk_stats* out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

@@ -317,6 +317,22 @@ class PoPathsStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoWalkInfo(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint32) for name in ("ploidy", "n_cands", "depth", "start_of_block")] + [("n_block_reads", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PoWalkStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_cands_in", "n_cands_out", "depth", "n_block_reads", "n_new_reads")] + \
+               [("words_per_slot", ctypes.c_uint32), ("advanced", ctypes.c_uint32)] + \
+               [(name, ctypes.c_float) for name in ("ms_bits", "ms_advance", "ms_total")] + [("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class PoNodeOrderStats(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint64), ("ms_first_contained", ctypes.c_float), ("ms_rank", ctypes.c_float),
                 ("ms_total", ctypes.c_float)]
@@ -448,6 +464,16 @@ SYMBOLS = [
     ("po_paths_sizes", ctypes.c_int, [_P, ctypes.POINTER(PoPathsDims)]),
     ("po_paths_copy", ctypes.c_int, [_P] + [ctypes.c_void_p] * 9),
     ("po_get_paths_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPathsStats)]),
+    ("po_walk_create", ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    ("po_walk_reset", ctypes.c_int, [_P]),
+    ("po_walk_info_get", ctypes.c_int, [_P, ctypes.POINTER(PoWalkInfo)]),
+    ("po_walk_step", ctypes.c_int, [_P, _P, ctypes.POINTER(PoPhaseParams), ctypes.POINTER(PoPhaseInput), ctypes.c_void_p, ctypes.c_uint32,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_walk_best", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+    ("po_walk_history", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    ("po_walk_read_sets", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_walk_stats", ctypes.c_int, [_P, ctypes.POINTER(PoWalkStats)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

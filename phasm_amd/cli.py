@@ -30,6 +30,9 @@ from __future__ import annotations
 import argparse
 import logging
 import sys
+from typing import Optional
+
+import numpy as np
 
 from .io import daligner, gfa
 from .io.fasta import read_fasta, reverse_complement
@@ -371,6 +374,110 @@ def spell_contigs(args) -> int:
     return len(seqs)
 
 
+class PhasingError(Exception):
+    """What the reference's ``BubbleChainPhaser`` raises for a graph it cannot start on (phasm/phasing.py:172-192)."""
+
+
+def phase_chain_of(gf, paths) -> Optional[int]:
+    """The chain ``phase()`` walks on graph file ``gf`` with the bubbles ``paths`` (a ``phasing.BubblePaths``): None when no
+    top-level bubble has an interior (the no-bubble branch); else the chain whose first entrance is the one node of
+    in-degree 0 -- anything else is a ``PhasingError`` with the reference's sentence."""
+    if all(paths.is_bare(b) for b in range(len(paths))):
+        return None
+    heads = {int(v) for v in gf.edges[:, 1].tolist()}
+    starts = [int(n) for n in gf.node_order if int(n) not in heads]
+    if len(starts) > 1:
+        raise PhasingError("There are multiple nodes with in-degree 0, not sure what the start point is.")
+    table = paths.bubbles
+    first = [b for b in range(len(paths)) if starts and int(table["position"][b]) == 0 and int(table["entrance"][b]) == starts[0]
+             and not paths.is_bare(b)]
+    if not first:
+        raise PhasingError("Unexpected starting point '%s', this is not a bubble entrance" % (gf.node_name(starts[0]) if starts else None))
+    return int(table["chain"][first[0]])
+
+
+def phase_entries(base: str, blocks):
+    """``(name, node path, include_last)`` of every FASTA entry of a phased subgraph: ``{base}.haploblock{i}.{j}`` for every
+    haplotype of block i, ``{base}.largebubble{i}`` for the first haplotype of a large bubble's block alone."""
+    for i, block in enumerate(blocks):
+        for j, haplotype in enumerate(block.haplotypes):
+            if block.from_large_bubble:
+                yield "%s.largebubble%d" % (base, i), haplotype, block.include_last
+                break
+            yield "%s.haploblock%d.%d" % (base, i, j), haplotype, block.include_last
+
+
+def _subgraph_bubble_paths(path, device):
+    """(graph file, BubblePaths) of a subgraph; every bubble of up to 64 paths -- what one device call can score -- is listed."""
+    from . import layout
+    graph, paths, _ = layout.graph_file_bubble_paths(path, 64, device=device)
+    return graph, paths
+
+
+def phase(args) -> int:
+    """`phasm phase` (phasm/cli/assembler.py:331-418): per subgraph either the one contig of a graph without bubbles, or the
+    haploblocks of its bubble chain -- the walk of ``phasing.phase_chain`` with the candidate sets resident on the device.
+    The reads go on the handle once; the alignments are indexed there once, when the first subgraph with bubbles needs them;
+    all sequences of a subgraph are spelled in one device call."""
+    import random
+    from . import phasing, spelling
+    if not 1 <= args.ploidy <= 8:
+        raise SystemExit("phase: the ploidy must be 1 to 8")
+    choose = random.Random(args.seed).choice
+    overlapper = ExactOverlapper(device=args.device)
+    overlapper.add_fasta(args.reads_fasta, both_strands=True)
+    reads_of = spelling.ReadMap.of(overlapper)
+    index, n_entries = None, 0
+    for path in args.subgraphs:
+        gf, paths = _subgraph_bubble_paths(path, args.device)
+        base = spelling.contig_name(path)
+        try:
+            chain = phase_chain_of(gf, paths)
+        except PhasingError as e:
+            raise SystemExit("%s: %s" % (path, e))
+        if chain is None:
+            logger.info("%s: no bubbles, a simple contig path of %d nodes.", path, len(gf.node_order))
+            names, pieces = [base], [spelling.contig_pieces(gf, reads_of)]
+        else:
+            if index is None:
+                with open(args.alignments_gfa) as f:
+                    seg_names, _, rows = gfa.read_gfa2_rows(f)
+                to_read = np.asarray([reads_of[name + sign] for name in seg_names for sign in "+-"], dtype=np.int64)
+                if len(rows):
+                    rows[:, 0], rows[:, 1] = to_read[rows[:, 0]], to_read[rows[:, 1]]
+                res = overlapper.result_from_rows(rows)
+                index = overlapper.phase_index(res)
+                res.free()
+
+            def node_reads(n, gf=gf):
+                seg = int(n) >> 1
+                return [reads_of[r] for r in gf.fragments[seg][0]] if seg in gf.fragments else [reads_of[gf.node_name(n)]]
+
+            try:
+                bubbles = phasing.chain_bubbles_input(paths, chain, node_reads, is_merged=lambda n, gf=gf: (int(n) >> 1) in gf.fragments)
+            except ValueError as e:
+                raise SystemExit("%s: %s" % (path, e))
+            logger.info("%s: a bubble chain of %d bubbles, ploidy %d.", path, len(bubbles), args.ploidy)
+            walk = overlapper.phase_walk(args.ploidy)
+            try:
+                blocks = list(phasing.phase_chain(overlapper, overlapper, index, bubbles, node_reads, args.ploidy, args.min_spanning_reads,
+                                                  args.max_bubble_size, args.threshold, args.prune_factor, args.max_candidates,
+                                                  args.max_prune_rounds, args.prune_step_size, walk=walk, choose=choose))
+            finally:
+                walk.close()
+            entries = list(phase_entries(base, blocks))
+            names = [e[0] for e in entries]
+            pieces = [spelling.path_pieces(gf, nodes, reads_of, include_last) for _, nodes, include_last in entries]
+        for name, seq in zip(names, spelling.spell_pieces(overlapper, pieces)):
+            args.output.write(b">" + name.encode("utf-8") + b"\n" + seq + b"\n")
+        n_entries += len(names)
+    args.output.flush()
+    if index is not None:
+        index.free()
+    overlapper.close()
+    return n_entries
+
+
 def main(argv=None) -> int:
     parser = argparse.ArgumentParser(prog="phasm-amd", description="MI355X-native PHASM overlap step")
     parser.add_argument("-v", "--verbose", action="count", default=0)
@@ -492,7 +599,30 @@ def main(argv=None) -> int:
     bp.add_argument("--device", type=int, default=None)
     bp.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
     bp.set_defaults(func=bubble_paths)
+    # option names and defaults of `phasm phase`, assembler.py:572-656 (-D is not offered: the device returns no per-read
+    # probabilities)
+    ph = sub.add_parser("phase", help="`phasm phase`: phase the bubble chain of every subgraph and write the sequence of every "
+                                      "haplotype of every haploblock as FASTA (`>name`, then the sequence on ONE line); a subgraph "
+                                      "without bubbles gives the entry `spell-contigs` writes.")
+    ph.add_argument("-p", "--ploidy", type=int, required=True, help="the ploidy level (1 to 8)")
+    ph.add_argument("-s", "--min-spanning-reads", type=_int_in(0, 2**32 - 1), default=3,
+                    help="fewer spanning reads between two bubbles start a new haploblock (default: 3)")
+    ph.add_argument("-b", "--max-bubble-size", type=_int_in(0, 2**32 - 1), default=10,
+                    help="a bubble with more simple paths is phased on its own (default: 10)")
+    ph.add_argument("-t", "--threshold", type=float, default=1e-3, help="minimum relative likelihood of a candidate (default: 1e-3)")
+    ph.add_argument("-d", "--prune-factor", type=float, default=0.1, help="prune candidates below this factor of the best (default: 0.1)")
+    ph.add_argument("-c", "--max-candidates", type=_int_in(0, 2**32 - 1), default=500, help="candidates to prune down to (default: 500)")
+    ph.add_argument("-r", "--max-prune-rounds", type=_int_in(0, 1024), default=9, help="maximum number of pruning rounds (default: 9)")
+    ph.add_argument("-S", "--prune-step-size", type=float, default=0.1, help="raise of the prune factor per round (default: 0.1)")
+    ph.add_argument("-o", "--output", type=argparse.FileType("wb"), required=True, help="the FASTA file to write")
+    ph.add_argument("--device", type=int, default=None)
+    ph.add_argument("--seed", type=int, default=None, help="seed of the choice among equally likely candidates (default: unseeded)")
+    ph.add_argument("reads_fasta", help="the reads (FASTA); both strands go on the handle, as `overlap` adds them")
+    ph.add_argument("alignments_gfa", help="the GFA2 file with all pairwise local alignments")
+    ph.add_argument("subgraphs", nargs="+", help="the bubble chain / contig graph files (S, F and E lines)")
+    ph.set_defaults(func=phase)
     args = parser.parse_args(argv)
+    if not getattr(args, "func", None):    args = parser.parse_args(argv)
     if not getattr(args, "func", None):
         parser.print_help()
         return 1

@@ -50,6 +50,7 @@
 #include "relevant.hip.h"
 #include "spell.hip.h"
 #include "paths.hip.h"
+#include "walk.hip.h"
 
 namespace {
 
@@ -105,18 +106,19 @@ enum { QB_CNT, QB_NB, QB_COFF, QB_HOME, QB_BIDX, QB_BENT, QB_DONE, QB_COUNT, QB_
 // what a po_phase_paths result holds in HBM (po_result::d_pp): the table, the three CSR pairs, the offsets of the paths
 enum { PR_TABLE, PR_INOFF, PR_INNODES, PR_PREDOFF, PR_PREDNODE, PR_PREDW, PR_BPO, PR_POFF, PR_PATHS, PR_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 94;
+constexpr int EV_LAY_N = 96;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
        EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
-       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83 };
+       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
 static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
 static_assert(EV_PHASE_INDEX + 4 == EV_RELEVANT, "po_phase_index has four events");
 static_assert(EV_RELEVANT + 4 == EV_SPELL, "po_phase_relevant has four events");
 static_assert(EV_SPELL + 2 == EV_PATHS, "po_spell has two events");
-static_assert(EV_PATHS + 11 == EV_LAY_N, "the eleven events of po_phase_paths are the last of the layout events");
+static_assert(EV_PATHS + 11 == EV_WALK, "po_phase_paths has eleven events");
+static_assert(EV_WALK + 2 == EV_LAY_N, "the two events of po_walk_step are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -479,6 +481,11 @@ struct po_handle {
     // scoring and pruning of the haplotype extensions at one bubble (po_phase_branch, phase.hip.h)
     DevBuf d_ph[FB_N];
     po_phase_stats phstats = {};
+    // where the last run_phase left its final list and the paths' bitsets (in d_ph, until the next call that works there):
+    // what po_walk_step takes over
+    const uint32_t *ph_fcand = nullptr, *ph_fext = nullptr, *ph_pbits = nullptr;
+    const double* ph_frl = nullptr;
+    po_walk_stats wkstats = {};
     // the alignment index and the relevant reads of a bubble (po_phase_index, po_phase_relevant, relevant.hip.h)
     DevBuf d_rr[XB_N];
     po_phase_index_stats pxstats = {};
@@ -537,6 +544,16 @@ struct po_result {
     // po_phase_paths (special == 4): everything stays in HBM (d_pp, 32-bit offsets: the call refuses what does not fit them)
     DevBuf d_pp[PR_N];
     po_paths_dims pp = {};
+    // po_walk_create (special == 5): the candidate sets of a walk along a bubble chain (walk.hip.h).  On the device: the bit
+    // rows of the slots over block-stable read ids and the log_rl of the candidates, each as a ping-pong pair (wk_cur names
+    // the live half), and the links (parent, extension) of every advanced bubble, level after level (wk_level_off).  On the
+    // host: the block reads in the order they joined (stable id -> global id) and the same sorted by global id.
+    uint32_t wk_k = 0, wk_n_cands = 1, wk_W = 0;
+    int wk_cur = 0;
+    DevBuf d_wk_rows[2], d_wk_rl[2], d_wk_links, d_wk_tmp;
+    std::vector<uint64_t> wk_level_off;                          // depth + 1 entries once a bubble was advanced
+    std::vector<uint32_t> wk_reads;                              // stable id -> global id
+    std::vector<std::pair<uint32_t, uint32_t>> wk_sorted;        // (global id, stable id), ascending
     bool compact = false;   // (inside po_overlaps_to_host only) d_rows holds the verified-candidate records of `count` ROWS
 };
 
@@ -2998,6 +3015,7 @@ void release_device(po_result* r) {
                       &r->d_ixoff, &r->d_ixent, &r->d_ixlen})
         b->release();
     for (DevBuf& b : r->d_pp) b.release();
+    for (DevBuf* b : {&r->d_wk_rows[0], &r->d_wk_rows[1], &r->d_wk_rl[0], &r->d_wk_rl[1], &r->d_wk_links, &r->d_wk_tmp}) b->release();
 }
 
 // the grid of a kernel that strides over n items: eight workgroups of 256 per CU at the most
@@ -4772,8 +4790,8 @@ bool phase_offsets_ok(const uint32_t* off, uint64_t n_lists) {
 
 // The checks of po_phase_branch in front of the device, in the order the header lists them: the sentence of the first one
 // that fails, empty when the call may go on (Pk = P^k then).
-std::string phase_check(const po_phase_params& p, const po_phase_input& in, uint64_t& Pk) {
-    const std::string name = "po_phase_branch: ";
+std::string phase_check(const po_phase_params& p, const po_phase_input& in, uint64_t& Pk, const char* who = "po_phase_branch") {
+    const std::string name = std::string(who) + ": ";
     if (p.reserved || p.reserved2 || !(p.threshold >= 0.0) || p.n_levels > po::PH_MAX_LEVELS) return name + "bad parameters";
     if (p.ploidy < 1 || p.ploidy > po::PH_MAX_K) return name + "the ploidy must be 1 to 8";
     if (p.n_paths < 1 || p.n_paths > po::PH_MAX_P) return name + "the number of paths must be 1 to 64";
@@ -4799,9 +4817,17 @@ std::string phase_check(const po_phase_params& p, const po_phase_input& in, uint
     return std::string();
 }
 
+// the read sets of a walk (po_walk_step) in place of set_off / set_ids: bit rows of W words over ids below nb
+struct WalkRows {
+    const uint32_t* rows;
+    uint32_t W, nb;
+};
+
 po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input& in, uint32_t Pk, uint32_t* cand_out, uint32_t* ext_out,
-                    double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out) {
-    const char* const name = "po_phase_branch";
+                    double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out, const WalkRows* walk = nullptr) {
+    const char* const name = walk ? "po_walk_step" : "po_phase_branch";
+    h->ph_fcand = h->ph_fext = h->ph_pbits = nullptr;
+    h->ph_frl = nullptr;
     hipStream_t st = h->stream;
     po_phase_stats& S = h->phstats;
     S = po_phase_stats();
@@ -4826,7 +4852,7 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     PO_TRY(ensure(h, B[FB_PIDS], ((size_t)n_pids + 1) * 4));
     PO_TRY(ensure(h, B[FB_SOFF], ((size_t)n_slots + 1) * 4));
     PO_TRY(ensure(h, B[FB_SIDS], ((size_t)n_sids + 1) * 4));
-    PO_TRY(ensure(h, B[FB_SBITS], (size_t)n_slots * W * 4));
+    if (!walk) PO_TRY(ensure(h, B[FB_SBITS], (size_t)n_slots * W * 4));
     PO_TRY(ensure(h, B[FB_PBITS], (size_t)P * W * 4));
     PO_TRY(ensure(h, B[FB_SIV], (size_t)n_slots * Rr * sizeof(po::PhInterval)));
     PO_TRY(ensure(h, B[FB_PIV], (size_t)P * Rr * sizeof(po::PhInterval)));
@@ -4844,7 +4870,7 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     uint8_t* keep = B[FB_KEEP].as<uint8_t>();
     HIP_TRY(h, hipEventRecord(ev[0], st));
     HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
-    HIP_TRY(h, hipMemsetAsync(sbits, 0, (size_t)n_slots * W * 4, st));
+    if (!walk) HIP_TRY(h, hipMemsetAsync(sbits, 0, (size_t)n_slots * W * 4, st));
     HIP_TRY(h, hipMemsetAsync(pbits, 0, (size_t)P * W * 4, st));
     auto up = [&](void* dst, const void* src, size_t bytes) -> po_status {
         if (bytes) HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
@@ -4857,14 +4883,17 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     PO_TRY(up(a1, in.aln_a1, (size_t)n_aln * 4));
     PO_TRY(up(poff, in.path_off, ((size_t)P + 1) * 4));
     PO_TRY(up(pids, in.path_ids, (size_t)n_pids * 4));
-    PO_TRY(up(soff, in.set_off, ((size_t)n_slots + 1) * 4));
-    PO_TRY(up(sids, in.set_ids, (size_t)n_sids * 4));
+    if (!walk) {
+        PO_TRY(up(soff, in.set_off, ((size_t)n_slots + 1) * 4));
+        PO_TRY(up(sids, in.set_ids, (size_t)n_sids * 4));
+    }
     // the bitsets, the interval of every (read set, read) and (path, read)
-    hipLaunchKernelGGL(po::k_ph_bits, dim3(stride_grid(h, n_slots)), dim3(256), 0, st, n_slots, soff, sids, nb, W, sbits);
+    if (!walk) hipLaunchKernelGGL(po::k_ph_bits, dim3(stride_grid(h, n_slots)), dim3(256), 0, st, n_slots, soff, sids, nb, W, sbits);
     hipLaunchKernelGGL(po::k_ph_bits, dim3(stride_grid(h, P)), dim3(256), 0, st, P, poff, pids, nb, W, pbits);
     if (R) {
-        hipLaunchKernelGGL(po::k_ph_intervals, dim3(stride_grid(h, (uint64_t)n_slots * R)), dim3(256), 0, st, n_slots, R, nb, W, sbits, aln_off,
-                           aln_b, a0, a1, om, siv);
+        // (a walk's rows are shorter than this call's: ids at or past their length read as 0)
+        hipLaunchKernelGGL(po::k_ph_intervals, dim3(stride_grid(h, (uint64_t)n_slots * R)), dim3(256), 0, st, n_slots, R, walk ? walk->nb : nb,
+                           walk ? walk->W : W, walk ? walk->rows : sbits, aln_off, aln_b, a0, a1, om, siv);
         hipLaunchKernelGGL(po::k_ph_intervals, dim3(stride_grid(h, (uint64_t)P * R)), dim3(256), 0, st, P, R, nb, W, pbits, aln_off, aln_b, a0, a1,
                            om, piv);
     }
@@ -4977,12 +5006,265 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     PO_TRY(land_outputs(h, {{fcand, n_give * 4, cand_out}, {fext, n_give * 4, ext_out}, {frl, n_give * 8, rl_out},
                             {table, (size_t)n_slots * P * 8, table_out}}, cnt, po::PK_N));
     *n_out = n_final;
+    h->ph_fcand = fcand;
+    h->ph_fext = fext;
+    h->ph_frl = frl;
+    h->ph_pbits = pbits;
     (void)hipEventElapsedTime(&S.ms_intervals, ev[0], ev[1]);
     (void)hipEventElapsedTime(&S.ms_table, ev[1], ev[2]);
     (void)hipEventElapsedTime(&S.ms_extend, ev[2], ev[3]);
     (void)hipEventElapsedTime(&S.ms_filter, ev[3], ev[4]);
     (void)hipEventElapsedTime(&S.ms_prune, ev[4], ev[5]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[5]);
+    return PO_OK;
+}
+
+// ---- the candidate sets of a walk along a bubble chain, resident on the device (po_walk_*, walk.hip.h) -----------------------
+
+constexpr uint8_t WALK_KIND = 5;   // po_result::special of a walk
+
+// A buffer of a walk that must hold at least `need` bytes and KEEP its first `used` bytes (ensure() grows without them).
+// It belongs to a result, so it never comes out of the handle's arena.
+po_status walk_grow(po_handle* h, DevBuf& b, size_t used, size_t need) {
+    if (need <= b.cap) return PO_OK;
+    DevBuf bigger;
+    PO_TRY(ensure(h, bigger, need + need / 2, 1.0, false));
+    if (used) {
+        hipError_t e = hipMemcpyAsync(bigger.p, b.p, used, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            bigger.release();
+            return fail(h, PO_ERR_HIP, std::string("po_walk_step: keeping the links of the walk: ") + hipGetErrorString(e));
+        }
+    }
+    b.release();
+    b = bigger;
+    return PO_OK;
+}
+
+void walk_clear(po_result* w) {
+    w->wk_n_cands = 1;
+    w->wk_W = 0;
+    w->wk_level_off.clear();
+    w->wk_reads.clear();
+    w->wk_sorted.clear();
+}
+
+inline uint32_t walk_depth(const po_result* w) { return w->wk_level_off.empty() ? 0u : (uint32_t)(w->wk_level_off.size() - 1); }
+
+// The checks of po_walk_step that po_phase_branch does not have, in the order the header lists them.
+std::string walk_check(const po_handle* h, const po_result* w, const po_phase_params& p, const po_phase_input& in, const uint32_t* b_reads) {
+    const std::string name = "po_walk_step: ";
+    if (w->special != WALK_KIND) return name + "needs the result of po_walk_create";
+    if (w->h != h) return name + "the walk belongs to another handle";
+    if (in.set_off || in.set_ids) return name + "set_off and set_ids must be NULL: the read sets are the walk's";
+    if (p.ploidy != w->wk_k) return name + "the ploidy is not the walk's";
+    if (p.n_cands != w->wk_n_cands) return name + "n_cands is not the number of candidates the walk holds";
+    if ((p.start_of_block != 0) != (walk_depth(w) == 0)) return name + "start_of_block is not the walk's";
+    if (p.n_b && !b_reads) return name + "b_reads is missing";
+    for (uint32_t j = 1; j < p.n_b; ++j)
+        if (b_reads[j] <= b_reads[j - 1]) return name + "b_reads is not strictly ascending";
+    return std::string();
+}
+
+// what the three calls that ask a walk check first: the sentence, empty when the call may go on
+std::string walk_asked(const po_result* walk, const char* who, const uint32_t* cands, uint64_t n) {
+    const std::string name = std::string(who) + ": ";
+    if (walk->special != WALK_KIND) return std::string(who) + " needs the result of po_walk_create";
+    if (n >= (1ull << 31)) return name + "too many candidates named in one call";
+    if (n && !cands) return name + "the candidates are missing";
+    for (uint64_t q = 0; q < n; ++q)
+        if (cands[q] >= walk->wk_n_cands) return name + "a candidate is not below the number the walk holds";
+    return std::string();
+}
+
+po_status run_walk_step(po_handle* h, po_result* w, const po_phase_params& p, const po_phase_input& in, const uint32_t* b_reads, bool advance,
+                        uint32_t* cand_out, uint32_t* ext_out, double* rl_out, uint64_t cap, uint64_t* n_out) {
+    hipStream_t st = h->stream;
+    po_walk_stats& S = h->wkstats;
+    S = po_walk_stats();
+    const uint32_t k = p.ploidy, P = p.n_paths, C = p.n_cands, R = p.n_reads;
+    const uint32_t n_block = (uint32_t)w->wk_reads.size();
+    S.n_cands_in = S.n_cands_out = C;
+    S.depth = walk_depth(w);
+    S.n_block_reads = n_block;
+    S.words_per_slot = w->wk_W;
+    // the block-stable id of every b read: one merge of two ascending lists; the new ones are numbered in the order of b_reads
+    std::vector<uint32_t> xl(p.n_b), fresh;
+    {
+        size_t at = 0;
+        for (uint32_t j = 0; j < p.n_b; ++j) {
+            while (at < w->wk_sorted.size() && w->wk_sorted[at].first < b_reads[j]) ++at;
+            if (at < w->wk_sorted.size() && w->wk_sorted[at].first == b_reads[j]) {
+                xl[j] = w->wk_sorted[at].second;
+            } else {
+                xl[j] = n_block + (uint32_t)fresh.size();
+                fresh.push_back(b_reads[j]);
+            }
+        }
+    }
+    S.n_new_reads = fresh.size();
+    if ((uint64_t)n_block + fresh.size() >= (1ull << 31)) return fail(h, PO_ERR_CAPACITY, "po_walk_step: more than 2^31 - 1 reads in one block");
+    const uint32_t nb = n_block + (uint32_t)fresh.size();
+    const uint32_t n_aln = R ? in.aln_off[R] : 0, n_pids = in.path_off[P];
+    std::vector<uint32_t> aln_b(n_aln), path_ids(n_pids), no_sets((size_t)C * k + 1, 0u);
+    for (uint32_t j = 0; j < n_aln; ++j) aln_b[j] = xl[in.aln_b[j]];          // (every local id is below n_b: phase_check)
+    for (uint32_t j = 0; j < n_pids; ++j) path_ids[j] = xl[in.path_ids[j]];
+    po_phase_params p2 = p;
+    p2.n_b = nb;
+    po_phase_input in2 = in;
+    in2.aln_b = aln_b.data();
+    in2.path_ids = path_ids.data();
+    in2.set_off = no_sets.data();
+    in2.set_ids = nullptr;
+    uint64_t Pk = 1;
+    for (uint32_t i = 0; i < k; ++i) Pk *= P;
+    const WalkRows rows{w->d_wk_rows[w->wk_cur].as<uint32_t>(), w->wk_W, w->wk_W ? n_block : 0u};
+    uint64_t n_final64 = 0;
+    PO_TRY(run_phase(h, p2, in2, (uint32_t)Pk, cand_out, ext_out, rl_out, cap, nullptr, &n_final64, &rows));
+    const po_phase_stats& F = h->phstats;
+    S.ms_bits = F.ms_intervals;
+    S.ms_total = F.ms_total;
+    if (advance && n_final64) {
+        // the other half of each pair takes the new state; nothing of the live half changes before the launch has succeeded
+        const uint32_t n_new = (uint32_t)n_final64, W_new = std::max(1u, cdiv(nb, 32)), depth = walk_depth(w);
+        const int nxt = w->wk_cur ^ 1;
+        const uint64_t links_used = depth ? w->wk_level_off[depth] : 0;
+        PO_TRY(ensure(h, w->d_wk_rows[nxt], (size_t)n_new * k * W_new * 4, 1.0, false));
+        PO_TRY(ensure(h, w->d_wk_rl[nxt], (size_t)n_new * 8, 1.0, false));
+        PO_TRY(walk_grow(h, w->d_wk_links, (size_t)links_used * sizeof(po::WkLink), (size_t)(links_used + n_new) * sizeof(po::WkLink)));
+        hipEvent_t* ev = h->ev_lay + EV_WALK;
+        HIP_TRY(h, hipEventRecord(ev[0], st));
+        hipLaunchKernelGGL(po::k_wk_advance, dim3(stride_grid(h, (uint64_t)n_new * k * W_new)), dim3(256), 0, st, n_new, C, k, P, w->wk_W, W_new,
+                           rows.rows, h->ph_pbits, h->ph_fcand, h->ph_fext, h->ph_frl, w->d_wk_rows[nxt].as<uint32_t>(),
+                           w->d_wk_links.as<po::WkLink>() + links_used, w->d_wk_rl[nxt].as<double>());
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(ev[1], st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        (void)hipEventElapsedTime(&S.ms_advance, ev[0], ev[1]);
+        S.ms_total += S.ms_advance;
+        // the state becomes the list
+        if (w->wk_level_off.empty()) w->wk_level_off.push_back(0);
+        w->wk_level_off.push_back(links_used + n_new);
+        w->wk_cur = nxt;
+        w->wk_n_cands = n_new;
+        w->wk_W = W_new;
+        for (uint32_t g : fresh) w->wk_reads.push_back(g);
+        if (!fresh.empty()) {
+            std::vector<std::pair<uint32_t, uint32_t>> merged(w->wk_sorted.size() + fresh.size()), added(fresh.size());
+            for (size_t j = 0; j < fresh.size(); ++j) added[j] = {fresh[j], n_block + (uint32_t)j};   // (ascending: b_reads is)
+            std::merge(w->wk_sorted.begin(), w->wk_sorted.end(), added.begin(), added.end(), merged.begin());
+            w->wk_sorted.swap(merged);
+        }
+        S.advanced = 1;
+        S.n_cands_out = n_new;
+        S.depth = walk_depth(w);
+        S.n_block_reads = w->wk_reads.size();
+        S.words_per_slot = W_new;
+    }
+    *n_out = n_final64;
+    return PO_OK;
+}
+
+// prune(candidate_sets, 1.0) on the state's log_rl: every candidate at the early returns, else those equal to the greatest
+po_status run_walk_best(po_handle* h, po_result* w, uint32_t* cands_out, uint64_t cap, uint64_t* n_out, double* max_rl_out) {
+    const uint32_t n = w->wk_n_cands;
+    double max_rl = -(double)INFINITY;
+    auto everyone = [&] {
+        for (uint64_t j = 0; j < std::min<uint64_t>(cap, n); ++j)
+            if (cands_out) cands_out[j] = (uint32_t)j;
+        *n_out = n;
+        if (max_rl_out) *max_rl_out = max_rl;
+        return PO_OK;
+    };
+    if (walk_depth(w) == 0) return everyone();   // (one candidate, log_rl = -inf: nothing lies on the device)
+    hipStream_t st = h->stream;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    const size_t at_keep = 256, at_place = at_keep + (((size_t)n + 255) & ~size_t(255)), at_out = at_place + ((size_t)n + 1) * 4;
+    PO_TRY(ensure(h, w->d_wk_tmp, at_out + ((size_t)n + 1) * 4, 1.0, false));
+    char* tmp = w->d_wk_tmp.as<char>();
+    unsigned long long* key_d = reinterpret_cast<unsigned long long*>(tmp);
+    uint8_t* keep = reinterpret_cast<uint8_t*>(tmp + at_keep);
+    uint32_t *place = reinterpret_cast<uint32_t*>(tmp + at_place), *out = reinterpret_cast<uint32_t*>(tmp + at_out);
+    const double* rl = w->d_wk_rl[w->wk_cur].as<double>();
+    HIP_TRY(h, hipMemsetAsync(key_d, 0, 8, st));
+    hipLaunchKernelGGL(po::k_wk_max, dim3(stride_grid(h, n)), dim3(256), 0, st, n, rl, key_d);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(land_outputs(h, {}, key_d, 1));
+    const uint64_t key = h->pinned[16];
+    if (!key) return fail(h, PO_ERR_HIP, "internal: the candidates of po_walk_best have no greatest log_rl");
+    const uint64_t bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
+    std::memcpy(&max_rl, &bits, 8);
+    if (n < 2 || max_rl == -(double)INFINITY) return everyone();
+    hipLaunchKernelGGL(po::k_ph_survive, dim3(stride_grid(h, n)), dim3(256), 0, st, n, rl, max_rl, 0.0, keep);   // log10(1.0)
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint8_t>(h, keep, n, place, &h->pinned[3]));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n_best = h->pinned[3];
+    if (!n_best || n_best > n) return fail(h, PO_ERR_HIP, "internal: the tie set of po_walk_best does not add up");
+    hipLaunchKernelGGL(po::k_wk_pick, dim3(stride_grid(h, n)), dim3(256), 0, st, n, (uint32_t)n_best, keep, place, out);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(land_outputs(h, {{out, (size_t)std::min<uint64_t>(cap, n_best) * 4, cands_out}}, key_d, 1));
+    *n_out = n_best;
+    if (max_rl_out) *max_rl_out = max_rl;
+    return PO_OK;
+}
+
+po_status run_walk_history(po_handle* h, po_result* w, const uint32_t* cands, uint32_t n, uint32_t* ext_out) {
+    const uint32_t depth = walk_depth(w);
+    if (!n || !depth) return PO_OK;
+    hipStream_t st = h->stream;
+    const size_t at_cands = (((size_t)depth + 1) * 8 + 255) & ~size_t(255), at_out = at_cands + ((((size_t)n + 1) * 4 + 255) & ~size_t(255));
+    PO_TRY(ensure(h, w->d_wk_tmp, at_out + (size_t)n * depth * 4, 1.0, false));
+    char* tmp = w->d_wk_tmp.as<char>();
+    unsigned long long* off_d = reinterpret_cast<unsigned long long*>(tmp);
+    uint32_t *cands_d = reinterpret_cast<uint32_t*>(tmp + at_cands), *out = reinterpret_cast<uint32_t*>(tmp + at_out);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the level offsets go up as they are");
+    HIP_TRY(h, hipMemcpyAsync(off_d, w->wk_level_off.data(), ((size_t)depth + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(cands_d, cands, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(po::k_wk_trace, dim3(stride_grid(h, n)), dim3(256), 0, st, n, depth, off_d, w->d_wk_links.as<po::WkLink>(), cands_d, out);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(land_outputs(h, {{out, (size_t)n * depth * 4, ext_out}}, off_d, 1));
+    return PO_OK;
+}
+
+// the bit rows of the named candidates come home; their bits become global read ids on the host, ascending per set
+po_status run_walk_read_sets(po_handle* h, po_result* w, const uint32_t* cands, uint32_t n, uint64_t* off_out, uint32_t* ids_out, uint64_t cap,
+                             uint64_t* n_ids_out) {
+    const uint32_t k = w->wk_k, W = walk_depth(w) ? w->wk_W : 0;
+    const size_t row_bytes = (size_t)k * W * 4;
+    uint64_t total = 0;
+    if (off_out) off_out[0] = 0;
+    const uint32_t* land = nullptr;
+    if (n && row_bytes) {
+        hipStream_t st = h->stream;
+        PO_TRY(ensure_host(h, h->scratch_host, (size_t)n * row_bytes));
+        const char* rows = w->d_wk_rows[w->wk_cur].as<char>();
+        for (uint32_t q = 0; q < n; ++q)
+            HIP_TRY(h, hipMemcpyAsync(static_cast<char*>(h->scratch_host.p) + (size_t)q * row_bytes, rows + (size_t)cands[q] * row_bytes, row_bytes,
+                                      hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        land = static_cast<const uint32_t*>(h->scratch_host.p);
+    }
+    std::vector<uint32_t> one;
+    for (uint64_t s = 0; s < (uint64_t)n * k; ++s) {
+        one.clear();
+        for (uint32_t x = 0; land && x < W; ++x) {
+            uint32_t word = land[s * W + x];
+            while (word) {
+                const uint32_t id = x * 32 + (uint32_t)__builtin_ctz(word);
+                word &= word - 1;
+                if (id < w->wk_reads.size()) one.push_back(w->wk_reads[id]);
+            }
+        }
+        std::sort(one.begin(), one.end());
+        for (uint32_t g : one) {
+            if (ids_out && total < cap) ids_out[total] = g;
+            ++total;
+        }
+        if (off_out) off_out[s + 1] = total;
+    }
+    *n_ids_out = total;
     return PO_OK;
 }
 
@@ -7678,6 +7960,99 @@ po_status po_phase_branch(po_handle* h, const po_phase_params* params, const po_
 }
 
 po_status po_get_phase_stats(const po_handle* h, po_phase_stats* out) { return get_stats(h, &po_handle::phstats, out); }
+
+po_status po_walk_create(po_handle* h, uint32_t ploidy, po_result** walk_out) {
+    if (!h) return PO_ERR_INVALID;
+    if (!walk_out) return fail(h, PO_ERR_INVALID, "po_walk_create: no room for the walk");
+    *walk_out = nullptr;
+    if (ploidy < 1 || ploidy > po::PH_MAX_K) return fail(h, PO_ERR_INVALID, "po_walk_create: the ploidy must be 1 to 8");
+    // (the device is not touched: a walk that has not advanced holds nothing there)
+    return new_edge_result(h, "po_walk_create", walk_out, [&](po_result* r) {
+        r->special = WALK_KIND;
+        r->elem = 1;
+        r->wk_k = ploidy;
+        walk_clear(r);
+        return PO_OK;
+    });
+}
+
+po_status po_walk_reset(po_result* walk) {
+    if (!walk) return PO_ERR_INVALID;
+    if (walk->special != WALK_KIND) return fail(walk->h, PO_ERR_INVALID, "po_walk_reset needs the result of po_walk_create");
+    walk_clear(walk);
+    return PO_OK;
+}
+
+po_status po_walk_info_get(const po_result* walk, po_walk_info* info) {
+    if (!walk || !info) return PO_ERR_INVALID;
+    if (walk->special != WALK_KIND) return fail(walk->h, PO_ERR_INVALID, "po_walk_info_get needs the result of po_walk_create");
+    info->ploidy = walk->wk_k;
+    info->n_cands = walk->wk_n_cands;
+    info->depth = walk_depth(walk);
+    info->start_of_block = info->depth == 0;
+    info->n_block_reads = walk->wk_reads.size();
+    return PO_OK;
+}
+
+po_status po_walk_step(po_handle* h, po_result* walk, const po_phase_params* params, const po_phase_input* input, const uint32_t* b_reads,
+                       uint32_t advance, uint32_t* cand_out, uint32_t* ext_out, double* rl_out, uint64_t cap, uint64_t* n_out) {
+    if (!h) return PO_ERR_INVALID;
+    if (!n_out) return fail(h, PO_ERR_INVALID, "po_walk_step: no room for the number of entries");
+    *n_out = 0;
+    if (!walk) return fail(h, PO_ERR_INVALID, "po_walk_step: no walk");
+    if (!params || !input) return fail(h, PO_ERR_INVALID, "po_walk_step: no parameters");
+    std::string said = walk_check(h, walk, *params, *input, b_reads);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    uint64_t Pk = 0;
+    {
+        // (po_phase_branch's own checks, on the bubble with every read set empty)
+        std::vector<uint32_t> no_sets((size_t)params->n_cands * params->ploidy + 1, 0u);
+        po_phase_input as_branch = *input;
+        as_branch.set_off = no_sets.data();
+        said = phase_check(*params, as_branch, Pk, "po_walk_step");
+    }
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return guarded_run(h, "po_walk_step", [&] {
+        return run_walk_step(h, walk, *params, *input, b_reads, advance != 0, cand_out, ext_out, rl_out, cap, n_out);
+    });
+}
+
+po_status po_walk_best(po_result* walk, uint32_t* cands_out, uint64_t cap, uint64_t* n_out, double* max_rl_out) {
+    if (!walk) return PO_ERR_INVALID;
+    po_handle* h = walk->h;
+    if (!n_out) return fail(h, PO_ERR_INVALID, "po_walk_best: no room for the number of candidates");
+    *n_out = 0;
+    const std::string said = walk_asked(walk, "po_walk_best", nullptr, 0);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    if (walk_depth(walk)) PO_TRY(init_device(h));
+    return guarded_run(h, "po_walk_best", [&] { return run_walk_best(h, walk, cands_out, cap, n_out, max_rl_out); });
+}
+
+po_status po_walk_history(po_result* walk, const uint32_t* cands, uint64_t n, uint32_t* ext_out) {
+    if (!walk) return PO_ERR_INVALID;
+    po_handle* h = walk->h;
+    const std::string said = walk_asked(walk, "po_walk_history", cands, n);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    if (n && walk_depth(walk) && !ext_out) return fail(h, PO_ERR_INVALID, "po_walk_history: no room for the extensions");
+    if (walk_depth(walk)) PO_TRY(init_device(h));
+    return guarded_run(h, "po_walk_history", [&] { return run_walk_history(h, walk, cands, (uint32_t)n, ext_out); });
+}
+
+po_status po_walk_read_sets(po_result* walk, const uint32_t* cands, uint64_t n, uint64_t* off_out, uint32_t* ids_out, uint64_t cap,
+                            uint64_t* n_ids_out) {
+    if (!walk) return PO_ERR_INVALID;
+    po_handle* h = walk->h;
+    if (!n_ids_out) return fail(h, PO_ERR_INVALID, "po_walk_read_sets: no room for the number of ids");
+    *n_ids_out = 0;
+    const std::string said = walk_asked(walk, "po_walk_read_sets", cands, n);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    if (walk_depth(walk)) PO_TRY(init_device(h));
+    return guarded_run(h, "po_walk_read_sets", [&] { return run_walk_read_sets(h, walk, cands, (uint32_t)n, off_out, ids_out, cap, n_ids_out); });
+}
+
+po_status po_get_walk_stats(const po_handle* h, po_walk_stats* out) { return get_stats(h, &po_handle::wkstats, out); }
 
 po_status po_phase_index(po_handle* h, po_result* rows, po_result** index_out) {
     if (!h || !rows || !index_out) return PO_ERR_INVALID;

@@ -77,6 +77,120 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p) if len(a) else None
 
 
+class DeviceWalk:
+    """Owns one walk (``po_walk_create``): the candidate sets of ``BubbleChainPhaser`` on the device.  The interface of
+    ``phasm_amd.phasing.HostWalk``."""
+
+    def __init__(self, owner: "ExactOverlapper", ploidy: int):
+        if not 0 <= int(ploidy) < 2**32:
+            raise ValueError("po_walk_create: the ploidy must be 1 to 8")
+        self._owner, self._lib = owner, _lib.load()
+        self._ptr = ctypes.c_void_p()
+        _check(owner._h, self._lib.po_walk_create(owner._h, int(ploidy), ctypes.byref(self._ptr)))
+        self.ploidy = int(ploidy)
+
+    def _call(self, status: int):
+        _check(self._owner._h, status)
+
+    def info(self) -> dict:
+        out = _lib.PoWalkInfo()
+        self._call(self._lib.po_walk_info_get(self._ptr, ctypes.byref(out)))
+        return out.as_dict()
+
+    @property
+    def start_of_block(self) -> bool:
+        return bool(self.info()["start_of_block"])
+
+    def reset(self) -> None:
+        self._call(self._lib.po_walk_reset(self._ptr))
+
+    def phase_stats(self) -> dict:
+        return self._owner.phase_stats()
+
+    def walk_stats(self) -> dict:
+        return self._owner.walk_stats()
+
+    def step(self, rel, path_reads, start_of_block, threshold: float = 0.0, min_spanning_reads: int = 0, levels=None,
+             max_candidates: int = 0, advance: bool = True, cap: Optional[int] = None):
+        """``po_walk_step``: ``po_phase_branch`` on the bubble whose read sets are the walk's.  ``rel``: the
+        ``RelevantReads`` of the bubble; ``path_reads[p]``: the interior reads of path p as global ids (MergedReads
+        expanded).  The other arguments and the result ``(cand, ext, rl)`` are those of ``ExactOverlapper.phase_branch``.
+        ``advance``: the final list becomes the walk's candidates (where it has an entry)."""
+        from .phasing import walk_paths
+        if not 0 <= int(min_spanning_reads) < 2**32 or not 0 <= int(max_candidates) < 2**32:
+            raise ValueError("min_spanning_reads and max_candidates must fit 32 bits")
+        path_off, path_ids = walk_paths(rel, path_reads)
+        lv = np.ascontiguousarray(levels if levels is not None else [], dtype=np.float64)
+        arrays = [np.ascontiguousarray(a, dtype=dt) for a, dt in (
+            (rel.overlap_max, np.int32), (rel.aln_off, np.uint32), (rel.aln_b, np.uint32), (rel.aln_a0, np.int32), (rel.aln_a1, np.int32),
+            (path_off, np.uint32), (path_ids, np.uint32))]
+        R, P = len(rel.rel_reads), len(path_off) - 1
+        if len(arrays[0]) != R or len(arrays[1]) != R + 1 or len({len(arrays[2]), len(arrays[3]), len(arrays[4])}) != 1 or \
+                (R and len(arrays[2]) != int(arrays[1][-1])):
+            raise ValueError("the arrays of the relevant reads do not have the lengths their sizes and offsets give")
+        b_reads = np.ascontiguousarray(rel.b_reads, dtype=np.uint32)
+        n_cands = self.info()["n_cands"]
+        prm = PoPhaseParams(self.ploidy, P, n_cands, R, len(b_reads), int(bool(start_of_block)), int(min_spanning_reads),
+                            int(levels is not None), int(max_candidates), len(lv), float(threshold), 0, 0)
+        as_p = lambda a: a.ctypes.data if len(a) else None   # noqa: E731
+        inp = PoPhaseInput(*[as_p(a) for a in arrays], None, None, as_p(lv))
+        if n_cands * P ** self.ploidy >= 2**31:
+            raise ValueError("po_walk_step: too many extensions for one call")
+        call = lambda adv, c, e, r, room: self._call(self._lib.po_walk_step(   # noqa: E731
+            self._owner._h, self._ptr, ctypes.byref(prm), ctypes.byref(inp), _ptr(b_reads), int(bool(adv)), _ptr(c), _ptr(e), _ptr(r), room,
+            ctypes.byref(n)))
+        n = ctypes.c_uint64()
+        none = np.zeros(0, dtype=np.uint32)
+        room = n_cands * P ** self.ploidy if cap is None else int(cap)
+        if cap is None and room > 1 << 22:
+            call(False, none, none, none.astype(np.float64), 0)   # (a peek for the count: the step itself may run only once)
+            room = int(n.value)
+        cand, ext, rl = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.float64)
+        call(advance, cand, ext, rl, room)
+        m = min(room, int(n.value))
+        return cand[:m].copy(), ext[:m].copy(), rl[:m].copy()
+
+    def best(self):
+        """``po_walk_best``: ``prune(candidate_sets, 1.0)`` -- ``(candidates, greatest log_rl)``."""
+        room = self.info()["n_cands"]
+        out = np.zeros(room, dtype=np.uint32)
+        n, top = ctypes.c_uint64(), ctypes.c_double()
+        self._call(self._lib.po_walk_best(self._ptr, _ptr(out), room, ctypes.byref(n), ctypes.byref(top)))
+        return out[:int(n.value)].tolist(), float(top.value)
+
+    def history(self, cands) -> np.ndarray:
+        """``po_walk_history``: the extension id of each named candidate at every advanced bubble of the block, oldest first."""
+        cands = np.ascontiguousarray(list(cands), dtype=np.uint32)
+        depth = self.info()["depth"]
+        out = np.zeros((len(cands), depth), dtype=np.uint32)
+        self._call(self._lib.po_walk_history(self._ptr, _ptr(cands), len(cands), out.ctypes.data if out.size else None))
+        return out
+
+    def read_sets(self, cands) -> list:
+        """``po_walk_read_sets``: the k read sets of each named candidate as ascending lists of global read ids."""
+        cands = np.ascontiguousarray(list(cands), dtype=np.uint32)
+        off = np.zeros(len(cands) * self.ploidy + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        self._call(self._lib.po_walk_read_sets(self._ptr, _ptr(cands), len(cands), off.ctypes.data, None, 0, ctypes.byref(n)))
+        ids = np.zeros(int(n.value), dtype=np.uint32)
+        if len(ids):
+            self._call(self._lib.po_walk_read_sets(self._ptr, _ptr(cands), len(cands), off.ctypes.data, ids.ctypes.data, len(ids), ctypes.byref(n)))
+        off, k = off.tolist(), self.ploidy
+        return [[ids[off[q * k + i]:off[q * k + i + 1]].tolist() for i in range(k)] for q in range(len(cands))]
+
+    def close(self) -> None:
+        if getattr(self, "_ptr", None):
+            self._lib.po_result_free(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            if self._owner._h:
+                self.close()
+        except Exception:
+            pass
+
+
 class OverlapResult:
     """Owns one ``po_result``: rows stay on the device until asked for."""
 
@@ -641,6 +755,14 @@ class ExactOverlapper:
 
     def phase_stats(self) -> dict:
         return self._stats(self._lib.po_get_phase_stats, PoPhaseStats)
+
+    def phase_walk(self, ploidy: int) -> "DeviceWalk":
+        """``po_walk_create``: the candidate sets of a walk along a bubble chain, resident on the device from bubble to bubble
+        (``phasm_amd.phasing.phase_chain`` drives it)."""
+        return DeviceWalk(self, ploidy)
+
+    def walk_stats(self) -> dict:
+        return self._stats(self._lib.po_get_walk_stats, _lib.PoWalkStats)
 
     def phase_index(self, rows: OverlapResult) -> OverlapResult:
         """``po_phase_index``: the reference's ``read_alignments`` mapping of a row result, on the device.  The result holds

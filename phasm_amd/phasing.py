@@ -39,11 +39,19 @@ predecessors of the exit with their edge weights -- for every top-level bubble o
 
 Here ``ov`` is anything with ``phase_paths``: an ``ExactOverlapper`` or a ``HostPaths`` (plain Python, like ``HostScorer``).
 
-Not here: the walk loop of ``phase()`` itself, ``new_block`` and the final ``prune(.., 1.0)`` with its ``random.choice`` among
-ties, expanding nodes to reads (``get_all_reads``), a ``phase`` command, ``CoverageModel`` (unused by the reference)."""
+The walk loop of ``phase()`` itself, ``new_block`` and the final ``prune(.., 1.0)`` (phasing.py:182-364), with the candidate sets
+resident on the device from bubble to bubble, through ``po_walk_*``:
+
+    walk = ov.phase_walk(ploidy)                                                     # a DeviceWalk; HostWalk(scorer, ploidy) in numpy
+    for block in phase_chain(ov, ov, index, chain_bubbles_input(paths, chain, reads_of_node), reads_of_node, ploidy, walk=walk):
+        block.haplotypes, block.read_sets, block.include_last, block.from_large_bubble, block.log_rl, block.tie
+
+Not here: ``CoverageModel`` (unused by the reference), the debug data log, per-read probabilities."""
 from __future__ import annotations
 
 import math
+import random
+from collections import namedtuple
 from dataclasses import dataclass, field, replace
 from typing import Callable, Iterable, List, Optional, Sequence
 
@@ -443,6 +451,255 @@ class HostIndex:
                     m = min(m, edge_len - int(sp["a0"][j]))
             om.append(m)
         return RelevantReads(u32(sorted(ca)), u32(rel), i32(om), u32(aln_off), u32(aln_b), i32(a0), i32(a1), u32(G), len(spanning), fell_back)
+
+
+# ---- the walk along a bubble chain with resident candidates (po_walk_*) -----------------------------
+
+Haploblock = namedtuple("Haploblock", "haplotypes read_sets include_last from_large_bubble log_rl tie")
+
+
+def walk_paths(rel: RelevantReads, path_reads):
+    """``(path_off, path_ids)`` of a step: the interior reads of every path as LOCAL ids of ``rel.b_reads`` (reads outside it
+    can never match and are dropped, as in ``bubble_from_relevant``)."""
+    b = bubble_from_relevant(rel, 1, path_reads, [[[]]])
+    return b.path_off, b.path_ids
+
+
+class HostWalk:
+    """The contract of ``po_walk_*`` in numpy on a SCORER (a ``HostScorer``): the candidate sets of a walk as Python sets of
+    global read ids, for machines without a GPU and for the tests.  Like ``HostScorer`` it is no fallback: nothing here picks
+    it on its own."""
+
+    def __init__(self, scorer, ploidy: int):
+        if not 1 <= int(ploidy) <= 8:
+            raise ValueError("po_walk_create: the ploidy must be 1 to 8")
+        self.scorer, self.ploidy = scorer, int(ploidy)
+        self._stats = {}
+        self.reset()
+
+    def reset(self) -> None:
+        self._sets = [[set() for _ in range(self.ploidy)]]
+        self._rl = [-math.inf]
+        self._hist = [[]]
+        self._block = set()
+
+    @property
+    def start_of_block(self) -> bool:
+        return not self._hist[0]
+
+    def info(self) -> dict:
+        depth = len(self._hist[0])
+        return {"ploidy": self.ploidy, "n_cands": len(self._sets), "depth": depth, "start_of_block": int(depth == 0),
+                "n_block_reads": len(self._block)}
+
+    def phase_stats(self) -> dict:
+        return self.scorer.phase_stats()
+
+    def walk_stats(self) -> dict:
+        return dict(self._stats)
+
+    def step(self, rel: RelevantReads, path_reads, start_of_block, threshold: float = 0.0, min_spanning_reads: int = 0, levels=None,
+             max_candidates: int = 0, advance: bool = True, cap: Optional[int] = None):
+        if bool(start_of_block) != self.start_of_block:
+            raise ValueError("po_walk_step: start_of_block is not the walk's")
+        b_reads = [int(x) for x in rel.b_reads]
+        if any(y <= x for x, y in zip(b_reads, b_reads[1:])):
+            raise ValueError("po_walk_step: b_reads is not strictly ascending")
+        bubble = bubble_from_relevant(rel, self.ploidy, path_reads, self._sets)
+        cand, ext, rl = self.scorer.phase_branch(bubble, start_of_block, min_spanning_reads, threshold, levels=levels,
+                                                 max_candidates=max_candidates)
+        n_in = len(self._sets)
+        fresh = set(b_reads) - self._block
+        advanced = bool(advance) and len(rl) > 0
+        if advanced:
+            inside = set(b_reads)
+            interiors = [set(int(x) for x in p) & inside for p in path_reads]
+            sets, hist = [], []
+            for c, e in zip(cand.tolist(), ext.tolist()):
+                digits = ext_digits(e, bubble.n_paths, self.ploidy)
+                sets.append([self._sets[c][i] | interiors[d] for i, d in enumerate(digits)])
+                hist.append(self._hist[c] + [int(e)])
+            self._sets, self._hist, self._rl = sets, hist, [float(x) for x in rl]
+            self._block |= fresh
+        self._stats = {"n_cands_in": n_in, "n_cands_out": len(self._sets), "depth": len(self._hist[0]), "n_block_reads": len(self._block),
+                       "n_new_reads": len(fresh), "words_per_slot": (len(self._block) + 31) // 32 if self._hist[0] else 0,
+                       "advanced": int(advanced)}
+        n = len(rl) if cap is None else min(int(cap), len(rl))
+        return cand[:n], ext[:n], rl[:n]
+
+    def best(self):
+        """``prune(candidate_sets, 1.0)``: ``(candidates, greatest log_rl)``."""
+        top = max(self._rl)
+        if len(self._rl) < 2 or top == -math.inf:
+            return list(range(len(self._rl))), top
+        return [j for j, x in enumerate(self._rl) if x - top >= 0.0], top
+
+    def _named(self, cands):
+        cands = [int(c) for c in cands]
+        if any(not 0 <= c < len(self._sets) for c in cands):
+            raise ValueError("a candidate is not below the number the walk holds")
+        return cands
+
+    def history(self, cands) -> np.ndarray:
+        cands = self._named(cands)
+        return np.asarray([self._hist[c] for c in cands], dtype=np.uint32).reshape(len(cands), len(self._hist[0]))
+
+    def read_sets(self, cands) -> list:
+        return [[sorted(s) for s in self._sets[c]] for c in self._named(cands)]
+
+    def close(self) -> None:
+        pass
+
+
+def chain_bubbles_input(bubble_paths: "BubblePaths", chain: int, reads_of_node: Callable, is_merged: Optional[Callable] = None) -> List[dict]:
+    """The bubbles of one chain in the order of the walk, as ``phase_chain`` takes them: ``entrance``, ``exit``, ``paths``
+    (node tuples, both ends included), ``interior_nodes``, ``interior_reads`` (MergedReads expanded through
+    ``reads_of_node(node) -> read ids``, every read once) and ``preds`` (the predecessors of the exit that are plain reads, as
+    read ids, with their edge lengths: a merged predecessor is no key of the alignments and is left out).  ``is_merged(node)``:
+    default, a node is merged unless ``reads_of_node`` gives the node itself (node ids that are read ids)."""
+    if is_merged is None:
+        is_merged = lambda x: [int(r) for r in reads_of_node(x)] != [int(x)]   # noqa: E731
+    out = []
+    for b in bubble_paths.chain_bubbles(chain):
+        inside = bubble_paths.interior_of(b)
+        preds = [(int(list(reads_of_node(p))[0]), int(weight)) for p, weight in bubble_paths.preds_of(b) if not is_merged(p)]
+        out.append({"entrance": int(bubble_paths.bubbles["entrance"][b]), "exit": int(bubble_paths.bubbles["exit"][b]),
+                    "paths": [tuple(int(x) for x in p) for p in bubble_paths.paths_of(b)], "interior_nodes": [int(x) for x in inside],
+                    "interior_reads": list(dict.fromkeys(int(r) for x in inside for r in reads_of_node(x))), "preds": preds})
+    return out
+
+
+def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy: int, min_spanning_reads: int = 3, max_bubble_size: int = 10,
+                threshold=1e-3, prune_factor=0.1, max_candidates: int = 500, max_prune_rounds: int = 9, prune_step_size: float = 0.1,
+                walk=None, choose: Callable = random.choice, on_step: Optional[Callable] = None):
+    """``BubbleChainPhaser.phase()`` (phasm/phasing.py:182-364) over ``bubbles`` (``chain_bubbles_input``), arm by arm, as a
+    generator of ``Haploblock``.  ``scorer``: what ``score_paths`` needs at a large bubble; ``source`` / ``index``: what
+    ``relevant_reads`` needs; ``walk``: a ``DeviceWalk`` (``ExactOverlapper.phase_walk``) or a ``HostWalk`` -- None: the
+    scorer's own ``phase_walk(ploidy)``, closed at the end.  ``threshold`` (of the number of relevant reads) and
+    ``prune_factor`` (of the length of the kept list) may be callables.  ``choose`` picks one candidate of a tie set (a list of
+    candidate numbers).  ``on_step`` receives one dict per turn of the loop (the keys of a trace step of tests/walk_utils.py that the walk knows
+    without extra device work, and under ``steps`` the raw ``(cand, ext, rl)`` of every step call) and one with ``final`` at the
+    end (``prune_in``, the advanced bubbles of the last block, the two host sets).
+    ``prev_graph_reads`` and ``prev_aligning_reads`` are host sets.  One difference from the reference: a bubble that keeps no
+    candidate even as the start of a block makes the reference loop for ever; here it raises ``ValueError``."""
+    k = int(ploidy)
+    own = walk is None
+    if own:
+        walk = scorer.phase_walk(k)
+    if walk.info()["ploidy"] != k:
+        raise ValueError("the walk's ploidy is not %d" % k)
+    prev_graph, prev_aligning, block_paths, block_bubbles = set(), set(), [], []
+    expand = lambda nodes: [int(r) for x in nodes for r in reads_of_node(x)]   # noqa: E731
+
+    def as_yield(block, kind):
+        return {"kind": kind, "include_last": int(block.include_last), "tie": block.tie, "haplotypes": block.haplotypes,
+                "read_sets": block.read_sets}
+
+    def best_block(include_last):
+        tie, top = walk.best()
+        pick = int(choose(list(tie)))
+        haplotypes = [[] for _ in range(k)]
+        for paths, e in zip(block_paths, walk.history([pick]).reshape(-1).tolist()):
+            for h, d in zip(haplotypes, ext_digits(e, len(paths), k)):
+                path = list(paths[d])
+                h.extend(path[1:] if h and h[-1] == path[0] else path)
+        return Haploblock(haplotypes, walk.read_sets([pick])[0], include_last, False, float(top), [int(c) for c in tie])
+
+    def new_block():
+        block = best_block(False)
+        walk.reset()
+        prev_graph.clear()
+        prev_aligning.clear()
+        del block_paths[:], block_bubbles[:]
+        return block
+
+    try:
+        i = 0
+        while i < len(bubbles):
+            b = bubbles[i]
+            paths = [tuple(p) for p in b["paths"]]
+            path_reads = [expand(path[1:-1]) for path in paths]
+            start = walk.start_of_block
+            s = {"bubble": i, "start": int(start), "arm": "skipped", "broke": 0, "fell_back": 0, "yields": [], "steps": []}
+            large = len(paths) > max_bubble_size
+            rel = relevant_reads(source, index, b["interior_reads"], [] if large else sorted(prev_graph), sorted(prev_aligning), b["preds"],
+                                 start or large, 0 if large else min_spanning_reads)
+            s.update({"cur_aligning": rel.cur_aligning.tolist(), "n_spanning": int(rel.n_spanning), "rel_reads": rel.rel_reads.tolist(),
+                      "overlap_max": rel.overlap_max.tolist(), "aln_off": rel.aln_off.tolist(),
+                      "aln_y": [int(rel.b_reads[x]) for x in rel.aln_b.tolist()], "aln_a0": rel.aln_a0.tolist(), "aln_a1": rel.aln_a1.tolist(),
+                      "n_b": len(rel.b_reads)})
+            if (large and not start) or rel.fell_back:
+                block = new_block()
+                s["yields"].append(as_yield(block, "new_block"))
+                s["broke"], s["fell_back"] = 1, int(rel.fell_back)
+                yield block
+                start = True
+            if large:
+                scores = score_paths(scorer, bubble_from_relevant(rel, k, path_reads, [[[] for _ in range(k)]]))
+                s["scores"], s["best"] = scores.tolist(), best_paths(scores, k)
+                s["winner"], s["arm"] = s["best"][0], "large"
+                block = Haploblock([list(paths[s["winner"]])] + [[] for _ in range(k - 1)],
+                                   [sorted(set(path_reads[s["winner"]]))] + [[] for _ in range(k - 1)], False, True, -math.inf, None)
+                s["yields"].append(as_yield(block, "large"))
+                if on_step:
+                    on_step(s)
+                yield block
+                i += 1
+                continue
+            if len(rel.aln_b) == 0:
+                if on_step:
+                    on_step(s)
+                i += 1
+                continue
+            R = len(rel.rel_reads)
+            level = threshold(R) if callable(threshold) else threshold
+            factor = prune_factor
+            s["n_cands_in"] = walk.info()["n_cands"]
+            if callable(factor):
+                cand, ext, rl = walk.step(rel, path_reads, start, level, min_spanning_reads, levels=None, advance=False)
+                s["kept_cand"], s["kept_ext"], s["kept_rl"] = cand.tolist(), ext.tolist(), rl.tolist()
+                s["steps"].append((cand, ext, rl))
+                factor = factor(len(rl)) if len(rl) >= 2 else 0.0
+            cand, ext, rl = walk.step(rel, path_reads, start, level, min_spanning_reads,
+                                      levels=prune_levels(float(factor), float(prune_step_size), int(max_prune_rounds)),
+                                      max_candidates=int(max_candidates), advance=True)
+            s["steps"].append((cand, ext, rl))
+            s["phase_stats"] = walk.phase_stats()
+            s["n_kept"] = int(s["phase_stats"]["n_kept"])
+            s["prune_factor"] = None if s["n_kept"] < 2 else float(factor)
+            s["surv_cand"], s["surv_ext"], s["surv_rl"] = cand.tolist(), ext.tolist(), rl.tolist()
+            s["arm"] = "advanced"
+            if len(rl):
+                block_paths.append(paths)
+                block_bubbles.append(i)
+                prev_graph.update(int(r) for r in b["interior_reads"])
+                prev_aligning.update(s["cur_aligning"])
+                if on_step:
+                    on_step(s)
+                i += 1
+                continue
+            if start:
+                raise ValueError("bubble %d (%s .. %s) keeps no candidate even as the start of a block" % (i, b.get("entrance"), b.get("exit")))
+            block = new_block()
+            s["yields"].append(as_yield(block, "new_block"))
+            s["arm"] = "retry"
+            if on_step:
+                on_step(s)
+            yield block
+        final = {"final": True, "yields": [], "block_bubbles": list(block_bubbles), "prev_graph": sorted(prev_graph),
+                 "prev_aligning": sorted(prev_aligning)}
+        if not walk.start_of_block:
+            final["prune_in"] = walk.info()["n_cands"]
+            block = best_block(True)
+            final["yields"].append(as_yield(block, "final"))
+            if on_step:
+                on_step(final)
+            yield block
+        elif on_step:
+            on_step(final)
+    finally:
+        if own:
+            walk.close()
 
 
 # ---- paths, interior and exit predecessors of every top-level bubble (po_phase_paths, DESIGN.md section 3.9r) ---------------
