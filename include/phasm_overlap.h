@@ -430,8 +430,9 @@ typedef struct {
  * starts with (po_layout_partition), the superbubbles of the acyclic partitions (po_layout_superbubbles), the bubble
  * chains built from them (po_layout_bubblechains) and the contigs outside the chains (po_layout_contigs); of `phasm phase`
  * the scoring and pruning of the haplotype extensions at one bubble (po_phase_branch) and the relevant reads of a bubble
- * (po_phase_index, po_phase_relevant).  graph_to_dag, the superbubbles of the cyclic partitions and the rest of phasing (the
- * bubble walk, new blocks, spelling) are not part of it. */
+ * (po_phase_index, po_phase_relevant).  The superbubbles of the cyclic partitions (what the reference reaches through
+ * graph_to_dag) come from po_layout_superbubbles_all, by a scheme of its own; the chains, contigs and paths still take the
+ * acyclic partitions only. */
 po_status po_layout_tips(po_handle* h, po_result* edges, const po_tips_params* params, uint8_t* edge_flags_out,
                          po_result** kept_out);
 po_status po_get_tips_stats(const po_handle* h, po_tips_stats* out);
@@ -735,8 +736,8 @@ typedef struct {
  *                    PO_NO_NODE: superbubble_nodes(g, s, t) is {s, t} plus the nodes whose chain of node_inside reaches s
  *   node_flags_out   PO_SB_* bits of every node
  *   bubbles_out      one entry per superbubble, in the order of the entrances' ranks (room for n_order entries)
- * Any of the four may be NULL; *n_bubbles_out is always written.  The cyclic partitions (graph_to_dag) are not covered;
- * the order in which the reference's finder yields the pairs is not reproduced; where an acyclic partition holds a
+ * Any of the four may be NULL; *n_bubbles_out is always written.  The cyclic partitions are not covered here
+ * (po_layout_superbubbles_all covers them); the order in which the reference's finder yields the pairs is not reproduced; where an acyclic partition holds a
  * self-loop or lacks 'r_' or 're_' the definition above applies, not the finder's behaviour.  Only integers are involved:
  * every output is the same on every run (the round counts of the stats are statistics).  An edge with an end that is not
  * in the node order is counted in n_invalid; the call then fails with PO_ERR_INVALID and writes nothing.  Device memory
@@ -750,6 +751,62 @@ po_status po_layout_superbubbles(po_handle* h, po_result* graph, const po_superb
                                  uint32_t* node_inside_out, uint8_t* node_flags_out, po_superbubble* bubbles_out,
                                  uint64_t* n_bubbles_out);
 po_status po_get_superbubble_stats(const po_handle* h, po_superbubble_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The superbubbles of the WHOLE graph, the cyclic partitions included: what find_superbubbles (phasm/bubbles.py:397-445)
+ * reaches through graph_to_dag (bubbles.py:104-171) on every non-singleton SCC, plus the acyclic partitions, in one call.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t reserved;           /* must be 0                                                                    */
+} po_superbubble_all_params;
+
+typedef struct {
+    uint64_t n_nodes;            /* nodes of the graph (those in its node order)                                 */
+    uint64_t n_edges;
+    uint64_t n_invalid;          /* edges with an end that is not in the node order (the call fails then)        */
+    uint64_t n_bubbles, n_nested;
+    uint64_t n_cyclic_bubbles;   /* superbubbles whose entrance lies in a non-singleton SCC                       */
+    uint64_t n_split;            /* nodes split in two, the largest number of any run                            */
+    uint64_t n_rootless;         /* non-singleton SCCs without an edge from or to the outside (whole components) */
+    uint64_t n_certified;        /* rootless SCCs whose runs ended with a root that lies on every cycle          */
+    uint64_t n_edge_filtered;    /* pairs dropped because the graph has the edge exit -> entrance                */
+    uint32_t n_split_levels;     /* SCC stages that split a node, the largest number of any run                  */
+    uint32_t n_root_runs;        /* runs of the whole scheme: 1 unless a rootless SCC needs more roots           */
+    uint32_t n_scc_rounds;       /* rounds of all SCC stages                                                     */
+    uint32_t n_batches;          /* readbacks of all round loops                                                 */
+    float ms_ranks, ms_split, ms_bubbles, ms_merge, ms_total;   /* the three in the middle: summed over the runs  */
+} po_superbubble_all_stats;
+
+/* `graph` is a graph result of this handle, of the kinds po_layout_partition takes; it stays valid and unchanged.  A pair
+ * (s, t) of nodes, s != t, is a SUPERBUBBLE iff (1) t is reachable from s; (2) the set U of nodes reachable from s without
+ * passing t equals the set of nodes that reach t without passing s; (3) G[U] is acyclic (a self-loop on any member of U is
+ * a cycle, and so is an edge t -> s); (4) no other t' in U satisfies (1)-(3) with s.  This is the definition of
+ * po_layout_superbubbles applied to the graph itself instead of to its acyclic partition; by the partition theorem of Sung
+ * et al. it is the union of the same definition over everything partition_graph yields (each non-singleton SCC closed by
+ * 'r_' / 're_', then the singletons).  So on the nodes whose SCC is a singleton the four outputs say exactly what
+ * po_layout_superbubbles says (PO_SB_SELF_LOOP is set on every node with an edge (u, u) here, singleton or not).
+ * The outputs, the NULL rules, PO_NO_NODE, the PO_SB_* bits, NESTED and n_inside are those of po_layout_superbubbles.
+ * Not reproduced: the order in which the reference yields the pairs, its random.choice of a DFS root in an SCC without
+ * 'r_', and its behaviour where its finder raises.
+ * The scheme is ROOT SPLITTING: a node is split into a source that keeps its out-edges and a sink
+ * that takes all its in-edges; per level one node of every SCC that is left, until none is; the stage of
+ * po_layout_superbubbles runs on that graph of n_order + n_split ranks.  An SCC that is a whole weakly connected
+ * component (n_rootless) is run once more per node of one shortest cycle through its lowest-ranked node, up to the first
+ * node that lies on every cycle: n_root_runs is 1 + the largest number of such extra runs, at worst the length of that
+ * cycle.  Only integers are involved: every output is the same on every run (round counts and batches are statistics).
+ * An edge with an end that is not in the node order is counted in n_invalid; the call then fails with PO_ERR_INVALID and
+ * writes nothing.  Device memory beyond the inputs is linear: at most 402 bytes per node (308: the workspaces of
+ * po_layout_superbubbles, all but the sort and the node -> rank words twice, for the ranks of the flat graph; 94 its own)
+ * and 25 per edge (17 + 8).  params may be NULL.  An empty graph with an empty order: PO_OK, 0 superbubbles.  Every loop is bounded on the
+ * host: the round loops as in po_layout_superbubbles, the split levels by n_order + 2, the runs by the cycle's length;
+ * reaching a bound is PO_ERR_HIP with a message, never a result.  There is no CPU fallback: without a GPU the call returns
+ * PO_ERR_HIP.  A row result, a result of another handle, reserved != 0, n_bubbles_out NULL: PO_ERR_INVALID.
+ * po_layout_bubblechains, po_layout_contigs and po_phase_paths still work on the acyclic partitions only. */
+po_status po_layout_superbubbles_all(po_handle* h, po_result* graph, const po_superbubble_all_params* params, uint32_t* node_exit_out,
+                                     uint32_t* node_inside_out, uint8_t* node_flags_out, po_superbubble* bubbles_out,
+                                     uint64_t* n_bubbles_out);
+po_status po_get_superbubble_all_stats(const po_handle* h, po_superbubble_all_stats* out);
 
 /* ---------------------------------------------------------------------------------------------
  * The bubble chains of `phasm chain`: build_bubblechains (phasm/assembly_graph.py:594-652), as cli/assembler.py:272

@@ -190,6 +190,22 @@ class PoSuperbubbleStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoSuperbubbleAllParams(ctypes.Structure):
+    _fields_ = [("reserved", ctypes.c_uint32)]
+
+
+class PoSuperbubbleAllStats(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("n_edges", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64), ("n_bubbles", ctypes.c_uint64),
+                ("n_nested", ctypes.c_uint64), ("n_cyclic_bubbles", ctypes.c_uint64), ("n_split", ctypes.c_uint64),
+                ("n_rootless", ctypes.c_uint64), ("n_certified", ctypes.c_uint64), ("n_edge_filtered", ctypes.c_uint64),
+                ("n_split_levels", ctypes.c_uint32), ("n_root_runs", ctypes.c_uint32), ("n_scc_rounds", ctypes.c_uint32),
+                ("n_batches", ctypes.c_uint32), ("ms_ranks", ctypes.c_float), ("ms_split", ctypes.c_float), ("ms_bubbles", ctypes.c_float),
+                ("ms_merge", ctypes.c_float), ("ms_total", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoBubblechainParams(ctypes.Structure):
     _fields_ = [("min_nodes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
@@ -440,6 +456,9 @@ SYMBOLS = [
     ("po_layout_superbubbles", ctypes.c_int, [_P, _P, ctypes.POINTER(PoSuperbubbleParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_superbubble_stats", ctypes.c_int, [_P, ctypes.POINTER(PoSuperbubbleStats)]),
+    ("po_layout_superbubbles_all", ctypes.c_int, [_P, _P, ctypes.POINTER(PoSuperbubbleAllParams), ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_superbubble_all_stats", ctypes.c_int, [_P, ctypes.POINTER(PoSuperbubbleAllStats)]),
     ("po_layout_bubblechains", ctypes.c_int, [_P, _P, ctypes.POINTER(PoBubblechainParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_bubblechain_stats", ctypes.c_int, [_P, ctypes.POINTER(PoBubblechainStats)]),

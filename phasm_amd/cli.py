@@ -296,7 +296,7 @@ def chain_components(args) -> int:
     contigs = getattr(args, "contigs", False)
     g = layout.chain_components(args.graph_gfa, device=args.device, partitions=args.partitions, superbubbles=args.superbubbles,
                                 bubblechains=args.bubblechains or contigs, min_nodes=args.min_nodes, contigs=contigs,
-                                min_length=args.min_length)
+                                min_length=args.min_length, cyclic=getattr(args, "cyclic", False))
     logger.info("Enumerate weakly connected components in the graph...")
     n = layout.write_component_graphs(args.output_dir, g, formats)
     for parts in g.partitions or ():
@@ -312,6 +312,12 @@ def chain_components(args) -> int:
         top = np.bincount(comp_of[entrances[g.superbubbles.table["nested"] == 0]], minlength=len(g.components))
         for i in range(len(g.components)):
             logger.info("Connected component %d: %d superbubbles in its acyclic partition, %d of them not nested.", i, per[i], top[i])
+        if g.superbubbles_all is not None:   # (a superbubble lies in one partition: those the acyclic call lacks lie in an SCC)
+            every = g.superbubbles_all.table["entrance"].astype(np.int64)
+            per_all = np.bincount(comp_of[every], minlength=len(g.components))
+            for i in range(len(g.components)):
+                logger.info("Connected component %d: %d superbubbles in all its partitions, %d of them in non-singleton SCCs.", i,
+                            per_all[i], per_all[i] - per[i])
     if getattr(args, "as_chain", False):   # (the last line of `phasm chain`, assembler.py:308-310)
         logger.info("Built %d bubblechains and %d contigs from %d weakly connected components.",
                     sum(len(x) for x in g.component_chains), sum(len(x) for x in g.component_contigs), n)
@@ -565,6 +571,8 @@ def main(argv=None) -> int:
                    help="with --contigs: drop contigs shorter than this many bases (default: 5000)")
     k.add_argument("--superbubbles", action="store_true",
                    help="also log, per component, the number of superbubbles of its acyclic partition")
+    k.add_argument("--cyclic", action="store_true",
+                   help="with --superbubbles: also log, per component, the superbubbles of all its partitions, the cyclic ones included")
     k.add_argument("--partitions", action="store_true",
                    help="also log, per component, the partitions superbubble detection starts with (strongly connected components)")
     k.add_argument("graph_gfa", help="the graph file (S, F and E lines)")

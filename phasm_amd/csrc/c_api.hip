@@ -44,6 +44,7 @@
 #include "components.hip.h"
 #include "partition.hip.h"
 #include "superbubbles.hip.h"
+#include "cyclic.hip.h"
 #include "bubblechains.hip.h"
 #include "contigs.hip.h"
 #include "phase.hip.h"
@@ -76,6 +77,15 @@ enum { PB_LIVE, PB_SCC, PB_COLOUR, PB_MARK, PB_HASIN, PB_HASOUT, PB_NODESCC, PB_
 // workspaces of po_layout_superbubbles (superbubbles.hip.h) beyond those of the rank scaffold and of po_layout_partition
 enum { UB_CNT, UB_W, UB_CIN, UB_COUT, UB_OFFIN, UB_OFFOUT, UB_CURIN, UB_CUROUT, UB_LISTIN, UB_LISTOUT, UB_LVLF, UB_LVLB, UB_IDOM, UB_IPDOM,
        UB_DEPTH, UB_EXIT, UB_ENCL, UB_INSIDE, UB_TOTAL, UB_DEAD, UB_EXITOUT, UB_INSIDEOUT, UB_FLAGSOUT, UB_TABLE, UB_N };
+// workspaces of po_layout_superbubbles_all (cyclic.hip.h) beyond those of the rank scaffold, po_layout_partition and
+// po_layout_superbubbles, all three for twice the ranks: counters; per rank the split byte and its prefix sum, the root a run
+// gives a rootless SCC, the SCC of the graph itself, the bytes "in a non-singleton SCC" / "lowest rank of a rootless SCC" /
+// "not certified" / "root of the cycle search" / "(s, t) with an edge t -> s" / "has a self-loop", the merged pairs, holders,
+// sizes, totals and bytes, the four words of the cycle search; per flat rank its node and its original rank; per SCC of the
+// flat graph the three lowest ranks; the flat edge list
+enum { YB_CNT, YB_SPLIT, YB_SIDX, YB_ROOTOF, YB_SCC0, YB_CYCLIC0, YB_ROOTLESS, YB_UNCERTAIN, YB_ISROOT, YB_FILTERED, YB_LOOP, YB_MEXIT,
+       YB_MINSIDE, YB_MSIZE, YB_MTOTAL, YB_MISEXIT, YB_MFILTERED, YB_MROOT, YB_DIST, YB_PAR, YB_DIN, YB_PIN, YB_NODE, YB_ORIG, YB_BESTIN,
+       YB_BESTOUT, YB_BESTLOW, YB_FLAT, YB_N };
 // workspaces of po_layout_bubblechains (bubblechains.hip.h) beyond those of the rank scaffold, po_layout_partition and
 // po_layout_superbubbles
 enum { HB_CNT, HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOPS1, HB_NHEAD, HB_NPOS, HB_CB, HB_CN, HB_LAST, HB_CE,
@@ -106,11 +116,11 @@ enum { QB_CNT, QB_NB, QB_COFF, QB_HOME, QB_BIDX, QB_BENT, QB_DONE, QB_COUNT, QB_
 // what a po_phase_paths result holds in HBM (po_result::d_pp): the table, the three CSR pairs, the offsets of the paths
 enum { PR_TABLE, PR_INOFF, PR_INNODES, PR_PREDOFF, PR_PREDNODE, PR_PREDW, PR_BPO, PR_POFF, PR_PATHS, PR_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 96;
+constexpr int EV_LAY_N = 106;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
        EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
-       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94 };
+       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94, EV_CYCLIC = 96 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
 static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
@@ -118,7 +128,8 @@ static_assert(EV_PHASE_INDEX + 4 == EV_RELEVANT, "po_phase_index has four events
 static_assert(EV_RELEVANT + 4 == EV_SPELL, "po_phase_relevant has four events");
 static_assert(EV_SPELL + 2 == EV_PATHS, "po_spell has two events");
 static_assert(EV_PATHS + 11 == EV_WALK, "po_phase_paths has eleven events");
-static_assert(EV_WALK + 2 == EV_LAY_N, "the two events of po_walk_step are the last of the layout events");
+static_assert(EV_WALK + 2 == EV_CYCLIC, "po_walk_step has two events");
+static_assert(EV_CYCLIC + 10 == EV_LAY_N, "the ten events of po_layout_superbubbles_all are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -472,6 +483,9 @@ struct po_handle {
     // the superbubbles of the acyclic partitions (po_layout_superbubbles, superbubbles.hip.h)
     DevBuf d_sb[UB_N];
     po_superbubble_stats sbstats = {};
+    // the superbubbles of the whole graph, the cyclic partitions included (po_layout_superbubbles_all, cyclic.hip.h)
+    DevBuf d_cy[YB_N];
+    po_superbubble_all_stats sastats = {};
     // the bubble chains (po_layout_bubblechains, bubblechains.hip.h)
     DevBuf d_bc[HB_N];
     po_bubblechain_stats bcstats = {};
@@ -4037,20 +4051,10 @@ struct SccOps : RoundOps {
 // events, the caller's stats): ranked_open with the workspaces of d_scc and the caller's `own`, the rounds of scc_drive,
 // the numbering of the roots, the table, the class byte per edge and the flag byte per rank, all left in d_scc; the
 // counters in R.cnt.  Records R.ev[2] behind the rounds.  W is filled whatever the outcome.  !R.ev: nothing to do.
-template <class Stats, class Own>
-po_status scc_stage(po_handle* h, po_result* graph, const std::string& name, int ev_first, Stats& S, Own&& own, RankedGraph& R,
-                    po::SccWork& W, uint32_t& n_scc) {
+// scc_rounds is everything behind the open, on whatever ranks and edge ends R names (po_layout_superbubbles_all: a flat graph).
+po_status scc_rounds(po_handle* h, const std::string& name, const RankedGraph& R, po::SccWork& W, uint32_t& n_scc) {
     hipStream_t st = h->stream;
     DevBuf* B = h->d_scc;
-    // (the identity words land in `colour`: colour[r] = r is where the first forward phase starts anyway)
-    PO_TRY(ranked_open(h, graph, name, ev_first, po::PC_N, S, B[PB_COLOUR], [&](size_t nn, size_t ne) {
-        for (int k : {PB_SCC, PB_COLOUR, PB_NODESCC, PB_FLAGW}) PO_TRY(ensure(h, B[k], nn * 4));
-        for (int k : {PB_LIVE, PB_MARK, PB_HASIN, PB_HASOUT, PB_FLAGS}) PO_TRY(ensure(h, B[k], nn));
-        PO_TRY(ensure(h, B[PB_TABLE], nn * sizeof(po::Scc)));
-        PO_TRY(ensure(h, B[PB_ECLASS], ne));
-        return own(nn, ne);
-    }, R));
-    if (!R.ev) return PO_OK;
     const uint32_t n = R.n, n_order = R.n_order;
     uint32_t *scc = B[PB_SCC].as<uint32_t>(), *colour = B[PB_COLOUR].as<uint32_t>(), *node_scc = B[PB_NODESCC].as<uint32_t>(),
              *flagw = B[PB_FLAGW].as<uint32_t>();
@@ -4084,6 +4088,22 @@ po_status scc_stage(po_handle* h, po_result* graph, const std::string& name, int
         HIP_TRY(h, hipGetLastError());
     }
     return PO_OK;
+}
+
+template <class Stats, class Own>
+po_status scc_stage(po_handle* h, po_result* graph, const std::string& name, int ev_first, Stats& S, Own&& own, RankedGraph& R,
+                    po::SccWork& W, uint32_t& n_scc) {
+    DevBuf* B = h->d_scc;
+    // (the identity words land in `colour`: colour[r] = r is where the first forward phase starts anyway)
+    PO_TRY(ranked_open(h, graph, name, ev_first, po::PC_N, S, B[PB_COLOUR], [&](size_t nn, size_t ne) {
+        for (int k : {PB_SCC, PB_COLOUR, PB_NODESCC, PB_FLAGW}) PO_TRY(ensure(h, B[k], nn * 4));
+        for (int k : {PB_LIVE, PB_MARK, PB_HASIN, PB_HASOUT, PB_FLAGS}) PO_TRY(ensure(h, B[k], nn));
+        PO_TRY(ensure(h, B[PB_TABLE], nn * sizeof(po::Scc)));
+        PO_TRY(ensure(h, B[PB_ECLASS], ne));
+        return own(nn, ne);
+    }, R));
+    if (!R.ev) return PO_OK;
+    return scc_rounds(h, name, R, W, n_scc);
 }
 
 po_status run_partition(po_handle* h, po_result* graph, uint32_t* node_out, uint8_t* flags_out, uint8_t* class_out, po_scc* table_out,
@@ -4131,6 +4151,9 @@ struct SbWork {
     uint32_t n_levels_forward = 0, n_levels_backward = 0, n_scc_rounds = 0, n_level_rounds = 0, n_discard_rounds = 0, n_batches = 0;
 };
 
+template <class Seed>
+po_status superbubble_dag(po_handle* h, const char* const name, const RankedGraph& R, uint32_t n_scc, SbWork& S, Seed&& seed);
+
 // The superbubble stage on the device, as po_layout_superbubbles and po_layout_bubblechains run it (`name`, the first of
 // the caller's events, the caller's stats for ranked_open): scc_stage with the workspaces of d_sb and the caller's `own`,
 // then everything up to the table, all left in d_sb -- the byte "enters a surviving bubble" per rank in R.root, the number
@@ -4139,7 +4162,6 @@ struct SbWork {
 template <class Stats, class Own>
 po_status superbubble_stage(po_handle* h, po_result* graph, const char* const name, int ev_first, Stats& stats, Own&& own, RankedGraph& R,
                             SbWork& S) {
-    hipStream_t st = h->stream;
     DevBuf* B = h->d_sb;
     po::SccWork W;
     uint32_t n_scc = 0;
@@ -4157,9 +4179,19 @@ po_status superbubble_stage(po_handle* h, po_result* graph, const char* const na
     S.n_batches = W.batches;
     PO_TRY(staged);
     if (!R.ev || !R.n_order) return PO_OK;
+    HIP_TRY(h, hipEventRecord(R.ev[3], h->stream));
+    return superbubble_dag(h, name, R, n_scc, S, [] { return false; });
+}
+
+// Everything behind the SCC stage, on whatever ranks and edge ends R names (po_layout_superbubbles_all: a flat graph), with
+// the SCCs, classes and flags that scc_rounds left in d_scc for them.  seed() may mark bubbles dead before the discard rounds
+// (it runs behind k_sb_encl; true: it launched something, so the rounds run even without a self-loop).
+template <class Seed>
+po_status superbubble_dag(po_handle* h, const char* const name, const RankedGraph& R, uint32_t n_scc, SbWork& S, Seed&& seed) {
+    hipStream_t st = h->stream;
+    DevBuf* B = h->d_sb;
     const uint32_t n = R.n, n_order = R.n_order;
     hipEvent_t* ev = R.ev;
-    HIP_TRY(h, hipEventRecord(ev[3], st));
     unsigned long long* cnt = B[UB_CNT].as<unsigned long long>();
     uint32_t *w = B[UB_W].as<uint32_t>(), *cin = B[UB_CIN].as<uint32_t>(), *cout = B[UB_COUT].as<uint32_t>(),
              *off_in = B[UB_OFFIN].as<uint32_t>(), *off_out = B[UB_OFFOUT].as<uint32_t>(), *cur_in = B[UB_CURIN].as<uint32_t>(),
@@ -4228,8 +4260,9 @@ po_status superbubble_stage(po_handle* h, po_result* graph, const char* const na
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[5], st));
     // self-loops discard bubbles, and a discarded bubble the one around it: rounds, bounded by round_phase
-    if (S.n_self_loop_nodes) {
-        hipLaunchKernelGGL(po::k_sb_dead_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, w, idom, exit_of, encl, dead);
+    const bool seeded = seed();
+    if (S.n_self_loop_nodes) hipLaunchKernelGGL(po::k_sb_dead_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, w, idom, exit_of, encl, dead);
+    if (S.n_self_loop_nodes || seeded) {
         how = po::round_phase(ops, n_real, [&](uint32_t j) {
             hipLaunchKernelGGL(po::k_sb_dead_round, dim3(R.rank_grid), dim3(256), 0, st, n_order, exit_of, encl, dead, R.rcnt + j);
         }, S.n_discard_rounds, S.n_batches, ignored);
@@ -4294,6 +4327,250 @@ po_status run_superbubbles(po_handle* h, po_result* graph, uint32_t* exit_out, u
     (void)hipEventElapsedTime(&S.ms_dominators, ev[4], ev[5]);
     (void)hipEventElapsedTime(&S.ms_label, ev[5], ev[6]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[6]);
+    return PO_OK;
+}
+
+// ---- the superbubbles of the whole graph, the cyclic partitions included (po_layout_superbubbles_all, cyclic.hip.h) -------
+
+// Root splitting.  A RUN builds, level by level, a flat graph without a non-singleton SCC -- the SCC
+// stage on the current flat graph (scc_rounds), one more split rank per SCC that is left -- and finds its superbubbles with
+// superbubble_dag; the pairs come back by original rank and are merged into the words of d_cy.  One run suffices unless an
+// SCC is rootless and its lowest rank is not certified; then the nodes of one shortest cycle through that rank root further
+// runs, up to the first certified one.  The levels are bounded by n_order + 2, the runs by the longest of those cycles.
+po_status run_superbubbles_all(po_handle* h, po_result* graph, uint32_t* exit_out, uint32_t* inside_out, uint8_t* flags_out,
+                               po_superbubble* table_out, uint64_t* n_bubbles_out) {
+    const char* const name = "po_layout_superbubbles_all";
+    hipStream_t st = h->stream;
+    po_superbubble_all_stats& S = h->sastats;
+    S = po_superbubble_all_stats();
+    DevBuf *Y = h->d_cy, *P = h->d_scc, *U = h->d_sb, *K = h->d_rank;
+    RankedGraph R;
+    PO_TRY(ranked_open(h, graph, name, EV_CYCLIC, po::PC_N, S, P[PB_COLOUR], [&](size_t nn, size_t ne) {
+        const size_t n2 = 2 * nn;   // (a flat graph has at most twice the ranks)
+        for (int k : {RK_INDEX}) PO_TRY(ensure(h, K[k], n2 * 4));
+        PO_TRY(ensure(h, K[RK_ROOT], n2));
+        for (int k : {PB_SCC, PB_COLOUR, PB_NODESCC, PB_FLAGW}) PO_TRY(ensure(h, P[k], n2 * 4));
+        for (int k : {PB_LIVE, PB_MARK, PB_HASIN, PB_HASOUT, PB_FLAGS}) PO_TRY(ensure(h, P[k], n2));
+        PO_TRY(ensure(h, P[PB_TABLE], n2 * sizeof(po::Scc)));
+        PO_TRY(ensure(h, P[PB_ECLASS], ne));
+        PO_TRY(ensure(h, U[UB_CNT], 128));
+        for (int k : {UB_W, UB_CIN, UB_COUT, UB_OFFIN, UB_OFFOUT, UB_CURIN, UB_CUROUT, UB_LVLF, UB_LVLB, UB_IDOM, UB_IPDOM, UB_DEPTH, UB_EXIT,
+                      UB_ENCL, UB_INSIDE, UB_TOTAL, UB_EXITOUT, UB_INSIDEOUT})
+            PO_TRY(ensure(h, U[k], n2 * 4));
+        for (int k : {UB_DEAD, UB_FLAGSOUT}) PO_TRY(ensure(h, U[k], n2));
+        for (int k : {UB_LISTIN, UB_LISTOUT}) PO_TRY(ensure(h, U[k], ne * 4));
+        PO_TRY(ensure(h, U[UB_TABLE], n2 * sizeof(po::Bubble)));
+        PO_TRY(ensure(h, Y[YB_CNT], 128));
+        for (int k : {YB_SIDX, YB_ROOTOF, YB_SCC0, YB_MEXIT, YB_MINSIDE, YB_MSIZE, YB_MTOTAL, YB_DIST, YB_PAR, YB_DIN, YB_PIN})
+            PO_TRY(ensure(h, Y[k], nn * 4));
+        for (int k : {YB_SPLIT, YB_CYCLIC0, YB_ROOTLESS, YB_UNCERTAIN, YB_ISROOT, YB_FILTERED, YB_LOOP, YB_MISEXIT, YB_MFILTERED, YB_MROOT})
+            PO_TRY(ensure(h, Y[k], nn));
+        for (int k : {YB_NODE, YB_ORIG, YB_BESTIN, YB_BESTOUT, YB_BESTLOW}) PO_TRY(ensure(h, Y[k], n2 * 4));
+        return ensure(h, Y[YB_FLAT], ne * sizeof(po::EdgeRanks));
+    }, R));
+    if (!R.ev || !R.n_order) return PO_OK;
+    R.root = K[RK_ROOT].as<uint8_t>();   // (both grew behind ranked_open's own sizes)
+    R.index = K[RK_INDEX].as<uint32_t>();
+    const uint32_t n = R.n, n0 = R.n_order;
+    hipEvent_t* ev = R.ev;
+    unsigned long long* cnt = Y[YB_CNT].as<unsigned long long>();
+    uint32_t *sidx = Y[YB_SIDX].as<uint32_t>(), *root_of = Y[YB_ROOTOF].as<uint32_t>(), *scc0 = Y[YB_SCC0].as<uint32_t>(),
+             *m_exit = Y[YB_MEXIT].as<uint32_t>(), *m_inside = Y[YB_MINSIDE].as<uint32_t>(), *m_size = Y[YB_MSIZE].as<uint32_t>(),
+             *m_total = Y[YB_MTOTAL].as<uint32_t>(), *dist = Y[YB_DIST].as<uint32_t>(), *par = Y[YB_PAR].as<uint32_t>(),
+             *din = Y[YB_DIN].as<uint32_t>(), *pin = Y[YB_PIN].as<uint32_t>(), *flat_node = Y[YB_NODE].as<uint32_t>(),
+             *orig = Y[YB_ORIG].as<uint32_t>(), *best_in = Y[YB_BESTIN].as<uint32_t>(), *best_out = Y[YB_BESTOUT].as<uint32_t>(),
+             *best_low = Y[YB_BESTLOW].as<uint32_t>();
+    uint8_t *split = Y[YB_SPLIT].as<uint8_t>(), *cyclic0 = Y[YB_CYCLIC0].as<uint8_t>(), *rootless = Y[YB_ROOTLESS].as<uint8_t>(),
+            *uncertain = Y[YB_UNCERTAIN].as<uint8_t>(), *is_root = Y[YB_ISROOT].as<uint8_t>(), *filtered = Y[YB_FILTERED].as<uint8_t>(),
+            *loop = Y[YB_LOOP].as<uint8_t>(), *m_is_exit = Y[YB_MISEXIT].as<uint8_t>(), *m_filtered = Y[YB_MFILTERED].as<uint8_t>(),
+            *m_root = Y[YB_MROOT].as<uint8_t>();
+    po::EdgeRanks* flat = Y[YB_FLAT].as<po::EdgeRanks>();
+    const uint32_t *node_scc = P[PB_NODESCC].as<uint32_t>(), *scc = P[PB_SCC].as<uint32_t>();
+    const po::Scc* scc_table = P[PB_TABLE].as<po::Scc>();
+    const uint8_t* pflags = P[PB_FLAGS].as<uint8_t>();
+    uint32_t *exit_of = U[UB_EXIT].as<uint32_t>(), *inside = U[UB_INSIDE].as<uint32_t>(), *total = U[UB_TOTAL].as<uint32_t>();
+    uint8_t* dead = U[UB_DEAD].as<uint8_t>();
+    volatile uint64_t* C = h->pinned + 96;   // this call's counters on the host
+    auto counters_home = [&]() -> po_status {
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, R.cnt, po::PC_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 96, cnt, po::YC_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        return PO_OK;
+    };
+    // the merged words, the self-loops, every rootless SCC's first root: its lowest rank
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
+    for (uint32_t* p : {m_exit, m_inside, m_size, m_total}) HIP_TRY(h, hipMemsetAsync(p, 0xFF, (size_t)n0 * 4, st));
+    for (uint8_t* p : {loop, m_is_exit, m_filtered, rootless}) HIP_TRY(h, hipMemsetAsync(p, 0, n0, st));
+    if (n) hipLaunchKernelGGL(po::k_cy_loops, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n0, loop);
+    HIP_TRY(h, hipGetLastError());
+    std::vector<uint32_t> roots(n0);
+    for (uint32_t r = 0; r < n0; ++r) roots[r] = r;
+    struct Rootless {
+        uint32_t low;
+        std::vector<uint32_t> cycle;   // the nodes behind `low` on one shortest cycle through it, forward
+        bool done;
+    };
+    std::vector<Rootless> open_sccs;
+    std::vector<uint8_t> bytes_a(n0), bytes_b(n0);
+    float ms_split = 0, ms_bubbles = 0, ms_merge = 0;
+    for (uint32_t run = 0;; ++run) {
+        HIP_TRY(h, hipEventRecord(ev[7], st));
+        HIP_TRY(h, hipMemcpyAsync(root_of, roots.data(), (size_t)n0 * 4, hipMemcpyHostToDevice, st));
+        for (uint8_t* p : {split, uncertain, filtered}) HIP_TRY(h, hipMemsetAsync(p, 0, n0, st));
+        // the levels: the flat graph of the ranks split so far, its SCCs, one more split rank per non-singleton SCC
+        RankedGraph F = R;
+        uint32_t n_split = 0, n_scc = 0;
+        for (uint32_t level = 0;; ++level) {
+            if (level > (uint64_t)n0 + 1) return fail(h, PO_ERR_HIP, std::string("internal: ") + name + " reached its bound of n_order + 2 split levels");
+            const uint32_t n_flat = n0 + n_split;
+            PO_TRY(prefix_sum<uint8_t>(h, split, n0, sidx, &h->pinned[4]));
+            if (n) hipLaunchKernelGGL(po::k_cy_flat, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n0, split, sidx, n_split, flat);
+            hipLaunchKernelGGL(po::k_cy_ranks, dim3(R.rank_grid), dim3(256), 0, st, n0, R.val, split, sidx, n_split, flat_node, orig);
+            HIP_TRY(h, hipMemsetAsync(R.cnt, 0, 128, st));
+            F.ends = flat;
+            F.val = flat_node;
+            F.n_order = n_flat;
+            F.rank_grid = stride_grid(h, n_flat);
+            po::SccWork W;
+            const po_status staged = scc_rounds(h, name, F, W, n_scc);
+            S.n_scc_rounds += W.trim_rounds + W.forward_rounds + W.backward_rounds;
+            S.n_batches += W.batches;
+            PO_TRY(staged);
+            if (h->pinned[4] != n_split) return fail(h, PO_ERR_HIP, std::string("internal: the split ranks of ") + name + " do not add up");
+            if (level == 0) hipLaunchKernelGGL(po::k_cy_level0, dim3(R.rank_grid), dim3(256), 0, st, n0, n_scc, node_scc, scc_table, scc, scc0, cyclic0);
+            if (level == 1) hipLaunchKernelGGL(po::k_cy_uncertain, dim3(R.rank_grid), dim3(256), 0, st, n0, n_scc, node_scc, scc_table, scc0, uncertain);
+            PO_TRY(counters_home());
+            const uint64_t singles = h->pinned[16 + po::PC_SINGLE];
+            if (singles > n_scc || n_scc > n_flat) return fail(h, PO_ERR_HIP, std::string("internal: the SCCs of ") + name + " do not add up");
+            const uint32_t n_cyclic = n_scc - (uint32_t)singles;
+            if (!n_cyclic) break;
+            if (n_cyclic > n0 - n_split) return fail(h, PO_ERR_HIP, std::string("internal: ") + name + " found more SCCs than unsplit nodes");
+            for (uint32_t* p : {best_in, best_out, best_low}) HIP_TRY(h, hipMemsetAsync(p, 0xFF, (size_t)n_scc * 4, st));
+            hipLaunchKernelGGL(po::k_cy_choose, dim3(R.rank_grid), dim3(256), 0, st, n0, n_scc, node_scc, scc_table, pflags, best_in, best_out,
+                               best_low);
+            hipLaunchKernelGGL(po::k_cy_apply, dim3(stride_grid(h, n_scc)), dim3(256), 0, st, n0, n_scc, scc_table, best_in, best_out, best_low,
+                               level == 0 ? root_of : (const uint32_t*)nullptr, level == 0 && run == 0 ? rootless : (uint8_t*)nullptr, split, cnt);
+            HIP_TRY(h, hipGetLastError());
+            n_split += n_cyclic;
+            S.n_split_levels = std::max(S.n_split_levels, level + 1);
+        }
+        S.n_split = std::max<uint64_t>(S.n_split, n_split);
+        if (C[po::YC_BAD]) return fail(h, PO_ERR_HIP, std::string("internal: ") + name + " found no root for an SCC");
+        if (run == 0) S.n_rootless = C[po::YC_ROOTLESS];
+        // the stage of po_layout_superbubbles on the flat graph; the two drops of the lemma seed its discards
+        const uint32_t n_flat = n0 + n_split;
+        F.ev = ev;
+        HIP_TRY(h, hipEventRecord(ev[3], st));
+        SbWork W;
+        const po_status staged = superbubble_dag(h, name, F, n_scc, W, [&] {
+            if (n) hipLaunchKernelGGL(po::k_cy_seed_edges, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n0, n_flat, exit_of, orig, filtered);
+            hipLaunchKernelGGL(po::k_cy_seed_ranks, dim3(R.rank_grid), dim3(256), 0, st, n0, n_flat, exit_of, orig, filtered, dead, m_filtered);
+            return true;
+        });
+        S.n_batches += W.n_batches;
+        PO_TRY(staged);
+        hipLaunchKernelGGL(po::k_cy_merge, dim3(R.rank_grid), dim3(256), 0, st, n0, n_flat, orig, F.root, exit_of, inside, total, m_exit, m_inside,
+                           m_size, m_total, m_is_exit);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(ev[8], st));
+        ++S.n_root_runs;
+        // which rootless SCCs this run's root certified; the others go on along their cycle
+        const bool more = S.n_rootless && (run == 0 || !open_sccs.empty());
+        if (more)
+            PO_TRY(land_outputs(h, {{uncertain, n0, bytes_a.data()}, {rootless, run == 0 ? n0 : 0u, bytes_b.data()}}, cnt, po::YC_N));
+        else
+            HIP_TRY(h, hipStreamSynchronize(st));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[7], ev[3]) == hipSuccess) ms_split += ms;
+        if (hipEventElapsedTime(&ms, ev[3], ev[6]) == hipSuccess) ms_bubbles += ms;
+        if (hipEventElapsedTime(&ms, ev[6], ev[8]) == hipSuccess) ms_merge += ms;
+        if (!more) break;
+        if (run == 0) {
+            uint64_t seen = 0;
+            for (uint32_t r = 0; r < n0; ++r) {
+                if (!bytes_b[r]) continue;
+                ++seen;
+                if (bytes_a[r]) open_sccs.push_back(Rootless{r, {}, false});
+                else ++S.n_certified;
+            }
+            if (seen != S.n_rootless) return fail(h, PO_ERR_HIP, std::string("internal: the rootless SCCs of ") + name + " do not add up");
+            if (open_sccs.empty()) break;
+            // one shortest cycle through the root of each: distances in rounds, the lowest-ranked parents, the walk back
+            hipLaunchKernelGGL(po::k_cy_bfs_init, dim3(R.rank_grid), dim3(256), 0, st, n0, rootless, uncertain, is_root, dist, par, din, pin);
+            RoundOps ops{h, st, R.rcnt};
+            uint32_t rounds = 0;
+            uint64_t ignored = 0;
+            const int how = po::round_phase(ops, n0, [&](uint32_t j) {
+                if (n) hipLaunchKernelGGL(po::k_cy_bfs_round, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n0, is_root, dist, din, R.rcnt + j);
+            }, rounds, S.n_batches, ignored);
+            if (how == po::ROUNDS_FAILED) HIP_TRY(h, ops.err != hipSuccess ? ops.err : hipErrorUnknown);
+            if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, std::string("internal: the cycle search of ") + name + " reached its bound of n_order + 2 rounds");
+            if (n) hipLaunchKernelGGL(po::k_cy_bfs_parents, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n0, is_root, dist, din, par, pin);
+            std::vector<uint32_t> h_par(n0), h_din(n0), h_pin(n0);
+            PO_TRY(land_outputs(h, {{par, (size_t)n0 * 4, h_par.data()}, {din, (size_t)n0 * 4, h_din.data()}, {pin, (size_t)n0 * 4, h_pin.data()}},
+                                cnt, po::YC_N));
+            for (Rootless& x : open_sccs) {
+                const uint32_t len = h_din[x.low];
+                uint32_t v = h_pin[x.low];
+                bool ok = len >= 1 && len <= n0;
+                for (uint32_t i = 1; ok && i < len; ++i) {
+                    ok = v < n0 && v != x.low;
+                    if (ok) {
+                        x.cycle.push_back(v);
+                        v = h_par[v];
+                    }
+                }
+                if (!ok || v != x.low) return fail(h, PO_ERR_HIP, std::string("internal: the cycle walk of ") + name + " does not close");
+                std::reverse(x.cycle.begin(), x.cycle.end());
+            }
+        } else {
+            for (Rootless& x : open_sccs)
+                if (!x.done && !bytes_a[x.low]) {
+                    x.done = true;
+                    ++S.n_certified;
+                }
+        }
+        bool any = false;
+        for (Rootless& x : open_sccs) {
+            if (x.done) continue;
+            if (run >= x.cycle.size()) {   // the end of the cycle
+                x.done = true;
+                continue;
+            }
+            roots[x.low] = x.cycle[run];
+            any = true;
+        }
+        if (!any) break;
+    }
+    // the outputs by rank, the table in entrance-rank order
+    hipLaunchKernelGGL(po::k_cy_final, dim3(R.rank_grid), dim3(256), 0, st, n0, R.val, m_exit, m_inside, m_is_exit, loop, m_filtered, cyclic0,
+                       m_root, U[UB_EXITOUT].as<uint32_t>(), U[UB_INSIDEOUT].as<uint32_t>(), U[UB_FLAGSOUT].as<uint8_t>(), cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint8_t>(h, m_root, n0, R.index, &h->pinned[2]));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n64 = h->pinned[2];
+    if (n64 > n0) return fail(h, PO_ERR_HIP, std::string("internal: the bubbles of ") + name + " do not add up");
+    const uint32_t n_bubbles = (uint32_t)n64;
+    if (n_bubbles)
+        hipLaunchKernelGGL(po::k_sb_table, dim3(R.rank_grid), dim3(256), 0, st, n0, n_bubbles, R.val, m_root, R.index, m_exit, m_inside, m_total,
+                           U[UB_TABLE].as<po::Bubble>());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[9], st));
+    PO_TRY(land_outputs(h, {{U[UB_TABLE].p, (size_t)n_bubbles * sizeof(po_superbubble), table_out},
+                            {U[UB_EXITOUT].p, (size_t)n0 * 4, exit_out}, {U[UB_INSIDEOUT].p, (size_t)n0 * 4, inside_out},
+                            {U[UB_FLAGSOUT].p, n0, flags_out}}, cnt, po::YC_N));
+    S.n_bubbles = n_bubbles;
+    S.n_nested = h->pinned[16 + po::YC_NESTED];
+    S.n_cyclic_bubbles = h->pinned[16 + po::YC_CYCLIC];
+    S.n_edge_filtered = h->pinned[16 + po::YC_FILTERED];
+    if (S.n_nested > n_bubbles || S.n_cyclic_bubbles > n_bubbles) return fail(h, PO_ERR_HIP, std::string("internal: the counts of ") + name + " do not add up");
+    *n_bubbles_out = n_bubbles;
+    S.ms_split = ms_split;
+    S.ms_bubbles = ms_bubbles;
+    S.ms_merge = ms_merge;
+    (void)hipEventElapsedTime(&S.ms_ranks, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[9]);
     return PO_OK;
 }
 
@@ -6058,6 +6335,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_cc) b.release();
         for (DevBuf& b : h->d_scc) b.release();
         for (DevBuf& b : h->d_sb) b.release();
+        for (DevBuf& b : h->d_cy) b.release();
         for (DevBuf& b : h->d_bc) b.release();
         for (DevBuf& b : h->d_ct) b.release();
         for (DevBuf& b : h->d_ph) b.release();
@@ -7921,6 +8199,15 @@ po_status po_layout_superbubbles(po_handle* h, po_result* graph, const po_superb
 }
 
 po_status po_get_superbubble_stats(const po_handle* h, po_superbubble_stats* out) { return get_stats(h, &po_handle::sbstats, out); }
+
+po_status po_layout_superbubbles_all(po_handle* h, po_result* graph, const po_superbubble_all_params* params, uint32_t* node_exit_out,
+                                     uint32_t* node_inside_out, uint8_t* node_flags_out, po_superbubble* bubbles_out, uint64_t* n_bubbles_out) {
+    return graph_call(h, graph, "po_layout_superbubbles_all", !params || params->reserved == 0, "superbubbles", n_bubbles_out, [&] {
+        return run_superbubbles_all(h, graph, node_exit_out, node_inside_out, node_flags_out, bubbles_out, n_bubbles_out);
+    });
+}
+
+po_status po_get_superbubble_all_stats(const po_handle* h, po_superbubble_all_stats* out) { return get_stats(h, &po_handle::sastats, out); }
 
 po_status po_layout_bubblechains(po_handle* h, po_result* graph, const po_bubblechain_params* params, uint32_t* node_chain_out,
                                  uint32_t* node_bubble_out, uint32_t* edge_chain_out, po_bubblechain* chains_out, uint64_t* n_chains_out) {

@@ -37,8 +37,9 @@ starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).
 ``component{i}.contig{j}.*`` and the edge attribute ``contig``: every file `phasm chain` writes.
 What follows that point: of `phasm phase` the scoring and pruning of the haplotype extensions at one bubble is
 ``phasm_amd.phasing`` (``po_phase_branch``), as are the relevant reads of a bubble (``po_phase_index``, ``po_phase_relevant``);
-``graph_to_dag`` for the cyclic partitions and the rest of phasing (the bubble walk, new blocks, spelling sequences) are out
-of scope.
+the superbubbles of the cyclic partitions (what the reference reaches through ``graph_to_dag``) come from
+``superbubbles(..., cyclic=True)`` (``po_layout_superbubbles_all``, root splitting: DESIGN.md section 3.9t); the chains, the
+contigs and the paths still take the acyclic partitions only.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -651,9 +652,15 @@ def _groups_by_value(values: np.ndarray, ranks: np.ndarray) -> dict:
     return out
 
 
-def superbubbles(ov: ExactOverlapper, graph_res: OverlapResult) -> Superbubbles:
+def superbubbles(ov, graph_res: Optional[OverlapResult], cyclic: bool = False) -> Superbubbles:
     """``po_layout_superbubbles`` on a graph result of ``ov`` (an edge result, a merged graph or a ``graph_from_edges``
-    result), which stays valid and in HBM."""
+    result), which stays valid and in HBM.  ``cyclic=True``: ``po_layout_superbubbles_all`` instead -- the superbubbles of
+    the whole graph, those of the cyclic partitions included; ``ov`` may then be a
+    ``cyclic.HostSuperbubblesAll``, which holds its own graph (``graph_res`` is ignored)."""
+    if cyclic:
+        order = graph_res.node_order() if isinstance(ov, ExactOverlapper) else ov.node_order()
+        node_exit, node_inside, flags, table = ov.layout_superbubbles_all(graph_res, len(order))
+        return Superbubbles(order, node_exit, node_inside, flags, table, ov.superbubble_all_stats())
     order = graph_res.node_order()
     node_exit, node_inside, flags, table = ov.layout_superbubbles(graph_res, len(order))
     return Superbubbles(order, node_exit, node_inside, flags, table, ov.superbubble_stats())
@@ -819,7 +826,8 @@ def induced_edges(graph_edges: np.ndarray, nodes: Sequence[int]) -> np.ndarray:
 class ChainGraph:
     """What ``chain_components`` hands to the writers: the graph file as read (``phasm_amd.io.gfa.GraphFile``) and its
     components; with ``partitions=True`` also the strongly connected components and, per component, the partitions that
-    superbubble detection starts with; with ``superbubbles=True`` also the superbubbles of the acyclic partitions; with
+    superbubble detection starts with; with ``superbubbles=True`` also the superbubbles of the acyclic partitions (with
+    ``cyclic=True`` on top those of all partitions, the cyclic ones included, in ``superbubbles_all``); with
     ``bubblechains=True`` also the bubble chains and, per component, the chains in it (``chains_by_component``); with
     ``contigs=True`` also the contigs outside the chains and, per component, the contigs in it (``contigs_by_component``)."""
     graph: object
@@ -827,6 +835,7 @@ class ChainGraph:
     sccs: Optional[StrongComponents] = None
     partitions: Optional[List[List[Partition]]] = None
     superbubbles: Optional[Superbubbles] = None
+    superbubbles_all: Optional[Superbubbles] = None
     bubblechains: Optional[BubbleChains] = None
     component_chains: Optional[List[List[int]]] = None
     contigs: Optional[Contigs] = None
@@ -834,10 +843,12 @@ class ChainGraph:
 
 
 def chain_components(path: str, device: Optional[int] = None, partitions: bool = False, superbubbles: bool = False,
-                     bubblechains: bool = False, min_nodes: int = 1, contigs: bool = False, min_length: int = 5000) -> ChainGraph:
+                     bubblechains: bool = False, min_nodes: int = 1, contigs: bool = False, min_length: int = 5000,
+                     cyclic: bool = False) -> ChainGraph:
     """The start of `phasm chain` on a graph file: ``read_graph_gfa``, one segment per ``S`` line on a fresh handle, the
     graph on the device (``graph_from_edges``) and its weakly connected components; with ``partitions`` also
-    ``strongly_connected_components`` and ``superbubble_partitions``; with ``superbubbles`` also ``superbubbles``; with
+    ``strongly_connected_components`` and ``superbubble_partitions``; with ``superbubbles`` also ``superbubbles`` (and with
+    ``cyclic`` on top ``superbubbles(..., cyclic=True)``: those of all partitions, in ``superbubbles_all``); with
     ``bubblechains`` also ``bubble_chains`` (``min_nodes`` as in ``build_bubblechains``) and ``chains_by_component``; with
     ``contigs`` also ``identify_contigs`` outside those chains (``min_length`` as `phasm chain -l`) and
     ``contigs_by_component``."""
@@ -856,6 +867,8 @@ def chain_components(path: str, device: Optional[int] = None, partitions: bool =
                 out.partitions = superbubble_partitions(out.sccs, out.components)
             if superbubbles:
                 out.superbubbles = _superbubbles(ov, res)
+                if cyclic:
+                    out.superbubbles_all = _superbubbles(ov, res, cyclic=True)
             if bubblechains:
                 out.bubblechains = bubble_chains(ov, res, min_nodes, out.superbubbles)
                 out.component_chains = chains_by_component(out.bubblechains, out.components)

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats, PoSpellInput, PoSpellStats
+from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, PoSuperbubbleAllParams, PoSuperbubbleAllStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats, PoSpellInput, PoSpellStats
 from .phasing import BubblePaths, RelevantReads
 from .spelling import spell_arrays
 
@@ -665,6 +665,16 @@ class ExactOverlapper:
 
     def superbubble_stats(self) -> dict:
         return self._stats(self._lib.po_get_superbubble_stats, PoSuperbubbleStats)
+
+    def layout_superbubbles_all(self, graph: OverlapResult, n_order: Optional[int] = None):
+        """``po_layout_superbubbles_all``: the superbubbles of the whole graph, the cyclic partitions included, by root
+        splitting (DESIGN.md section 3.9t).  ``graph`` stays valid and in HBM.  Returns what ``layout_superbubbles`` returns;
+        on the nodes whose SCC is a singleton the entries are the same."""
+        return self._graph_stage(self._lib.po_layout_superbubbles_all, graph, PoSuperbubbleAllParams(0), n_order,
+                                 [(np.uint32, "node"), (np.uint32, "node"), (np.uint8, "node"), (SUPERBUBBLE_DTYPE, "node")])
+
+    def superbubble_all_stats(self) -> dict:
+        return self._stats(self._lib.po_get_superbubble_all_stats, PoSuperbubbleAllStats)
 
     def layout_bubblechains(self, graph: OverlapResult, min_nodes: int = 1, n_order: Optional[int] = None):
         """``po_layout_bubblechains``: the bubble chains of a graph result (of the kinds ``layout_components`` takes), which

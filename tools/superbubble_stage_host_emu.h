@@ -1,4 +1,4 @@
-// What superbubbles_host_emu.cpp and bubblechains_host_emu.cpp share: the SCC stage and the superbubble stage behind the rank
+// What superbubbles_host_emu.cpp, bubblechains_host_emu.cpp and cyclic_host_emu.cpp share: the SCC stage and the superbubble stage behind the rank
 // prologue of rank_host_emu.h, launched as scc_stage and superbubble_stage (c_api.hip) launch them -- the same memsets, the
 // same bounds, the batches and the stop at the first round that changes nothing from round_phase of components.hip.h.
 // Included after superbubbles.hip.h, `using namespace po` and rank_host_emu.h.  The workspaces start as a call before could
@@ -74,10 +74,17 @@ struct SuperbubbleStage {
     uint64_t n_real = 0, n_dedges = 0, levels_f = 0, levels_b = 0, beyond = 0, per_level = 0;
 
     // false: a bound was reached and "bound WHAT" is on stdout.  With an empty order only the SCC stage runs.
-    bool run(RankedInput& g, std::vector<uint32_t>& colour);
+    bool run(RankedInput& g, std::vector<uint32_t>& colour) {
+        if (!scc_rounds(g, colour)) return false;
+        return !g.n_order || dag(g, [] { return false; });
+    }
+    // the two halves, as scc_rounds and superbubble_dag (c_api.hip) launch them; cyclic_host_emu.cpp runs them on flat graphs.
+    // seed() may mark bubbles dead before the discard rounds (true: it did something, so the rounds run)
+    bool scc_rounds(RankedInput& g, std::vector<uint32_t>& colour);
+    template <class Seed> bool dag(RankedInput& g, Seed&& seed);
 };
 
-inline bool SuperbubbleStage::run(RankedInput& g, std::vector<uint32_t>& colour) {
+inline bool SuperbubbleStage::scc_rounds(RankedInput& g, std::vector<uint32_t>& colour) {
     const uint32_t n = g.n, n_order = g.n_order, nn = g.nn;
     const std::vector<EdgeRanks>& ends = g.ends;
     // ---- the SCC stage, as scc_stage launches it
@@ -102,7 +109,13 @@ inline bool SuperbubbleStage::run(RankedInput& g, std::vector<uint32_t>& colour)
         LAUNCH(3, 4, k_scc_flags(n_order, n_scc, node_scc.data(), flagw.data(), sccs.data(), pflags.data()));
         LAUNCH(3, 4, k_scc_max(sccs.data(), n_scc, g.cnt));
     }
-    if (!n_order) return true;
+    return true;
+}
+
+template <class Seed>
+inline bool SuperbubbleStage::dag(RankedInput& g, Seed&& seed) {
+    const uint32_t n = g.n, n_order = g.n_order, nn = g.nn;
+    const std::vector<EdgeRanks>& ends = g.ends;
     // ---- the superbubbles, as run_superbubbles launches them
     for (auto* v : {&w, &cin, &cout, &off_in, &off_out, &cur_in, &cur_out, &lvl_f, &lvl_b, &idom, &ipdom, &depth, &exit_of, &encl, &inside, &total,
                     &d_exit, &d_inside})
@@ -145,8 +158,9 @@ inline bool SuperbubbleStage::run(RankedInput& g, std::vector<uint32_t>& colour)
     LAUNCH(3, 4, k_sb_pairs(n_order, w.data(), idom.data(), ipdom.data(), exit_of.data()));
     for (uint32_t l = 1; l <= levels_f; ++l, ++per_level)
         LAUNCH(3, 4, k_sb_encl(n_order, l, lvl_f.data(), idom.data(), exit_of.data(), encl.data()));
-    if (cnt[BC_LOOPS]) {
-        LAUNCH(3, 4, k_sb_dead_init(n_order, w.data(), idom.data(), exit_of.data(), encl.data(), dead.data()));
+    const bool seeded = seed();
+    if (cnt[BC_LOOPS]) LAUNCH(3, 4, k_sb_dead_init(n_order, w.data(), idom.data(), exit_of.data(), encl.data(), dead.data()));
+    if (cnt[BC_LOOPS] || seeded) {
         how = round_phase(ops, n_real, [&](uint32_t j) {
             ops.note(j);
             LAUNCH(3, 4, k_sb_dead_round(n_order, exit_of.data(), encl.data(), dead.data(), ops.rcnt + j));
