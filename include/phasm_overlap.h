@@ -802,7 +802,8 @@ typedef struct {
  * host: the round loops as in po_layout_superbubbles, the split levels by n_order + 2, the runs by the cycle's length;
  * reaching a bound is PO_ERR_HIP with a message, never a result.  There is no CPU fallback: without a GPU the call returns
  * PO_ERR_HIP.  A row result, a result of another handle, reserved != 0, n_bubbles_out NULL: PO_ERR_INVALID.
- * po_layout_bubblechains, po_layout_contigs and po_phase_paths still work on the acyclic partitions only. */
+ * po_layout_bubblechains_all and po_layout_contigs_all build on this call's stage; po_layout_bubblechains, po_layout_contigs
+ * and po_phase_paths still work on the acyclic partitions only. */
 po_status po_layout_superbubbles_all(po_handle* h, po_result* graph, const po_superbubble_all_params* params, uint32_t* node_exit_out,
                                      uint32_t* node_inside_out, uint8_t* node_flags_out, po_superbubble* bubbles_out,
                                      uint64_t* n_bubbles_out);
@@ -874,6 +875,66 @@ po_status po_layout_bubblechains(po_handle* h, po_result* graph, const po_bubble
                                  uint32_t* node_bubble_out, uint32_t* edge_chain_out, po_bubblechain* chains_out,
                                  uint64_t* n_chains_out);
 po_status po_get_bubblechain_stats(const po_handle* h, po_bubblechain_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The bubble chains of the WHOLE graph, the cyclic partitions included: po_layout_bubblechains behind the stage of
+ * po_layout_superbubbles_all instead of po_layout_superbubbles.  A weak component that is one cycle (a circular chromosome,
+ * a plasmid) becomes a RING CHAIN.
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint64_t n_nodes;            /* the fields of po_bubblechain_stats, with the same meaning ...                */
+    uint64_t n_edges;
+    uint64_t n_bubbles;          /* superbubbles of the whole graph, nested ones included                        */
+    uint64_t n_top;
+    uint64_t n_chains;
+    uint64_t n_short;
+    uint64_t n_chain_nodes, n_chain_edges;
+    uint64_t n_invalid;
+    uint64_t n_ring_chains;      /* ... and: ring chains found, those that min_nodes dropped included            */
+    uint64_t n_ring_bubbles;     /* top-level bubbles on them                                                    */
+    uint64_t n_cyclic_bubbles;   /* as po_superbubble_all_stats; 0: the election of the ring leaders did not run */
+    uint32_t max_chain_bubbles;
+    uint32_t n_nest_rounds, n_chain_rounds;
+    uint32_t n_batches;
+    uint32_t n_ring_rounds;      /* rounds of the election: ceil(log2(n_top)) + 1 where it ran, else 0           */
+    uint32_t n_root_runs, n_split_levels;   /* of the first stage, as po_superbubble_all_stats                   */
+    uint32_t reserved;
+    float ms_superbubbles, ms_chains, ms_label, ms_total;
+} po_bubblechain_all_stats;
+
+/* `graph` is a graph result of this handle, of the kinds po_layout_superbubbles_all takes; it stays valid and unchanged.
+ * Ranks, superbubbles, `nested` and the node_inside chains are exactly those of po_layout_superbubbles_all.  TOP-LEVEL
+ * bubbles, LINKS, the NODES and EDGES of a chain, the min_nodes filter, the four outputs, their NULL rules and PO_NO_NODE are
+ * those of po_layout_bubblechains.  A node still enters at most one top-level bubble and exits at most one, but inside an
+ * SCC the links need not be acyclic: they form disjoint paths and RINGS, (s0, s1) -> (s1, s2) -> ... -> (sk-1, s0).  A
+ * path is a chain as before, its HEAD the entrance that is no top-level exit.  A RING CHAIN holds ALL the bubbles of its
+ * ring; its head is the entrance with the lowest rank on the ring, the positions count the bubbles from there along the
+ * links, and
+ *   last_exit == first_entrance     (this equality marks a ring chain: on a path chain the two differ)
+ *   n_bubbles                       all bubbles of the ring
+ *   node_bubble_out of the head     0, the bubble it enters (it is also the exit of the last bubble)
+ * Chains, rings among them, are numbered by the rank of their heads.  On a graph in which every SCC is a singleton the
+ * outputs are byte-equal to po_layout_bubblechains'.
+ * Not reproduced, beyond what po_layout_bubblechains and po_layout_superbubbles_all list: on a ring the reference's
+ * build_bubblechains starts its walk at an arbitrary entrance (the iteration order of a Python set) and stops ONE BUBBLE
+ * SHORT, because at the closing bubble both ends are already visited; its node set is this call's minus the strict
+ * interior of exactly one top-level bubble of the ring (DESIGN.md section 3.9u has the evidence).
+ * The ring leaders are elected by a fixed number of pointer-doubling rounds, ceil(log2(n_top)) + 1, without a readback;
+ * the election runs only when the first stage reported n_cyclic_bubbles > 0.  Only integers are involved: every output is
+ * the same on every run.  An edge with an end that is not in the node order is counted in n_invalid; the call then fails
+ * with PO_ERR_INVALID and writes nothing.  Device memory beyond the inputs is linear: at most 510 bytes per node (402 of them
+ * po_layout_superbubbles_all's, whose workspaces the call fills first; 92 those of po_layout_bubblechains; 16 the two buffer
+ * pairs of the election) and 29 per edge (25 + 4).  params may be NULL (min_nodes 1).  An empty graph with an empty order:
+ * PO_OK, 0 chains.  Every loop is bounded on the host as in po_layout_superbubbles_all and po_layout_bubblechains, the
+ * election by its fixed count; heads and ring leaders that do not add up, or a node whose ranking reached no head, are
+ * PO_ERR_HIP with a message, never a result.  There is no CPU fallback: without a GPU the call returns PO_ERR_HIP.  A row
+ * result, a result of another handle, reserved != 0, min_nodes == 0, n_chains_out NULL: PO_ERR_INVALID.
+ * po_phase_paths, and with it `phasm phase` and the walk, still take the acyclic partitions only. */
+po_status po_layout_bubblechains_all(po_handle* h, po_result* graph, const po_bubblechain_params* params, uint32_t* node_chain_out,
+                                     uint32_t* node_bubble_out, uint32_t* edge_chain_out, po_bubblechain* chains_out,
+                                     uint64_t* n_chains_out);
+po_status po_get_bubblechain_all_stats(const po_handle* h, po_bubblechain_all_stats* out);
 
 /* ---------------------------------------------------------------------------------------------
  * The contigs of `phasm chain` outside the bubble chains: identify_contigs (phasm/assembly_graph.py:655-718), as
@@ -950,6 +1011,15 @@ typedef struct {
 po_status po_layout_contigs(po_handle* h, po_result* graph, const po_contig_params* params, const uint8_t* exclude_in,
                             uint32_t* edge_contig_out, uint32_t* edge_pos_out, po_contig* contigs_out, uint64_t* n_contigs_out);
 po_status po_get_contig_stats(const po_handle* h, po_contig_stats* out);
+
+/* po_layout_contigs with the chains of po_layout_bubblechains_all: with exclude_in == NULL the call runs that call's stages
+ * first and X = the nodes that carry one of ITS chains after the min_nodes filter, ring chains included, so no piece of a
+ * circular component that is a ring chain is reported as a contig.  The definition of the contigs, the parameters, the
+ * outputs, their NULL rules, the limits and the errors are those of po_layout_contigs; with exclude_in != NULL the two calls
+ * do the same.  Device memory: as po_layout_contigs, with what po_layout_bubblechains_all takes in place of
+ * po_layout_bubblechains.  The stats are those of po_get_contig_stats. */
+po_status po_layout_contigs_all(po_handle* h, po_result* graph, const po_contig_params* params, const uint8_t* exclude_in,
+                                uint32_t* edge_contig_out, uint32_t* edge_pos_out, po_contig* contigs_out, uint64_t* n_contigs_out);
 
 /* ---------------------------------------------------------------------------------------------
  * The hot loop of `phasm phase`: BubbleChainPhaser.branch -- generate_new_hsets and calculate_rl, phasm/phasing.py:421-480,

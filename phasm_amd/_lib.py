@@ -222,6 +222,18 @@ class PoBubblechainStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoBubblechainAllStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+                    "n_nodes", "n_edges", "n_bubbles", "n_top", "n_chains", "n_short", "n_chain_nodes", "n_chain_edges", "n_invalid",
+                    "n_ring_chains", "n_ring_bubbles", "n_cyclic_bubbles")] + \
+               [(name, ctypes.c_uint32) for name in ("max_chain_bubbles", "n_nest_rounds", "n_chain_rounds", "n_batches", "n_ring_rounds",
+                                                     "n_root_runs", "n_split_levels", "reserved")] + \
+               [(name, ctypes.c_float) for name in ("ms_superbubbles", "ms_chains", "ms_label", "ms_total")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoContigParams(ctypes.Structure):
     _fields_ = [("min_contig_len", ctypes.c_uint64), ("min_nodes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
@@ -462,6 +474,11 @@ SYMBOLS = [
     ("po_layout_bubblechains", ctypes.c_int, [_P, _P, ctypes.POINTER(PoBubblechainParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_bubblechain_stats", ctypes.c_int, [_P, ctypes.POINTER(PoBubblechainStats)]),
+    ("po_layout_bubblechains_all", ctypes.c_int, [_P, _P, ctypes.POINTER(PoBubblechainParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_get_bubblechain_all_stats", ctypes.c_int, [_P, ctypes.POINTER(PoBubblechainAllStats)]),
+    ("po_layout_contigs_all", ctypes.c_int, [_P, _P, ctypes.POINTER(PoContigParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_layout_contigs", ctypes.c_int, [_P, _P, ctypes.POINTER(PoContigParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_contig_stats", ctypes.c_int, [_P, ctypes.POINTER(PoContigStats)]),

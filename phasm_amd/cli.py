@@ -572,7 +572,8 @@ def main(argv=None) -> int:
     k.add_argument("--superbubbles", action="store_true",
                    help="also log, per component, the number of superbubbles of its acyclic partition")
     k.add_argument("--cyclic", action="store_true",
-                   help="with --superbubbles: also log, per component, the superbubbles of all its partitions, the cyclic ones included")
+                   help="with --superbubbles: also log, per component, the superbubbles of all its partitions, the cyclic ones included; "
+                        "with --bubblechains / --contigs: build them on those superbubbles, so a circular component is one ring chain")
     k.add_argument("--partitions", action="store_true",
                    help="also log, per component, the partitions superbubble detection starts with (strongly connected components)")
     k.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
@@ -585,6 +586,9 @@ def main(argv=None) -> int:
     m.add_argument("-f", "--format", default="gfa2", help="comma separated: gfa1, gfa2, graphml (default: gfa2)")
     m.add_argument("-o", "--output-dir", required=True)
     m.add_argument("--device", type=int, default=None)
+    m.add_argument("--cyclic", action="store_true",
+                   help="build the chains on the superbubbles of all partitions, the cyclic ones included: a circular component is one "
+                        "ring chain that holds all its bubbles (the reference stops one bubble short of closing the ring)")
     m.add_argument("graph_gfa", help="the graph file (S, F and E lines)")
     m.set_defaults(func=chain_components, bubblechains=True, contigs=True, min_nodes=1, superbubbles=False, partitions=False, as_chain=True)
     sc = sub.add_parser("spell-contigs", help="Per graph file that is one simple path (or one node) its sequence as one FASTA entry "

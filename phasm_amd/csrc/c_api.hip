@@ -30,6 +30,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -46,6 +47,7 @@
 #include "superbubbles.hip.h"
 #include "cyclic.hip.h"
 #include "bubblechains.hip.h"
+#include "ringchains.hip.h"
 #include "contigs.hip.h"
 #include "phase.hip.h"
 #include "relevant.hip.h"
@@ -87,9 +89,10 @@ enum { YB_CNT, YB_SPLIT, YB_SIDX, YB_ROOTOF, YB_SCC0, YB_CYCLIC0, YB_ROOTLESS, Y
        YB_MINSIDE, YB_MSIZE, YB_MTOTAL, YB_MISEXIT, YB_MFILTERED, YB_MROOT, YB_DIST, YB_PAR, YB_DIN, YB_PIN, YB_NODE, YB_ORIG, YB_BESTIN,
        YB_BESTOUT, YB_BESTLOW, YB_FLAT, YB_N };
 // workspaces of po_layout_bubblechains (bubblechains.hip.h) beyond those of the rank scaffold, po_layout_partition and
-// po_layout_superbubbles
+// po_layout_superbubbles; the last four are the two buffer pairs of the ring election (ringchains.hip.h), which only
+// po_layout_bubblechains_all and po_layout_contigs_all take
 enum { HB_CNT, HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOPS1, HB_NHEAD, HB_NPOS, HB_CB, HB_CN, HB_LAST, HB_CE,
-       HB_CHAINOUT, HB_BUBBLEOUT, HB_EDGEOUT, HB_TABLE, HB_N };
+       HB_CHAINOUT, HB_BUBBLEOUT, HB_EDGEOUT, HB_TABLE, HB_RPTR0, HB_RPTR1, HB_RMN0, HB_RMN1, HB_N };
 // workspaces of po_layout_contigs (contigs.hip.h) beyond those of the rank scaffold and, without an exclude set from the caller,
 // of the three stages that po_layout_bubblechains runs
 enum { CB_CNT, CB_EXCL, CB_LEN, CB_INDEG, CB_OUTDEG, CB_INE, CB_NLEN, CB_CLS, CB_JB0, CB_JB1, CB_HOPS0, CB_HOPS1, CB_WS0, CB_WS1, CB_CJ0,
@@ -116,11 +119,11 @@ enum { QB_CNT, QB_NB, QB_COFF, QB_HOME, QB_BIDX, QB_BENT, QB_DONE, QB_COUNT, QB_
 // what a po_phase_paths result holds in HBM (po_result::d_pp): the table, the three CSR pairs, the offsets of the paths
 enum { PR_TABLE, PR_INOFF, PR_INNODES, PR_PREDOFF, PR_PREDNODE, PR_PREDW, PR_BPO, PR_POFF, PR_PATHS, PR_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 106;
+constexpr int EV_LAY_N = 134;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
        EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
-       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94, EV_CYCLIC = 96 };
+       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94, EV_CYCLIC = 96, EV_CHAINS_ALL = 106, EV_CONTIGS_ALL = 118 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
 static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
@@ -129,7 +132,9 @@ static_assert(EV_RELEVANT + 4 == EV_SPELL, "po_phase_relevant has four events");
 static_assert(EV_SPELL + 2 == EV_PATHS, "po_spell has two events");
 static_assert(EV_PATHS + 11 == EV_WALK, "po_phase_paths has eleven events");
 static_assert(EV_WALK + 2 == EV_CYCLIC, "po_walk_step has two events");
-static_assert(EV_CYCLIC + 10 == EV_LAY_N, "the ten events of po_layout_superbubbles_all are the last of the layout events");
+static_assert(EV_CYCLIC + 10 == EV_CHAINS_ALL, "po_layout_superbubbles_all has ten events");
+static_assert(EV_CHAINS_ALL + 12 == EV_CONTIGS_ALL, "po_layout_bubblechains_all has twelve events: those ten and two of its own");
+static_assert(EV_CONTIGS_ALL + 16 == EV_LAY_N, "the sixteen events of po_layout_contigs_all are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -489,6 +494,7 @@ struct po_handle {
     // the bubble chains (po_layout_bubblechains, bubblechains.hip.h)
     DevBuf d_bc[HB_N];
     po_bubblechain_stats bcstats = {};
+    po_bubblechain_all_stats bcastats = {};   // (po_layout_bubblechains_all: the same stage behind po_layout_superbubbles_all's)
     // the contigs outside the bubble chains (po_layout_contigs, contigs.hip.h)
     DevBuf d_ct[CB_N];
     po_contig_stats ctstats = {};
@@ -4337,15 +4343,19 @@ po_status run_superbubbles(po_handle* h, po_result* graph, uint32_t* exit_out, u
 // superbubble_dag; the pairs come back by original rank and are merged into the words of d_cy.  One run suffices unless an
 // SCC is rootless and its lowest rank is not certified; then the nodes of one shortest cycle through that rank root further
 // runs, up to the first certified one.  The levels are bounded by n_order + 2, the runs by the longest of those cycles.
-po_status run_superbubbles_all(po_handle* h, po_result* graph, uint32_t* exit_out, uint32_t* inside_out, uint8_t* flags_out,
-                               po_superbubble* table_out, uint64_t* n_bubbles_out) {
-    const char* const name = "po_layout_superbubbles_all";
+//
+// The stage, as po_layout_superbubbles_all, po_layout_bubblechains_all and po_layout_contigs_all run it (`name`, the first of
+// the caller's ten events, the caller's stats for ranked_open, the caller's `own` workspaces): everything up to the table,
+// left per ORIGINAL rank -- the byte "enters a surviving bubble" in YB_MROOT, exit_of in YB_MEXIT, the holder in YB_MINSIDE,
+// n_inside in YB_MTOTAL, the number of every entrance in R.index, the three outputs by rank and the table in d_sb; the
+// counters in YB_CNT, not yet on the host (superbubble_all_counts).  Records ev[9] behind the table.  S is filled whatever
+// the outcome.  !R.ev or !R.n_order: nothing to do.
+template <class Stats, class Own>
+po_status superbubble_all_stage(po_handle* h, po_result* graph, const char* const name, int ev_first, Stats& stats, Own&& own, RankedGraph& R,
+                                po_superbubble_all_stats& S) {
     hipStream_t st = h->stream;
-    po_superbubble_all_stats& S = h->sastats;
-    S = po_superbubble_all_stats();
     DevBuf *Y = h->d_cy, *P = h->d_scc, *U = h->d_sb, *K = h->d_rank;
-    RankedGraph R;
-    PO_TRY(ranked_open(h, graph, name, EV_CYCLIC, po::PC_N, S, P[PB_COLOUR], [&](size_t nn, size_t ne) {
+    PO_TRY(ranked_open(h, graph, name, ev_first, po::PC_N, stats, P[PB_COLOUR], [&](size_t nn, size_t ne) {
         const size_t n2 = 2 * nn;   // (a flat graph has at most twice the ranks)
         for (int k : {RK_INDEX}) PO_TRY(ensure(h, K[k], n2 * 4));
         PO_TRY(ensure(h, K[RK_ROOT], n2));
@@ -4366,7 +4376,8 @@ po_status run_superbubbles_all(po_handle* h, po_result* graph, uint32_t* exit_ou
         for (int k : {YB_SPLIT, YB_CYCLIC0, YB_ROOTLESS, YB_UNCERTAIN, YB_ISROOT, YB_FILTERED, YB_LOOP, YB_MISEXIT, YB_MFILTERED, YB_MROOT})
             PO_TRY(ensure(h, Y[k], nn));
         for (int k : {YB_NODE, YB_ORIG, YB_BESTIN, YB_BESTOUT, YB_BESTLOW}) PO_TRY(ensure(h, Y[k], n2 * 4));
-        return ensure(h, Y[YB_FLAT], ne * sizeof(po::EdgeRanks));
+        PO_TRY(ensure(h, Y[YB_FLAT], ne * sizeof(po::EdgeRanks)));
+        return own(nn, ne);
     }, R));
     if (!R.ev || !R.n_order) return PO_OK;
     R.root = K[RK_ROOT].as<uint8_t>();   // (both grew behind ranked_open's own sizes)
@@ -4557,18 +4568,39 @@ po_status run_superbubbles_all(po_handle* h, po_result* graph, uint32_t* exit_ou
                            U[UB_TABLE].as<po::Bubble>());
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[9], st));
-    PO_TRY(land_outputs(h, {{U[UB_TABLE].p, (size_t)n_bubbles * sizeof(po_superbubble), table_out},
-                            {U[UB_EXITOUT].p, (size_t)n0 * 4, exit_out}, {U[UB_INSIDEOUT].p, (size_t)n0 * 4, inside_out},
-                            {U[UB_FLAGSOUT].p, n0, flags_out}}, cnt, po::YC_N));
     S.n_bubbles = n_bubbles;
-    S.n_nested = h->pinned[16 + po::YC_NESTED];
-    S.n_cyclic_bubbles = h->pinned[16 + po::YC_CYCLIC];
-    S.n_edge_filtered = h->pinned[16 + po::YC_FILTERED];
-    if (S.n_nested > n_bubbles || S.n_cyclic_bubbles > n_bubbles) return fail(h, PO_ERR_HIP, std::string("internal: the counts of ") + name + " do not add up");
-    *n_bubbles_out = n_bubbles;
     S.ms_split = ms_split;
     S.ms_bubbles = ms_bubbles;
     S.ms_merge = ms_merge;
+    return PO_OK;
+}
+
+// the stage's counters, once a synchronise has brought the YC_N words of YB_CNT to words 16.. of the landing zone
+po_status superbubble_all_counts(po_handle* h, const char* const name, po_superbubble_all_stats& S) {
+    S.n_nested = h->pinned[16 + po::YC_NESTED];
+    S.n_cyclic_bubbles = h->pinned[16 + po::YC_CYCLIC];
+    S.n_edge_filtered = h->pinned[16 + po::YC_FILTERED];
+    if (S.n_nested > S.n_bubbles || S.n_cyclic_bubbles > S.n_bubbles)
+        return fail(h, PO_ERR_HIP, std::string("internal: the counts of ") + name + " do not add up");
+    return PO_OK;
+}
+
+po_status run_superbubbles_all(po_handle* h, po_result* graph, uint32_t* exit_out, uint32_t* inside_out, uint8_t* flags_out,
+                               po_superbubble* table_out, uint64_t* n_bubbles_out) {
+    const char* const name = "po_layout_superbubbles_all";
+    po_superbubble_all_stats& S = h->sastats;
+    S = po_superbubble_all_stats();
+    DevBuf* U = h->d_sb;
+    RankedGraph R;
+    PO_TRY(superbubble_all_stage(h, graph, name, EV_CYCLIC, S, [](size_t, size_t) { return PO_OK; }, R, S));
+    if (!R.ev || !R.n_order) return PO_OK;
+    const uint32_t n0 = R.n_order, n_bubbles = (uint32_t)S.n_bubbles;
+    hipEvent_t* ev = R.ev;
+    PO_TRY(land_outputs(h, {{U[UB_TABLE].p, (size_t)n_bubbles * sizeof(po_superbubble), table_out},
+                            {U[UB_EXITOUT].p, (size_t)n0 * 4, exit_out}, {U[UB_INSIDEOUT].p, (size_t)n0 * 4, inside_out},
+                            {U[UB_FLAGSOUT].p, n0, flags_out}}, h->d_cy[YB_CNT].as<unsigned long long>(), po::YC_N));
+    PO_TRY(superbubble_all_counts(h, name, S));
+    *n_bubbles_out = n_bubbles;
     (void)hipEventElapsedTime(&S.ms_ranks, ev[0], ev[1]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[9]);
     return PO_OK;
@@ -4578,21 +4610,80 @@ po_status run_superbubbles_all(po_handle* h, po_result* graph, uint32_t* exit_ou
 
 // what the bubble-chain stage counts, for the stats of its callers
 struct BcWork {
-    uint64_t n_bubbles = 0, n_top = 0, n_chains = 0, n_short = 0, n_chain_nodes = 0, n_chain_edges = 0;
-    uint32_t max_chain_bubbles = 0, n_nest_rounds = 0, n_chain_rounds = 0, n_batches = 0;
+    uint64_t n_bubbles = 0, n_top = 0, n_chains = 0, n_short = 0, n_chain_nodes = 0, n_chain_edges = 0, n_ring_chains = 0, n_ring_bubbles = 0;
+    uint32_t max_chain_bubbles = 0, n_nest_rounds = 0, n_chain_rounds = 0, n_batches = 0, n_ring_rounds = 0;
+    int ev_last = 6;   // the last event of the bubble source: the stage records the two behind it
+};
+
+// What a bubble source leaves for the bubble-chain stage, per rank of the graph: the byte "enters a surviving bubble",
+// exit_of, the holder, and the counts.  `rings`: bubbles may lie inside an SCC, so their links may close to rings.
+struct BubbleSource {
+    const uint8_t* enters = nullptr;
+    const uint32_t *exit_of = nullptr, *inside = nullptr;
+    uint64_t n_bubbles = 0, n_nested = 0;
+    uint32_t n_batches = 0;
+    int ev_last = 6;
+    bool rings = false;
+};
+
+// the superbubbles of the acyclic partitions: superbubble_stage, as po_layout_bubblechains, po_layout_contigs and
+// po_phase_paths take them
+struct AcyclicBubbles {
+    template <class Stats, class Own>
+    po_status operator()(po_handle* h, po_result* graph, const char* const name, int ev_first, Stats& stats, Own&& own, RankedGraph& R,
+                         BubbleSource& src) const {
+        SbWork W;
+        const po_status staged = superbubble_stage(h, graph, name, ev_first, stats, own, R, W);
+        src.n_bubbles = W.n_bubbles;
+        src.n_nested = W.n_nested;
+        src.n_batches = W.n_batches;
+        PO_TRY(staged);
+        src.enters = R.root;
+        src.exit_of = h->d_sb[UB_EXIT].as<uint32_t>();
+        src.inside = h->d_sb[UB_INSIDE].as<uint32_t>();
+        return PO_OK;
+    }
+};
+
+// the superbubbles of the whole graph: superbubble_all_stage, its counters brought home (one synchronise more), as
+// po_layout_bubblechains_all and po_layout_contigs_all take them.  A holds the first stage's stats.
+struct CyclicBubbles {
+    po_superbubble_all_stats& A;
+    template <class Stats, class Own>
+    po_status operator()(po_handle* h, po_result* graph, const char* const name, int ev_first, Stats& stats, Own&& own, RankedGraph& R,
+                         BubbleSource& src) const {
+        src.ev_last = 9;
+        const po_status staged = superbubble_all_stage(h, graph, name, ev_first, stats, own, R, A);
+        src.n_batches = A.n_batches;
+        PO_TRY(staged);
+        if (!R.ev || !R.n_order) return PO_OK;
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 16, h->d_cy[YB_CNT].p, po::YC_N * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        PO_TRY(superbubble_all_counts(h, name, A));
+        src.n_bubbles = A.n_bubbles;
+        src.n_nested = A.n_nested;
+        src.rings = A.n_cyclic_bubbles > 0;   // (rings exist only inside SCCs)
+        src.enters = h->d_cy[YB_MROOT].as<uint8_t>();
+        src.exit_of = h->d_cy[YB_MEXIT].as<uint32_t>();
+        src.inside = h->d_cy[YB_MINSIDE].as<uint32_t>();
+        return PO_OK;
+    }
 };
 
 // The bubble-chain stage on the device, as po_layout_bubblechains and po_layout_contigs run it (`name`, the first of the
-// caller's events, the caller's stats for ranked_open): superbubble_stage with the workspaces of d_bc and the caller's `own`,
-// then everything up to the table and the three arrays, all left in d_bc -- the chain per rank in HB_CHAINOUT; the counters
-// in HB_CNT.  Records ev[7] and ev[8].  S is filled whatever the outcome.  !R.ev or !R.n_order: nothing to do.
-template <class Stats, class Own>
+// caller's events, the caller's stats for ranked_open): the bubble source -- AcyclicBubbles, or CyclicBubbles for the calls
+// that end in _all -- with the workspaces of d_bc and the caller's `own`, then everything up to the table and the three
+// arrays, all left in d_bc -- the chain per rank in HB_CHAINOUT; the counters in HB_CNT.  Records the two events behind the
+// source's last (ev[7] and ev[8] behind AcyclicBubbles).  Where the source says that links may close to rings, the election
+// of ringchains.hip.h runs between the heads and the ranking.  S is filled whatever the outcome.  !R.ev or !R.n_order:
+// nothing to do.
+template <class Stats, class Own, class Source = AcyclicBubbles>
 po_status bubblechain_stage(po_handle* h, po_result* graph, const char* const name, int ev_first, Stats& stats, uint32_t min_nodes, Own&& own,
-                            RankedGraph& R, BcWork& S) {
+                            RankedGraph& R, BcWork& S, Source&& source = Source()) {
     hipStream_t st = h->stream;
     DevBuf* B = h->d_bc;
-    SbWork W;
-    const po_status staged = superbubble_stage(h, graph, name, ev_first, stats, [&](size_t nn, size_t ne) {
+    BubbleSource W;
+    const po_status staged = source(h, graph, name, ev_first, stats, [&](size_t nn, size_t ne) {
         PO_TRY(ensure(h, B[HB_CNT], 128));
         for (int k : {HB_FW, HB_NEXT, HB_PRED, HB_TOP, HB_JB0, HB_JB1, HB_HOPS0, HB_HOPS1, HB_NHEAD, HB_NPOS, HB_CB, HB_CN, HB_LAST, HB_CHAINOUT,
                       HB_BUBBLEOUT})
@@ -4600,10 +4691,13 @@ po_status bubblechain_stage(po_handle* h, po_result* graph, const char* const na
         PO_TRY(ensure(h, B[HB_CE], nn * 8));
         PO_TRY(ensure(h, B[HB_EDGEOUT], ne * 4));
         PO_TRY(ensure(h, B[HB_TABLE], nn * sizeof(po::BubbleChain)));
+        if (!std::is_same<typename std::decay<Source>::type, AcyclicBubbles>::value)
+            for (int k : {HB_RPTR0, HB_RPTR1, HB_RMN0, HB_RMN1}) PO_TRY(ensure(h, B[k], nn * 4));
         return own(nn, ne);
     }, R, W);
     S.n_bubbles = W.n_bubbles;
     S.n_batches = W.n_batches;
+    S.ev_last = W.ev_last;
     PO_TRY(staged);
     if (!R.ev || !R.n_order) return PO_OK;
     const uint32_t n = R.n, n_order = R.n_order;
@@ -4615,24 +4709,42 @@ po_status bubblechain_stage(po_handle* h, po_result* graph, const char* const na
              *last = B[HB_LAST].as<uint32_t>(), *d_chain = B[HB_CHAINOUT].as<uint32_t>(), *d_bubble = B[HB_BUBBLEOUT].as<uint32_t>(),
              *d_edge = B[HB_EDGEOUT].as<uint32_t>();
     po::BubbleChain* table = B[HB_TABLE].as<po::BubbleChain>();
-    const uint32_t *exit_of = h->d_sb[UB_EXIT].as<uint32_t>(), *inside = h->d_sb[UB_INSIDE].as<uint32_t>();
+    const uint32_t *exit_of = W.exit_of, *inside = W.inside;
+    const int n_counters = W.rings ? (int)po::HKR_N : (int)po::HK_N;
     volatile uint64_t* C = h->pinned + 48;   // this stage's counters on the host (words 16.. and 32.. are the scaffold's)
     auto counters_home = [&]() -> po_status {
         HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(h->pinned + 48, cnt, po::HK_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(h->pinned + 48, cnt, (size_t)n_counters * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         return PO_OK;
     };
-    // top-level entrances (R.root still holds the byte "enters a surviving bubble"), their links, the heads
+    // top-level entrances (the source's byte "enters a surviving bubble"; R.root itself behind AcyclicBubbles), their links,
+    // the heads
     HIP_TRY(h, hipMemsetAsync(cnt, 0, 128, st));
-    hipLaunchKernelGGL(po::k_bc_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, R.root, inside, fw, next, pred, top, cb, cn, ce, last);
+    hipLaunchKernelGGL(po::k_bc_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, W.enters, inside, fw, next, pred, top, cb, cn, ce, last);
     hipLaunchKernelGGL(po::k_bc_link, dim3(R.rank_grid), dim3(256), 0, st, n_order, fw, exit_of, next, pred, cnt);
     hipLaunchKernelGGL(po::k_bc_heads, dim3(R.rank_grid), dim3(256), 0, st, n_order, pred, fw, jb[0], hops[0], cnt);
     PO_TRY(counters_home());
-    const uint64_t n_top = C[po::HK_TOP], n_heads = C[po::HK_HEADS];
-    if (n_top + W.n_nested != W.n_bubbles || n_heads > n_top || (n_top && !n_heads))
+    const uint64_t n_top = C[po::HK_TOP];
+    uint64_t n_heads = C[po::HK_HEADS];
+    if (n_top + W.n_nested != W.n_bubbles || n_heads > n_top || (n_top && !n_heads && !W.rings))
         return fail(h, PO_ERR_HIP, std::string("internal: the top-level bubbles of ") + name + " do not add up");
     S.n_top = n_top;
+    // one leader per ring of links: a fixed number of doubling rounds between two buffer pairs, nothing read back between them
+    if (n_top && W.rings) {
+        uint32_t *ptr[2] = {B[HB_RPTR0].as<uint32_t>(), B[HB_RPTR1].as<uint32_t>()}, *mn[2] = {B[HB_RMN0].as<uint32_t>(), B[HB_RMN1].as<uint32_t>()};
+        const uint32_t rounds = po::ring_rounds(n_top);
+        hipLaunchKernelGGL(po::k_rc_init, dim3(R.rank_grid), dim3(256), 0, st, n_order, jb[0], ptr[0], mn[0]);
+        for (uint32_t k = 0; k < rounds; ++k)
+            hipLaunchKernelGGL(po::k_rc_round, dim3(R.rank_grid), dim3(256), 0, st, n_order, ptr[k & 1], mn[k & 1], ptr[(k & 1) ^ 1], mn[(k & 1) ^ 1]);
+        hipLaunchKernelGGL(po::k_rc_leaders, dim3(R.rank_grid), dim3(256), 0, st, n_order, ptr[rounds & 1], mn[rounds & 1], fw, jb[0], hops[0], cnt);
+        PO_TRY(counters_home());
+        S.n_ring_rounds = rounds;
+        S.n_ring_chains = C[po::HKR_RINGS];
+        if (C[po::HK_HEADS] != n_heads + S.n_ring_chains || C[po::HK_HEADS] > n_top || !C[po::HK_HEADS])
+            return fail(h, PO_ERR_HIP, std::string("internal: the heads and ring leaders of ") + name + " do not add up");
+        n_heads = C[po::HK_HEADS];
+    }
     RoundOps ops{h, st, R.rcnt};
     uint64_t ignored = 0;
     // the outermost holder of every rank inside a bubble: needed only where a bubble lies inside another
@@ -4655,10 +4767,11 @@ po_status bubblechain_stage(po_handle* h, po_result* graph, const char* const na
         if (how != po::ROUNDS_DONE) return fail(h, PO_ERR_HIP, std::string("internal: the ranking of ") + name + " reached its bound of top-level + 2 rounds");
     }
     const uint32_t fin = launched & 1;
-    HIP_TRY(h, hipEventRecord(ev[7], st));
+    HIP_TRY(h, hipEventRecord(ev[W.ev_last + 1], st));
     // chain and position of every rank, the sums per head, the filter, the numbering of the surviving heads
     hipLaunchKernelGGL(po::k_bc_place, dim3(R.rank_grid), dim3(256), 0, st, n_order, fw, next, pred, top, exit_of, jb[fin], hops[fin], nhead, npos,
                        cb, cn, last, cnt);
+    if (S.n_ring_chains) hipLaunchKernelGGL(po::k_rc_close, dim3(R.rank_grid), dim3(256), 0, st, n_order, fw, cb, last, cnt);
     if (n) hipLaunchKernelGGL(po::k_bc_edges, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, nhead, ce);
     hipLaunchKernelGGL(po::k_bc_filter, dim3(R.rank_grid), dim3(256), 0, st, n_order, min_nodes, fw, cb, cn, ce, R.root, cnt);
     HIP_TRY(h, hipGetLastError());
@@ -4675,12 +4788,17 @@ po_status bubblechain_stage(po_handle* h, po_result* graph, const char* const na
     S.n_chain_nodes = C[po::HK_CNODES];
     S.n_chain_edges = C[po::HK_CEDGES];
     S.max_chain_bubbles = (uint32_t)C[po::HK_MAXB];
+    if (S.n_ring_chains) {
+        S.n_ring_bubbles = C[po::HKR_RBUBBLES];
+        if (S.n_ring_bubbles < S.n_ring_chains || S.n_ring_bubbles > n_top)
+            return fail(h, PO_ERR_HIP, std::string("internal: the ring chains of ") + name + " do not add up");
+    }
     if (n_chains)
         hipLaunchKernelGGL(po::k_bc_table, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_chains, R.val, R.root, R.index, last, cb, cn, ce, table);
     hipLaunchKernelGGL(po::k_bc_nodes, dim3(R.rank_grid), dim3(256), 0, st, n_order, n_chains, R.root, R.index, nhead, npos, d_chain, d_bubble);
     if (n) hipLaunchKernelGGL(po::k_bc_edge_out, dim3(R.edge_grid), dim3(256), 0, st, R.ends, n, n_order, d_chain, d_edge);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipEventRecord(ev[8], st));
+    HIP_TRY(h, hipEventRecord(ev[W.ev_last + 2], st));
     return PO_OK;
 }
 
@@ -4716,6 +4834,50 @@ po_status run_bubblechains(po_handle* h, po_result* graph, uint32_t min_nodes, u
     (void)hipEventElapsedTime(&S.ms_chains, ev[6], ev[7]);
     (void)hipEventElapsedTime(&S.ms_label, ev[7], ev[8]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[8]);
+    return PO_OK;
+}
+
+// The same behind the superbubbles of the whole graph (CyclicBubbles): a chain may be a ring, its head the lowest-ranked
+// entrance and its last exit that head again.
+po_status run_bubblechains_all(po_handle* h, po_result* graph, uint32_t min_nodes, uint32_t* chain_out, uint32_t* bubble_out,
+                               uint32_t* edge_out, po_bubblechain* table_out, uint64_t* n_chains_out) {
+    po_bubblechain_all_stats& S = h->bcastats;
+    S = po_bubblechain_all_stats();
+    DevBuf* B = h->d_bc;
+    RankedGraph R;
+    BcWork W;
+    po_superbubble_all_stats A = {};
+    const po_status staged = bubblechain_stage(h, graph, "po_layout_bubblechains_all", EV_CHAINS_ALL, S, min_nodes,
+                                               [](size_t, size_t) { return PO_OK; }, R, W, CyclicBubbles{A});
+    S.n_bubbles = W.n_bubbles;
+    S.n_top = W.n_top;
+    S.n_chains = W.n_chains;
+    S.n_short = W.n_short;
+    S.n_chain_nodes = W.n_chain_nodes;
+    S.n_chain_edges = W.n_chain_edges;
+    S.n_ring_chains = W.n_ring_chains;
+    S.n_ring_bubbles = W.n_ring_bubbles;
+    S.n_cyclic_bubbles = A.n_cyclic_bubbles;
+    S.max_chain_bubbles = W.max_chain_bubbles;
+    S.n_nest_rounds = W.n_nest_rounds;
+    S.n_chain_rounds = W.n_chain_rounds;
+    S.n_batches = W.n_batches;
+    S.n_ring_rounds = W.n_ring_rounds;
+    S.n_root_runs = A.n_root_runs;
+    S.n_split_levels = A.n_split_levels;
+    PO_TRY(staged);
+    if (!R.ev || !R.n_order) return PO_OK;
+    const uint32_t n = R.n, n_order = R.n_order, n_chains = (uint32_t)W.n_chains;
+    hipEvent_t* ev = R.ev;
+    const int e = W.ev_last;
+    PO_TRY(land_outputs(h, {{B[HB_TABLE].p, (size_t)n_chains * sizeof(po_bubblechain), table_out},
+                            {B[HB_CHAINOUT].p, (size_t)n_order * 4, chain_out}, {B[HB_BUBBLEOUT].p, (size_t)n_order * 4, bubble_out},
+                            {B[HB_EDGEOUT].p, (size_t)n * 4, edge_out}}, B[HB_CNT].as<unsigned long long>(), po::HKR_N));
+    *n_chains_out = n_chains;
+    (void)hipEventElapsedTime(&S.ms_superbubbles, ev[0], ev[e]);
+    (void)hipEventElapsedTime(&S.ms_chains, ev[e], ev[e + 1]);
+    (void)hipEventElapsedTime(&S.ms_label, ev[e + 1], ev[e + 2]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[e + 2]);
     return PO_OK;
 }
 
@@ -4892,9 +5054,11 @@ po_status run_paths(po_handle* h, po_result* graph, uint64_t max_paths, po_resul
 
 // ---- the contigs outside the bubble chains (po_layout_contigs, contigs.hip.h) ----------------------------------------------
 
+// `cyclic`: po_layout_contigs_all -- without an exclude set the chains are those of po_layout_bubblechains_all.
 po_status run_contigs(po_handle* h, po_result* graph, uint64_t min_len, uint32_t min_nodes, const uint8_t* exclude_in, uint32_t* contig_out,
-                      uint32_t* pos_out, po_contig* table_out, uint64_t* n_contigs_out) {
-    const char* const name = "po_layout_contigs";
+                      uint32_t* pos_out, po_contig* table_out, uint64_t* n_contigs_out, bool cyclic = false) {
+    const char* const name = cyclic ? "po_layout_contigs_all" : "po_layout_contigs";
+    const int ev_first = cyclic ? EV_CONTIGS_ALL : EV_CONTIGS;
     hipStream_t st = h->stream;
     po_contig_stats& S = h->ctstats;
     S = po_contig_stats();
@@ -4920,14 +5084,16 @@ po_status run_contigs(po_handle* h, po_result* graph, uint64_t min_len, uint32_t
     // the ranks; without an exclude set the bubble chains too (their chain word per rank is the set)
     int e0 = 1;   // the event behind the stage run first
     if (exclude_in) {
-        PO_TRY(ranked_open(h, graph, name, EV_CONTIGS, po::KC_N, S, B[CB_INE], own, R));   // (the identity words: overwritten below)
+        PO_TRY(ranked_open(h, graph, name, ev_first, po::KC_N, S, B[CB_INE], own, R));   // (the identity words: overwritten below)
     } else {
         BcWork W;
-        const po_status staged = bubblechain_stage(h, graph, name, EV_CONTIGS, S, min_nodes, own, R, W);
+        po_superbubble_all_stats A = {};
+        const po_status staged = cyclic ? bubblechain_stage(h, graph, name, ev_first, S, min_nodes, own, R, W, CyclicBubbles{A})
+                                        : bubblechain_stage(h, graph, name, ev_first, S, min_nodes, own, R, W);
         S.n_chains = W.n_chains;
         S.n_batches = W.n_batches;
         PO_TRY(staged);
-        e0 = 8;
+        e0 = W.ev_last + 2;
     }
     if (!R.ev) return PO_OK;
     const uint32_t n = R.n, n_order = R.n_order;
@@ -8219,6 +8385,26 @@ po_status po_layout_bubblechains(po_handle* h, po_result* graph, const po_bubble
 }
 
 po_status po_get_bubblechain_stats(const po_handle* h, po_bubblechain_stats* out) { return get_stats(h, &po_handle::bcstats, out); }
+
+po_status po_layout_bubblechains_all(po_handle* h, po_result* graph, const po_bubblechain_params* params, uint32_t* node_chain_out,
+                                     uint32_t* node_bubble_out, uint32_t* edge_chain_out, po_bubblechain* chains_out, uint64_t* n_chains_out) {
+    return graph_call(h, graph, "po_layout_bubblechains_all", !params || (params->reserved == 0 && params->min_nodes != 0), "bubble chains",
+                      n_chains_out, [&] {
+        return run_bubblechains_all(h, graph, params ? params->min_nodes : 1u, node_chain_out, node_bubble_out, edge_chain_out, chains_out,
+                                    n_chains_out);
+    });
+}
+
+po_status po_get_bubblechain_all_stats(const po_handle* h, po_bubblechain_all_stats* out) { return get_stats(h, &po_handle::bcastats, out); }
+
+po_status po_layout_contigs_all(po_handle* h, po_result* graph, const po_contig_params* params, const uint8_t* exclude_in,
+                                uint32_t* edge_contig_out, uint32_t* edge_pos_out, po_contig* contigs_out, uint64_t* n_contigs_out) {
+    return graph_call(h, graph, "po_layout_contigs_all", !params || (params->reserved == 0 && params->min_nodes != 0), "contigs", n_contigs_out,
+                      [&] {
+        return run_contigs(h, graph, params ? params->min_contig_len : 5000ull, params ? params->min_nodes : 1u, exclude_in, edge_contig_out,
+                           edge_pos_out, contigs_out, n_contigs_out, true);
+    });
+}
 
 po_status po_layout_contigs(po_handle* h, po_result* graph, const po_contig_params* params, const uint8_t* exclude_in,
                             uint32_t* edge_contig_out, uint32_t* edge_pos_out, po_contig* contigs_out, uint64_t* n_contigs_out) {

@@ -323,3 +323,109 @@ class HostSuperbubblesAll:
 
     def superbubble_all_stats(self) -> dict:
         return dict(self.stats)
+
+    # ---- the bubble chains behind these superbubbles, ring chains included ----------------------
+
+    def layout_bubblechains_all(self, graph=None, min_nodes: int = 1, n_nodes=None):
+        """``po_layout_bubblechains_all`` by the device's scheme (bubblechains.hip.h with ringchains.hip.h between the heads
+        and the ranking), on ranks: the top-level entrances, their links, the heads; one leader per RING of links -- the
+        doubling election, run synchronously for exactly ceil(log2(n_top)) + 1 rounds; the ranking from every head and
+        leader; head and position of every rank; the sums, the ``min_nodes`` filter, the numbering by head rank.  Returns
+        what ``ExactOverlapper.layout_bubblechains_all`` returns; ``bubblechain_all_stats()`` the integer stats."""
+        if not 1 <= int(min_nodes) <= 0xFFFFFFFF:
+            raise ValueError("po_layout_bubblechains_all: bad parameters")
+        node_exit, node_inside, flags, sb_table = self.layout_superbubbles_all()
+        sb = dict(self.stats)
+        n0, eu, ev, order = len(self.order), self.eu, self.ev, self.order
+        rank = {x: r for r, x in enumerate(order)}
+        none = 0xFFFFFFFF
+        exit_of = [rank[int(t)] if int(t) != none else NONE for t in node_exit]
+        inside = [rank[int(s)] if int(s) != none else NONE for s in node_inside]
+        top = [exit_of[r] != NONE and inside[r] == NONE for r in range(n0)]
+        nxt, pred = [NONE] * n0, [NONE] * n0
+        for r in range(n0):
+            if top[r]:
+                pred[exit_of[r]] = r
+                if top[exit_of[r]]:
+                    nxt[r] = exit_of[r]
+        head = [top[r] and pred[r] == NONE for r in range(n0)]
+        n_top, n_path_heads = sum(top), sum(head)
+        # the election: ptr = pred of a linked top-level entrance, else the rank itself; mn = the rank
+        ring, rounds = [False] * n0, 0
+        if n_top and sb["n_cyclic_bubbles"]:
+            ptr = [pred[r] if top[r] and pred[r] != NONE else r for r in range(n0)]
+            mn = list(range(n0))
+            rounds = max(n_top - 1, 0).bit_length() + 1
+            for _ in range(rounds):
+                mn = [min(mn[r], mn[ptr[r]]) for r in range(n0)]
+                ptr = [ptr[ptr[r]] for r in range(n0)]
+            for r in range(n0):
+                if mn[r] == r and top[r] and not head[r] and not head[ptr[r]]:
+                    ring[r] = True
+            for r in range(n0):
+                head[r] = head[r] or ring[r]
+        n_heads = sum(head)
+        if n_heads != n_path_heads + sum(ring) or (n_top and not n_heads):
+            raise RuntimeError("internal: the heads and ring leaders of po_layout_bubblechains_all do not add up")
+        # the ranking: every top-level entrance reaches its head along pred (a leader's link in is cut)
+        home, pos, last = [NONE] * n0, [NONE] * n0, {}
+        for hd in range(n0):
+            if not head[hd]:
+                continue
+            s, k = hd, 0
+            while True:
+                if k > n_top:
+                    raise RuntimeError("internal: the ranking of po_layout_bubblechains_all reached its bound")
+                home[s], pos[s] = hd, k
+                t = nxt[s]
+                if t == NONE or t == hd:
+                    last[hd] = exit_of[s]
+                    break
+                s, k = t, k + 1
+        if any(top[r] and home[r] == NONE for r in range(n0)):
+            raise RuntimeError("internal: a node of po_layout_bubblechains_all reached no head")
+        nhead, npos = [NONE] * n0, [NONE] * n0
+        cb, cn, ce = [0] * n0, [0] * n0, [0] * n0
+        for r in range(n0):
+            if top[r]:
+                s = r
+            elif pred[r] != NONE:                     # a last exit: the bubble it exits
+                s = pred[r]
+            else:
+                s = inside[r]
+                while s != NONE and inside[s] != NONE:   # the outermost holder
+                    s = inside[s]
+            if s == NONE:
+                continue
+            if not top[s] or home[s] == NONE:
+                raise RuntimeError("internal: a node of po_layout_bubblechains_all reached no head")
+            nhead[r], npos[r] = home[s], pos[s]
+            cn[home[s]] += 1
+            cb[home[s]] += top[r]
+        for a, b in zip(eu, ev):
+            if nhead[a] != NONE and nhead[a] == nhead[b]:
+                ce[nhead[a]] += 1
+        kept = [r for r in range(n0) if head[r] and cn[r] >= min_nodes]
+        number = {r: i for i, r in enumerate(kept)}
+        node_chain, node_bubble = np.full(n0, none, np.uint32), np.full(n0, none, np.uint32)
+        for r in range(n0):
+            if nhead[r] in number:
+                node_chain[r], node_bubble[r] = number[nhead[r]], npos[r]
+        edge_chain = np.full(len(eu), none, np.uint32)
+        for e, (a, b) in enumerate(zip(eu, ev)):
+            if node_chain[a] == node_chain[b]:
+                edge_chain[e] = node_chain[a]
+        table = np.zeros(len(kept), dtype=[("first_entrance", "<u4"), ("last_exit", "<u4"), ("n_bubbles", "<u4"), ("n_nodes", "<u4"),
+                                           ("n_edges", "<u8")])
+        for i, r in enumerate(kept):
+            table[i] = (order[r], order[last[r]], cb[r], cn[r], ce[r])
+        self.chain_stats = {"n_nodes": n0, "n_edges": len(eu), "n_bubbles": sb["n_bubbles"], "n_top": n_top, "n_chains": len(kept),
+                            "n_short": n_heads - len(kept), "n_chain_nodes": sum(cn[r] for r in kept),
+                            "n_chain_edges": sum(ce[r] for r in kept), "n_invalid": 0, "n_ring_chains": sum(ring),
+                            "n_ring_bubbles": sum(cb[r] for r in range(n0) if ring[r]), "n_cyclic_bubbles": sb["n_cyclic_bubbles"],
+                            "max_chain_bubbles": max([cb[r] for r in range(n0) if head[r]], default=0), "n_ring_rounds": rounds,
+                            "n_root_runs": sb["n_root_runs"], "n_split_levels": sb["n_split_levels"]}
+        return node_chain, node_bubble, edge_chain, table
+
+    def bubblechain_all_stats(self) -> dict:
+        return dict(self.chain_stats)

@@ -38,8 +38,9 @@ starts with inside each component: ``partition_graph`` (phasm/bubbles.py:32-84).
 What follows that point: of `phasm phase` the scoring and pruning of the haplotype extensions at one bubble is
 ``phasm_amd.phasing`` (``po_phase_branch``), as are the relevant reads of a bubble (``po_phase_index``, ``po_phase_relevant``);
 the superbubbles of the cyclic partitions (what the reference reaches through ``graph_to_dag``) come from
-``superbubbles(..., cyclic=True)`` (``po_layout_superbubbles_all``, root splitting: DESIGN.md section 3.9t); the chains, the
-contigs and the paths still take the acyclic partitions only.
+``superbubbles(..., cyclic=True)`` (``po_layout_superbubbles_all``, root splitting: DESIGN.md section 3.9t), and with ``cyclic=True`` the chains and the contigs
+build on them (``po_layout_bubblechains_all`` / ``po_layout_contigs_all``, ring chains: section 3.9u); the paths still take
+the acyclic partitions only.
 No CPU fallback: without the HIP library and a GPU these functions raise.
 """
 from __future__ import annotations
@@ -721,11 +722,21 @@ class BubbleChains:
         return out
 
 
-def bubble_chains(ov: ExactOverlapper, graph_res: OverlapResult, min_nodes: int = 1,
-                  superbubbles: Optional[Superbubbles] = None) -> BubbleChains:
+def bubble_chains(ov, graph_res: Optional[OverlapResult], min_nodes: int = 1, superbubbles: Optional[Superbubbles] = None,
+                  cyclic: bool = False) -> BubbleChains:
     """``po_layout_bubblechains`` on a graph result of ``ov`` (an edge result, a merged graph or a ``graph_from_edges``
     result), which stays valid and in HBM; ``superbubbles``: ``layout.superbubbles`` of the same graph, if the caller has
-    them (computed here otherwise: ``bubbles_of`` reads the exits from them)."""
+    them (computed here otherwise: ``bubbles_of`` reads the exits from them).  ``cyclic=True``:
+    ``po_layout_bubblechains_all`` instead -- the chains behind the superbubbles of the whole graph, RING CHAINS included
+    (DESIGN.md section 3.9u); ``superbubbles`` are then those of ``superbubbles(..., cyclic=True)``, so ``bubbles_of`` walks
+    a ring once round, ``stats`` is ``po_get_bubblechain_all_stats``, and ``ov`` may be a ``cyclic.HostSuperbubblesAll``,
+    which holds its own graph (``graph_res`` is ignored)."""
+    if cyclic:
+        order = graph_res.node_order() if isinstance(ov, ExactOverlapper) else ov.node_order()
+        if superbubbles is None:
+            superbubbles = _superbubbles(ov, graph_res, cyclic=True)
+        node_chain, node_bubble, edge_chain, table = ov.layout_bubblechains_all(graph_res, min_nodes, len(order))
+        return BubbleChains(order, node_chain, node_bubble, edge_chain, table, superbubbles.node_exit, ov.bubblechain_all_stats())
     order = graph_res.node_order()
     if superbubbles is None:
         superbubbles = _superbubbles(ov, graph_res)
@@ -785,12 +796,14 @@ class Contigs:
 
 
 def identify_contigs(ov: ExactOverlapper, graph_res: OverlapResult, min_contig_len: int = 5000, min_nodes: int = 1,
-                     exclude=None) -> Contigs:
+                     exclude=None, cyclic: bool = False) -> Contigs:
     """``po_layout_contigs`` on a graph result of ``ov`` (an edge result, a merged graph or a ``graph_from_edges`` result),
     which stays valid and in HBM.  ``exclude`` None: the nodes of the bubble chains (``min_nodes`` as in ``bubble_chains``),
-    built on the device by the same call; else one flag per node, parallel to the node order."""
+    built on the device by the same call; else one flag per node, parallel to the node order.  ``cyclic=True``:
+    ``po_layout_contigs_all`` instead -- the chains are those of ``bubble_chains(..., cyclic=True)``, ring chains included."""
     order = graph_res.node_order()
-    edge_contig, edge_pos, table = ov.layout_contigs(graph_res, min_contig_len, min_nodes, exclude, len(order))
+    stage = ov.layout_contigs_all if cyclic else ov.layout_contigs
+    edge_contig, edge_pos, table = stage(graph_res, min_contig_len, min_nodes, exclude, len(order))
     rows = graph_res.rows()
     ends = np.stack([rows["u"], rows["v"]], axis=1) if len(rows) else np.zeros((0, 2), dtype=np.uint32)
     return Contigs(order, edge_contig, edge_pos, table, ov.contig_stats(), ends)
@@ -829,7 +842,9 @@ class ChainGraph:
     superbubble detection starts with; with ``superbubbles=True`` also the superbubbles of the acyclic partitions (with
     ``cyclic=True`` on top those of all partitions, the cyclic ones included, in ``superbubbles_all``); with
     ``bubblechains=True`` also the bubble chains and, per component, the chains in it (``chains_by_component``); with
-    ``contigs=True`` also the contigs outside the chains and, per component, the contigs in it (``contigs_by_component``)."""
+    ``contigs=True`` also the contigs outside the chains and, per component, the contigs in it (``contigs_by_component``).
+    With ``cyclic=True`` the chains and the contigs build on the superbubbles of all partitions: a circular component is a
+    ring chain."""
     graph: object
     components: Components
     sccs: Optional[StrongComponents] = None
@@ -851,7 +866,8 @@ def chain_components(path: str, device: Optional[int] = None, partitions: bool =
     ``cyclic`` on top ``superbubbles(..., cyclic=True)``: those of all partitions, in ``superbubbles_all``); with
     ``bubblechains`` also ``bubble_chains`` (``min_nodes`` as in ``build_bubblechains``) and ``chains_by_component``; with
     ``contigs`` also ``identify_contigs`` outside those chains (``min_length`` as `phasm chain -l`) and
-    ``contigs_by_component``."""
+    ``contigs_by_component``; ``cyclic`` feeds both (``bubble_chains(..., cyclic=True)``, ``identify_contigs(...,
+    cyclic=True)``)."""
     from .io import gfa
     with open(path) as f:
         graph = gfa.read_graph_gfa(f)
@@ -870,10 +886,12 @@ def chain_components(path: str, device: Optional[int] = None, partitions: bool =
                 if cyclic:
                     out.superbubbles_all = _superbubbles(ov, res, cyclic=True)
             if bubblechains:
-                out.bubblechains = bubble_chains(ov, res, min_nodes, out.superbubbles)
+                if cyclic and out.superbubbles_all is None:
+                    out.superbubbles_all = _superbubbles(ov, res, cyclic=True)
+                out.bubblechains = bubble_chains(ov, res, min_nodes, out.superbubbles_all if cyclic else out.superbubbles, cyclic=cyclic)
                 out.component_chains = chains_by_component(out.bubblechains, out.components)
             if contigs:
-                out.contigs = identify_contigs(ov, res, min_length, min_nodes)
+                out.contigs = identify_contigs(ov, res, min_length, min_nodes, cyclic=cyclic)
                 out.component_contigs = contigs_by_component(out.contigs, out.components)
             return out
         finally:

@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, PoSuperbubbleAllParams, PoSuperbubbleAllStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats, PoSpellInput, PoSpellStats
+from ._lib import CAND_DTYPE, CONTIG_DTYPE, EDGE_DTYPE, PoContigParams, PoContigStats, ROW_DTYPE, PoLayoutParams, PoLayoutStats, PoNodeOrderStats, PoReduceParams, PoReduceStats, PoStats, PoTipsParams, PoTipsStats, PoDiamondParams, PoDiamondStats, PoMergeParams, PoMergeStats, PoCoverageParams, PoCoverageStats, COVERAGE_DTYPE, PoComponentsParams, PoComponentsStats, COMPONENT_DTYPE, PoPartitionParams, PoPartitionStats, SCC_DTYPE, PoSuperbubbleParams, PoSuperbubbleStats, PoSuperbubbleAllParams, PoSuperbubbleAllStats, SUPERBUBBLE_DTYPE, PoBubblechainParams, PoBubblechainStats, PoBubblechainAllStats, BUBBLECHAIN_DTYPE, PoPhaseParams, PoPhaseInput, PoPhaseStats, ALIGNMENT_DTYPE, PoPhaseIndexStats, PoRelevantParams, PoRelevantInput, PoRelevantDims, PoRelevantStats, PoSpellInput, PoSpellStats
 from .phasing import BubblePaths, RelevantReads
 from .spelling import spell_arrays
 
@@ -692,6 +692,26 @@ class ExactOverlapper:
     def bubblechain_stats(self) -> dict:
         return self._stats(self._lib.po_get_bubblechain_stats, PoBubblechainStats)
 
+    def layout_bubblechains_all(self, graph: OverlapResult, min_nodes: int = 1, n_order: Optional[int] = None):
+        """``po_layout_bubblechains_all``: ``layout_bubblechains`` behind the superbubbles of the whole graph
+        (``layout_superbubbles_all``), the cyclic partitions included.  Returns what
+        ``layout_bubblechains`` returns.  A RING CHAIN -- the top-level bubbles of a circular component, linked round -- holds
+        all its bubbles; its head is the lowest-ranked entrance and ``last_exit == first_entrance`` marks it.  On a graph
+        without a non-singleton SCC the arrays are byte-equal to ``layout_bubblechains``'."""
+        if not 0 <= int(min_nodes) <= 0xFFFFFFFF:
+            raise ValueError("min_nodes does not fit 32 bits")
+        return self._graph_stage(self._lib.po_layout_bubblechains_all, graph, PoBubblechainParams(int(min_nodes), 0), n_order,
+                                 [(np.uint32, "node"), (np.uint32, "node"), (np.uint32, "edge"), (BUBBLECHAIN_DTYPE, "node")])
+
+    def bubblechain_all_stats(self) -> dict:
+        return self._stats(self._lib.po_get_bubblechain_all_stats, PoBubblechainAllStats)
+
+    def layout_contigs_all(self, graph: OverlapResult, min_contig_len: int = 5000, min_nodes: int = 1, exclude=None,
+                           n_order: Optional[int] = None):
+        """``po_layout_contigs_all``: ``layout_contigs`` with the chains of ``layout_bubblechains_all`` as the exclude set
+        when ``exclude`` is None, ring chains included.  Arguments, result and stats (``contig_stats``) as ``layout_contigs``."""
+        return self._contig_stage(self._lib.po_layout_contigs_all, graph, min_contig_len, min_nodes, exclude, n_order)
+
     def layout_contigs(self, graph: OverlapResult, min_contig_len: int = 5000, min_nodes: int = 1, exclude=None,
                        n_order: Optional[int] = None):
         """``po_layout_contigs``: the contigs of a graph result (of the kinds ``layout_components`` takes), which stays
@@ -703,6 +723,9 @@ class ExactOverlapper:
         contig's path (``NO_NODE`` where there is none); one entry (``first_node``, ``last_node``, ``n_nodes``,
         ``first_edge``, ``length``) per contig: the paths by (rank of the first node, head edge), then the one-node contigs
         by rank."""
+        return self._contig_stage(self._lib.po_layout_contigs, graph, min_contig_len, min_nodes, exclude, n_order)
+
+    def _contig_stage(self, fn, graph: OverlapResult, min_contig_len: int, min_nodes: int, exclude, n_order: Optional[int]):
         if not 0 <= int(min_nodes) <= 0xFFFFFFFF:
             raise ValueError("min_nodes does not fit 32 bits")
         if not 0 <= int(min_contig_len) < 2**64:
@@ -717,8 +740,8 @@ class ExactOverlapper:
         edge_contig, edge_pos = np.zeros(len(graph), dtype=np.uint32), np.zeros(len(graph), dtype=np.uint32)
         table = np.zeros(int(n_order) + len(graph), dtype=CONTIG_DTYPE)
         n = ctypes.c_uint64()
-        _check(self._h, self._lib.po_layout_contigs(self._h, graph._ptr, ctypes.byref(prm), _ptr(exclude) if exclude is not None else None,
-                                                    _ptr(edge_contig), _ptr(edge_pos), _ptr(table), ctypes.byref(n)))
+        _check(self._h, fn(self._h, graph._ptr, ctypes.byref(prm), _ptr(exclude) if exclude is not None else None, _ptr(edge_contig),
+                           _ptr(edge_pos), _ptr(table), ctypes.byref(n)))
         return edge_contig, edge_pos, table[:int(n.value)].copy()
 
     def contig_stats(self) -> dict:
