@@ -1323,6 +1323,74 @@ po_status po_paths_copy(po_result* out, po_bubble_paths* bubbles, uint64_t* insi
 po_status po_get_paths_stats(const po_handle* h, po_paths_stats* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * The large-bubble arm of `phasm phase`: phase_large_bubble (phasm/phasing.py:633-685) on a bubble whose paths po_phase_paths
+ * left listed in HBM -- every listed path scored against the relevant reads, the n_best best of them named -- for a bubble of
+ * any listed size (po_phase_branch stops at 64 paths).  phasm_amd/csrc/large.hip.h, DESIGN.md section 3.9v.
+ * Not part of it: the relevant reads (po_phase_relevant), the reads of a node (the caller's), spelling the winner (po_spell).
+ * --------------------------------------------------------------------------------------------- */
+
+typedef struct {
+    uint32_t bubble;             /* index into the table of the paths result                                        */
+    uint32_t n_reads;            /* R >= 1: the relevant reads                                                      */
+    uint32_t n_b;                /* local read ids are 0..n_b-1                                                     */
+    uint32_t n_best;             /* 1..8: how many of the best paths to name                                        */
+    uint32_t reserved;           /* must be 0                                                                       */
+} po_large_params;
+
+typedef struct {
+    const int32_t* overlap_max;  /* [n_reads]; these five are exactly those fields of po_phase_input                */
+    const uint32_t* aln_off;     /* [n_reads + 1]                                                                   */
+    const uint32_t* aln_b;
+    const int32_t* aln_a0;
+    const int32_t* aln_a1;
+    const uint32_t* node_off;    /* [n_nodes + 1]: the local read ids of interior node i are node_off[i] .. node_off[i+1]-1 */
+    const uint32_t* node_ids;    /* the local ids of the reads of every interior node, in the order of the bubble's
+                                    inside_nodes; a merged node has several, a node whose reads no alignment names none */
+    uint32_t n_nodes;            /* must be the bubble's n_inside                                                   */
+} po_large_input;
+
+typedef struct {
+    uint64_t n_paths, n_inside, n_reads;
+    uint64_t max_path_nodes;     /* nodes of the bubble's longest listed path, both ends included                   */
+    float ms_intervals;          /* uploads, slot map, bitsets and intervals of the interior nodes                  */
+    float ms_score, ms_best, ms_total;
+} po_large_stats;
+
+/* po_phase_large.  `paths` is a po_phase_paths result of this handle; it stays valid and unchanged.
+ * SCORE.  For path p of the bubble (numbered as bubble_path_off numbers them, from 0 within the bubble), in float64,
+ *     sum[p] = sum over the relevant reads r of f(r; the reads of the interior nodes of p),  score[p] = sum[p] / n_reads
+ *   with f as in po_phase_branch.  The interval (S0, E) is kept per (interior node, read) and a path joins those of its nodes
+ *   with min and max.  The sum runs in the order of po_phase_branch's table, so sum[p] has the bits of S[0][0][p] of that call
+ *   with ploidy 1, one candidate and an empty read set on the same paths; the division happens on the device, once per path.
+ *   A path without interior nodes (an edge from entrance to exit) scores 0.0.
+ * BEST.  best_out[0 .. n-1], n = *n_best_out = min(n_best, n_paths), are the indices within the bubble that
+ *   sorted(range(P), key=score.get, reverse=True)[:n_best] gives: descending by score, among equal scores the lower index
+ *   first.  best_score_out[j] is score[best_out[j]].  Integer atomics on an order-keeping key, then on the index; no
+ *   floating-point atomics: the same input gives the same bits on every run.
+ * scores_out (may be NULL) receives all n_paths scores; nothing else of size n_paths leaves the device.
+ * REJECTIONS, each PO_ERR_INVALID with a sentence in po_last_error, checked on the host before a kernel runs, the outputs
+ *   untouched (*n_best_out = 0 where it is given), in this order: a NULL argument; reserved != 0; n_best outside 1..8;
+ *   n_reads == 0 (the reference divides by zero there); a missing array; offsets that do not start at 0 or that decrease; a
+ *   local id >= n_b; a result that is no paths result or belongs to another handle; bubble >= n_bubbles; a bubble whose paths
+ *   were not listed (PO_PATHS_UNLISTED); n_nodes != the bubble's n_inside (the last two need the result's table, which comes
+ *   to the host once per result).
+ * Device memory beyond the inputs: 8 * n_inside * n_reads bytes for the intervals, 4 * ceil(n_b / 32) per interior node, one
+ * word per node of the graph for the slot map, 8 * n_paths for the scores.  Every loop is bounded on the host.  There is no
+ * CPU fallback: without a GPU a valid call returns PO_ERR_HIP. */
+po_status po_phase_large(po_handle* h, po_result* paths, const po_large_params* params, const po_large_input* input,
+                         uint64_t* best_out, double* best_score_out, double* scores_out, uint32_t* n_best_out);
+po_status po_get_large_stats(const po_handle* h, po_large_stats* out);
+
+/* The listed paths first .. first + count - 1 of a po_phase_paths result, numbered as bubble_path_off numbers them:
+ * path_off_out[0 .. count] are offsets into path_nodes_out RELATIVE to the first path (path_off_out[0] = 0), path_nodes_out the
+ * nodes, both ends of each path included.  *n_nodes_out is always the number of nodes of the range; cap is the room of
+ * path_nodes_out in nodes.  Either array may be NULL (cap is ignored without path_nodes_out).  Rejections: PO_ERR_INVALID
+ * for a NULL result or n_nodes_out, a result that is no paths result, a range that ends past the listed paths;
+ * PO_ERR_CAPACITY, with *n_nodes_out set and nothing written, when cap is too small. */
+po_status po_paths_copy_paths(po_result* paths, uint64_t first, uint64_t count, uint64_t* path_off_out, uint32_t* path_nodes_out,
+                              uint64_t cap, uint64_t* n_nodes_out);
+
+/* ---------------------------------------------------------------------------------------------
  * The walk of `phasm phase` along a bubble chain with the candidate sets RESIDENT on the device: what
  * BubbleChainPhaser carries from bubble to bubble (candidate_sets with their read sets and log_rl, phasm/phasing.py:125-142),
  * the take-over of the survivors (phasing.py:311-319), new_block's reset (phasing.py:343-364) and prune(.., 1.0) of new_block

@@ -345,6 +345,23 @@ class PoPathsStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoLargeParams(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint32) for name in ("bubble", "n_reads", "n_b", "n_best", "reserved")]
+
+
+class PoLargeInput(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ("overlap_max", "aln_off", "aln_b", "aln_a0", "aln_a1", "node_off", "node_ids")] + \
+               [("n_nodes", ctypes.c_uint32)]
+
+
+class PoLargeStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_paths", "n_inside", "n_reads", "max_path_nodes")] + \
+               [(name, ctypes.c_float) for name in ("ms_intervals", "ms_score", "ms_best", "ms_total")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PoWalkInfo(ctypes.Structure):
     _fields_ = [(name, ctypes.c_uint32) for name in ("ploidy", "n_cands", "depth", "start_of_block")] + [("n_block_reads", ctypes.c_uint64)]
 
@@ -500,6 +517,11 @@ SYMBOLS = [
     ("po_paths_sizes", ctypes.c_int, [_P, ctypes.POINTER(PoPathsDims)]),
     ("po_paths_copy", ctypes.c_int, [_P] + [ctypes.c_void_p] * 9),
     ("po_get_paths_stats", ctypes.c_int, [_P, ctypes.POINTER(PoPathsStats)]),
+    ("po_phase_large", ctypes.c_int, [_P, _P, ctypes.POINTER(PoLargeParams), ctypes.POINTER(PoLargeInput), ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
+    ("po_get_large_stats", ctypes.c_int, [_P, ctypes.POINTER(PoLargeStats)]),
+    ("po_paths_copy_paths", ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.POINTER(ctypes.c_uint64)]),
     ("po_walk_create", ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(_P)]),
     ("po_walk_reset", ctypes.c_int, [_P]),
     ("po_walk_info_get", ctypes.c_int, [_P, ctypes.POINTER(PoWalkInfo)]),

@@ -413,10 +413,15 @@ def phase_entries(base: str, blocks):
             yield "%s.haploblock%d.%d" % (base, i, j), haplotype, block.include_last
 
 
-def _subgraph_bubble_paths(path, device):
-    """(graph file, BubblePaths) of a subgraph; every bubble of up to 64 paths -- what one device call can score -- is listed."""
+HOST_PATHS = 64                  # a bubble of up to this many paths comes to the host: what the branch arm can score in one call
+MAX_LISTED_PATHS = 1 << 20       # --max-listed-paths: the paths of a larger bubble are not listed at all
+
+
+def _subgraph_bubble_paths(path, device, max_listed=MAX_LISTED_PATHS):
+    """(graph file, DevicePaths) of a subgraph, to be closed: every bubble of up to ``max_listed`` paths is listed and stays on
+    the device; the walk fetches the paths of the bubbles of up to 64 paths and scores the larger ones where they are."""
     from . import layout
-    graph, paths, _ = layout.graph_file_bubble_paths(path, 64, device=device)
+    graph, paths, _ = layout.graph_file_device_paths(path, max(int(max_listed), HOST_PATHS), device=device)
     return graph, paths
 
 
@@ -424,7 +429,9 @@ def phase(args) -> int:
     """`phasm phase` (phasm/cli/assembler.py:331-418): per subgraph either the one contig of a graph without bubbles, or the
     haploblocks of its bubble chain -- the walk of ``phasing.phase_chain`` with the candidate sets resident on the device.
     The reads go on the handle once; the alignments are indexed there once, when the first subgraph with bubbles needs them;
-    all sequences of a subgraph are spelled in one device call."""
+    all sequences of a subgraph are spelled in one device call.  The paths of a subgraph's bubbles stay on the device
+    (``--max-listed-paths`` caps what is listed): those of a bubble of up to 64 paths come home for the branch arm, a larger
+    bubble is scored where its paths are (``po_phase_large``) and only the winner comes home."""
     import random
     from . import phasing, spelling
     if not 1 <= args.ploidy <= 8:
@@ -434,46 +441,64 @@ def phase(args) -> int:
     overlapper.add_fasta(args.reads_fasta, both_strands=True)
     reads_of = spelling.ReadMap.of(overlapper)
     index, n_entries = None, 0
+    max_listed = int(getattr(args, "max_listed_paths", MAX_LISTED_PATHS))
     for path in args.subgraphs:
-        gf, paths = _subgraph_bubble_paths(path, args.device)
-        base = spelling.contig_name(path)
         try:
-            chain = phase_chain_of(gf, paths)
-        except PhasingError as e:
-            raise SystemExit("%s: %s" % (path, e))
-        if chain is None:
-            logger.info("%s: no bubbles, a simple contig path of %d nodes.", path, len(gf.node_order))
-            names, pieces = [base], [spelling.contig_pieces(gf, reads_of)]
-        else:
-            if index is None:
-                with open(args.alignments_gfa) as f:
-                    seg_names, _, rows = gfa.read_gfa2_rows(f)
-                to_read = np.asarray([reads_of[name + sign] for name in seg_names for sign in "+-"], dtype=np.int64)
-                if len(rows):
-                    rows[:, 0], rows[:, 1] = to_read[rows[:, 0]], to_read[rows[:, 1]]
-                res = overlapper.result_from_rows(rows)
-                index = overlapper.phase_index(res)
-                res.free()
-
-            def node_reads(n, gf=gf):
-                seg = int(n) >> 1
-                return [reads_of[r] for r in gf.fragments[seg][0]] if seg in gf.fragments else [reads_of[gf.node_name(n)]]
-
+            gf, paths = _subgraph_bubble_paths(path, args.device, **({} if max_listed == MAX_LISTED_PATHS else {"max_listed": max_listed}))
+        except OverflowError as e:
+            raise SystemExit("%s: %s (lower --max-listed-paths)" % (path, e))
+        try:
+            base = spelling.contig_name(path)
             try:
-                bubbles = phasing.chain_bubbles_input(paths, chain, node_reads, is_merged=lambda n, gf=gf: (int(n) >> 1) in gf.fragments)
-            except ValueError as e:
+                chain = phase_chain_of(gf, paths)
+            except PhasingError as e:
                 raise SystemExit("%s: %s" % (path, e))
-            logger.info("%s: a bubble chain of %d bubbles, ploidy %d.", path, len(bubbles), args.ploidy)
-            walk = overlapper.phase_walk(args.ploidy)
-            try:
-                blocks = list(phasing.phase_chain(overlapper, overlapper, index, bubbles, node_reads, args.ploidy, args.min_spanning_reads,
-                                                  args.max_bubble_size, args.threshold, args.prune_factor, args.max_candidates,
-                                                  args.max_prune_rounds, args.prune_step_size, walk=walk, choose=choose))
-            finally:
-                walk.close()
-            entries = list(phase_entries(base, blocks))
-            names = [e[0] for e in entries]
-            pieces = [spelling.path_pieces(gf, nodes, reads_of, include_last) for _, nodes, include_last in entries]
+            if chain is None:
+                logger.info("%s: no bubbles, a simple contig path of %d nodes.", path, len(gf.node_order))
+                names, pieces = [base], [spelling.contig_pieces(gf, reads_of)]
+            else:
+                if index is None:
+                    with open(args.alignments_gfa) as f:
+                        seg_names, _, rows = gfa.read_gfa2_rows(f)
+                    to_read = np.asarray([reads_of[name + sign] for name in seg_names for sign in "+-"], dtype=np.int64)
+                    if len(rows):
+                        rows[:, 0], rows[:, 1] = to_read[rows[:, 0]], to_read[rows[:, 1]]
+                    res = overlapper.result_from_rows(rows)
+                    index = overlapper.phase_index(res)
+                    res.free()
+
+                def node_reads(n, gf=gf):
+                    seg = int(n) >> 1
+                    return [reads_of[r] for r in gf.fragments[seg][0]] if seg in gf.fragments else [reads_of[gf.node_name(n)]]
+
+                for b in paths.chain_bubbles(chain):
+                    if not paths.is_listed(b) and int(paths.bubbles["n_paths"][b]) > max(max_listed, HOST_PATHS):
+                        raise SystemExit("%s: bubble %d has %s paths, more than --max-listed-paths %d: they were not listed" %
+                                         (path, b, phasing.paths_text(paths.bubbles["n_paths"][b]), max_listed))
+                try:
+                    bubbles = phasing.chain_bubbles_input(paths, chain, node_reads, is_merged=lambda n, gf=gf: (int(n) >> 1) in gf.fragments,
+                                                          **({"resident_above": HOST_PATHS} if hasattr(paths, "score_large") else {}))
+                except ValueError as e:
+                    raise SystemExit("%s: %s" % (path, e))
+                for i, b in enumerate(bubbles):
+                    if b.get("paths") is None and b["n_paths"] <= args.max_bubble_size:
+                        raise SystemExit("%s: bubble %d (%s .. %s) has %d paths: more than the 64 the branch arm takes, and no large bubble "
+                                         "with --max-bubble-size %d" % (path, i, gf.node_name(b["entrance"]), gf.node_name(b["exit"]),
+                                                                        b["n_paths"], args.max_bubble_size))
+                logger.info("%s: a bubble chain of %d bubbles, ploidy %d.", path, len(bubbles), args.ploidy)
+                walk = overlapper.phase_walk(args.ploidy)
+                try:
+                    blocks = list(phasing.phase_chain(overlapper, overlapper, index, bubbles, node_reads, args.ploidy, args.min_spanning_reads,
+                                                      args.max_bubble_size, args.threshold, args.prune_factor, args.max_candidates,
+                                                      args.max_prune_rounds, args.prune_step_size, walk=walk, choose=choose))
+                finally:
+                    walk.close()
+                entries = list(phase_entries(base, blocks))
+                names = [e[0] for e in entries]
+                pieces = [spelling.path_pieces(gf, nodes, reads_of, include_last) for _, nodes, include_last in entries]
+        finally:
+            if hasattr(paths, "close"):
+                paths.close()
         for name, seq in zip(names, spelling.spell_pieces(overlapper, pieces)):
             args.output.write(b">" + name.encode("utf-8") + b"\n" + seq + b"\n")
         n_entries += len(names)
@@ -627,6 +652,9 @@ def main(argv=None) -> int:
     ph.add_argument("-r", "--max-prune-rounds", type=_int_in(0, 1024), default=9, help="maximum number of pruning rounds (default: 9)")
     ph.add_argument("-S", "--prune-step-size", type=float, default=0.1, help="raise of the prune factor per round (default: 0.1)")
     ph.add_argument("-o", "--output", type=argparse.FileType("wb"), required=True, help="the FASTA file to write")
+    ph.add_argument("--max-listed-paths", type=_int_in(1, 2**30 - 1), default=MAX_LISTED_PATHS,
+                    help="the paths of a bubble are listed on the device, and the bubble can be phased, only up to this many: a cap on "
+                         "device memory (default: 2^20)")
     ph.add_argument("--device", type=int, default=None)
     ph.add_argument("--seed", type=int, default=None, help="seed of the choice among equally likely candidates (default: unseeded)")
     ph.add_argument("reads_fasta", help="the reads (FASTA); both strands go on the handle, as `overlap` adds them")

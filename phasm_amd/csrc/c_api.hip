@@ -54,6 +54,7 @@
 #include "spell.hip.h"
 #include "paths.hip.h"
 #include "walk.hip.h"
+#include "large.hip.h"
 
 namespace {
 
@@ -118,12 +119,15 @@ enum { QB_CNT, QB_NB, QB_COFF, QB_HOME, QB_BIDX, QB_BENT, QB_DONE, QB_COUNT, QB_
        QB_NLIST, QB_NPRED, QB_NIN, QB_PLEN, QB_N };
 // what a po_phase_paths result holds in HBM (po_result::d_pp): the table, the three CSR pairs, the offsets of the paths
 enum { PR_TABLE, PR_INOFF, PR_INNODES, PR_PREDOFF, PR_PREDNODE, PR_PREDW, PR_BPO, PR_POFF, PR_PATHS, PR_N };
+// workspaces of po_phase_large (large.hip.h): counters, the uploaded inputs, the bitsets and intervals of the interior nodes,
+// the slot of every node of the graph, the score of every listed path of the bubble
+enum { LB_CNT, LB_OM, LB_ALNOFF, LB_ALNB, LB_A0, LB_A1, LB_NOFF, LB_NIDS, LB_NBITS, LB_NIV, LB_SLOT, LB_SCORE, LB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 134;
+constexpr int EV_LAY_N = 138;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
        EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
-       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94, EV_CYCLIC = 96, EV_CHAINS_ALL = 106, EV_CONTIGS_ALL = 118 };
+       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94, EV_CYCLIC = 96, EV_CHAINS_ALL = 106, EV_CONTIGS_ALL = 118, EV_LARGE = 134 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
 static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
@@ -134,7 +138,8 @@ static_assert(EV_PATHS + 11 == EV_WALK, "po_phase_paths has eleven events");
 static_assert(EV_WALK + 2 == EV_CYCLIC, "po_walk_step has two events");
 static_assert(EV_CYCLIC + 10 == EV_CHAINS_ALL, "po_layout_superbubbles_all has ten events");
 static_assert(EV_CHAINS_ALL + 12 == EV_CONTIGS_ALL, "po_layout_bubblechains_all has twelve events: those ten and two of its own");
-static_assert(EV_CONTIGS_ALL + 16 == EV_LAY_N, "the sixteen events of po_layout_contigs_all are the last of the layout events");
+static_assert(EV_CONTIGS_ALL + 16 == EV_LARGE, "po_layout_contigs_all has sixteen events");
+static_assert(EV_LARGE + 4 == EV_LAY_N, "the four events of po_phase_large are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -516,6 +521,9 @@ struct po_handle {
     // paths, interior and exit predecessors of every top-level bubble (po_phase_paths, paths.hip.h)
     DevBuf d_pp[QB_N];
     po_paths_stats ppstats = {};
+    // every listed path of a large bubble scored, the best of them named (po_phase_large, large.hip.h)
+    DevBuf d_lg[LB_N];
+    po_large_stats lgstats = {};
 };
 
 struct po_result {
@@ -564,6 +572,11 @@ struct po_result {
     // po_phase_paths (special == 4): everything stays in HBM (d_pp, 32-bit offsets: the call refuses what does not fit them)
     DevBuf d_pp[PR_N];
     po_paths_dims pp = {};
+    // the node ids of its graph are below pp_n_total; the table, inside_off and bubble_path_off on the host once
+    // po_phase_large or po_paths_copy_paths asked for them (they are bubble-sized)
+    uint32_t pp_n_total = 0;
+    std::vector<po_bubble_paths> pp_table;
+    std::vector<uint32_t> pp_inoff, pp_bpo;
     // po_walk_create (special == 5): the candidate sets of a walk along a bubble chain (walk.hip.h).  On the device: the bit
     // rows of the slots over block-stable read ids and the log_rl of the candidates, each as a ping-pong pair (wk_cur names
     // the live half), and the links (parent, extension) of every advanced bubble, level after level (wk_level_off).  On the
@@ -3043,6 +3056,9 @@ uint32_t stride_grid(const po_handle* h, uint64_t n) {
     return std::max<uint32_t>(1u, std::min<uint32_t>(cdiv(n, 256), (uint32_t)h->n_cu * 8));
 }
 
+// the workgroups of k_lg_score at the most (one path each per step): eight of 256 threads per CU
+uint32_t large_grid_cap(const po_handle* h) { return (uint32_t)h->n_cu * 8; }
+
 // the events of the layout calls, made by the first of them on a handle
 po_status lay_events(po_handle* h) {
     for (hipEvent_t& e : h->ev_lay)
@@ -5045,6 +5061,7 @@ po_status run_paths(po_handle* h, po_result* graph, uint64_t max_paths, po_resul
     S.n_path_nodes = n_path_nodes;
     S.max_path_nodes = C[po::QK_MAXLEN];
     r->pp = po_paths_dims{n_b, n_inside, n_preds, n_listed, n_path_nodes};
+    r->pp_n_total = R.n_total;
     (void)hipEventElapsedTime(&S.ms_chains, ev[0], ev[8]);
     (void)hipEventElapsedTime(&S.ms_count, ev[8], ev[9]);
     (void)hipEventElapsedTime(&S.ms_list, ev[9], ev[10]);
@@ -5459,6 +5476,145 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     (void)hipEventElapsedTime(&S.ms_filter, ev[3], ev[4]);
     (void)hipEventElapsedTime(&S.ms_prune, ev[4], ev[5]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[5]);
+    return PO_OK;
+}
+
+// ---- every listed path of a large bubble scored, the best of them named (po_phase_large, large.hip.h) ------------------------
+
+// The checks of po_phase_large that need neither the result nor the device, in the order the header lists them: the sentence
+// of the first one that fails, empty when the call may go on.
+std::string large_check(const po_large_params& p, const po_large_input& in) {
+    const std::string name = "po_phase_large: ";
+    if (p.reserved) return name + "bad parameters";
+    if (p.n_best < 1 || p.n_best > po::LG_MAX_BEST) return name + "n_best must be 1 to 8";
+    if (!p.n_reads) return name + "there must be at least one relevant read";
+    if (!in.overlap_max || !in.aln_off || !in.node_off) return name + "an input array is missing";
+    if (!phase_offsets_ok(in.aln_off, p.n_reads)) return name + "the offsets of the alignments do not start at 0 or decrease";
+    if (!phase_offsets_ok(in.node_off, in.n_nodes)) return name + "the offsets of the interior nodes do not start at 0 or decrease";
+    const uint32_t n_aln = in.aln_off[p.n_reads], n_ids = in.node_off[in.n_nodes];
+    if ((n_aln && (!in.aln_b || !in.aln_a0 || !in.aln_a1)) || (n_ids && !in.node_ids)) return name + "an input array is missing";
+    for (uint32_t j = 0; j < n_aln; ++j)
+        if (in.aln_b[j] >= p.n_b) return name + "a local read id is not below n_b";
+    for (uint32_t j = 0; j < n_ids; ++j)
+        if (in.node_ids[j] >= p.n_b) return name + "a local read id is not below n_b";
+    return std::string();
+}
+
+// the table, inside_off and bubble_path_off of a paths result on the host (they are bubble-sized), fetched once
+po_status paths_home(po_handle* h, po_result* r) {
+    const size_t nb = (size_t)r->pp.n_bubbles;
+    if (r->pp_table.size() == nb && r->pp_bpo.size() == nb + 1) return PO_OK;
+    std::vector<po_bubble_paths> table(nb);
+    std::vector<uint32_t> inoff(nb + 1, 0u), bpo(nb + 1, 0u);
+    if (nb) {
+        hipStream_t st = h->stream;
+        HIP_TRY(h, hipMemcpyAsync(table.data(), r->d_pp[PR_TABLE].p, nb * sizeof(po_bubble_paths), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(inoff.data(), r->d_pp[PR_INOFF].p, (nb + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(bpo.data(), r->d_pp[PR_BPO].p, (nb + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    r->pp_table.swap(table);
+    r->pp_inoff.swap(inoff);
+    r->pp_bpo.swap(bpo);
+    return PO_OK;
+}
+
+po_status run_large(po_handle* h, po_result* r, const po_large_params& p, const po_large_input& in, uint64_t* best_out, double* best_score_out,
+                    double* scores_out, uint32_t* n_best_out) {
+    const std::string name = "po_phase_large: ";
+    hipStream_t st = h->stream;
+    po_large_stats& S = h->lgstats;
+    S = po_large_stats();
+    PO_TRY(paths_home(h, r));
+    const po_bubble_paths& T = r->pp_table[p.bubble];
+    if (T.flags & PO_PATHS_UNLISTED)
+        return fail(h, PO_ERR_INVALID, name + "the paths of bubble " + std::to_string(p.bubble) + " were not listed (more than max_paths)");
+    if (in.n_nodes != T.n_inside)
+        return fail(h, PO_ERR_INVALID, name + "n_nodes is " + std::to_string(in.n_nodes) + ", bubble " + std::to_string(p.bubble) + " has " +
+                                           std::to_string(T.n_inside) + " interior nodes");
+    const uint32_t first = r->pp_bpo[p.bubble], P = r->pp_bpo[p.bubble + 1] - first, in_first = r->pp_inoff[p.bubble];
+    const uint32_t n_inside = T.n_inside, R = p.n_reads, nb = p.n_b, W = std::max(1u, cdiv(nb, 32)), n_total = r->pp_n_total;
+    if (P != T.n_paths || r->pp_inoff[p.bubble + 1] - in_first != n_inside || (uint64_t)first + P > r->pp.n_listed_paths)
+        return fail(h, PO_ERR_HIP, "internal: the table of the paths result of po_phase_large does not add up");
+    const uint32_t n_aln = in.aln_off[R], n_ids = in.node_off[n_inside];
+    DevBuf* B = h->d_lg;
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_LARGE;
+    // everything is sized by the inputs and allocated before the first launch
+    PO_TRY(ensure(h, B[LB_CNT], 256));
+    for (int b : {LB_OM, LB_ALNOFF}) PO_TRY(ensure(h, B[b], ((size_t)R + 1) * 4));
+    for (int b : {LB_ALNB, LB_A0, LB_A1}) PO_TRY(ensure(h, B[b], ((size_t)n_aln + 1) * 4));
+    PO_TRY(ensure(h, B[LB_NOFF], ((size_t)n_inside + 1) * 4));
+    PO_TRY(ensure(h, B[LB_NIDS], ((size_t)n_ids + 1) * 4));
+    PO_TRY(ensure(h, B[LB_NBITS], std::max<size_t>((size_t)n_inside * W * 4, 256)));
+    PO_TRY(ensure(h, B[LB_NIV], std::max<size_t>((size_t)n_inside * R * sizeof(po::PhInterval), 256)));
+    PO_TRY(ensure(h, B[LB_SLOT], ((size_t)n_total + 1) * 4));
+    PO_TRY(ensure(h, B[LB_SCORE], ((size_t)P + 1) * 8));
+    unsigned long long* cnt = B[LB_CNT].as<unsigned long long>();
+    int32_t *om = B[LB_OM].as<int32_t>(), *a0 = B[LB_A0].as<int32_t>(), *a1 = B[LB_A1].as<int32_t>();
+    uint32_t *aln_off = B[LB_ALNOFF].as<uint32_t>(), *aln_b = B[LB_ALNB].as<uint32_t>(), *noff = B[LB_NOFF].as<uint32_t>(),
+             *nids = B[LB_NIDS].as<uint32_t>(), *nbits = B[LB_NBITS].as<uint32_t>(), *slot_of = B[LB_SLOT].as<uint32_t>();
+    po::PhInterval* niv = B[LB_NIV].as<po::PhInterval>();
+    double* score = B[LB_SCORE].as<double>();
+    const uint32_t *poff = r->d_pp[PR_POFF].as<uint32_t>() + first, *path_nodes = r->d_pp[PR_PATHS].as<uint32_t>(),
+                   *inside_nodes = r->d_pp[PR_INNODES].as<uint32_t>() + in_first;
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    static_assert(po::LK_N * 8 <= 256, "the counters of po_phase_large fit their buffer");
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, (size_t)po::LK_BEST * 8, st));
+    HIP_TRY(h, hipMemsetAsync(cnt + po::LK_BEST, 0xFF, (size_t)po::LG_MAX_BEST * 8, st));   // (LG_NO_INDEX)
+    HIP_TRY(h, hipMemsetAsync(slot_of, 0xFF, ((size_t)n_total + 1) * 4, st));               // (LG_NO_SLOT)
+    HIP_TRY(h, hipMemsetAsync(nbits, 0, std::max<size_t>((size_t)n_inside * W * 4, 4), st));
+    auto up = [&](void* dst, const void* src, size_t bytes) -> po_status {
+        if (bytes) HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+        return PO_OK;
+    };
+    PO_TRY(up(om, in.overlap_max, (size_t)R * 4));
+    PO_TRY(up(aln_off, in.aln_off, ((size_t)R + 1) * 4));
+    PO_TRY(up(aln_b, in.aln_b, (size_t)n_aln * 4));
+    PO_TRY(up(a0, in.aln_a0, (size_t)n_aln * 4));
+    PO_TRY(up(a1, in.aln_a1, (size_t)n_aln * 4));
+    PO_TRY(up(noff, in.node_off, ((size_t)n_inside + 1) * 4));
+    PO_TRY(up(nids, in.node_ids, (size_t)n_ids * 4));
+    if (n_inside) {
+        hipLaunchKernelGGL(po::k_lg_slots, dim3(stride_grid(h, n_inside)), dim3(256), 0, st, n_inside, inside_nodes, n_total, slot_of);
+        hipLaunchKernelGGL(po::k_ph_bits, dim3(stride_grid(h, n_inside)), dim3(256), 0, st, n_inside, noff, nids, nb, W, nbits);
+        hipLaunchKernelGGL(po::k_ph_intervals, dim3(stride_grid(h, (uint64_t)n_inside * R)), dim3(256), 0, st, n_inside, R, nb, W, nbits, aln_off,
+                           aln_b, a0, a1, om, niv);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    const uint32_t wg_cap = large_grid_cap(h);
+    hipLaunchKernelGGL(po::k_lg_score, dim3(std::max(1u, std::min(P, wg_cap))), dim3(256), 0, st, P, R, n_inside, n_total, poff, path_nodes, slot_of,
+                       niv, om, score, cnt);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    const uint32_t n_best = (uint32_t)std::min<uint64_t>(p.n_best, P);
+    for (uint32_t j = 0; j < n_best; ++j) {
+        hipLaunchKernelGGL(po::k_lg_best_key, dim3(stride_grid(h, P)), dim3(256), 0, st, P, j, score, cnt);
+        hipLaunchKernelGGL(po::k_lg_best_idx, dim3(stride_grid(h, P)), dim3(256), 0, st, P, j, score, cnt);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    PO_TRY(land_outputs(h, {{score, (size_t)P * 8, scores_out}}, cnt, po::LK_N));
+    const volatile uint64_t* C = h->pinned + 16;
+    for (uint32_t j = 0; j < n_best; ++j) {
+        const uint64_t key = C[po::LK_KEY + j], at = C[po::LK_BEST + j];
+        if (!key || at >= P) return fail(h, PO_ERR_HIP, "internal: the selection of po_phase_large found no path");
+        for (uint32_t i = 0; i < j; ++i)
+            if (C[po::LK_BEST + i] == at) return fail(h, PO_ERR_HIP, "internal: the selection of po_phase_large named a path twice");
+        const uint64_t bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
+        if (best_out) best_out[j] = at;
+        if (best_score_out) std::memcpy(best_score_out + j, &bits, 8);
+    }
+    *n_best_out = n_best;
+    S.n_paths = P;
+    S.n_inside = n_inside;
+    S.n_reads = R;
+    S.max_path_nodes = C[po::LK_MAXLEN];
+    (void)hipEventElapsedTime(&S.ms_intervals, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&S.ms_score, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&S.ms_best, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
     return PO_OK;
 }
 
@@ -6508,6 +6664,7 @@ void po_destroy(po_handle* h) {
         for (DevBuf& b : h->d_rr) b.release();
         for (DevBuf& b : h->d_sp) b.release();
         for (DevBuf& b : h->d_pp) b.release();
+        for (DevBuf& b : h->d_lg) b.release();
         const bool pooled = kit_give(h);
         if (!pooled) {
         for (int i = 0; i < 2 * EV_N; ++i) (void)hipEventDestroy(h->ev_sets[i / EV_N][i % EV_N]);
@@ -8717,6 +8874,65 @@ po_status po_paths_copy(po_result* out, po_bubble_paths* bubbles, uint64_t* insi
 }
 
 po_status po_get_paths_stats(const po_handle* h, po_paths_stats* out) { return get_stats(h, &po_handle::ppstats, out); }
+
+po_status po_phase_large(po_handle* h, po_result* paths, const po_large_params* params, const po_large_input* input, uint64_t* best_out,
+                         double* best_score_out, double* scores_out, uint32_t* n_best_out) {
+    const std::string name = "po_phase_large: ";
+    if (!h) return PO_ERR_INVALID;
+    if (!n_best_out) return fail(h, PO_ERR_INVALID, name + "no room for the number of best paths");
+    *n_best_out = 0;
+    if (!paths) return fail(h, PO_ERR_INVALID, name + "no paths result");
+    if (!params || !input) return fail(h, PO_ERR_INVALID, name + "no parameters");
+    if (!best_out || !best_score_out) return fail(h, PO_ERR_INVALID, name + "no room for the best paths");
+    const std::string said = large_check(*params, *input);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    if (paths->special != 4) return fail(h, PO_ERR_INVALID, "po_phase_large needs the result of po_phase_paths");
+    if (paths->h != h) return fail(h, PO_ERR_INVALID, name + "the paths result belongs to another handle");
+    if (params->bubble >= paths->pp.n_bubbles)
+        return fail(h, PO_ERR_INVALID, name + "bubble " + std::to_string(params->bubble) + " is not below the " +
+                                           std::to_string(paths->pp.n_bubbles) + " bubbles of the result");
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return guarded_run(h, "po_phase_large", [&] { return run_large(h, paths, *params, *input, best_out, best_score_out, scores_out, n_best_out); });
+}
+
+po_status po_get_large_stats(const po_handle* h, po_large_stats* out) { return get_stats(h, &po_handle::lgstats, out); }
+
+po_status po_paths_copy_paths(po_result* paths, uint64_t first, uint64_t count, uint64_t* path_off_out, uint32_t* path_nodes_out, uint64_t cap,
+                              uint64_t* n_nodes_out) {
+    if (!paths) return PO_ERR_INVALID;
+    po_handle* h = paths->h;
+    const std::string name = "po_paths_copy_paths: ";
+    if (!n_nodes_out) return fail(h, PO_ERR_INVALID, name + "no room for the number of nodes");
+    *n_nodes_out = 0;
+    if (paths->special != 4) return fail(h, PO_ERR_INVALID, "po_paths_copy_paths needs the result of po_phase_paths");
+    const uint64_t n_listed = paths->pp.n_listed_paths;
+    if (first > n_listed || count > n_listed - first)
+        return fail(h, PO_ERR_INVALID, name + "paths " + std::to_string(first) + " .. " + std::to_string(first) + " + " + std::to_string(count) +
+                                           " end past the " + std::to_string(n_listed) + " listed paths");
+    if (!count) {
+        if (path_off_out) path_off_out[0] = 0;
+        return PO_OK;
+    }
+    return guarded_run(h, "po_paths_copy_paths", [&] {
+        hipStream_t st = h->stream;
+        std::vector<uint32_t> off((size_t)count + 1);
+        HIP_TRY(h, hipMemcpyAsync(off.data(), paths->d_pp[PR_POFF].as<uint32_t>() + first, ((size_t)count + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        const uint64_t lo = off[0], hi = off[(size_t)count];
+        if (hi < lo || hi > paths->pp.n_path_nodes) return fail(h, PO_ERR_HIP, "internal: the path offsets of po_paths_copy_paths do not add up");
+        *n_nodes_out = hi - lo;
+        if (path_nodes_out && cap < hi - lo)
+            return fail(h, PO_ERR_CAPACITY, name + "the paths hold " + std::to_string(hi - lo) + " nodes, there is room for " + std::to_string(cap));
+        if (path_nodes_out && hi > lo) {
+            HIP_TRY(h, hipMemcpyAsync(path_nodes_out, paths->d_pp[PR_PATHS].as<uint32_t>() + lo, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+        }
+        if (path_off_out)
+            for (size_t j = 0; j <= (size_t)count; ++j) path_off_out[j] = off[j] - lo;
+        return PO_OK;
+    });
+}
 
 po_status po_result_merged_paths(po_result* r, uint64_t* n_paths, uint64_t* n_members, uint64_t* offsets_out, uint64_t cap_paths,
                                  uint32_t* members_out, int32_t* prefix_out, uint64_t cap_members, int64_t* lengths_out) {

@@ -921,6 +921,28 @@ def graph_file_bubble_paths(path: str, max_paths: int = 0, device: Optional[int]
         ov.close()
 
 
+def graph_file_device_paths(path: str, max_paths: int = 0, device: Optional[int] = None):
+    """``graph_file_bubble_paths`` with the listed paths KEPT on the device: ``(graph file, DevicePaths, stats)``.  The fresh
+    handle the graph was put on lives as long as the ``DevicePaths``, whose ``close()`` closes it too."""
+    from .io import gfa
+    with open(path) as f:
+        graph = gfa.read_graph_gfa(f)
+    ov = ExactOverlapper(device=device)
+    try:
+        for name, n in zip(graph.names, graph.lengths.tolist()):
+            ov.add_segment(name, n)
+        res = ov.graph_from_edges(graph.edges, graph.node_order)
+        try:
+            paths = ov.phase_paths_resident(res, max_paths)
+        finally:
+            res.free()
+        paths._owned.append(ov)
+        return graph, paths, ov.paths_stats()
+    except BaseException:
+        ov.close()
+        raise
+
+
 def component_gfa2_lines(graph, nodes: Sequence[int], edges: np.ndarray) -> List[str]:
     """What ``gfa2_write_graph`` (phasm/io/gfa.py:281-326) writes for the subgraph of ``nodes`` (in node order) with
     ``edges`` (rows of ``graph.edges``, input order)."""

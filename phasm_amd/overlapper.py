@@ -191,6 +191,109 @@ class DeviceWalk:
             pass
 
 
+class DevicePaths(BubblePaths):
+    """Owns a ``po_phase_paths`` result that STAYS on the device (``ExactOverlapper.phase_paths_resident``).  The bubble-sized
+    arrays -- table, interiors, exit predecessors, ``bubble_path_off`` -- come home once; the listed paths do not:
+    ``paths_of(b)`` and ``path_of(b, p)`` fetch a range through ``po_paths_copy_paths``, ``score_large`` scores every listed
+    path of a bubble where it is (``po_phase_large``).  The accessors are those of ``phasm_amd.phasing.BubblePaths``
+    (``path_off`` and ``path_nodes`` stay empty).  ``close()`` frees the device result (and whatever ``owned`` names, in
+    order: the handle of a graph that lives only for these paths); the graph it was listed from may be freed before."""
+
+    def __init__(self, owner: "ExactOverlapper", ptr, owned=()):
+        self._owner, self._lib, self._ptr, self._owned = owner, _lib.load(), ptr, list(owned)
+        try:
+            d = _lib.PoPathsDims()
+            _check(owner._h, self._lib.po_paths_sizes(ptr, ctypes.byref(d)))
+            nb = int(d.n_bubbles)
+            super().__init__(np.zeros(nb, _lib.BUBBLE_PATHS_DTYPE), np.zeros(nb + 1, np.uint64), np.zeros(int(d.n_inside_nodes), np.uint32),
+                             np.zeros(nb + 1, np.uint64), np.zeros(int(d.n_preds), np.uint32), np.zeros(int(d.n_preds), np.int32),
+                             np.zeros(nb + 1, np.uint64), np.zeros(1, np.uint64), np.zeros(0, np.uint32))
+            self.n_listed_paths, self.n_path_nodes = int(d.n_listed_paths), int(d.n_path_nodes)
+            _check(owner._h, self._lib.po_paths_copy(ptr, _ptr(self.bubbles), _ptr(self.inside_off), _ptr(self.inside_nodes), _ptr(self.pred_off),
+                                                     _ptr(self.pred_node), _ptr(self.pred_weight), _ptr(self.bubble_path_off), None, None))
+        except Exception:
+            self.close()
+            raise
+
+    def _range(self, first: int, count: int):
+        """``(offsets relative to the first path, nodes)`` of the listed paths first .. first + count - 1."""
+        if self._ptr is None:
+            raise ValueError("the device paths are closed")
+        off, n = np.zeros(count + 1, dtype=np.uint64), ctypes.c_uint64()
+        _check(self._owner._h, self._lib.po_paths_copy_paths(self._ptr, int(first), int(count), _ptr(off), None, 0, ctypes.byref(n)))
+        nodes = np.zeros(int(n.value), dtype=np.uint32)
+        _check(self._owner._h, self._lib.po_paths_copy_paths(self._ptr, int(first), int(count), None, _ptr(nodes), len(nodes), ctypes.byref(n)))
+        return off, nodes
+
+    def paths_of(self, b: int) -> List[tuple]:
+        """``BubblePaths.paths_of``, fetched from the device when asked."""
+        if not self.is_listed(b):
+            return super().paths_of(b)   # (raises: the paths were not listed)
+        first, last = int(self.bubble_path_off[b]), int(self.bubble_path_off[b + 1])
+        off, nodes = self._range(first, last - first)
+        return [tuple(nodes[int(off[p]):int(off[p + 1])].tolist()) for p in range(last - first)]
+
+    def path_of(self, b: int, p: int) -> tuple:
+        """Listed path ``p`` (0-based within bubble b) alone, both ends included."""
+        first, n = int(self.bubble_path_off[b]), int(self.bubble_path_off[b + 1]) - int(self.bubble_path_off[b])
+        if not self.is_listed(b) or not 0 <= int(p) < n:
+            raise ValueError("bubble %d has no listed path %d" % (b, p))
+        return tuple(self._range(first + int(p), 1)[1].tolist())
+
+    def score_large(self, b: int, rel: "RelevantReads", reads_of_node, n_best: int, want_scores: bool = False):
+        """``po_phase_large`` on bubble b: ``(best, best_scores, scores or None)`` -- the ``n_best`` best path indices within the
+        bubble as ``sorted(range(P), key=score.get, reverse=True)[:n_best]`` gives them, their scores, and with
+        ``want_scores`` the score of every listed path.  ``rel``: the relevant reads (``phasing.relevant_reads``);
+        ``reads_of_node(node)``: the read ids of a node."""
+        from .phasing import large_node_lists
+        if self._ptr is None:
+            raise ValueError("the device paths are closed")
+        if not 0 <= int(b) < len(self) or not 0 <= int(n_best) < 2**32:
+            raise ValueError("po_phase_large: bubble %d is not below the %d bubbles of the result" % (b, len(self)))
+        R = len(rel.rel_reads)
+        if R == 0:
+            raise ZeroDivisionError("no relevant reads")
+        node_off, node_ids = large_node_lists(rel, self.interior_of(b), reads_of_node)
+        arrays = [np.ascontiguousarray(a, dtype=dt) for a, dt in (
+            (rel.overlap_max, np.int32), (rel.aln_off, np.uint32), (rel.aln_b, np.uint32), (rel.aln_a0, np.int32), (rel.aln_a1, np.int32),
+            (node_off, np.uint32), (node_ids, np.uint32))]
+        if len(arrays[0]) != R or len(arrays[1]) != R + 1 or len({len(arrays[2]), len(arrays[3]), len(arrays[4])}) != 1 or \
+                len(arrays[2]) != int(arrays[1][-1]):
+            raise ValueError("the arrays of the relevant reads do not have the lengths their offsets give")
+        prm = _lib.PoLargeParams(int(b), R, len(rel.b_reads), int(n_best), 0)
+        inp = _lib.PoLargeInput(*[a.ctypes.data if len(a) else None for a in arrays], len(node_off) - 1)
+        n_paths = int(self.bubble_path_off[b + 1]) - int(self.bubble_path_off[b])
+        best, best_scores = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.float64)
+        scores = np.zeros(n_paths if want_scores else 0, dtype=np.float64)
+        n = ctypes.c_uint32()
+        _check(self._owner._h, self._lib.po_phase_large(self._owner._h, self._ptr, ctypes.byref(prm), ctypes.byref(inp), _ptr(best),
+                                                        _ptr(best_scores), _ptr(scores), ctypes.byref(n)))
+        k = int(n.value)
+        return [int(x) for x in best[:k]], best_scores[:k].copy(), (scores if want_scores else None)
+
+    def large_stats(self) -> dict:
+        return self._owner.large_stats()
+
+    def close(self) -> None:
+        if getattr(self, "_ptr", None) is not None:
+            self._lib.po_result_free(self._ptr)
+            self._ptr = None
+        while getattr(self, "_owned", None):
+            self._owned.pop(0).close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class OverlapResult:
     """Owns one ``po_result``: rows stay on the device until asked for."""
 
@@ -909,6 +1012,24 @@ class ExactOverlapper:
 
     def paths_stats(self) -> dict:
         return self._stats(self._lib.po_get_paths_stats, _lib.PoPathsStats)
+
+    def phase_paths_resident(self, graph: OverlapResult, max_paths: int = 0) -> "DevicePaths":
+        """``po_phase_paths`` with the result KEPT on the device: a ``DevicePaths``, to be closed.  What ``phase_paths`` brings
+        home except the listed paths themselves, which are fetched by range or scored where they are
+        (``DevicePaths.score_large``).  Too many paths to list in one call: OverflowError (lower ``max_paths``)."""
+        if not 0 <= int(max_paths) < 2**64:
+            raise ValueError("max_paths does not fit 64 bits")
+        prm = _lib.PoPathsParams(int(max_paths), 0)
+        r = ctypes.c_void_p()
+        st = self._lib.po_phase_paths(self._h, graph._ptr, ctypes.byref(prm), ctypes.byref(r))
+        if st == _lib.PO_ERR_CAPACITY:
+            msg = self._lib.po_last_error(self._h)
+            raise OverflowError(msg.decode("utf-8", "replace") if msg else "po_phase_paths: too many paths in one call")
+        _check(self._h, st)
+        return DevicePaths(self, r)
+
+    def large_stats(self) -> dict:
+        return self._stats(self._lib.po_get_large_stats, _lib.PoLargeStats)
 
     def graph_from_edges(self, edges, node_order) -> OverlapResult:
         """``po_graph_from_edges``: a graph result from caller-supplied edges (structured EDGE_DTYPE or int array [n, 4]:

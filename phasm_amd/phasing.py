@@ -46,6 +46,18 @@ resident on the device from bubble to bubble, through ``po_walk_*`` (DESIGN.md s
     for block in phase_chain(ov, ov, index, chain_bubbles_input(paths, chain, reads_of_node), reads_of_node, ploidy, walk=walk):
         block.haplotypes, block.read_sets, block.include_last, block.from_large_bubble, block.log_rl, block.tie
 
+The large arm of that walk for a bubble of ANY listed size (``phase_large_bubble``, phasing.py:633-685), with the paths
+RESIDENT on the device, through ``po_phase_large``: the score of a path decomposes over its interior
+nodes, so an interval per (interior node, read) suffices and every listed path is scored where ``po_phase_paths`` left it:
+
+    paths = ov.phase_paths_resident(graph_res, max_listed_paths)                     # a DevicePaths; close() it
+    bubbles = chain_bubbles_input(paths, chain, reads_of_node, resident_above=64)    # larger bubbles: "paths": None, "scorer"
+    best, best_scores, scores = paths.score_large(b, rel, reads_of_node, n_best)     # what phase_chain calls at such a bubble
+    paths.path_of(b, best[0])                                                        # the winner's node tuple alone
+
+``HostResidentPaths(bubble_paths)`` is the same interface in numpy over a fully listed ``BubblePaths`` (the same
+decomposition and tie rule; its summation order may differ from the device's).  Like ``HostScorer`` it is no fallback.
+
 Not here: ``CoverageModel`` (unused by the reference), the debug data log, per-read probabilities."""
 from __future__ import annotations
 
@@ -551,18 +563,28 @@ class HostWalk:
         pass
 
 
-def chain_bubbles_input(bubble_paths: "BubblePaths", chain: int, reads_of_node: Callable, is_merged: Optional[Callable] = None) -> List[dict]:
+def chain_bubbles_input(bubble_paths: "BubblePaths", chain: int, reads_of_node: Callable, is_merged: Optional[Callable] = None,
+                        resident_above: Optional[int] = None) -> List[dict]:
     """The bubbles of one chain in the order of the walk, as ``phase_chain`` takes them: ``entrance``, ``exit``, ``paths``
     (node tuples, both ends included), ``interior_nodes``, ``interior_reads`` (MergedReads expanded through
     ``reads_of_node(node) -> read ids``, every read once) and ``preds`` (the predecessors of the exit that are plain reads, as
     read ids, with their edge lengths: a merged predecessor is no key of the alignments and is left out).  ``is_merged(node)``:
-    default, a node is merged unless ``reads_of_node`` gives the node itself (node ids that are read ids)."""
+    default, a node is merged unless ``reads_of_node`` gives the node itself (node ids that are read ids).
+    ``resident_above`` (with a ``DevicePaths`` or a ``HostResidentPaths``): the paths of a bubble with more paths than this
+    stay where they are -- its ``paths`` is None, ``n_paths`` the count and ``scorer`` a ``ResidentBubble`` that
+    ``phase_chain`` asks at its large arm."""
     if is_merged is None:
         is_merged = lambda x: [int(r) for r in reads_of_node(x)] != [int(x)]   # noqa: E731
     out = []
     for b in bubble_paths.chain_bubbles(chain):
         inside = bubble_paths.interior_of(b)
         preds = [(int(list(reads_of_node(p))[0]), int(weight)) for p, weight in bubble_paths.preds_of(b) if not is_merged(p)]
+        if resident_above is not None and bubble_paths.is_listed(b) and bubble_paths.is_large(b, resident_above):
+            out.append({"entrance": int(bubble_paths.bubbles["entrance"][b]), "exit": int(bubble_paths.bubbles["exit"][b]), "paths": None,
+                        "n_paths": int(bubble_paths.bubbles["n_paths"][b]), "scorer": ResidentBubble(bubble_paths, b),
+                        "interior_nodes": [int(x) for x in inside],
+                        "interior_reads": list(dict.fromkeys(int(r) for x in inside for r in reads_of_node(x))), "preds": preds})
+            continue
         out.append({"entrance": int(bubble_paths.bubbles["entrance"][b]), "exit": int(bubble_paths.bubbles["exit"][b]),
                     "paths": [tuple(int(x) for x in p) for p in bubble_paths.paths_of(b)], "interior_nodes": [int(x) for x in inside],
                     "interior_reads": list(dict.fromkeys(int(r) for x in inside for r in reads_of_node(x))), "preds": preds})
@@ -571,7 +593,7 @@ def chain_bubbles_input(bubble_paths: "BubblePaths", chain: int, reads_of_node: 
 
 def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy: int, min_spanning_reads: int = 3, max_bubble_size: int = 10,
                 threshold=1e-3, prune_factor=0.1, max_candidates: int = 500, max_prune_rounds: int = 9, prune_step_size: float = 0.1,
-                walk=None, choose: Callable = random.choice, on_step: Optional[Callable] = None):
+                walk=None, choose: Callable = random.choice, on_step: Optional[Callable] = None, large_scores: bool = False):
     """``BubbleChainPhaser.phase()`` (phasm/phasing.py:182-364) over ``bubbles`` (``chain_bubbles_input``), arm by arm, as a
     generator of ``Haploblock``.  ``scorer``: what ``score_paths`` needs at a large bubble; ``source`` / ``index``: what
     ``relevant_reads`` needs; ``walk``: a ``DeviceWalk`` (``ExactOverlapper.phase_walk``) or a ``HostWalk`` -- None: the
@@ -580,6 +602,11 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
     candidate numbers).  ``on_step`` receives one dict per turn of the loop (the keys of a trace step of tests/walk_utils.py that the walk knows
     without extra device work, and under ``steps`` the raw ``(cand, ext, rl)`` of every step call) and one with ``final`` at the
     end (``prune_in``, the advanced bubbles of the last block, the two host sets).
+    A bubble whose ``paths`` is absent or None keeps them elsewhere (``chain_bubbles_input`` with ``resident_above``): it
+    gives ``n_paths`` and a ``scorer`` with ``score_large(rel, reads_of_node, n_best, want_scores)`` and ``path_of(p)``.  At
+    the large arm that scorer is asked with the relevant reads and only the winner's node tuple is fetched; ``on_step`` gets
+    ``best``, ``winner`` and ``arm``, and ``scores`` only with ``large_scores``.  Such a bubble that is NOT large cannot be
+    walked (the branch arm needs its paths on the host, at most 64 of them): ``ValueError`` naming the bubble.
     ``prev_graph_reads`` and ``prev_aligning_reads`` are host sets.  One difference from the reference: a bubble that keeps no
     candidate even as the start of a block makes the reference loop for ever; here it raises ``ValueError``."""
     k = int(ploidy)
@@ -617,11 +644,21 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
         i = 0
         while i < len(bubbles):
             b = bubbles[i]
-            paths = [tuple(p) for p in b["paths"]]
-            path_reads = [expand(path[1:-1]) for path in paths]
+            resident = b.get("paths") is None
+            if resident:
+                n_here = int(b["n_paths"])
+                if n_here <= max_bubble_size:
+                    raise ValueError("bubble %d (%s .. %s) has %d paths that are not on the host: only a large bubble (more than "
+                                     "max_bubble_size = %d paths) is scored where its paths are" %
+                                     (i, b.get("entrance"), b.get("exit"), n_here, max_bubble_size))
+                paths, path_reads = None, None
+            else:
+                paths = [tuple(p) for p in b["paths"]]
+                path_reads = [expand(path[1:-1]) for path in paths]
+                n_here = len(paths)
             start = walk.start_of_block
             s = {"bubble": i, "start": int(start), "arm": "skipped", "broke": 0, "fell_back": 0, "yields": [], "steps": []}
-            large = len(paths) > max_bubble_size
+            large = n_here > max_bubble_size
             rel = relevant_reads(source, index, b["interior_reads"], [] if large else sorted(prev_graph), sorted(prev_aligning), b["preds"],
                                  start or large, 0 if large else min_spanning_reads)
             s.update({"cur_aligning": rel.cur_aligning.tolist(), "n_spanning": int(rel.n_spanning), "rel_reads": rel.rel_reads.tolist(),
@@ -634,6 +671,20 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
                 s["broke"], s["fell_back"] = 1, int(rel.fell_back)
                 yield block
                 start = True
+            if large and resident:
+                best, _, scores = b["scorer"].score_large(rel, reads_of_node, k, want_scores=large_scores)
+                if scores is not None:
+                    s["scores"] = np.asarray(scores).tolist()
+                s["best"], s["winner"], s["arm"] = [int(p) for p in best], int(best[0]), "large"
+                winner = tuple(int(x) for x in b["scorer"].path_of(s["winner"]))
+                block = Haploblock([list(winner)] + [[] for _ in range(k - 1)],
+                                   [sorted(set(expand(winner[1:-1])))] + [[] for _ in range(k - 1)], False, True, -math.inf, None)
+                s["yields"].append(as_yield(block, "large"))
+                if on_step:
+                    on_step(s)
+                yield block
+                i += 1
+                continue
             if large:
                 scores = score_paths(scorer, bubble_from_relevant(rel, k, path_reads, [[[] for _ in range(k)]]))
                 s["scores"], s["best"] = scores.tolist(), best_paths(scores, k)
@@ -702,6 +753,76 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
             walk.close()
 
 
+# ---- every listed path of a large bubble scored where it is (po_phase_large) -------------------------
+
+def large_node_lists(rel: RelevantReads, interior_nodes, reads_of_node: Callable):
+    """``(node_off, node_ids)`` of ``po_phase_large``: per interior node, in the order given, the LOCAL ids (places in
+    ``rel.b_reads``) of its reads, ascending, every read once; reads outside ``rel.b_reads`` can never match and are dropped."""
+    b_reads = np.asarray(rel.b_reads, dtype=np.int64)
+    lists = []
+    for node in interior_nodes:
+        ids = np.unique(np.asarray([int(r) for r in reads_of_node(node)], dtype=np.int64))
+        at = np.searchsorted(b_reads, ids)
+        ok = at < len(b_reads)
+        ok[ok] = b_reads[at[ok]] == ids[ok]
+        lists.append(at[ok].tolist())
+    return _csr(lists)
+
+
+def best_of_scores(scores: np.ndarray, n_best: int) -> List[int]:
+    """``best_paths`` without a Python sort over every path: descending by score, among equal scores the lower index first."""
+    scores = np.asarray(scores, dtype=np.float64)
+    order = np.lexsort((np.arange(len(scores)), -scores))
+    return [int(p) for p in order[:int(n_best)]]
+
+
+def host_score_large(rel: RelevantReads, node_off, node_ids, interior_nodes, paths) -> np.ndarray:
+    """The scores of ``po_phase_large`` in numpy: the interval of every (interior node, read), joined along every path with min
+    and max, ``f`` summed over the reads and divided by their number.  ``paths``: node tuples with both ends."""
+    R = len(rel.rel_reads)
+    if R == 0:
+        raise ZeroDivisionError("no relevant reads")
+    n_inside = len(interior_nodes)
+    as_sets = PackedBubble(1, n_inside, 1, R, len(rel.b_reads), np.asarray(rel.overlap_max, dtype=np.int32), np.asarray(rel.aln_off, dtype=np.uint32),
+                           np.asarray(rel.aln_b, dtype=np.uint32), np.asarray(rel.aln_a0, dtype=np.int32), np.asarray(rel.aln_a1, dtype=np.int32),
+                           np.asarray(node_off, dtype=np.uint32), np.asarray(node_ids, dtype=np.uint32), np.zeros(2, np.uint32), np.zeros(0, np.uint32))
+    s0, e = HostScorer._intervals(as_sets, as_sets.path_off, as_sets.path_ids, n_inside)
+    s0 = np.vstack([s0, np.full((1, R), NO_START, dtype=np.int64)])      # (slot n_inside: no node)
+    e = np.vstack([e, np.zeros((1, R), dtype=np.int64)])
+    slot = {int(x): j for j, x in enumerate(interior_nodes)}
+    om = np.asarray(rel.overlap_max, dtype=np.float64)
+    out = np.zeros(len(paths), dtype=np.float64)
+    step = max(1, (1 << 22) // max(1, R))                                  # (paths per block: about 32 MB of joins at a time)
+    for lo in range(0, len(paths), step):
+        block = paths[lo:lo + step]
+        longest = max([len(p) - 2 for p in block] + [1])
+        idx = np.full((len(block), longest), n_inside, dtype=np.int64)
+        for j, p in enumerate(block):
+            inner = [slot[int(x)] for x in tuple(p)[1:-1] if int(x) in slot]
+            idx[j, :len(inner)] = inner
+        ps0, pe = np.full((len(block), R), NO_START, dtype=np.int64), np.zeros((len(block), R), dtype=np.int64)
+        for c in range(longest):
+            ps0 = np.minimum(ps0, s0[idx[:, c]])
+            pe = np.maximum(pe, e[idx[:, c]])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[lo:lo + len(block)] = np.where(ps0 < pe, (pe - ps0) / om[None, :], 0.0).sum(axis=1) / R
+    return out
+
+
+class ResidentBubble:
+    """One bubble of a ``DevicePaths`` or ``HostResidentPaths``: what ``phase_chain`` asks at the large arm of a bubble whose
+    paths are not on the host."""
+
+    def __init__(self, src, b: int):
+        self.src, self.b = src, int(b)
+
+    def score_large(self, rel: RelevantReads, reads_of_node: Callable, n_best: int, want_scores: bool = False):
+        return self.src.score_large(self.b, rel, reads_of_node, n_best, want_scores=want_scores)
+
+    def path_of(self, p: int) -> tuple:
+        return self.src.path_of(self.b, p)
+
+
 # ---- paths, interior and exit predecessors of every top-level bubble (po_phase_paths, DESIGN.md section 3.9r) ---------------
 
 @dataclass
@@ -762,6 +883,43 @@ class BubblePaths:
 def paths_text(n_paths) -> str:
     """A path count as the tools print it: a saturated one as a lower bound."""
     return ">=2^64-1" if int(n_paths) == PATHS_MANY else str(int(n_paths))
+
+
+class HostResidentPaths(BubblePaths):
+    """The interface of ``ExactOverlapper.phase_paths_resident`` (a ``DevicePaths``) in numpy over a ``BubblePaths`` whose
+    paths are all on the host: for machines without a GPU and for the tests.  It is no fallback: nothing here picks it on its
+    own.  The same decomposition over the interior nodes and the same tie rule; the order of its float64 sums may differ."""
+
+    def __init__(self, listed: BubblePaths):
+        super().__init__(listed.bubbles, listed.inside_off, listed.inside_nodes, listed.pred_off, listed.pred_node, listed.pred_weight,
+                         listed.bubble_path_off, listed.path_off, listed.path_nodes)
+        self._stats = {}
+
+    def path_of(self, b: int, p: int) -> tuple:
+        first, n = int(self.bubble_path_off[b]), int(self.bubble_path_off[b + 1]) - int(self.bubble_path_off[b])
+        if not self.is_listed(b) or not 0 <= int(p) < n:
+            raise ValueError("bubble %d has no listed path %d" % (b, p))
+        g = first + int(p)
+        return tuple(self.path_nodes[int(self.path_off[g]):int(self.path_off[g + 1])].tolist())
+
+    def score_large(self, b: int, rel: RelevantReads, reads_of_node: Callable, n_best: int, want_scores: bool = False):
+        """``(best, best_scores, scores or None)``: what ``po_phase_large`` gives for bubble b."""
+        if not 1 <= int(n_best) <= 8:
+            raise ValueError("po_phase_large: n_best must be 1 to 8")
+        paths = self.paths_of(b)
+        inside = self.interior_of(b)
+        node_off, node_ids = large_node_lists(rel, inside, reads_of_node)
+        scores = host_score_large(rel, node_off, node_ids, inside, paths)
+        best = best_of_scores(scores, n_best)
+        self._stats = {"n_paths": len(paths), "n_inside": len(inside), "n_reads": len(rel.rel_reads),
+                       "max_path_nodes": max([len(p) for p in paths] + [0])}
+        return best, scores[best].copy(), (scores if want_scores else None)
+
+    def large_stats(self) -> dict:
+        return dict(self._stats)
+
+    def close(self) -> None:
+        pass
 
 
 def bubble_paths(src, graph, max_paths: int = 0) -> BubblePaths:
