@@ -1396,7 +1396,7 @@ po_status po_paths_copy_paths(po_result* paths, uint64_t first, uint64_t count, 
  * the take-over of the survivors (phasing.py:311-319), new_block's reset (phasing.py:343-364) and prune(.., 1.0) of new_block
  * and of the end of phase() (phasing.py:335-339, 347).  phasm_amd/csrc/walk.hip.h, DESIGN.md section 3.9s.
  * Not part of it: the loop itself and its arms (phasm_amd/phasing.py, phase_chain), prev_graph_reads / prev_aligning_reads
- * (host lists of the caller), the choice among ties.
+ * (host lists of the caller on this route; the walk's own on the resident route further down), the choice among ties.
  * --------------------------------------------------------------------------------------------- */
 
 typedef struct {
@@ -1415,8 +1415,10 @@ typedef struct {
     uint32_t advanced;           /* the step took its final list over                                               */
     float ms_bits;               /* path bitsets and the intervals of slots and paths (ms_intervals of the phase stats) */
     float ms_advance;            /* k_wk_advance                                                                    */
-    float ms_total;              /* ms_total of the phase stats + ms_advance                                        */
-    uint32_t reserved;
+    float ms_total;              /* ms_total of the phase stats + ms_advance + ms_resident                          */
+    float ms_resident;           /* po_walk_step_resident: the k_rs_ kernels (new reads and their scan, the translation
+                                    of aln_b and of the path ids, the commit of the map and of the two sets); 0 after
+                                    po_walk_step                                                                    */
 } po_walk_stats;
 
 /* A WALK is a result of a kind of its own: it belongs to one handle, po_result_count is 0, po_result_free frees it; every
@@ -1463,6 +1465,55 @@ po_status po_walk_history(po_result* walk, const uint32_t* cands, uint64_t n, ui
 po_status po_walk_read_sets(po_result* walk, const uint32_t* cands, uint64_t n, uint64_t* off_out, uint32_t* ids_out, uint64_t cap,
                             uint64_t* n_ids_out);
 po_status po_get_walk_stats(const po_handle* h, po_walk_stats* out);
+
+/* THE RESIDENT ROUTE through one step of the walk (phasm_amd/csrc/resident.hip.h): the gather and the
+ * step of one bubble without the host between them.  Per bubble only the interior reads, the exit predecessors and the path
+ * reads (global ids) go up; only the sizes of the gather and the (cand, ext, rl) list come home.  po_walk_step stays as it is.
+ * The walk owns two bitsets over the handle's read ids, prev_graph and prev_aligning (ceil(n_ids / 32) words each), empty
+ * after po_walk_create and po_walk_reset, and the map of the block-stable ids on the device: stable_of[global id] (4 bytes per
+ * read of the handle) and global_of[stable id].  Creating and resetting still touch no device: what a reset has to clear is
+ * cleared at the next device call, the map over the old block's reads alone.
+ * po_walk_relevant: the gather of po_phase_relevant with prev_graph and prev_aligning taken from the walk
+ *   (input.prev_graph / prev_aligning must be NULL with count 0).  without_prev_graph != 0 takes prev_graph as empty (what the
+ *   walk does at a large bubble); prev_aligning still counts toward n_spanning.  The arrays, the bitsets of cur_graph and
+ *   cur_aligning and the ranks of G stay in device buffers of the WALK (no other call on the handle overwrites them).  *out is a
+ *   result of the kind po_phase_relevant returns: po_relevant_sizes works at once, po_relevant_copy fetches the arrays from the
+ *   device and gives byte for byte what po_phase_relevant gives for the same sets passed as lists.  A walk holds ONE live
+ *   gather: the next po_walk_relevant on it, a po_walk_reset (but see below) or the freeing of the walk makes the earlier
+ *   result stale; po_relevant_copy and the step refuse a stale result (PO_ERR_INVALID with a sentence).  It is freed with
+ *   po_result_free like any result, before or after its walk.  po_get_relevant_stats: the sizes; ms_alignments is 0 and
+ *   ms_total ends where the lists are made, because the last launches are not waited for.
+ * po_walk_step_resident: po_walk_step on the gather `rel`.  Of input only path_off, path_ids -- GLOBAL read ids -- and levels
+ *   are given, every other pointer must be NULL.  params.n_reads and params.n_b must equal the gather's n_relevant and n_b;
+ *   n_cands, ploidy and start_of_block the walk's.  rel must be the walk's live gather, made at the walk's present depth; one
+ *   exception: a gather with fell_back (or made with mode 1) is accepted after ONE po_walk_reset (new_block() followed by the
+ *   step on the same relevant reads).  A path id that is not in the gather's b_reads is dropped.  The block-stable ids follow
+ *   the rule of po_walk_step: a read known to the block keeps its id, the reads of b_reads new to the block get n_block + their
+ *   rank among the new ones in the order of b_reads; so (cand, ext, rl), the state and the stats are those of po_walk_step on
+ *   the same arrays.  Commit rule as po_walk_step's: advance == 0 or an empty final list changes nothing -- not the candidates,
+ *   not the map, not the two sets -- so a peek followed by the advancing call on the same rel numbers the new reads
+ *   identically.  A step that advances also joins cur_graph to prev_graph and cur_aligning to prev_aligning.
+ *   ONE ROUTE PER BLOCK: after a block's first advancing step by one route, the other route's step -- and after po_walk_step
+ *   also po_walk_relevant -- is refused until po_walk_reset.  po_walk_info_get, po_walk_best, po_walk_history and
+ *   po_walk_read_sets work on either route (po_walk_read_sets brings global_of home when asked).
+ * po_walk_prev_copy: prev_graph (which 0) or prev_aligning (which 1) as an ascending list, up to cap ids; *n_out is the full
+ *   count.
+ * Rejections, each PO_ERR_INVALID with a sentence, decided on the host before the device is touched, outputs and state
+ * untouched: NULL out / n_out, walk, index, rel, params or input; reserved != 0; mode > 1; non-NULL previous lists; an id >=
+ * po_num_sequences; a walk, index or rel of another handle or of another kind; a stale rel; any po_phase_input pointer other
+ * than the three being non-NULL; the five mismatches (n_reads, n_b, ploidy, n_cands, start_of_block) and a gather of another
+ * depth; the other route inside a block; which > 1.  There is no CPU fallback: without a GPU a valid call returns PO_ERR_HIP. */
+typedef struct {
+    uint32_t mode;               /* as po_relevant_params                                                           */
+    uint32_t min_spanning_reads;
+    uint32_t without_prev_graph; /* non-zero: prev_graph counts as empty                                            */
+    uint32_t reserved;           /* must be 0                                                                       */
+} po_walk_relevant_params;
+po_status po_walk_relevant(po_handle* h, po_result* walk, po_result* index, const po_walk_relevant_params* params,
+                           const po_relevant_input* input, po_result** out);
+po_status po_walk_step_resident(po_handle* h, po_result* walk, po_result* rel, const po_phase_params* params, const po_phase_input* input,
+                                uint32_t advance, uint32_t* cand_out, uint32_t* ext_out, double* rl_out, uint64_t cap, uint64_t* n_out);
+po_status po_walk_prev_copy(po_result* walk, uint32_t which, uint32_t* ids_out, uint64_t cap, uint64_t* n_out);
 
 /* A graph that did not come from po_layout_edges: `edges` over the handle's oriented reads (2i / 2i+1 of segment i of
  * po_add_segment or po_add_sequence) and the order of its nodes.  Checked on the host before anything touches the

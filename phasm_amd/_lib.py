@@ -289,6 +289,10 @@ class PoRelevantParams(ctypes.Structure):
     _fields_ = [(name, ctypes.c_uint32) for name in ("mode", "min_spanning_reads", "reserved", "reserved2")]
 
 
+class PoWalkRelevantParams(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint32) for name in ("mode", "min_spanning_reads", "without_prev_graph", "reserved")]
+
+
 class PoRelevantInput(ctypes.Structure):
     _fields_ = [("cur_graph", ctypes.c_void_p), ("n_cur_graph", ctypes.c_uint64), ("prev_graph", ctypes.c_void_p),
                 ("n_prev_graph", ctypes.c_uint64), ("prev_aligning", ctypes.c_void_p), ("n_prev_aligning", ctypes.c_uint64),
@@ -372,10 +376,10 @@ class PoWalkInfo(ctypes.Structure):
 class PoWalkStats(ctypes.Structure):
     _fields_ = [(name, ctypes.c_uint64) for name in ("n_cands_in", "n_cands_out", "depth", "n_block_reads", "n_new_reads")] + \
                [("words_per_slot", ctypes.c_uint32), ("advanced", ctypes.c_uint32)] + \
-               [(name, ctypes.c_float) for name in ("ms_bits", "ms_advance", "ms_total")] + [("reserved", ctypes.c_uint32)]
+               [(name, ctypes.c_float) for name in ("ms_bits", "ms_advance", "ms_total", "ms_resident")]
 
     def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class PoNodeOrderStats(ctypes.Structure):
@@ -532,6 +536,10 @@ SYMBOLS = [
     ("po_walk_read_sets", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                          ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_walk_stats", ctypes.c_int, [_P, ctypes.POINTER(PoWalkStats)]),
+    ("po_walk_relevant", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(PoWalkRelevantParams), ctypes.POINTER(PoRelevantInput), ctypes.POINTER(_P)]),
+    ("po_walk_step_resident", ctypes.c_int, [_P, _P, _P, ctypes.POINTER(PoPhaseParams), ctypes.POINTER(PoPhaseInput), ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("po_walk_prev_copy", ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_graph_from_edges", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_P)]),
     ("po_result_node_order", ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("po_get_node_order_stats", ctypes.c_int, [_P, ctypes.POINTER(PoNodeOrderStats)]),

@@ -431,7 +431,9 @@ def phase(args) -> int:
     The reads go on the handle once; the alignments are indexed there once, when the first subgraph with bubbles needs them;
     all sequences of a subgraph are spelled in one device call.  The paths of a subgraph's bubbles stay on the device
     (``--max-listed-paths`` caps what is listed): those of a bubble of up to 64 paths come home for the branch arm, a larger
-    bubble is scored where its paths are (``po_phase_large``) and only the winner comes home."""
+    bubble is scored where its paths are (``po_phase_large``) and only the winner comes home.  The walk takes the resident
+    route: the previous sets and the relevant reads of a bubble stay on the device between the gather and
+    the step; ``--host-sets`` takes the route through host lists and arrays, with the same output."""
     import random
     from . import phasing, spelling
     if not 1 <= args.ploidy <= 8:
@@ -490,7 +492,8 @@ def phase(args) -> int:
                 try:
                     blocks = list(phasing.phase_chain(overlapper, overlapper, index, bubbles, node_reads, args.ploidy, args.min_spanning_reads,
                                                       args.max_bubble_size, args.threshold, args.prune_factor, args.max_candidates,
-                                                      args.max_prune_rounds, args.prune_step_size, walk=walk, choose=choose))
+                                                      args.max_prune_rounds, args.prune_step_size, walk=walk, choose=choose,
+                                                      resident=not getattr(args, "host_sets", False)))
                 finally:
                     walk.close()
                 entries = list(phase_entries(base, blocks))
@@ -656,6 +659,9 @@ def main(argv=None) -> int:
                     help="the paths of a bubble are listed on the device, and the bubble can be phased, only up to this many: a cap on "
                          "device memory (default: 2^20)")
     ph.add_argument("--device", type=int, default=None)
+    ph.add_argument("--host-sets", action="store_true",
+                    help="keep prev_graph_reads / prev_aligning_reads and the relevant reads of every bubble on the host (po_phase_relevant + "
+                         "po_walk_step) instead of on the device (po_walk_relevant + po_walk_step_resident); the output is the same")
     ph.add_argument("--seed", type=int, default=None, help="seed of the choice among equally likely candidates (default: unseeded)")
     ph.add_argument("reads_fasta", help="the reads (FASTA); both strands go on the handle, as `overlap` adds them")
     ph.add_argument("alignments_gfa", help="the GFA2 file with all pairwise local alignments")

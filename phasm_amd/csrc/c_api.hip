@@ -54,6 +54,7 @@
 #include "spell.hip.h"
 #include "paths.hip.h"
 #include "walk.hip.h"
+#include "resident.hip.h"
 #include "large.hip.h"
 
 namespace {
@@ -123,11 +124,11 @@ enum { PR_TABLE, PR_INOFF, PR_INNODES, PR_PREDOFF, PR_PREDNODE, PR_PREDW, PR_BPO
 // the slot of every node of the graph, the score of every listed path of the bubble
 enum { LB_CNT, LB_OM, LB_ALNOFF, LB_ALNB, LB_A0, LB_A1, LB_NOFF, LB_NIDS, LB_NBITS, LB_NIV, LB_SLOT, LB_SCORE, LB_N };
 // events of the layout calls: one count for the handle and for the kit that carries them from a closed handle to the next
-constexpr int EV_LAY_N = 138;
+constexpr int EV_LAY_N = 143;
 // the first event of each call's slice of po_handle::ev_lay (a slice ends where the next begins)
 enum { EV_EDGES = 0, EV_REDUCE = 4, EV_TIPS = 9, EV_NODE_ORDER = 15, EV_DIAMONDS = 18, EV_MERGE = 22, EV_COVERAGE = 27, EV_COMPONENTS = 30,
        EV_PARTITION = 34, EV_SUPERBUBBLES = 38, EV_BUBBLECHAINS = 45, EV_CONTIGS = 54, EV_PHASE = 67, EV_PHASE_INDEX = 73,
-       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94, EV_CYCLIC = 96, EV_CHAINS_ALL = 106, EV_CONTIGS_ALL = 118, EV_LARGE = 134 };
+       EV_RELEVANT = 77, EV_SPELL = 81, EV_PATHS = 83, EV_WALK = 94, EV_CYCLIC = 96, EV_CHAINS_ALL = 106, EV_CONTIGS_ALL = 118, EV_LARGE = 134, EV_RESIDENT = 138 };
 static_assert(EV_BUBBLECHAINS + 9 == EV_CONTIGS, "po_layout_bubblechains has nine events");
 static_assert(EV_CONTIGS + 13 == EV_PHASE, "po_layout_contigs has thirteen events");
 static_assert(EV_PHASE + 6 == EV_PHASE_INDEX, "po_phase_branch has six events");
@@ -139,7 +140,8 @@ static_assert(EV_WALK + 2 == EV_CYCLIC, "po_walk_step has two events");
 static_assert(EV_CYCLIC + 10 == EV_CHAINS_ALL, "po_layout_superbubbles_all has ten events");
 static_assert(EV_CHAINS_ALL + 12 == EV_CONTIGS_ALL, "po_layout_bubblechains_all has twelve events: those ten and two of its own");
 static_assert(EV_CONTIGS_ALL + 16 == EV_LARGE, "po_layout_contigs_all has sixteen events");
-static_assert(EV_LARGE + 4 == EV_LAY_N, "the four events of po_phase_large are the last of the layout events");
+static_assert(EV_LARGE + 4 == EV_RESIDENT, "po_phase_large has four events");
+static_assert(EV_RESIDENT + 5 == EV_LAY_N, "the five events of po_walk_step_resident are the last of the layout events");
 constexpr int TIP_BATCH = 24;   // rounds of po_layout_tips per readback (words [32..55] of the landing zone)
 
 struct DevBuf {
@@ -587,6 +589,21 @@ struct po_result {
     std::vector<uint64_t> wk_level_off;                          // depth + 1 entries once a bubble was advanced
     std::vector<uint32_t> wk_reads;                              // stable id -> global id
     std::vector<std::pair<uint32_t, uint32_t>> wk_sorted;        // (global id, stable id), ascending
+    // The RESIDENT route of a walk (po_walk_relevant, po_walk_step_resident; resident.hip.h).  wk_route: which route the block
+    // advanced by (0 none yet, 1 the host map wk_sorted, 2 the device map).  On the device: the workspaces and outputs of the
+    // walk's one live gather (d_rs_rel, the XB_* of po_phase_relevant), the bitsets prev_graph and prev_aligning over the
+    // handle's read ids, stable_of[global id] and global_of[stable id], and the step's scratch (flags, ranks, translation,
+    // the rewritten aln_b, the path ids).  rs_n_block: the block reads of route 2.  A reset only notes what the next device
+    // call has to clear: rs_unmap_n entries of global_of to un-map, rs_clear_prev the two bitsets.
+    uint8_t wk_route = 0;
+    DevBuf d_rs_rel[XB_N], d_rs_prev, d_rs_stable, d_rs_global, d_rs_step[6];
+    uint32_t rs_n_ids = 0, rs_n_block = 0, rs_unmap_n = 0, rs_prevg_bound = 0;
+    bool rs_clear_prev = false;
+    po_result* rs_live = nullptr;                                // the gather result that names d_rs_rel, if one does
+    // A gather result of po_walk_relevant (special == 2 with rv_walk set): the arrays stay in the walk's d_rs_rel.
+    po_result* rv_walk = nullptr;                                // the walk it belongs to (nulled when that walk is freed)
+    bool rv_resident = false, rv_stale = false, rv_empty = false, rv_used_prev = false;
+    uint32_t rv_depth = 0, rv_resets = 0, rv_mode = 0;
     bool compact = false;   // (inside po_overlaps_to_host only) d_rows holds the verified-candidate records of `count` ROWS
 };
 
@@ -3049,6 +3066,17 @@ void release_device(po_result* r) {
         b->release();
     for (DevBuf& b : r->d_pp) b.release();
     for (DevBuf* b : {&r->d_wk_rows[0], &r->d_wk_rows[1], &r->d_wk_rl[0], &r->d_wk_rl[1], &r->d_wk_links, &r->d_wk_tmp}) b->release();
+    for (DevBuf& b : r->d_rs_rel) b.release();
+    for (DevBuf& b : r->d_rs_step) b.release();
+    for (DevBuf* b : {&r->d_rs_prev, &r->d_rs_stable, &r->d_rs_global}) b->release();
+    // a walk and its live gather know of each other: whichever goes first tells the other
+    if (r->rs_live) {
+        r->rs_live->rv_stale = true;
+        r->rs_live->rv_walk = nullptr;
+        r->rs_live = nullptr;
+    }
+    if (r->rv_walk && r->rv_walk->rs_live == r) r->rv_walk->rs_live = nullptr;
+    r->rv_walk = nullptr;
 }
 
 // the grid of a kernel that strides over n items: eight workgroups of 256 per CU at the most
@@ -5283,9 +5311,19 @@ struct WalkRows {
     uint32_t W, nb;
 };
 
+// the inputs of a step that are on the device already (po_walk_step_resident): used where they lie, nothing of them goes up
+struct PhaseDev {
+    const int32_t* om;
+    const uint32_t *aln_off, *aln_b;
+    const int32_t *a0, *a1;
+    const uint32_t* pids;
+    uint32_t n_aln, n_pids;
+};
+
 po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input& in, uint32_t Pk, uint32_t* cand_out, uint32_t* ext_out,
-                    double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out, const WalkRows* walk = nullptr) {
-    const char* const name = walk ? "po_walk_step" : "po_phase_branch";
+                    double* rl_out, uint64_t cap, double* table_out, uint64_t* n_out, const WalkRows* walk = nullptr,
+                    const PhaseDev* dev = nullptr) {
+    const char* const name = dev ? "po_walk_step_resident" : walk ? "po_walk_step" : "po_phase_branch";
     h->ph_fcand = h->ph_fext = h->ph_pbits = nullptr;
     h->ph_frl = nullptr;
     hipStream_t st = h->stream;
@@ -5297,7 +5335,7 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     DevBuf* B = h->d_ph;
     const uint32_t k = p.ploidy, P = p.n_paths, C = p.n_cands, R = p.n_reads, nb = p.n_b, W = std::max(1u, cdiv(nb, 32));
     const uint32_t N = C * Pk, n_slots = C * k;   // (both below 2^31: phase_check)
-    const uint32_t n_aln = R ? in.aln_off[R] : 0, n_pids = in.path_off[P], n_sids = in.set_off[n_slots];
+    const uint32_t n_aln = dev ? dev->n_aln : (R ? in.aln_off[R] : 0), n_pids = dev ? dev->n_pids : in.path_off[P], n_sids = in.set_off[n_slots];
     const size_t Rr = std::max<size_t>(R, 1);
     PO_TRY(lay_events(h));
     hipEvent_t* ev = h->ev_lay + EV_PHASE;
@@ -5306,10 +5344,12 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     PO_TRY(ensure(h, B[FB_CNT], 128));
     PO_TRY(ensure(h, B[FB_HIST], (po::PH_MAX_LEVELS + 1) * 8));
     PO_TRY(ensure(h, B[FB_LEVELS], po::PH_MAX_LEVELS * 8));
-    for (int b : {FB_OM, FB_ALNOFF}) PO_TRY(ensure(h, B[b], ((size_t)R + 1) * 4));
-    for (int b : {FB_ALNB, FB_A0, FB_A1}) PO_TRY(ensure(h, B[b], ((size_t)n_aln + 1) * 4));
+    if (!dev) {
+        for (int b : {FB_OM, FB_ALNOFF}) PO_TRY(ensure(h, B[b], ((size_t)R + 1) * 4));
+        for (int b : {FB_ALNB, FB_A0, FB_A1}) PO_TRY(ensure(h, B[b], ((size_t)n_aln + 1) * 4));
+        PO_TRY(ensure(h, B[FB_PIDS], ((size_t)n_pids + 1) * 4));
+    }
     PO_TRY(ensure(h, B[FB_POFF], ((size_t)P + 1) * 4));
-    PO_TRY(ensure(h, B[FB_PIDS], ((size_t)n_pids + 1) * 4));
     PO_TRY(ensure(h, B[FB_SOFF], ((size_t)n_slots + 1) * 4));
     PO_TRY(ensure(h, B[FB_SIDS], ((size_t)n_sids + 1) * 4));
     if (!walk) PO_TRY(ensure(h, B[FB_SBITS], (size_t)n_slots * W * 4));
@@ -5321,9 +5361,12 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
     PO_TRY(ensure(h, B[FB_KEEP], N));
     PO_TRY(ensure(h, B[FB_PLACE], (size_t)N * 4));
     unsigned long long *cnt = B[FB_CNT].as<unsigned long long>(), *hist = B[FB_HIST].as<unsigned long long>();
-    int32_t *om = B[FB_OM].as<int32_t>(), *a0 = B[FB_A0].as<int32_t>(), *a1 = B[FB_A1].as<int32_t>();
-    uint32_t *aln_off = B[FB_ALNOFF].as<uint32_t>(), *aln_b = B[FB_ALNB].as<uint32_t>(), *poff = B[FB_POFF].as<uint32_t>(),
-             *pids = B[FB_PIDS].as<uint32_t>(), *soff = B[FB_SOFF].as<uint32_t>(), *sids = B[FB_SIDS].as<uint32_t>(),
+    // (with `dev` the five arrays of the alignments and the path ids are read where the gather and the k_rs_ kernels left them)
+    int32_t *om = dev ? const_cast<int32_t*>(dev->om) : B[FB_OM].as<int32_t>(), *a0 = dev ? const_cast<int32_t*>(dev->a0) : B[FB_A0].as<int32_t>(),
+            *a1 = dev ? const_cast<int32_t*>(dev->a1) : B[FB_A1].as<int32_t>();
+    uint32_t *aln_off = dev ? const_cast<uint32_t*>(dev->aln_off) : B[FB_ALNOFF].as<uint32_t>(),
+             *aln_b = dev ? const_cast<uint32_t*>(dev->aln_b) : B[FB_ALNB].as<uint32_t>(), *poff = B[FB_POFF].as<uint32_t>(),
+             *pids = dev ? const_cast<uint32_t*>(dev->pids) : B[FB_PIDS].as<uint32_t>(), *soff = B[FB_SOFF].as<uint32_t>(), *sids = B[FB_SIDS].as<uint32_t>(),
              *sbits = B[FB_SBITS].as<uint32_t>(), *pbits = B[FB_PBITS].as<uint32_t>(), *place = B[FB_PLACE].as<uint32_t>();
     po::PhInterval *siv = B[FB_SIV].as<po::PhInterval>(), *piv = B[FB_PIV].as<po::PhInterval>();
     double *table = B[FB_TABLE].as<double>(), *rl = B[FB_RL].as<double>(), *levels = B[FB_LEVELS].as<double>();
@@ -5336,13 +5379,15 @@ po_status run_phase(po_handle* h, const po_phase_params& p, const po_phase_input
         if (bytes) HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
         return PO_OK;
     };
-    PO_TRY(up(om, in.overlap_max, (size_t)R * 4));
-    PO_TRY(up(aln_off, in.aln_off, R ? ((size_t)R + 1) * 4 : 0));
-    PO_TRY(up(aln_b, in.aln_b, (size_t)n_aln * 4));
-    PO_TRY(up(a0, in.aln_a0, (size_t)n_aln * 4));
-    PO_TRY(up(a1, in.aln_a1, (size_t)n_aln * 4));
+    if (!dev) {
+        PO_TRY(up(om, in.overlap_max, (size_t)R * 4));
+        PO_TRY(up(aln_off, in.aln_off, R ? ((size_t)R + 1) * 4 : 0));
+        PO_TRY(up(aln_b, in.aln_b, (size_t)n_aln * 4));
+        PO_TRY(up(a0, in.aln_a0, (size_t)n_aln * 4));
+        PO_TRY(up(a1, in.aln_a1, (size_t)n_aln * 4));
+        PO_TRY(up(pids, in.path_ids, (size_t)n_pids * 4));
+    }
     PO_TRY(up(poff, in.path_off, ((size_t)P + 1) * 4));
-    PO_TRY(up(pids, in.path_ids, (size_t)n_pids * 4));
     if (!walk) {
         PO_TRY(up(soff, in.set_off, ((size_t)n_slots + 1) * 4));
         PO_TRY(up(sids, in.set_ids, (size_t)n_sids * 4));
@@ -5647,6 +5692,25 @@ void walk_clear(po_result* w) {
     w->wk_level_off.clear();
     w->wk_reads.clear();
     w->wk_sorted.clear();
+    // the resident route: nothing on the device is touched here -- the next device call un-maps the old block and clears the sets
+    w->wk_route = 0;
+    if (w->rs_n_block) {
+        w->rs_unmap_n = w->rs_n_block;
+        w->rs_n_block = 0;
+    }
+    w->rs_clear_prev = w->d_rs_prev.p != nullptr;
+    w->rs_prevg_bound = 0;
+    if (po_result* g = w->rs_live) {
+        // new_block() and the step on the same relevant reads: a gather that fell back (or took every aligning read) lives on, once
+        if ((g->rv.fell_back || g->rv_mode == 1) && g->rv_resets == 0) {
+            g->rv_resets = 1;
+            g->rv_depth = 0;
+        } else {
+            g->rv_stale = true;
+            g->rv_walk = nullptr;   // (neither knows of the other any more: either may be freed first)
+            w->rs_live = nullptr;
+        }
+    }
 }
 
 inline uint32_t walk_depth(const po_result* w) { return w->wk_level_off.empty() ? 0u : (uint32_t)(w->wk_level_off.size() - 1); }
@@ -5660,6 +5724,7 @@ std::string walk_check(const po_handle* h, const po_result* w, const po_phase_pa
     if (p.ploidy != w->wk_k) return name + "the ploidy is not the walk's";
     if (p.n_cands != w->wk_n_cands) return name + "n_cands is not the number of candidates the walk holds";
     if ((p.start_of_block != 0) != (walk_depth(w) == 0)) return name + "start_of_block is not the walk's";
+    if (w->wk_route == 2) return name + "the block advanced by po_walk_step_resident: the two routes do not mix before po_walk_reset";
     if (p.n_b && !b_reads) return name + "b_reads is missing";
     for (uint32_t j = 1; j < p.n_b; ++j)
         if (b_reads[j] <= b_reads[j - 1]) return name + "b_reads is not strictly ascending";
@@ -5677,9 +5742,41 @@ std::string walk_asked(const po_result* walk, const char* who, const uint32_t* c
     return std::string();
 }
 
+// The final list of the step that has just run becomes the walk's candidates: the other half of each ping-pong pair takes the
+// new state (k_wk_advance); nothing of the live half changes before the launch has succeeded.  `also` launches what a route
+// commits beside it, in front of the one synchronise.  What maps the block's reads is the caller's.
+template <class Also>
+po_status walk_take_over(po_handle* h, po_result* w, const WalkRows& rows, uint32_t C, uint32_t P, uint32_t nb, uint32_t n_new, Also&& also) {
+    hipStream_t st = h->stream;
+    po_walk_stats& S = h->wkstats;
+    const uint32_t k = w->wk_k, W_new = std::max(1u, cdiv(nb, 32)), depth = walk_depth(w);
+    const int nxt = w->wk_cur ^ 1;
+    const uint64_t links_used = depth ? w->wk_level_off[depth] : 0;
+    PO_TRY(ensure(h, w->d_wk_rows[nxt], (size_t)n_new * k * W_new * 4, 1.0, false));
+    PO_TRY(ensure(h, w->d_wk_rl[nxt], (size_t)n_new * 8, 1.0, false));
+    PO_TRY(walk_grow(h, w->d_wk_links, (size_t)links_used * sizeof(po::WkLink), (size_t)(links_used + n_new) * sizeof(po::WkLink)));
+    hipEvent_t* ev = h->ev_lay + EV_WALK;
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(po::k_wk_advance, dim3(stride_grid(h, (uint64_t)n_new * k * W_new)), dim3(256), 0, st, n_new, C, k, P, w->wk_W, W_new,
+                       rows.rows, h->ph_pbits, h->ph_fcand, h->ph_fext, h->ph_frl, w->d_wk_rows[nxt].as<uint32_t>(),
+                       w->d_wk_links.as<po::WkLink>() + links_used, w->d_wk_rl[nxt].as<double>());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[1], st));
+    PO_TRY(also());
+    HIP_TRY(h, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&S.ms_advance, ev[0], ev[1]);
+    S.ms_total += S.ms_advance;
+    // the state becomes the list
+    if (w->wk_level_off.empty()) w->wk_level_off.push_back(0);
+    w->wk_level_off.push_back(links_used + n_new);
+    w->wk_cur = nxt;
+    w->wk_n_cands = n_new;
+    w->wk_W = W_new;
+    return PO_OK;
+}
+
 po_status run_walk_step(po_handle* h, po_result* w, const po_phase_params& p, const po_phase_input& in, const uint32_t* b_reads, bool advance,
                         uint32_t* cand_out, uint32_t* ext_out, double* rl_out, uint64_t cap, uint64_t* n_out) {
-    hipStream_t st = h->stream;
     po_walk_stats& S = h->wkstats;
     S = po_walk_stats();
     const uint32_t k = p.ploidy, P = p.n_paths, C = p.n_cands, R = p.n_reads;
@@ -5725,29 +5822,9 @@ po_status run_walk_step(po_handle* h, po_result* w, const po_phase_params& p, co
     S.ms_bits = F.ms_intervals;
     S.ms_total = F.ms_total;
     if (advance && n_final64) {
-        // the other half of each pair takes the new state; nothing of the live half changes before the launch has succeeded
-        const uint32_t n_new = (uint32_t)n_final64, W_new = std::max(1u, cdiv(nb, 32)), depth = walk_depth(w);
-        const int nxt = w->wk_cur ^ 1;
-        const uint64_t links_used = depth ? w->wk_level_off[depth] : 0;
-        PO_TRY(ensure(h, w->d_wk_rows[nxt], (size_t)n_new * k * W_new * 4, 1.0, false));
-        PO_TRY(ensure(h, w->d_wk_rl[nxt], (size_t)n_new * 8, 1.0, false));
-        PO_TRY(walk_grow(h, w->d_wk_links, (size_t)links_used * sizeof(po::WkLink), (size_t)(links_used + n_new) * sizeof(po::WkLink)));
-        hipEvent_t* ev = h->ev_lay + EV_WALK;
-        HIP_TRY(h, hipEventRecord(ev[0], st));
-        hipLaunchKernelGGL(po::k_wk_advance, dim3(stride_grid(h, (uint64_t)n_new * k * W_new)), dim3(256), 0, st, n_new, C, k, P, w->wk_W, W_new,
-                           rows.rows, h->ph_pbits, h->ph_fcand, h->ph_fext, h->ph_frl, w->d_wk_rows[nxt].as<uint32_t>(),
-                           w->d_wk_links.as<po::WkLink>() + links_used, w->d_wk_rl[nxt].as<double>());
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipEventRecord(ev[1], st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        (void)hipEventElapsedTime(&S.ms_advance, ev[0], ev[1]);
-        S.ms_total += S.ms_advance;
-        // the state becomes the list
-        if (w->wk_level_off.empty()) w->wk_level_off.push_back(0);
-        w->wk_level_off.push_back(links_used + n_new);
-        w->wk_cur = nxt;
-        w->wk_n_cands = n_new;
-        w->wk_W = W_new;
+        PO_TRY(walk_take_over(h, w, rows, C, P, nb, (uint32_t)n_final64, [] { return PO_OK; }));
+        const uint32_t n_new = (uint32_t)n_final64, W_new = w->wk_W;
+        w->wk_route = 1;
         for (uint32_t g : fresh) w->wk_reads.push_back(g);
         if (!fresh.empty()) {
             std::vector<std::pair<uint32_t, uint32_t>> merged(w->wk_sorted.size() + fresh.size()), added(fresh.size());
@@ -5844,6 +5921,14 @@ po_status run_walk_read_sets(po_handle* h, po_result* w, const uint32_t* cands, 
                                       hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         land = static_cast<const uint32_t*>(h->scratch_host.p);
+    }
+    if (w->wk_route == 2 && land && w->wk_reads.size() != w->rs_n_block) {
+        // the resident route keeps stable id -> global id on the device: it comes home when a read set is asked for
+        std::vector<uint32_t> home(w->rs_n_block);
+        HIP_TRY(h, hipMemcpyAsync(home.data(), w->d_rs_global.p, (size_t)w->rs_n_block * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        land = static_cast<const uint32_t*>(h->scratch_host.p);
+        w->wk_reads.swap(home);
     }
     std::vector<uint32_t> one;
     for (uint64_t s = 0; s < (uint64_t)n * k; ++s) {
@@ -5944,8 +6029,9 @@ po_status run_phase_index(po_handle* h, po_result* rows, po_result* r) {
 
 // The checks of po_phase_relevant in front of the device, in the order the header lists them: the sentence of the first one
 // that fails, empty when the call may go on.
-std::string relevant_check(const po_handle* h, const po_result* index, const po_relevant_params* p, const po_relevant_input* in) {
-    const std::string name = "po_phase_relevant: ";
+std::string relevant_check(const po_handle* h, const po_result* index, const po_relevant_params* p, const po_relevant_input* in,
+                           const char* who = "po_phase_relevant") {
+    const std::string name = std::string(who) + ": ";
     if (!p || !in) return name + "no parameters";
     if (p->reserved || p->reserved2) return name + "bad parameters";
     if (p->mode > 1) return name + "the mode must be 0 (spanning) or 1 (all)";
@@ -5964,8 +6050,43 @@ std::string relevant_check(const po_handle* h, const po_result* index, const po_
     return std::string();
 }
 
-po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_params& p, const po_relevant_input& in, po_result* r) {
-    const char* const name = "po_phase_relevant";
+// What the next device call on a walk's resident state does first: the two bitsets and stable_of exist for the handle's read
+// ids (prev_graph, then prev_aligning, W + 1 words each; stable_of all RS_NONE), and what a reset left to clear is cleared --
+// the map over the old block's reads alone, so a reset costs the block and not the read set.
+po_status rs_prepare(po_handle* h, po_result* w) {
+    hipStream_t st = h->stream;
+    const uint32_t n_ids = (uint32_t)h->len.size();
+    const size_t Wp = (size_t)cdiv(n_ids, 32) + 1;
+    if (!w->d_rs_prev.p || w->rs_n_ids != n_ids) {
+        if (w->d_rs_prev.p && (w->rs_live || w->rs_n_block || w->wk_route == 2))
+            return fail(h, PO_ERR_INVALID, "po_walk_relevant: reads were added to the handle inside a block of the walk");
+        PO_TRY(ensure(h, w->d_rs_prev, 2 * Wp * 4, 1.0, false));
+        PO_TRY(ensure(h, w->d_rs_stable, ((size_t)n_ids + 1) * 4, 1.0, false));
+        HIP_TRY(h, hipMemsetAsync(w->d_rs_prev.p, 0, 2 * Wp * 4, st));
+        HIP_TRY(h, hipMemsetAsync(w->d_rs_stable.p, 0xFF, ((size_t)n_ids + 1) * 4, st));   // (RS_NONE)
+        w->rs_n_ids = n_ids;
+        w->rs_unmap_n = 0;
+        w->rs_clear_prev = false;
+        return PO_OK;
+    }
+    if (w->rs_unmap_n) {
+        hipLaunchKernelGGL(po::k_rs_unmap, dim3(stride_grid(h, w->rs_unmap_n)), dim3(256), 0, st, w->rs_unmap_n, w->d_rs_global.as<uint32_t>(), n_ids,
+                           w->d_rs_stable.as<uint32_t>());
+        HIP_TRY(h, hipGetLastError());
+        w->rs_unmap_n = 0;
+    }
+    if (w->rs_clear_prev) {
+        HIP_TRY(h, hipMemsetAsync(w->d_rs_prev.p, 0, 2 * Wp * 4, st));
+        w->rs_clear_prev = false;
+    }
+    return PO_OK;
+}
+
+// `walk` (po_walk_relevant): the gather works in the walk's own buffers and leaves its arrays there; prev_aligning and --
+// unless `no_prev_graph` -- prev_graph are the walk's bitsets, and nothing but the sizes comes home.
+po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_params& p, const po_relevant_input& in, po_result* r,
+                       po_result* walk = nullptr, bool no_prev_graph = false) {
+    const char* const name = walk ? "po_walk_relevant" : "po_phase_relevant";
     hipStream_t st = h->stream;
     po_relevant_stats& S = h->rvstats;
     S = po_relevant_stats();
@@ -5974,11 +6095,27 @@ po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_p
     r->rv = po_relevant_dims();
     const uint32_t n_cur = (uint32_t)in.n_cur_graph, n_pg = (uint32_t)in.n_prev_graph, n_pa = (uint32_t)in.n_prev_aligning,
                    n_pred = (uint32_t)in.n_pred;
+    if (walk) {
+        // the walk's buffers are about to be written: the gather that lived there is stale from here on
+        if (walk->rs_live) {
+            walk->rs_live->rv_stale = true;
+            walk->rs_live->rv_walk = nullptr;
+            walk->rs_live = nullptr;
+        }
+        r->rv_resident = true;
+        r->rv_mode = p.mode;
+        r->rv_depth = walk->wk_level_off.empty() ? 0u : (uint32_t)(walk->wk_level_off.size() - 1);
+        r->rv_empty = !n_cur;
+        if (n_cur) PO_TRY(rs_prepare(h, walk));
+        r->rv_walk = walk;
+        walk->rs_live = r;
+    }
     if (!n_cur) return PO_OK;   // (every size 0)
     const uint32_t n_ids = index->ix_n_ids, n_keys = index->ix_n_keys, n_slots = index->ix_n_slots, W = cdiv(n_ids, 32);
     PO_TRY(lay_events(h));
     hipEvent_t* ev = h->ev_lay + EV_RELEVANT;
-    DevBuf* B = h->d_rr;
+    DevBuf* B = walk ? walk->d_rs_rel : h->d_rr;
+    const bool arena = !walk;   // (what belongs to a result is not carved out of the handle's arena)
     // the five lists behind one another, as one upload
     const size_t n_lists = (size_t)n_cur + n_pg + n_pa + 2 * (size_t)n_pred;
     std::vector<uint32_t> lists(n_lists);
@@ -5993,17 +6130,18 @@ po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_p
     }
     const size_t Wp = (size_t)W + 1;   // (a scan writes a closing sentinel)
     PO_TRY(ensure(h, h->d_scalars, 128));
-    PO_TRY(ensure(h, B[XB_CNT], 128));
-    PO_TRY(ensure(h, B[XB_LISTS], n_lists * 4));
-    PO_TRY(ensure(h, B[XB_BITS], 6 * Wp * 4));
-    PO_TRY(ensure(h, B[XB_WCNT], 3 * Wp * 4));
-    PO_TRY(ensure(h, B[XB_WRANK], 3 * Wp * 4));
+    PO_TRY(ensure(h, B[XB_CNT], 128, 1.0, arena));
+    PO_TRY(ensure(h, B[XB_LISTS], n_lists * 4, 1.0, arena));
+    PO_TRY(ensure(h, B[XB_BITS], 6 * Wp * 4, 1.0, arena));
+    PO_TRY(ensure(h, B[XB_WCNT], 3 * Wp * 4, 1.0, arena));
+    PO_TRY(ensure(h, B[XB_WRANK], 3 * Wp * 4, 1.0, arena));
     unsigned long long* cnt = B[XB_CNT].as<unsigned long long>();
     uint32_t* d_lists = B[XB_LISTS].as<uint32_t>();
     const uint32_t *d_cur = d_lists, *d_pg = d_cur + n_cur, *d_pa = d_pg + n_pg, *d_pred = d_pa + n_pa;
     const int32_t* d_plen = reinterpret_cast<const int32_t*>(d_pred + n_pred);
     uint32_t* bits = B[XB_BITS].as<uint32_t>();
-    uint32_t *ca = bits, *pa = bits + Wp, *gc = bits + 2 * Wp, *gp = bits + 3 * Wp, *rel = bits + 4 * Wp, *g = bits + 5 * Wp;
+    uint32_t *ca = bits, *gc = bits + 2 * Wp, *rel = bits + 4 * Wp, *g = bits + 5 * Wp;
+    uint32_t *pa = walk ? walk->d_rs_prev.as<uint32_t>() + Wp : bits + Wp, *gp = walk ? walk->d_rs_prev.as<uint32_t>() : bits + 3 * Wp;
     uint32_t *wcnt = B[XB_WCNT].as<uint32_t>(), *wrank = B[XB_WRANK].as<uint32_t>();
     const uint32_t* off = index->d_ixoff.as<uint32_t>();
     const po::RrEntry* entries = index->d_ixent.as<po::RrEntry>();
@@ -6026,16 +6164,18 @@ po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_p
     const uint64_t n_ca = h->pinned[16 + po::RG_CA], n_span = h->pinned[16 + po::RG_SPAN];
     if (n_ca > n_ids || n_span > n_ca) return fail(h, PO_ERR_HIP, std::string("internal: the aligning reads of ") + name + " do not add up");
     const bool fell_back = p.mode == 0 && n_span < p.min_spanning_reads, use_pa = p.mode == 0 && !fell_back;
-    const uint32_t n_rel = (uint32_t)(use_pa ? n_span : n_ca), g_room = fell_back ? n_cur : n_cur + n_pg;
-    PO_TRY(ensure(h, B[XB_CA], (n_ca + 1) * 4));
-    PO_TRY(ensure(h, B[XB_REL], ((size_t)n_rel + 1) * 4));
-    PO_TRY(ensure(h, B[XB_B], ((size_t)g_room + 1) * 4));
-    for (int k : {XB_ALNCNT, XB_ALNOFF, XB_OM}) PO_TRY(ensure(h, B[k], ((size_t)n_rel + 2) * 4));
+    const bool use_prev = !fell_back && !no_prev_graph;
+    // (the walk knows how many reads prev_graph holds at the most: that bounds G as n_prev_graph does)
+    const uint32_t n_rel = (uint32_t)(use_pa ? n_span : n_ca), g_room = !use_prev ? n_cur : n_cur + (walk ? walk->rs_prevg_bound : n_pg);
+    PO_TRY(ensure(h, B[XB_CA], (n_ca + 1) * 4, 1.0, arena));
+    PO_TRY(ensure(h, B[XB_REL], ((size_t)n_rel + 1) * 4, 1.0, arena));
+    PO_TRY(ensure(h, B[XB_B], ((size_t)g_room + 1) * 4, 1.0, arena));
+    for (int k : {XB_ALNCNT, XB_ALNOFF, XB_OM}) PO_TRY(ensure(h, B[k], ((size_t)n_rel + 2) * 4, 1.0, arena));
     uint32_t *l_ca = B[XB_CA].as<uint32_t>(), *l_rel = B[XB_REL].as<uint32_t>(), *l_b = B[XB_B].as<uint32_t>(),
              *aln_cnt = B[XB_ALNCNT].as<uint32_t>(), *aln_off = B[XB_ALNOFF].as<uint32_t>();
     int32_t* om = B[XB_OM].as<int32_t>();
     HIP_TRY(h, hipMemsetAsync(aln_off, 0, ((size_t)n_rel + 2) * 4, st));   // (no relevant read: the scan writes nothing)
-    hipLaunchKernelGGL(po::k_rr_select, dim3(word_grid), dim3(256), 0, st, ca, pa, gc, gp, W, (uint32_t)use_pa, (uint32_t)!fell_back, rel, g, wcnt,
+    hipLaunchKernelGGL(po::k_rr_select, dim3(word_grid), dim3(256), 0, st, ca, pa, gc, gp, W, (uint32_t)use_pa, (uint32_t)use_prev, rel, g, wcnt,
                        wcnt + Wp, wcnt + 2 * Wp);
     HIP_TRY(h, hipGetLastError());
     for (int k = 0; k < 3; ++k) PO_TRY(prefix_sum<uint32_t>(h, wcnt + k * Wp, W, wrank + k * Wp, &h->pinned[2 + k]));
@@ -6055,7 +6195,7 @@ po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_p
     const uint64_t n_b = h->pinned[4], n_aln = h->pinned[5];
     if (h->pinned[2] != n_ca || h->pinned[3] != n_rel || n_b > g_room || n_aln > n_keys)
         return fail(h, PO_ERR_HIP, std::string("internal: the lists of ") + name + " do not add up");
-    for (int k : {XB_ALNB, XB_A0, XB_A1}) PO_TRY(ensure(h, B[k], (n_aln + 1) * 4));
+    for (int k : {XB_ALNB, XB_A0, XB_A1}) PO_TRY(ensure(h, B[k], (n_aln + 1) * 4, 1.0, arena));
     uint32_t* aln_b = B[XB_ALNB].as<uint32_t>();
     int32_t *a0 = B[XB_A0].as<int32_t>(), *a1 = B[XB_A1].as<int32_t>();
     if (n_aln)
@@ -6063,6 +6203,20 @@ po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_p
                            aln_off, (uint32_t)n_aln, aln_b, a0, a1);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[3], st));
+    r->rv.n_cur_aligning = S.n_cur_aligning = n_ca;
+    r->rv.n_spanning = S.n_spanning = n_span;
+    r->rv.n_relevant = S.n_relevant = n_rel;
+    r->rv.n_alignments = S.n_alignments = n_aln;
+    r->rv.n_b = S.n_b = n_b;
+    r->rv.fell_back = S.fell_back = fell_back;
+    if (walk) {
+        // the arrays stay where they are; the last launches are not waited for, so their time is not in the figures
+        r->rv_used_prev = use_prev;
+        (void)hipEventElapsedTime(&S.ms_mark, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&S.ms_lists, ev[1], ev[2]);
+        S.ms_total = S.ms_mark + S.ms_lists;
+        return PO_OK;
+    }
     r->rv_ca.resize(n_ca);
     r->rv_rel.resize(n_rel);
     r->rv_om.resize(n_rel);
@@ -6074,16 +6228,202 @@ po_status run_relevant(po_handle* h, const po_result* index, const po_relevant_p
     PO_TRY(land_outputs(h, {{l_ca, n_ca * 4, r->rv_ca.data()}, {l_rel, (size_t)n_rel * 4, r->rv_rel.data()}, {om, (size_t)n_rel * 4, r->rv_om.data()},
                             {aln_off, ((size_t)n_rel + 1) * 4, r->rv_alnoff.data()}, {aln_b, n_aln * 4, r->rv_alnb.data()},
                             {a0, n_aln * 4, r->rv_a0.data()}, {a1, n_aln * 4, r->rv_a1.data()}, {l_b, n_b * 4, r->rv_b.data()}}, cnt, po::RG_N));
-    r->rv.n_cur_aligning = S.n_cur_aligning = n_ca;
-    r->rv.n_spanning = S.n_spanning = n_span;
-    r->rv.n_relevant = S.n_relevant = n_rel;
-    r->rv.n_alignments = S.n_alignments = n_aln;
-    r->rv.n_b = S.n_b = n_b;
-    r->rv.fell_back = S.fell_back = fell_back;
     (void)hipEventElapsedTime(&S.ms_mark, ev[0], ev[1]);
     (void)hipEventElapsedTime(&S.ms_lists, ev[1], ev[2]);
     (void)hipEventElapsedTime(&S.ms_alignments, ev[2], ev[3]);
     (void)hipEventElapsedTime(&S.ms_total, ev[0], ev[3]);
+    return PO_OK;
+}
+
+// ---- the resident route through one step of the walk (po_walk_relevant, po_walk_step_resident, resident.hip.h) -------------
+
+// is `rel` the live gather of walk `w`?  The sentence, empty when it is.
+std::string gather_live(const po_result* w, const po_result* rel, const char* who) {
+    const std::string name = std::string(who) + ": ";
+    if (rel->rv_stale || !rel->rv_walk)
+        return name + "the gather is stale: a later po_walk_relevant, a po_walk_reset or the freeing of its walk has taken its arrays";
+    if (w && rel->rv_walk != w) return name + "the gather belongs to another walk";
+    if (rel->rv_walk->rs_live != rel) return name + "the gather is stale: a later po_walk_relevant, a po_walk_reset or the freeing of its walk has taken its arrays";
+    return std::string();
+}
+
+// The checks of po_walk_step_resident in front of the device, in the order the header lists them.
+std::string resident_check(const po_handle* h, const po_result* w, const po_result* rel, const po_phase_params& p, const po_phase_input& in,
+                           uint64_t& Pk) {
+    const std::string name = "po_walk_step_resident: ";
+    if (w->special != WALK_KIND) return name + "needs the result of po_walk_create";
+    if (w->h != h) return name + "the walk belongs to another handle";
+    if (rel->special != 2 || !rel->rv_resident) return name + "needs the result of po_walk_relevant";
+    if (rel->h != h) return name + "the gather belongs to another handle";
+    const std::string stale = gather_live(w, rel, "po_walk_step_resident");
+    if (!stale.empty()) return stale;
+    if (in.overlap_max || in.aln_off || in.aln_b || in.aln_a0 || in.aln_a1 || in.set_off || in.set_ids)
+        return name + "only path_off, path_ids and levels are given: every other array must be NULL, it is the gather's or the walk's";
+    if (p.reserved || p.reserved2 || !(p.threshold >= 0.0) || p.n_levels > po::PH_MAX_LEVELS) return name + "bad parameters";
+    if (p.n_reads != rel->rv.n_relevant) return name + "n_reads is not the number of relevant reads of the gather";
+    if (p.n_b != rel->rv.n_b) return name + "n_b is not the number of b reads of the gather";
+    if (p.ploidy != w->wk_k) return name + "the ploidy is not the walk's";
+    if (p.n_cands != w->wk_n_cands) return name + "n_cands is not the number of candidates the walk holds";
+    if ((p.start_of_block != 0) != (walk_depth(w) == 0)) return name + "start_of_block is not the walk's";
+    if (rel->rv_depth != walk_depth(w)) return name + "the gather was made at another depth of the walk";
+    if (w->wk_route == 1) return name + "the block advanced by po_walk_step: the two routes do not mix before po_walk_reset";
+    if (p.n_paths < 1 || p.n_paths > po::PH_MAX_P) return name + "the number of paths must be 1 to 64";
+    Pk = 1;
+    for (uint32_t i = 0; i < p.ploidy; ++i) Pk *= p.n_paths;
+    if (Pk >= (1ull << 31) || Pk * p.n_cands >= (1ull << 31)) return name + "too many extensions for one call";
+    if (!in.path_off || (p.prune && p.n_levels && !in.levels)) return name + "an input array is missing";
+    if (!phase_offsets_ok(in.path_off, p.n_paths)) return name + "the offsets of the paths do not start at 0 or decrease";
+    const uint32_t n_pids = in.path_off[p.n_paths];
+    if (n_pids && !in.path_ids) return name + "an input array is missing";
+    const uint64_t n_ids = h->len.size();
+    for (uint32_t j = 0; j < n_pids; ++j)
+        if (in.path_ids[j] >= n_ids) return name + "a path names a read the handle does not hold";
+    return std::string();
+}
+
+enum { RS_FLAG, RS_RANK, RS_XL, RS_ALNB, RS_PIN, RS_PIDS, RS_N };
+
+po_status run_walk_step_resident(po_handle* h, po_result* w, po_result* rel, const po_phase_params& p, const po_phase_input& in, bool advance,
+                                 uint32_t* cand_out, uint32_t* ext_out, double* rl_out, uint64_t cap, uint64_t* n_out) {
+    static_assert(RS_N == sizeof(po_result::d_rs_step) / sizeof(DevBuf), "the scratch of the resident step");
+    hipStream_t st = h->stream;
+    po_walk_stats& S = h->wkstats;
+    S = po_walk_stats();
+    const uint32_t k = p.ploidy, P = p.n_paths, C = p.n_cands;
+    S.n_cands_in = S.n_cands_out = C;
+    S.depth = walk_depth(w);
+    S.words_per_slot = w->wk_W;
+    PO_TRY(rs_prepare(h, w));   // (what a reset left to clear, before anything reads the map)
+    const uint32_t n_block = w->rs_n_block, n_ids = w->rs_n_ids, n_b = (uint32_t)rel->rv.n_b, n_aln = (uint32_t)rel->rv.n_alignments;
+    const uint32_t n_pids = in.path_off[P];
+    const size_t Wp = (size_t)cdiv(n_ids, 32) + 1;
+    S.n_block_reads = n_block;
+    DevBuf *G = w->d_rs_rel, *T = w->d_rs_step;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    for (int b : {RS_FLAG, RS_XL}) PO_TRY(ensure(h, T[b], ((size_t)n_b + 1) * 4, 1.0, false));
+    PO_TRY(ensure(h, T[RS_RANK], ((size_t)n_b + 2) * 4, 1.0, false));
+    PO_TRY(ensure(h, T[RS_ALNB], ((size_t)n_aln + 1) * 4, 1.0, false));
+    for (int b : {RS_PIN, RS_PIDS}) PO_TRY(ensure(h, T[b], ((size_t)n_pids + 1) * 4, 1.0, false));
+    uint32_t *flag = T[RS_FLAG].as<uint32_t>(), *rank = T[RS_RANK].as<uint32_t>(), *xl = T[RS_XL].as<uint32_t>(), *alnb = T[RS_ALNB].as<uint32_t>(),
+             *pin = T[RS_PIN].as<uint32_t>(), *pids = T[RS_PIDS].as<uint32_t>();
+    uint32_t *stable_of = w->d_rs_stable.as<uint32_t>();
+    const uint32_t* b_reads = G[XB_B].as<uint32_t>();
+    PO_TRY(lay_events(h));
+    hipEvent_t* ev = h->ev_lay + EV_RESIDENT;   // (0..1 the flags and their scan, 2..3 the translation, 4 behind the commit)
+    if (n_pids) HIP_TRY(h, hipMemcpyAsync(pin, in.path_ids, (size_t)n_pids * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipEventRecord(ev[0], st));
+    // the reads of b_reads that are new to the block, numbered in the order of b_reads; the one count the host needs: W
+    uint64_t n_fresh = 0;
+    if (n_b) {
+        hipLaunchKernelGGL(po::k_rs_flag, dim3(stride_grid(h, n_b)), dim3(256), 0, st, n_b, b_reads, n_ids, stable_of, flag);
+        HIP_TRY(h, hipGetLastError());
+        PO_TRY(prefix_sum<uint32_t>(h, flag, n_b, rank, &h->pinned[2]));
+        HIP_TRY(h, hipEventRecord(ev[1], st));
+        HIP_TRY(h, hipStreamSynchronize(st));   // (the path ids are on the device too: the caller's array may go)
+        n_fresh = h->pinned[2];
+        if (n_fresh > n_b) return fail(h, PO_ERR_HIP, "internal: the new reads of po_walk_step_resident do not add up");
+    } else {
+        HIP_TRY(h, hipEventRecord(ev[1], st));
+        if (n_pids) HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    S.n_new_reads = n_fresh;
+    if ((uint64_t)n_block + n_fresh >= (1ull << 31)) return fail(h, PO_ERR_CAPACITY, "po_walk_step_resident: more than 2^31 - 1 reads in one block");
+    const uint32_t nb = n_block + (uint32_t)n_fresh;
+    HIP_TRY(h, hipEventRecord(ev[2], st));
+    if (n_b) {
+        hipLaunchKernelGGL(po::k_rs_local, dim3(stride_grid(h, n_b)), dim3(256), 0, st, n_b, b_reads, n_ids, stable_of, n_block, flag, rank, xl);
+        if (n_aln) hipLaunchKernelGGL(po::k_rs_alnb, dim3(stride_grid(h, n_aln)), dim3(256), 0, st, n_aln, G[XB_ALNB].as<uint32_t>(), n_b, xl, alnb);
+    }
+    if (n_pids) {
+        if (n_b)
+            hipLaunchKernelGGL(po::k_rs_paths, dim3(stride_grid(h, n_pids)), dim3(256), 0, st, n_pids, pin, n_ids, G[XB_BITS].as<uint32_t>() + 5 * Wp,
+                               G[XB_WRANK].as<uint32_t>() + 2 * Wp, n_b, xl, pids);
+        else
+            HIP_TRY(h, hipMemsetAsync(pids, 0xFF, (size_t)n_pids * 4, st));   // (no b read: every path read is outside, RS_NONE)
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(ev[3], st));
+    po_phase_params p2 = p;
+    p2.n_b = nb;
+    std::vector<uint32_t> no_sets((size_t)C * k + 1, 0u);
+    po_phase_input in2 = in;
+    in2.set_off = no_sets.data();
+    uint64_t Pk = 1;
+    for (uint32_t i = 0; i < k; ++i) Pk *= P;
+    const WalkRows rows{w->d_wk_rows[w->wk_cur].as<uint32_t>(), w->wk_W, w->wk_W ? n_block : 0u};
+    const PhaseDev dev{G[XB_OM].as<int32_t>(), G[XB_ALNOFF].as<uint32_t>(), alnb, G[XB_A0].as<int32_t>(), G[XB_A1].as<int32_t>(), pids, n_aln, n_pids};
+    uint64_t n_final64 = 0;
+    PO_TRY(run_phase(h, p2, in2, (uint32_t)Pk, cand_out, ext_out, rl_out, cap, nullptr, &n_final64, &rows, &dev));
+    const po_phase_stats& F = h->phstats;
+    S.ms_bits = F.ms_intervals;
+    S.ms_total = F.ms_total;
+    {   // (the synchronises of run_phase lie behind the four events)
+        float a = 0.f, b = 0.f;
+        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&b, ev[2], ev[3]);
+        S.ms_resident = a + b;
+        S.ms_total += S.ms_resident;
+    }
+    if (advance && n_final64) {
+        PO_TRY(walk_grow(h, w->d_rs_global, (size_t)n_block * 4, ((size_t)nb + 1) * 4));
+        PO_TRY(walk_take_over(h, w, rows, C, P, nb, (uint32_t)n_final64, [&]() -> po_status {
+            // the map and the two sets follow the candidates, in front of the same synchronise
+            if (n_fresh)
+                hipLaunchKernelGGL(po::k_rs_commit, dim3(stride_grid(h, n_b)), dim3(256), 0, st, n_b, b_reads, n_ids, flag, xl, nb, stable_of,
+                                   w->d_rs_global.as<uint32_t>());
+            if (!rel->rv_empty) {
+                uint32_t *bits = G[XB_BITS].as<uint32_t>(), *prev = w->d_rs_prev.as<uint32_t>();
+                hipLaunchKernelGGL(po::k_rs_or, dim3(stride_grid(h, Wp - 1)), dim3(256), 0, st, (uint32_t)(Wp - 1), bits + 2 * Wp, bits, prev, prev + Wp);
+            }
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipEventRecord(ev[4], st));
+            return PO_OK;
+        }));
+        {
+            float c = 0.f;
+            (void)hipEventElapsedTime(&c, (h->ev_lay + EV_WALK)[1], ev[4]);
+            S.ms_resident += c;
+            S.ms_total += c;
+        }
+        w->wk_route = 2;
+        w->rs_n_block = nb;
+        w->wk_reads.clear();   // (the host copy of global_of, fetched when po_walk_read_sets asks)
+        w->rs_prevg_bound = rel->rv_used_prev ? n_b : (uint32_t)std::min<uint64_t>(n_ids, (uint64_t)w->rs_prevg_bound + n_b);
+        S.advanced = 1;
+        S.n_cands_out = n_final64;
+        S.depth = walk_depth(w);
+        S.n_block_reads = nb;
+        S.words_per_slot = w->wk_W;
+    }
+    *n_out = n_final64;
+    return PO_OK;
+}
+
+// one of the walk's two sets as an ascending list: the set bits of every word, the library's prefix sum, k_rr_list
+po_status run_walk_prev_copy(po_handle* h, po_result* w, uint32_t which, uint32_t* ids_out, uint64_t cap, uint64_t* n_out) {
+    hipStream_t st = h->stream;
+    const uint32_t W = cdiv(w->rs_n_ids, 32);
+    const size_t Wp = (size_t)W + 1;
+    if (!W) return PO_OK;
+    PO_TRY(ensure(h, h->d_scalars, 128));
+    PO_TRY(ensure(h, w->d_wk_tmp, 2 * Wp * 4 + 256, 1.0, false));
+    uint32_t *cnt = w->d_wk_tmp.as<uint32_t>(), *rank = cnt + Wp;
+    const uint32_t* bits = w->d_rs_prev.as<uint32_t>() + (which ? Wp : 0);
+    hipLaunchKernelGGL(po::k_rs_popc, dim3(stride_grid(h, W)), dim3(256), 0, st, W, bits, cnt);
+    HIP_TRY(h, hipGetLastError());
+    PO_TRY(prefix_sum<uint32_t>(h, cnt, W, rank, &h->pinned[2]));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t n = h->pinned[2];
+    if (n > w->rs_n_ids) return fail(h, PO_ERR_HIP, "internal: the set of po_walk_prev_copy does not add up");
+    *n_out = n;
+    const size_t n_give = (size_t)std::min<uint64_t>(cap, n);
+    if (!n_give || !ids_out) return PO_OK;
+    PO_TRY(ensure(h, w->d_rs_step[RS_PIN], (n + 1) * 4, 1.0, false));
+    uint32_t* out = w->d_rs_step[RS_PIN].as<uint32_t>();
+    hipLaunchKernelGGL(po::k_rr_list, dim3(stride_grid(h, W)), dim3(256), 0, st, bits, rank, W, out, (uint32_t)n);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(ids_out, out, n_give * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
     return PO_OK;
 }
 
@@ -8620,7 +8960,7 @@ po_status po_walk_info_get(const po_result* walk, po_walk_info* info) {
     info->n_cands = walk->wk_n_cands;
     info->depth = walk_depth(walk);
     info->start_of_block = info->depth == 0;
-    info->n_block_reads = walk->wk_reads.size();
+    info->n_block_reads = walk->wk_route == 2 ? walk->rs_n_block : walk->wk_reads.size();
     return PO_OK;
 }
 
@@ -8647,6 +8987,63 @@ po_status po_walk_step(po_handle* h, po_result* walk, const po_phase_params* par
     return guarded_run(h, "po_walk_step", [&] {
         return run_walk_step(h, walk, *params, *input, b_reads, advance != 0, cand_out, ext_out, rl_out, cap, n_out);
     });
+}
+
+po_status po_walk_relevant(po_handle* h, po_result* walk, po_result* index, const po_walk_relevant_params* params,
+                           const po_relevant_input* input, po_result** out) {
+    if (!h) return PO_ERR_INVALID;
+    const std::string name = "po_walk_relevant: ";
+    if (!out) return fail(h, PO_ERR_INVALID, name + "no room for the result");
+    *out = nullptr;
+    if (!walk) return fail(h, PO_ERR_INVALID, name + "no walk");
+    if (!index) return fail(h, PO_ERR_INVALID, name + "no index");
+    if (!params || !input) return fail(h, PO_ERR_INVALID, name + "no parameters");
+    if (params->reserved) return fail(h, PO_ERR_INVALID, name + "bad parameters");
+    if (input->prev_graph || input->n_prev_graph || input->prev_aligning || input->n_prev_aligning)
+        return fail(h, PO_ERR_INVALID, name + "prev_graph and prev_aligning must be NULL with count 0: the two sets are the walk's");
+    if (walk->special != WALK_KIND) return fail(h, PO_ERR_INVALID, name + "needs the result of po_walk_create");
+    if (walk->h != h) return fail(h, PO_ERR_INVALID, name + "the walk belongs to another handle");
+    const po_relevant_params as_gather{params->mode, params->min_spanning_reads, 0, 0};
+    const std::string said = relevant_check(h, index, &as_gather, input, "po_walk_relevant");
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    if (walk->wk_route == 1)
+        return fail(h, PO_ERR_INVALID, name + "the block advanced by po_walk_step: the two routes do not mix before po_walk_reset");
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return new_edge_result(h, "po_walk_relevant", out, [&](po_result* r) {
+        return run_relevant(h, index, as_gather, *input, r, walk, params->without_prev_graph != 0);
+    });
+}
+
+po_status po_walk_step_resident(po_handle* h, po_result* walk, po_result* rel, const po_phase_params* params, const po_phase_input* input,
+                                uint32_t advance, uint32_t* cand_out, uint32_t* ext_out, double* rl_out, uint64_t cap, uint64_t* n_out) {
+    if (!h) return PO_ERR_INVALID;
+    const std::string name = "po_walk_step_resident: ";
+    if (!n_out) return fail(h, PO_ERR_INVALID, name + "no room for the number of entries");
+    *n_out = 0;
+    if (!walk) return fail(h, PO_ERR_INVALID, name + "no walk");
+    if (!rel) return fail(h, PO_ERR_INVALID, name + "no gather");
+    if (!params || !input) return fail(h, PO_ERR_INVALID, name + "no parameters");
+    uint64_t Pk = 0;
+    const std::string said = resident_check(h, walk, rel, *params, *input, Pk);
+    if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+    // (no CPU fallback)
+    PO_TRY(init_device(h));
+    return guarded_run(h, "po_walk_step_resident", [&] {
+        return run_walk_step_resident(h, walk, rel, *params, *input, advance != 0, cand_out, ext_out, rl_out, cap, n_out);
+    });
+}
+
+po_status po_walk_prev_copy(po_result* walk, uint32_t which, uint32_t* ids_out, uint64_t cap, uint64_t* n_out) {
+    if (!walk) return PO_ERR_INVALID;
+    po_handle* h = walk->h;
+    if (!n_out) return fail(h, PO_ERR_INVALID, "po_walk_prev_copy: no room for the number of ids");
+    *n_out = 0;
+    if (walk->special != WALK_KIND) return fail(h, PO_ERR_INVALID, "po_walk_prev_copy needs the result of po_walk_create");
+    if (which > 1) return fail(h, PO_ERR_INVALID, "po_walk_prev_copy: which must be 0 (prev_graph) or 1 (prev_aligning)");
+    if (!walk->d_rs_prev.p || walk->rs_clear_prev) return PO_OK;   // (both sets are empty: nothing lies on the device)
+    PO_TRY(init_device(h));
+    return guarded_run(h, "po_walk_prev_copy", [&] { return run_walk_prev_copy(h, walk, which, ids_out, cap, n_out); });
 }
 
 po_status po_walk_best(po_result* walk, uint32_t* cands_out, uint64_t cap, uint64_t* n_out, double* max_rl_out) {
@@ -8745,6 +9142,24 @@ po_status po_relevant_copy(po_result* out, uint32_t* cur_aligning, uint32_t* rel
                            uint32_t* aln_b, int32_t* aln_a0, int32_t* aln_a1, uint32_t* b_reads) {
     if (!out) return PO_ERR_INVALID;
     if (out->special != 2) return fail(out->h, PO_ERR_INVALID, "po_relevant_copy needs the result of po_phase_relevant");
+    if (out->rv_resident) {
+        // a gather of po_walk_relevant: the arrays are fetched from the walk's buffers, where the gather left them
+        po_handle* h = out->h;
+        const std::string said = gather_live(nullptr, out, "po_relevant_copy");
+        if (!said.empty()) return fail(h, PO_ERR_INVALID, said);
+        if (out->rv_empty) {
+            if (aln_off) aln_off[0] = 0;
+            return PO_OK;
+        }
+        PO_TRY(init_device(h));
+        const DevBuf* B = out->rv_walk->d_rs_rel;
+        const size_t n_ca = out->rv.n_cur_aligning, n_rel = out->rv.n_relevant, n_aln = out->rv.n_alignments, n_b = out->rv.n_b;
+        return guarded_run(h, "po_relevant_copy", [&] {
+            return land_outputs(h, {{B[XB_CA].p, n_ca * 4, cur_aligning}, {B[XB_REL].p, n_rel * 4, rel_reads}, {B[XB_OM].p, n_rel * 4, overlap_max},
+                                    {B[XB_ALNOFF].p, (n_rel + 1) * 4, aln_off}, {B[XB_ALNB].p, n_aln * 4, aln_b}, {B[XB_A0].p, n_aln * 4, aln_a0},
+                                    {B[XB_A1].p, n_aln * 4, aln_a1}, {B[XB_B].p, n_b * 4, b_reads}}, B[XB_CNT].as<unsigned long long>(), 1);
+        });
+    }
     auto give = [](void* dst, const void* src, size_t n) {
         if (dst && n) std::memcpy(dst, src, n * 4);
     };

@@ -150,6 +150,70 @@ class DeviceWalk:
         m = min(room, int(n.value))
         return cand[:m].copy(), ext[:m].copy(), rl[:m].copy()
 
+    def relevant(self, source, index, cur_graph, preds=(), start_of_block: bool = False, min_spanning_reads: int = 0,
+                 without_prev_graph: bool = False) -> "ResidentRelevant":
+        """``po_walk_relevant``: the gather of ``phase_relevant`` with ``prev_graph`` and ``prev_aligning`` taken from the walk,
+        its arrays staying on the device for ``step_resident``.  ``source`` is the walk's own overlapper (given for the
+        interface of ``HostWalk``); ``without_prev_graph``: ``prev_graph`` counts as empty (a large bubble)."""
+        if source is not None and source is not self._owner:
+            raise ValueError("po_walk_relevant: the walk belongs to another handle")
+        if not 0 <= int(min_spanning_reads) < 2**32:
+            raise ValueError("min_spanning_reads must fit 32 bits")
+        preds = list(preds)
+        cur = np.ascontiguousarray(list(cur_graph), dtype=np.uint32)
+        pred = np.ascontiguousarray([p[0] for p in preds], dtype=np.uint32)
+        plen = np.ascontiguousarray([p[1] for p in preds], dtype=np.int32)
+        as_p = lambda a: a.ctypes.data if len(a) else None   # noqa: E731
+        prm = _lib.PoWalkRelevantParams(int(bool(start_of_block)), int(min_spanning_reads), int(bool(without_prev_graph)), 0)
+        inp = PoRelevantInput(as_p(cur), len(cur), None, 0, None, 0, as_p(pred), as_p(plen), len(plen))
+        r = ctypes.c_void_p()
+        self._call(self._lib.po_walk_relevant(self._owner._h, self._ptr, index._ptr, ctypes.byref(prm), ctypes.byref(inp), ctypes.byref(r)))
+        return ResidentRelevant(self, r)
+
+    def step_resident(self, rel: "ResidentRelevant", path_reads, start_of_block, threshold: float = 0.0, min_spanning_reads: int = 0,
+                      levels=None, max_candidates: int = 0, advance: bool = True, cap: Optional[int] = None):
+        """``po_walk_step_resident``: ``step`` on the gather ``rel`` of ``relevant``, with nothing but the path reads (global
+        ids) going up.  The arguments and the result are those of ``step``."""
+        if not 0 <= int(min_spanning_reads) < 2**32 or not 0 <= int(max_candidates) < 2**32:
+            raise ValueError("min_spanning_reads and max_candidates must fit 32 bits")
+        lens = np.fromiter((len(p) for p in path_reads), dtype=np.int64, count=len(path_reads))
+        path_off = np.zeros(len(lens) + 1, dtype=np.uint32)
+        path_off[1:] = np.cumsum(lens)
+        path_ids = np.ascontiguousarray([r for p in path_reads for r in p], dtype=np.uint32)
+        lv = np.ascontiguousarray(levels if levels is not None else [], dtype=np.float64)
+        P, n_cands = len(lens), self.info()["n_cands"]
+        prm = PoPhaseParams(self.ploidy, P, n_cands, rel.n_relevant, rel.n_b, int(bool(start_of_block)), int(min_spanning_reads),
+                            int(levels is not None), int(max_candidates), len(lv), float(threshold), 0, 0)
+        as_p = lambda a: a.ctypes.data if len(a) else None   # noqa: E731
+        inp = PoPhaseInput(None, None, None, None, None, path_off.ctypes.data, as_p(path_ids), None, None, as_p(lv))
+        if n_cands * max(P, 1) ** self.ploidy >= 2**31:
+            raise ValueError("po_walk_step_resident: too many extensions for one call")
+        n = ctypes.c_uint64()
+        call = lambda adv, c, e, r, room: self._call(self._lib.po_walk_step_resident(   # noqa: E731
+            self._owner._h, self._ptr, rel._ptr, ctypes.byref(prm), ctypes.byref(inp), int(bool(adv)), _ptr(c), _ptr(e), _ptr(r), room,
+            ctypes.byref(n)))
+        none = np.zeros(0, dtype=np.uint32)
+        room = n_cands * P ** self.ploidy if cap is None else int(cap)
+        if cap is None and room > 1 << 22:
+            call(False, none, none, none.astype(np.float64), 0)   # (a peek for the count: the step itself may run only once)
+            room = int(n.value)
+        cand, ext, rl = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.float64)
+        call(advance, cand, ext, rl, room)
+        m = min(room, int(n.value))
+        return cand[:m].copy(), ext[:m].copy(), rl[:m].copy()
+
+    def prev_sets(self):
+        """``po_walk_prev_copy``: ``(prev_graph, prev_aligning)`` as ascending lists of global read ids."""
+        out = []
+        for which in (0, 1):
+            n = ctypes.c_uint64()
+            self._call(self._lib.po_walk_prev_copy(self._ptr, which, None, 0, ctypes.byref(n)))
+            ids = np.zeros(int(n.value), dtype=np.uint32)
+            if len(ids):
+                self._call(self._lib.po_walk_prev_copy(self._ptr, which, ids.ctypes.data, len(ids), ctypes.byref(n)))
+            out.append(ids.tolist())
+        return out[0], out[1]
+
     def best(self):
         """``po_walk_best``: ``prune(candidate_sets, 1.0)`` -- ``(candidates, greatest log_rl)``."""
         room = self.info()["n_cands"]
@@ -186,6 +250,44 @@ class DeviceWalk:
     def __del__(self):
         try:
             if self._owner._h:
+                self.close()
+        except Exception:
+            pass
+
+
+class ResidentRelevant:
+    """The gather of ``DeviceWalk.relevant`` (``po_walk_relevant``): its sizes as attributes; the arrays stay on the device until
+    ``fetch()`` asks for them.  It is live until the walk's next ``relevant``, a ``reset`` or the walk's ``close``."""
+
+    def __init__(self, walk: DeviceWalk, ptr):
+        self._walk, self._lib, self._ptr = walk, walk._lib, ptr
+        d = PoRelevantDims()
+        try:
+            walk._call(self._lib.po_relevant_sizes(ptr, ctypes.byref(d)))
+        except Exception:
+            self.close()
+            raise
+        self.n_cur_aligning, self.n_spanning, self.n_relevant = int(d.n_cur_aligning), int(d.n_spanning), int(d.n_relevant)
+        self.n_alignments, self.n_b, self.fell_back = int(d.n_alignments), int(d.n_b), bool(d.fell_back)
+
+    def fetch(self) -> "RelevantReads":
+        """``po_relevant_copy``: what ``phase_relevant`` returns for the same sets passed as lists."""
+        R, A = self.n_relevant, self.n_alignments
+        out = RelevantReads(np.zeros(self.n_cur_aligning, np.uint32), np.zeros(R, np.uint32), np.zeros(R, np.int32), np.zeros(R + 1, np.uint32),
+                            np.zeros(A, np.uint32), np.zeros(A, np.int32), np.zeros(A, np.int32), np.zeros(self.n_b, np.uint32),
+                            self.n_spanning, self.fell_back)
+        self._walk._call(self._lib.po_relevant_copy(self._ptr, _ptr(out.cur_aligning), _ptr(out.rel_reads), _ptr(out.overlap_max),
+                                                    _ptr(out.aln_off), _ptr(out.aln_b), _ptr(out.aln_a0), _ptr(out.aln_a1), _ptr(out.b_reads)))
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "_ptr", None):
+            self._lib.po_result_free(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            if self._walk._owner._h:
                 self.close()
         except Exception:
             pass

@@ -46,6 +46,14 @@ resident on the device from bubble to bubble, through ``po_walk_*`` (DESIGN.md s
     for block in phase_chain(ov, ov, index, chain_bubbles_input(paths, chain, reads_of_node), reads_of_node, ploidy, walk=walk):
         block.haplotypes, block.read_sets, block.include_last, block.from_large_bubble, block.log_rl, block.tie
 
+One turn of that loop without the host between the gather and the step -- ``prev_graph_reads`` / ``prev_aligning_reads`` as
+bitsets of the walk, the relevant arrays and the block-stable read ids on the device -- through ``po_walk_relevant`` and
+``po_walk_step_resident``; ``phase_chain(..., resident=True)`` walks by it:
+
+    rel = walk.relevant(ov, index, cur_graph, preds, start_of_block, min_spanning_reads)   # the six sizes; fetch() for the arrays
+    cand, ext, rl = walk.step_resident(rel, path_reads, start_of_block, threshold, min_spanning_reads, levels, max_candidates)
+    prev_graph, prev_aligning = walk.prev_sets()
+
 The large arm of that walk for a bubble of ANY listed size (``phase_large_bubble``, phasing.py:633-685), with the paths
 RESIDENT on the device, through ``po_phase_large``: the score of a path decomposes over its interior
 nodes, so an interval per (interior node, read) suffices and every listed path is scored where ``po_phase_paths`` left it:
@@ -494,6 +502,14 @@ class HostWalk:
         self._rl = [-math.inf]
         self._hist = [[]]
         self._block = set()
+        # the resident route (po_walk_relevant, po_walk_step_resident): the two previous sets and the one live gather
+        self._prev_graph, self._prev_aligning, self._route = set(), set(), 0
+        live = getattr(self, "_live", None)
+        if live is not None:
+            if (live.fell_back or live.mode == 1) and live.resets == 0:   # (new_block(), then the step on the same relevant reads)
+                live.resets, live.depth = 1, 0
+            else:
+                live.stale, self._live = True, None
 
     @property
     def start_of_block(self) -> bool:
@@ -514,6 +530,15 @@ class HostWalk:
              max_candidates: int = 0, advance: bool = True, cap: Optional[int] = None):
         if bool(start_of_block) != self.start_of_block:
             raise ValueError("po_walk_step: start_of_block is not the walk's")
+        if self._route == 2:
+            raise ValueError("po_walk_step: the block advanced by po_walk_step_resident: the two routes do not mix before po_walk_reset")
+        cand, ext, rl = self._step(rel, path_reads, start_of_block, threshold, min_spanning_reads, levels, max_candidates, advance)
+        if self._stats["advanced"]:
+            self._route = 1
+        n = len(rl) if cap is None else min(int(cap), len(rl))
+        return cand[:n], ext[:n], rl[:n]
+
+    def _step(self, rel: RelevantReads, path_reads, start_of_block, threshold, min_spanning_reads, levels, max_candidates, advance):
         b_reads = [int(x) for x in rel.b_reads]
         if any(y <= x for x, y in zip(b_reads, b_reads[1:])):
             raise ValueError("po_walk_step: b_reads is not strictly ascending")
@@ -536,8 +561,48 @@ class HostWalk:
         self._stats = {"n_cands_in": n_in, "n_cands_out": len(self._sets), "depth": len(self._hist[0]), "n_block_reads": len(self._block),
                        "n_new_reads": len(fresh), "words_per_slot": (len(self._block) + 31) // 32 if self._hist[0] else 0,
                        "advanced": int(advanced)}
+        return cand, ext, rl
+
+    def relevant(self, source, index, cur_graph, preds=(), start_of_block: bool = False, min_spanning_reads: int = 0,
+                 without_prev_graph: bool = False) -> "HostGather":
+        """``po_walk_relevant``: ``relevant_reads`` with ``prev_graph`` (empty with ``without_prev_graph``) and ``prev_aligning``
+        taken from the walk.  The walk holds one live gather: this call makes the one before stale."""
+        if self._route == 1:
+            raise ValueError("po_walk_relevant: the block advanced by po_walk_step: the two routes do not mix before po_walk_reset")
+        if getattr(self, "_live", None) is not None:
+            self._live.stale = True
+        cur_graph = [int(x) for x in cur_graph]
+        rel = relevant_reads(source, index, cur_graph, [] if without_prev_graph else sorted(self._prev_graph), sorted(self._prev_aligning),
+                             preds, start_of_block, min_spanning_reads)
+        self._live = HostGather(rel, cur_graph, 1 if start_of_block else 0, len(self._hist[0]))
+        return self._live
+
+    def step_resident(self, rel: "HostGather", path_reads, start_of_block, threshold: float = 0.0, min_spanning_reads: int = 0, levels=None,
+                      max_candidates: int = 0, advance: bool = True, cap: Optional[int] = None):
+        """``po_walk_step_resident``: ``step`` on the live gather; a step that advances joins the gather's ``cur_graph`` to
+        ``prev_graph`` and its ``cur_aligning`` to ``prev_aligning``."""
+        if not isinstance(rel, HostGather):
+            raise ValueError("po_walk_step_resident: needs the result of po_walk_relevant")
+        if rel.stale or rel is not getattr(self, "_live", None):
+            raise ValueError("po_walk_step_resident: the gather is stale: a later po_walk_relevant, a po_walk_reset or the freeing of "
+                             "its walk has taken its arrays")
+        if bool(start_of_block) != self.start_of_block:
+            raise ValueError("po_walk_step_resident: start_of_block is not the walk's")
+        if rel.depth != len(self._hist[0]):
+            raise ValueError("po_walk_step_resident: the gather was made at another depth of the walk")
+        if self._route == 1:
+            raise ValueError("po_walk_step_resident: the block advanced by po_walk_step: the two routes do not mix before po_walk_reset")
+        cand, ext, rl = self._step(rel.rel, path_reads, start_of_block, threshold, min_spanning_reads, levels, max_candidates, advance)
+        if self._stats["advanced"]:
+            self._route = 2
+            self._prev_graph.update(rel.cur_graph)
+            self._prev_aligning.update(int(x) for x in rel.rel.cur_aligning)
         n = len(rl) if cap is None else min(int(cap), len(rl))
         return cand[:n], ext[:n], rl[:n]
+
+    def prev_sets(self):
+        """``po_walk_prev_copy``: ``(prev_graph, prev_aligning)`` as ascending lists."""
+        return sorted(self._prev_graph), sorted(self._prev_aligning)
 
     def best(self):
         """``prune(candidate_sets, 1.0)``: ``(candidates, greatest log_rl)``."""
@@ -558,6 +623,25 @@ class HostWalk:
 
     def read_sets(self, cands) -> list:
         return [[sorted(s) for s in self._sets[c]] for c in self._named(cands)]
+
+    def close(self) -> None:
+        pass
+
+
+class HostGather:
+    """What ``HostWalk.relevant`` returns: the sizes of the gather as attributes, ``fetch()`` for the arrays, ``close()``."""
+
+    def __init__(self, rel: RelevantReads, cur_graph, mode: int, depth: int):
+        self.rel, self.cur_graph, self.mode, self.depth = rel, list(cur_graph), int(mode), int(depth)
+        self.stale, self.resets = False, 0
+        self.n_cur_aligning, self.n_spanning, self.n_relevant = len(rel.cur_aligning), int(rel.n_spanning), len(rel.rel_reads)
+        self.n_alignments, self.n_b, self.fell_back = len(rel.aln_b), len(rel.b_reads), bool(rel.fell_back)
+
+    def fetch(self) -> RelevantReads:
+        if self.stale:
+            raise ValueError("po_relevant_copy: the gather is stale: a later po_walk_relevant, a po_walk_reset or the freeing of its "
+                             "walk has taken its arrays")
+        return self.rel
 
     def close(self) -> None:
         pass
@@ -593,7 +677,8 @@ def chain_bubbles_input(bubble_paths: "BubblePaths", chain: int, reads_of_node: 
 
 def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy: int, min_spanning_reads: int = 3, max_bubble_size: int = 10,
                 threshold=1e-3, prune_factor=0.1, max_candidates: int = 500, max_prune_rounds: int = 9, prune_step_size: float = 0.1,
-                walk=None, choose: Callable = random.choice, on_step: Optional[Callable] = None, large_scores: bool = False):
+                walk=None, choose: Callable = random.choice, on_step: Optional[Callable] = None, large_scores: bool = False,
+                resident: bool = False):
     """``BubbleChainPhaser.phase()`` (phasm/phasing.py:182-364) over ``bubbles`` (``chain_bubbles_input``), arm by arm, as a
     generator of ``Haploblock``.  ``scorer``: what ``score_paths`` needs at a large bubble; ``source`` / ``index``: what
     ``relevant_reads`` needs; ``walk``: a ``DeviceWalk`` (``ExactOverlapper.phase_walk``) or a ``HostWalk`` -- None: the
@@ -607,7 +692,10 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
     the large arm that scorer is asked with the relevant reads and only the winner's node tuple is fetched; ``on_step`` gets
     ``best``, ``winner`` and ``arm``, and ``scores`` only with ``large_scores``.  Such a bubble that is NOT large cannot be
     walked (the branch arm needs its paths on the host, at most 64 of them): ``ValueError`` naming the bubble.
-    ``prev_graph_reads`` and ``prev_aligning_reads`` are host sets.  One difference from the reference: a bubble that keeps no
+    ``prev_graph_reads`` and ``prev_aligning_reads`` are host sets -- unless ``resident``: then they are the walk's
+    (``walk.relevant`` / ``walk.step_resident`` / ``walk.prev_sets``), the loop keeps none of its own and
+    the arrays of the relevant reads come to the host only where they are needed there: at the large arm and, for the keys of
+    the trace, when ``on_step`` is given.  Arms, yields and error sentences are the same.  One difference from the reference: a bubble that keeps no
     candidate even as the start of a block makes the reference loop for ever; here it raises ``ValueError``."""
     k = int(ploidy)
     own = walk is None
@@ -635,17 +723,21 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
     def new_block():
         block = best_block(False)
         walk.reset()
-        prev_graph.clear()
+        prev_graph.clear()        # (with `resident` the two stay empty: the sets are the walk's)
         prev_aligning.clear()
         del block_paths[:], block_bubbles[:]
         return block
 
+    gather = None
     try:
         i = 0
         while i < len(bubbles):
+            if gather is not None:
+                gather.close()
+                gather = None
             b = bubbles[i]
-            resident = b.get("paths") is None
-            if resident:
+            on_device = b.get("paths") is None
+            if on_device:
                 n_here = int(b["n_paths"])
                 if n_here <= max_bubble_size:
                     raise ValueError("bubble %d (%s .. %s) has %d paths that are not on the host: only a large bubble (more than "
@@ -659,19 +751,27 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
             start = walk.start_of_block
             s = {"bubble": i, "start": int(start), "arm": "skipped", "broke": 0, "fell_back": 0, "yields": [], "steps": []}
             large = n_here > max_bubble_size
-            rel = relevant_reads(source, index, b["interior_reads"], [] if large else sorted(prev_graph), sorted(prev_aligning), b["preds"],
-                                 start or large, 0 if large else min_spanning_reads)
-            s.update({"cur_aligning": rel.cur_aligning.tolist(), "n_spanning": int(rel.n_spanning), "rel_reads": rel.rel_reads.tolist(),
-                      "overlap_max": rel.overlap_max.tolist(), "aln_off": rel.aln_off.tolist(),
-                      "aln_y": [int(rel.b_reads[x]) for x in rel.aln_b.tolist()], "aln_a0": rel.aln_a0.tolist(), "aln_a1": rel.aln_a1.tolist(),
-                      "n_b": len(rel.b_reads)})
-            if (large and not start) or rel.fell_back:
+            if resident:
+                gather = walk.relevant(source, index, b["interior_reads"], b["preds"], start or large, 0 if large else min_spanning_reads,
+                                       without_prev_graph=large)
+                rel = gather.fetch() if large or on_step else None   # (before new_block() below: a reset may make the gather stale)
+                n_rel, n_aln, fell_back = gather.n_relevant, gather.n_alignments, gather.fell_back
+            else:
+                rel = relevant_reads(source, index, b["interior_reads"], [] if large else sorted(prev_graph), sorted(prev_aligning), b["preds"],
+                                     start or large, 0 if large else min_spanning_reads)
+                n_rel, n_aln, fell_back = len(rel.rel_reads), len(rel.aln_b), rel.fell_back
+            if rel is not None:
+                s.update({"cur_aligning": rel.cur_aligning.tolist(), "n_spanning": int(rel.n_spanning), "rel_reads": rel.rel_reads.tolist(),
+                          "overlap_max": rel.overlap_max.tolist(), "aln_off": rel.aln_off.tolist(),
+                          "aln_y": [int(rel.b_reads[x]) for x in rel.aln_b.tolist()], "aln_a0": rel.aln_a0.tolist(),
+                          "aln_a1": rel.aln_a1.tolist(), "n_b": len(rel.b_reads)})
+            if (large and not start) or fell_back:
                 block = new_block()
                 s["yields"].append(as_yield(block, "new_block"))
-                s["broke"], s["fell_back"] = 1, int(rel.fell_back)
+                s["broke"], s["fell_back"] = 1, int(fell_back)
                 yield block
                 start = True
-            if large and resident:
+            if large and on_device:
                 best, _, scores = b["scorer"].score_large(rel, reads_of_node, k, want_scores=large_scores)
                 if scores is not None:
                     s["scores"] = np.asarray(scores).tolist()
@@ -697,23 +797,24 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
                 yield block
                 i += 1
                 continue
-            if len(rel.aln_b) == 0:
+            if n_aln == 0:
                 if on_step:
                     on_step(s)
                 i += 1
                 continue
-            R = len(rel.rel_reads)
+            R = n_rel
             level = threshold(R) if callable(threshold) else threshold
+            step = (lambda *a, **kw: walk.step_resident(gather, *a, **kw)) if resident else (lambda *a, **kw: walk.step(rel, *a, **kw))
             factor = prune_factor
             s["n_cands_in"] = walk.info()["n_cands"]
             if callable(factor):
-                cand, ext, rl = walk.step(rel, path_reads, start, level, min_spanning_reads, levels=None, advance=False)
+                cand, ext, rl = step(path_reads, start, level, min_spanning_reads, levels=None, advance=False)
                 s["kept_cand"], s["kept_ext"], s["kept_rl"] = cand.tolist(), ext.tolist(), rl.tolist()
                 s["steps"].append((cand, ext, rl))
                 factor = factor(len(rl)) if len(rl) >= 2 else 0.0
-            cand, ext, rl = walk.step(rel, path_reads, start, level, min_spanning_reads,
-                                      levels=prune_levels(float(factor), float(prune_step_size), int(max_prune_rounds)),
-                                      max_candidates=int(max_candidates), advance=True)
+            cand, ext, rl = step(path_reads, start, level, min_spanning_reads,
+                                 levels=prune_levels(float(factor), float(prune_step_size), int(max_prune_rounds)),
+                                 max_candidates=int(max_candidates), advance=True)
             s["steps"].append((cand, ext, rl))
             s["phase_stats"] = walk.phase_stats()
             s["n_kept"] = int(s["phase_stats"]["n_kept"])
@@ -723,8 +824,9 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
             if len(rl):
                 block_paths.append(paths)
                 block_bubbles.append(i)
-                prev_graph.update(int(r) for r in b["interior_reads"])
-                prev_aligning.update(s["cur_aligning"])
+                if not resident:
+                    prev_graph.update(int(r) for r in b["interior_reads"])
+                    prev_aligning.update(s["cur_aligning"])
                 if on_step:
                     on_step(s)
                 i += 1
@@ -737,8 +839,12 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
             if on_step:
                 on_step(s)
             yield block
-        final = {"final": True, "yields": [], "block_bubbles": list(block_bubbles), "prev_graph": sorted(prev_graph),
-                 "prev_aligning": sorted(prev_aligning)}
+        if gather is not None:
+            gather.close()
+            gather = None
+        held = walk.prev_sets() if resident else (sorted(prev_graph), sorted(prev_aligning))
+        final = {"final": True, "yields": [], "block_bubbles": list(block_bubbles), "prev_graph": list(held[0]),
+                 "prev_aligning": list(held[1])}
         if not walk.start_of_block:
             final["prune_in"] = walk.info()["n_cands"]
             block = best_block(True)
@@ -749,6 +855,8 @@ def phase_chain(scorer, source, index, bubbles, reads_of_node: Callable, ploidy:
         elif on_step:
             on_step(final)
     finally:
+        if gather is not None:
+            gather.close()
         if own:
             walk.close()
 
